@@ -39,6 +39,27 @@ from mx_deepim_amd.symbols.deepIM_flownet import ENCODER  # noqa: E402
 
 FP32_PEAK_TFLOPS = 157.3   # MI355X_MICROARCH.md: fp32 matrix == fp32 vector peak
 HBM_PEAK_GBS = 8000.0
+DUMP_CAP_BYTES = 64 << 20  # --dump-outputs: at most this many bytes of .npy payload in all
+
+
+def dump_outputs(dirname, arrays, cap=DUMP_CAP_BYTES, seed=0):
+    """--dump-outputs: every array as dirname/<name>.npy, float32 (float64 stays float64). Every array's leading axis is the pair.
+    If they exceed `cap` together, each array above 1 MB keeps a fixed, seeded sample of its pairs (the same pairs for arrays of
+    the same pair count), and the kept pair indices go to <name>_pairs.npy (float64). -> {name: shape} of what was written."""
+    arrs = {k: np.ascontiguousarray(v, np.float64 if np.asarray(v).dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    big = [k for k, a in arrs.items() if a.nbytes > (1 << 20)]
+    if sum(a.nbytes for a in arrs.values()) > cap:
+        room = cap - sum(a.nbytes for k, a in arrs.items() if k not in big) - 4096 * len(big)   # index files and .npy headers
+        scale = room / float(sum(arrs[k].nbytes for k in big))
+        for k in big:
+            rows = arrs[k].shape[0]
+            idx = np.sort(np.random.default_rng(seed).choice(rows, max(1, int(rows * scale)), replace=False))
+            arrs[k] = np.ascontiguousarray(arrs[k][idx])
+            arrs[k + "_pairs"] = idx.astype(np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
+    return {k: list(a.shape) for k, a in arrs.items()}
 
 
 def encoder_flops_per_pair(cin=8, H=480, W=640):
@@ -471,7 +492,13 @@ def dry_run(args, rank, world, rdzv):
             assert np.array_equal(got[r, :counts[r]], want), "all-gather returned wrong poses for rank %d" % r
             assert not got[r, counts[r]:].any()
             off += counts[r]
-    # which GPU every rank's convenience calls would land on (Context.default(): LOCAL_RANK), and what it has opened (nothing, here)
+    if args.dump_outputs and rank == 0:             # what the stand-in computed: every rank's poses, as gathered
+        dump_outputs(args.dump_outputs, {"pose_est": np.concatenate([got[r, :counts[r]] for r in range(world)]).reshape(-1, 3, 4)
+                                         if world > 1 else pose})
+    # which GPU every rank's convenience calls would land on with a GPU per rank (Context.default(): DEEPIM_DEVICE, else LOCAL_RANK),
+    # and what it has opened (nothing, here). Context.default_device_id() is not called: it counts the visible GPUs through HIP,
+    # which would open the device in every rank of the rehearsal
+    Context.set_default(int(os.environ.get("DEEPIM_DEVICE", os.environ.get("LOCAL_RANK", "0"))))
     my = dict(comm_record(None), default_device=Context.default_device_id(), opened=list(Context.opened))
     recs = rdzv.all_gather(json.dumps(my).encode()) if world > 1 else [json.dumps(my).encode()]
     if rank == 0:
@@ -499,6 +526,8 @@ class Loop(object):
     def __init__(self, args, ctx, rdzv, comm, rank, world, B, Bmax, gbatch, strong, steps):
         self.args, self.ctx, self.rdzv, self.comm, self.rank, self.world = args, ctx, rdzv, comm, rank, world
         self.B, self.Bmax, self.NIT, self.steps = B, Bmax, args.iters, steps
+        self.counts = parallel.shard_counts(gbatch, world) if strong else [B] * world
+        self.outputs = None
         NIT, h = self.NIT, ctx.handle
         cfg = default_config()
         cfg.network.FP16_CONV = bool(args.fp16)
@@ -712,6 +741,8 @@ class Loop(object):
             self.step(None if self.step_graphs else self.enc_timers[s_])
         self.fence()
         dt = time.perf_counter() - t0
+        if self.args.dump_outputs:                # the last timed step's results, before the auxiliary steps below recompute them
+            self.outputs = self.last_outputs()
         for s_ in range(self.AUX_STEPS):          # outside the timed region: front end / re-render / pose gather, by HIP events
             self.step(self.enc_timers[s_] if self.step_graphs else None, self.zoom_timers[s_], self.render_timers[s_],
                       self.gather_timers[s_] if self.gather_timers else None)
@@ -730,6 +761,19 @@ class Loop(object):
         lib.deepim_zoom_status(h, ctypes.byref(st))
         assert np.all(np.isfinite(self.pose_cur.asnumpy())) and st.value == 0, ("bad poses / zoom status", st.value)
         return dt
+
+    def last_outputs(self):
+        """What the last step handed its caller, on the host: the refined poses (at N > 1 every rank's, from the all-gather, padding
+        dropped) and the last iteration's network outputs (this rank's pairs): se3, zoom_factor, and with --heads the mask and flow."""
+        A = self.net.act
+        out = {"pose_est": self.pose_cur.asnumpy(), "se3": A["se3"].asnumpy(), "zoom_factor": A["zoom_factor"].asnumpy()}
+        if self.args.heads:
+            out["mask_observed_pred"] = A["mask_observed_pred"].asnumpy()
+            out["flow_est"] = A["flow_est"].asnumpy()
+        if self.world > 1:
+            g = self.gather_out.asnumpy().reshape(self.world, self.Bmax, 3, 4)
+            out["pose_est"] = np.concatenate([g[r, :c] for r, c in enumerate(self.counts)])
+        return out
 
     def means(self):
         m = lambda rows: float(np.mean([t.elapsed_ms() for row in rows for t in row])) if rows and rows[0] else None   # noqa: E731
@@ -797,9 +841,16 @@ def main():
                     "encoder layer; the rocprofv3 passes of tools/run_profiles.sh cut the trace by iteration count and must not see them)")
     ap.add_argument("--full", action="store_true", help="print the full record (what bench_detail.json holds) as the final line instead "
                     "of the compact one the driver parses (used by the secondary runs and the tests that read its fields)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step "
+                    "computed as DIR/<name>.npy (float32): pose_est (the refined poses; every rank's at N > 1), se3 and zoom_factor of its "
+                    "last iteration, and with --heads mask_observed_pred and flow_est; at most 64 MB in all (above that the per-pixel "
+                    "arrays keep a fixed, seeded sample of pairs, listed in <name>_pairs.npy). Inputs and weights are seeded, so the same "
+                    "arguments give the same inputs on every run")
     ap.add_argument("--extras-budget", type=float, default=200.0, help="wall-clock budget in seconds for everything after the "
                     "timed region (parity, CPU baseline, other configs); what does not fit is reported as skipped")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     args.lit = args.lit == "on" or (args.lit == "auto" and args.fp16 and args.depth)
 
     rank = int(os.environ.get("RANK", "0"))
@@ -809,12 +860,12 @@ def main():
     # "rccl": device all-gather over RCCL; "host": the same exchange through the TCP rendezvous, on request (rehearsals with
     # several ranks on one visible GPU, where RCCL refuses duplicate devices)
     backend = os.environ.get("DEEPIM_BENCH_BACKEND", "rccl")
+    rdzv = parallel.Rendezvous(rank, world)          # no-op at world == 1
+    if args.dry_run:                                 # before any HIP call: a rehearsal's ranks never open a GPU
+        return dry_run(args, rank, world, rdzv)
     ndev = ctypes.c_int(0)
     lib.load().deepim_device_count(ctypes.byref(ndev))
     device_id = local_rank % max(1, ndev.value)
-    rdzv = parallel.Rendezvous(rank, world)          # no-op at world == 1
-    if args.dry_run:
-        return dry_run(args, rank, world, rdzv)
 
     Context.set_default(device_id)                   # convenience calls of the host mirrors (RT_transform, nd.array, …) follow this rank's GPU
     ctx = Context.get(device_id)
@@ -867,6 +918,9 @@ def main():
     assert B > 0, "more GPUs than pairs"
     L = Loop(args, ctx, rdzv, comm, rank, world, B, Bmax, gbatch, scaling == "strong", args.steps)
     dt = L.time(args.warmup)
+    if args.dump_outputs and rank == 0:
+        shapes = dump_outputs(args.dump_outputs, L.outputs)
+        sys.stderr.write("[bench] last timed step's outputs -> %s: %s\n" % (args.dump_outputs, shapes))
     cfg, net, params, batch, pose_cur, step = L.cfg, L.net, L.params, L.batch, L.pose_cur, L.step
     use_graph = L.use_graph
 

@@ -72,19 +72,26 @@ def test_library_exports_flow_with_cxx_linkage_too():
 
 
 def test_reference_header_client_links_against_the_library(tmp_path):
-    """Compile a C++ TU that includes the reference's gpu_flow.hpp unmodified and link it against libdeepim_hip.so
-    with --no-undefined (build container only: /root/reference is absent on the GPU box, where the prebuilt
-    oracle/_ref/libflow_hpp_client.so is called instead — tests/test_gpu_flow_reference.py)."""
+    """A C++ TU that includes the reference's gpu_flow.hpp unmodified links against libdeepim_hip.so: every symbol it leaves
+    undefined (stored in tests/golden/flow_ref_kernel_golden.npz by tests/golden/make_flow_ref_golden.py) is defined there.
+    Where the reference checkout is present (REFERENCE_DIR, default as in oracle/Makefile), the TU is also compiled and
+    linked with --no-undefined here, and must leave exactly the stored symbols undefined."""
     import subprocess
-    hdr = "/root/reference/lib/flow_c/gpu_flow.hpp"
+    import numpy as np
+    stored = [str(u) for u in np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden",
+                                                   "flow_ref_kernel_golden.npz"))["header_client_undefined"]]
+    assert stored == [CXX_FLOW], stored
+    syms = _dynsyms(runtime.LIB_PATH)
+    assert all(syms.get(u) == "T" for u in stored), stored
+    hdr = os.path.join(os.environ.get("REFERENCE_DIR", "/root/reference"), "lib", "flow_c", "gpu_flow.hpp")
     root = os.path.dirname(runtime._HERE)
     if not os.path.exists(hdr):
-        pytest.skip("reference checkout not present")
+        return
     out = str(tmp_path / "client.so")
     subprocess.run(["g++", "-O1", "-fPIC", "-shared", "-I" + os.path.dirname(hdr), "-o", out,
                     os.path.join(root, "oracle", "flow_hpp_client.cpp"), "-L" + os.path.dirname(runtime.LIB_PATH),
                     "-ldeepim_hip", "-Wl,--no-undefined"], check=True)
-    assert _dynsyms(out).get(CXX_FLOW) == "U"
+    assert sorted(k for k, v in _dynsyms(out).items() if v == "U") == stored
     assert "extern" not in open(hdr).read()          # the header really is C++-linkage; if that changes, so does B2
     prebuilt = os.path.join(root, "oracle", "_ref", "libflow_hpp_client.so")
     if os.path.exists(prebuilt):

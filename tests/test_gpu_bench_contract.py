@@ -8,6 +8,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -42,6 +43,26 @@ def test_bench_line_single_gpu():
     rf = d["roofline"]
     assert rf["bound"] == "mfma" and rf["unit"] == "TFLOP/s" and abs(rf["frac"] - rf["achieved"] / rf["peak"]) < 1e-4
     assert 0 < rf["frac"] < 1 and d["config"]["workload"]
+
+
+def test_bench_dump_outputs_of_the_last_timed_step(tmp_path):
+    """--dump-outputs: the last timed step's results as float32 .npy files — the refined poses and the last iteration's se3 /
+    zoom_factor — identical in two runs with the same arguments (seeded inputs), and with --steps the number of timed steps."""
+    got = []
+    for name, steps in (("a", "3"), ("b", "2")):
+        r = subprocess.run([sys.executable, "bench.py", "--steps", steps, "--warmup", "1", "--batch", "2", "--no-cpu-baseline",
+                            "--verify", "0", "--no-other-configs", "--no-layer-timings", "--dump-outputs", str(tmp_path / name)],
+                           cwd=ROOT, capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert _last_json(r.stdout)["steps"] == int(steps)
+        files = sorted(os.listdir(str(tmp_path / name)))
+        assert files == ["pose_est.npy", "se3.npy", "zoom_factor.npy"], files
+        got.append({f[:-4]: np.load(str(tmp_path / name / f)) for f in files})
+    a, b = got
+    assert a["pose_est"].shape == (2, 3, 4) and a["se3"].shape[0] == 2 and a["zoom_factor"].shape[0] == 2
+    for k in a:
+        assert a[k].dtype == np.float32 and np.all(np.isfinite(a[k])), k
+        np.testing.assert_array_equal(a[k], b[k], err_msg=k)
 
 
 @pytest.mark.parametrize("extra,bar", [([], 1e-4), (["--batch", "16"], 1e-4)], ids=["bs32_headline", "bs16_configs1"])

@@ -342,6 +342,7 @@ def test_default_context_follows_local_rank(monkeypatch):
     import re
     from mx_deepim_amd.runtime import Context
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    monkeypatch.setattr(Context, "visible_devices", staticmethod(lambda: 0))    # the selection alone; folding is checked below
     for env, want in (({}, 0), ({"LOCAL_RANK": "5"}, 5), ({"LOCAL_RANK": "5", "DEEPIM_DEVICE": "2"}, 2), ({"LOCAL_RANK": "x"}, 0)):
         monkeypatch.delenv("LOCAL_RANK", raising=False)
         monkeypatch.delenv("DEEPIM_DEVICE", raising=False)
@@ -505,6 +506,53 @@ def test_bench_final_line_is_compact_and_parseable():
     assert r.returncode == 0, r.stderr[-2000:]
     last = r.stdout.strip().splitlines()[-1]
     assert len(last) < 4096 and json.loads(last)["dry_run"] is True
+
+
+def test_bench_dump_outputs_stays_under_the_cap_with_a_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: float32 .npy files (float64 kept), small arrays whole, and above the cap every large array keeps
+    the same seeded sample of pairs, recorded in <name>_pairs.npy, so that two runs write identical files."""
+    import bench
+    rng = np.random.default_rng(1)
+    arrays = {"pose_est": rng.standard_normal((8, 3, 4)), "se3": rng.standard_normal((8, 7)).astype(np.float32),
+              "mask": rng.standard_normal((8, 1, 240, 320)).astype(np.float32),
+              "flow": rng.standard_normal((8, 2, 240, 320)).astype(np.float16)}
+    cap = 4 << 20                                        # 7.4 MB of arrays
+    shapes = bench.dump_outputs(str(tmp_path / "a"), arrays, cap=cap)
+    bench.dump_outputs(str(tmp_path / "b"), arrays, cap=cap)
+    files = sorted(os.listdir(str(tmp_path / "a")))
+    assert files == sorted(k + ".npy" for k in shapes) == sorted(os.listdir(str(tmp_path / "b")))
+    assert sum(os.path.getsize(str(tmp_path / "a" / f)) for f in files) <= cap
+    got = {f[:-4]: np.load(str(tmp_path / "a" / f)) for f in files}
+    for k, v in got.items():
+        assert v.dtype in (np.float32, np.float64), k
+        assert np.array_equal(v, np.load(str(tmp_path / "b" / (k + ".npy")))), k
+    assert got["pose_est"].dtype == np.float64 and np.array_equal(got["pose_est"], arrays["pose_est"])
+    assert np.array_equal(got["se3"], arrays["se3"])
+    idx = got["mask_pairs"].astype(int)
+    assert np.array_equal(idx, got["flow_pairs"]) and 0 < len(idx) < 8 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(got["mask"], arrays["mask"][idx])
+    assert np.array_equal(got["flow"], arrays["flow"][idx].astype(np.float32))
+    small = bench.dump_outputs(str(tmp_path / "c"), arrays, cap=64 << 20)       # under the cap: everything whole, no index files
+    assert small == {k: list(v.shape) for k, v in arrays.items()}
+
+
+def test_bench_dry_run_dumps_outputs(tmp_path):
+    """--dump-outputs end to end without a GPU: the dry run's stand-in poses, identical from run to run; --steps below 1 is refused."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    outs = []
+    for name in ("a", "b"):
+        r = subprocess.run([sys.executable, "bench.py", "--dry-run", "--steps", "3", "--warmup", "1", "--batch", "5",
+                            "--dump-outputs", str(tmp_path / name)], cwd=root, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert os.listdir(str(tmp_path / name)) == ["pose_est.npy"]
+        outs.append(np.load(str(tmp_path / name / "pose_est.npy")))
+    assert outs[0].dtype == np.float32 and outs[0].shape == (5, 3, 4) and np.array_equal(outs[0], outs[1])
+    assert np.array_equal(outs[0], np.arange(60, dtype=np.float32).reshape(5, 3, 4) + 4)      # 4 refinement iterations of pose += 1
+    r = subprocess.run([sys.executable, "bench.py", "--dry-run", "--steps", "0"], cwd=root, capture_output=True, text=True,
+                       timeout=300)
+    assert r.returncode != 0 and "--steps" in r.stderr
 
 
 def test_bench_roofline_block_is_physical(tmp_path):
