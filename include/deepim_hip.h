@@ -354,6 +354,17 @@ int deepim_conv2d_wino_forward_s2d(deepim_ctx* ctx, float* out, const float* in_
 int deepim_relayout_nc8_s2d(deepim_ctx* ctx, float* dst, const float* src, int B, int C, int H, int W, int to_s2d);
 int deepim_conv2d_wino_forward(deepim_ctx* ctx, float* out, const float* in, const float* packed_w, const float* bias,
                                int B, int Cin, int H, int W, int Cout, float slope, int out_nc8, int out_ctotal, int out_coff);
+/* conv1 (7x7 stride 2 pad 3, Cin 8, Cout 64, deepIM_flownet.py:63) as fp32 Winograd F(2x2,4x4) over its four input phases
+ * (csrc/wino_c1.hip): 81 (phase, position) GEMMs over the 8 channels per 2x2 tile, 2.42x fewer multiplies than the direct sum,
+ * within 1e-5 of the layer's range from it. `in` is the NCHW (B, 8, H, W) net input; `out` is NC8 (out_mode 1) or NC8 in
+ * space-to-depth order (out_mode 3, even output height and width: what the stride-2 Winograd layer conv2 reads). packed_w from
+ * deepim_conv1_wino_pack_weights (the layer's (64, 8, 7, 7) weights; size deepim_conv1_wino_packed_size() bytes). _preferred is 0
+ * for any other geometry and on a context in the canonical-summation-order configuration ("conv_max_split" = 1). */
+size_t deepim_conv1_wino_packed_size(void);
+int deepim_conv1_wino_preferred(deepim_ctx* ctx, int B, int Cin, int H, int W, int Cout);
+int deepim_conv1_wino_pack_weights(deepim_ctx* ctx, float* packed_w, const float* w /*64,8,7,7 dev*/);
+int deepim_conv1_wino_forward(deepim_ctx* ctx, float* out, const float* in, const float* packed_w, const float* bias,
+                              int B, int H, int W, float slope, int out_mode);
 /* The same 3x3 stride-1 pad-1 Convolution + bias + LeakyReLU layers (deepIM_flownet.py:77-101) as fp32 Winograd F(4,3) x F(2,3): 4-row x
  * 2-column output tiles, 24 positions, 3 multiply-adds per output, input and output channel instead of 4 (csrc/wino42.hip; Cout % 64 == 0,
  * Cin % 8 == 0; channel-blocked input, channel-blocked (out_nc8 = 1) or NCHW-slice (0) output). ~3e-6 of the layer's range from the direct

@@ -295,7 +295,7 @@ class deepIM_flownet(object):
                 pk = DeviceArray(ctx, (nb // 4,))
                 lib.deepim_conv_pack_weights(h, pk, self.params[name], cout, cin, kh, kw)
             self.packed[base] = pk
-        self.packed_wino, self.wino_s2d = {}, set()
+        self.packed_wino, self.wino_s2d, self.wino_conv1 = {}, set(), None
         if self.nc8 and getattr(self, "winograd", False) and not (self.fp16_conv or self.x3_conv or getattr(self, "is_train", False)):
             hh, ww, cin = H, W, self.cin
             L = lib.load()
@@ -312,6 +312,13 @@ class deepIM_flownet(object):
                     self.wino_s2d.add(name)
                 hh, ww = _out_hw(hh, ww, k, s_, p_)
                 cin = cout
+            # conv1 (7x7 stride 2, 8 -> 64) as Winograd F(2x2,4x4) over its four input phases (csrc/wino_c1.hip). A separate
+            # attribute: packed_wino / wino_s2d mean F(2x2,3x3) layers to the rest of the code
+            name0, cout0 = ENCODER[0][0], ENCODER[0][1]
+            if L.deepim_conv1_wino_preferred(h, B, self.cin, H, W, cout0):
+                pk = DeviceArray(ctx, (L.deepim_conv1_wino_packed_size() // 4,))
+                lib.deepim_conv1_wino_pack_weights(h, pk, self.params[name0 + "_weight"])
+                self.wino_conv1 = pk
         # fc6: the 84 MB weight in MFMA operand order, so the layer is one pass over the weights on the matrix cores
         nb = lib.load().deepim_fc_packed_size(256, 1024 * 8 * 10)
         self.packed["fc6"] = DeviceArray(ctx, (nb // 4,))
@@ -525,6 +532,11 @@ class deepIM_flownet(object):
             fwd = lib.deepim_conv2d_wino_forward_s2d if name in self.wino_s2d else lib.deepim_conv2d_wino_forward
             fwd(self.ctx.handle, self.act[name], src, self.packed_wino[name], self.params[name + "_bias"],      # s2d: 5x5 stride 2 over
                 self.B, cin, h, w, cout, ctypes.c_float(SLOPE), out_mode, 0, 0)                                  # the space-to-depth tensor
+        elif (self.nc8 and li == 0 and getattr(self, "wino_conv1", None) is not None and src.shape != (self.B, self.H, self.W, 8)
+              and lib.load().deepim_conv1_wino_preferred(self.ctx.handle, self.B, cin, h, w, cout)):
+            # (asked again per call: a context switched to the canonical order after bind keeps conv1 on the direct kernel)
+            lib.deepim_conv1_wino_forward(self.ctx.handle, self.act[name], src, self.wino_conv1, self.params[name + "_bias"],
+                                          self.B, h, w, ctypes.c_float(SLOPE), out_mode)
         elif self.nc8:
             in8 = 1 if (li > 0 or src.shape == (self.B, self.H, self.W, 8)) else 0     # conv1: NC8 records from the zoom front end
             lib.deepim_conv2d_forward_ex(self.ctx.handle, self.act[name], src, self.packed[name], self.params[name + "_bias"],
