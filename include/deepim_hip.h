@@ -438,6 +438,34 @@ int deepim_deconv4x4s2_crop_forward(deepim_ctx* ctx, float* out, const float* in
                                     const float* bias, int B, int Cin, int H, int W, int Cout,
                                     int Ho, int Wo, int crop_y, int crop_x, float slope,
                                     int out_ctotal, int out_coff);
+/* fp16 FlowNetS decoder (the fp16 conv path with the decoder in the graph; csrc/decoder_f16.hip). Tensors are NHWC fp16 records
+ * of `ctotal` channels; a layer reads channels [0, Cin_pad) of its input and writes a channel slice of its output.
+ * deconv5 / deconv4: Deconvolution k4 s2 p0 + bias + Crop(1,1) + LeakyReLU (deepIM_flownet.py:127-143,149-165) as four parity-class
+ * GEMMs on v_mfma_f32_32x32x16_f16 (fp16 weights x fp16 activations, fp32 accumulation, bias + LeakyReLU in fp32, one rounding at
+ * the store) into channels [out_coff, out_coff + Cout). Cout % 64 == 0, Cin_pad % 8 == 0 (input channels [Cin, Cin_pad) zero or
+ * finite: their packed weights are zero), out_coff % 4 == 0. w (Cin,Cout,4,4) fp32 → packed (deepim_deconv_f16_packed_size bytes). */
+size_t deepim_deconv_f16_packed_size(int Cin_pad, int Cout);
+int deepim_deconv_f16_pack_weights(deepim_ctx* ctx, void* packed, const float* w, int Cin, int Cin_pad, int Cout);
+int deepim_deconv4x4s2_crop_f16_forward(deepim_ctx* ctx, void* out_nhwc_f16, const void* in_nhwc_f16, const void* packed_w,
+                                        const float* bias, int B, int Cin_pad, int in_ctotal, int H, int W, int Cout, int Ho,
+                                        int Wo, float slope, int out_ctotal, int out_coff);
+/* Few-filter 3x3 stride-1 pad-1 Convolution + bias (Convolution1 / 2 / 3, mask_conv3) from an NHWC fp16 input into fp32 NCHW: up to
+ * 3 filters in one pass over the input, n0 of them into out0 (B,n0,H,W), n1 into out1 (B,n1,H,W) (n1 = 0, out1 = NULL: one tensor).
+ * fp16 weights x fp16 activations (products exact), fp32 sums, fp32 bias. w0 (n0,Cin,3,3), w1 (n1,Cin,3,3) fp32 → packed
+ * (deepim_fewout_f16_packed_size bytes); Cin_pad % 8 == 0, at most 2048. */
+size_t deepim_fewout_f16_packed_size(int Cin_pad);
+int deepim_fewout_f16_pack_weights(deepim_ctx* ctx, void* packed, const float* w0, int n0, const float* w1, int n1, int Cin,
+                                   int Cin_pad);
+int deepim_conv3x3_fewout_f16_forward(deepim_ctx* ctx, float* out0, int n0, float* out1, int n1, const void* in_nhwc_f16,
+                                      const void* packed_w, const float* bias0, const float* bias1, int B, int H, int W,
+                                      int in_ctotal, int Cin_pad);
+/* upsample_flow6to5 / 5to4: Deconvolution k4 s2 (2 → 2 channels) + bias + Crop(1,1) of an fp32 NCHW flow (B,2,H,W) in fp32,
+ * rounded once into channels [out_coff, out_coff + 2) of an NHWC fp16 output (Ho,Wo); w (2,2,4,4) fp32 as stored */
+int deepim_upsample_flow_f16_forward(deepim_ctx* ctx, void* out_nhwc_f16, const float* in, const float* w, const float* bias,
+                                     int B, int H, int W, int Ho, int Wo, int out_ctotal, int out_coff);
+/* NHWC fp16 channel-slice copy: dst[pix][dst_coff + c] = src[pix][src_coff + c], c < C, for npix pixels; all counts % 8 == 0 */
+int deepim_copy_channels_nhwc_f16(deepim_ctx* ctx, void* dst, int dst_ctotal, int dst_coff, const void* src, int src_ctotal,
+                                  int src_coff, int C, long npix);
 /* grouped (depthwise) Deconvolution k32 s16 no-bias + Crop(offset) to (Ho,Wo), times `scale`
  * (deepIM_flownet.py:185-200,326-340,636-648,687-702). w (C,1,32,32). */
 int deepim_upsample16_crop_forward(deepim_ctx* ctx, float* out, const float* in, const float* w,

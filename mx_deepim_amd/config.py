@@ -44,6 +44,7 @@ def default_config():
         TRAIN_ITER=True, TRAIN_ITER_SIZE=4,   # yaml :57-58 — refinement iterations inside one training step (module.py:1131-1137)
         X3_CONV=False,     # split-fp16 conv path: fp32-grade accuracy (≈1e-6) on the fp16 matrix cores (not a reference key)
         FP16_CONV=False,   # BASELINE config 5: fp16 conv path (not a reference key; the reference is fp32 only)
+        FP16_DECODER=True,  # with FP16_CONV and the decoder in the graph: decoder + flow / mask predictors in fp16 too (False: fp32 decoder)
     )
     cfg.train_iter = AttrDict(SE3_PM_LOSS=True, SE3_PM_LOSS_TYPE="L1", LW_PM=0.1, LW_FLOW=0.25, LW_MASK=0.03,
                               NUM_3D_SAMPLE=3000, SE3_PM_SL1_SCALAR=1.0, SE3_DIST_LOSS=False,

@@ -163,6 +163,10 @@ class deepIM_flownet(object):
         # split-fp16 conv path: fp32-grade products (hi·hi + hi·lo + lo·hi, fp32 accumulation) on the fp16 matrix cores for
         # conv2 … conv6_1; conv1 stays on the fp32 kernel. Within the 1e-4 bar (observed ~1e-6), not bit-exact.
         self.x3_conv = bool(n.get("X3_CONV", False)) and not self.fp16_conv
+        # fp16 conv path with the decoder in the graph: Concat2 / Concat3 stay NHWC fp16, deconv5 / deconv4 on the fp16 matrix cores,
+        # the few-filter predictors from the fp16 concats (csrc/decoder_f16.hip). network.FP16_DECODER = False: the fp32 decoder
+        # fed the encoder's fp16 activations converted to fp32 (the A/B baseline)
+        self.fp16_decoder = self.fp16_conv and self.with_decoder and bool(n.get("FP16_DECODER", True))
         self.nc8 = bool(cfg.network.get('NC8_CONV', True)) if hasattr(cfg.network, 'get') else True
         # the 3x3 stride-1 encoder layers as fp32 Winograd F(2x2,3x3) (csrc/wino.hip) wherever the layer fills the chip: same fp32
         # arithmetic, 2.25x fewer multiplies, a different summation (<= 1e-5 of the layer's range from the direct sum). Only on
@@ -393,9 +397,15 @@ class deepIM_flownet(object):
         A["pose_est"] = ctx.empty((B, 3, 4))
         if self.with_decoder:
             A["flow6"] = ctx.empty((B, 2, 8, 10))
-            A["Concat2"] = ctx.empty((B, 1026, 15, 20))
             A["flow5"] = ctx.empty((B, 2, 15, 20))
-            A["Concat3"] = ctx.empty((B, 770, 30, 40))
+            if self.fp16_decoder:
+                # NHWC fp16 concats, channels padded to a multiple of 8; the pad channels are zeroed here, once, and never written
+                A["Concat2_h"] = ctx.zeros((B, 15, 20, self.CONCAT2_H), dtype=np.float16)
+                A["Concat3_h"] = ctx.zeros((B, 30, 40, self.CONCAT3_H), dtype=np.float16)
+                self._bind_fp16_decoder()
+            else:
+                A["Concat2"] = ctx.empty((B, 1026, 15, 20))
+                A["Concat3"] = ctx.empty((B, 770, 30, 40))
         if self.with_mask_head:
             A["mask_lowres"] = ctx.empty((B, 1, 30, 40))
             A["mask_logits"] = ctx.empty((B, 1, H, W))
@@ -406,6 +416,54 @@ class deepIM_flownet(object):
             A["flow_est"] = ctx.empty((B, 2, H, W))
         ctx.sync()
         return self
+
+    CONCAT2_H, CONCAT3_H = 1032, 776   # Concat2 (1026 channels) / Concat3 (770) as NHWC fp16 records: multiples of 8
+
+    def _bind_fp16_decoder(self):
+        """One-time fp16 weight packs of the decoder and of the few-filter predictors (the fused Concat3 pass: mask_conv3 first,
+        then Convolution3, whichever of them the graph keeps)."""
+        L, h, P = lib.load(), self.ctx.handle, self.params
+        self.packed_dec16 = {}
+        for name, cin, cpad, cout in (("deconv5", 1024, 1024, 512), ("deconv4", 1026, self.CONCAT2_H, 256)):
+            pk = DeviceArray(self.ctx, (L.deepim_deconv_f16_packed_size(cpad, cout) // 2,), dtype=np.float16)
+            lib.deepim_deconv_f16_pack_weights(h, pk, P[name + "_weight"], cin, cpad, cout)
+            self.packed_dec16[name] = pk
+        heads = ([("mask_conv3", "mask_lowres", 1)] if self.with_mask_head else []) + \
+                ([("Convolution3", "flow_lowres", 2)] if self.with_flow_head else [])
+        self.heads16 = heads
+        for key, cin, cpad, convs in (("Convolution1", 1024, 1024, [("Convolution1", "flow6", 2)]),
+                                      ("Convolution2", 1026, self.CONCAT2_H, [("Convolution2", "flow5", 2)]),
+                                      ("heads", 770, self.CONCAT3_H, heads)):
+            if not convs:
+                continue
+            pk = DeviceArray(self.ctx, (L.deepim_fewout_f16_packed_size(cpad) // 2,), dtype=np.float16)
+            w1, n1 = (P[convs[1][0] + "_weight"], convs[1][2]) if len(convs) > 1 else (None, 0)
+            lib.deepim_fewout_f16_pack_weights(h, pk, P[convs[0][0] + "_weight"], convs[0][2], w1, n1, cin, cpad)
+            self.packed_dec16[key] = pk
+
+    def _fewout16(self, key, convs, src, ctotal, hh, ww):
+        A, P = self.act, self.params
+        (n0c, o0, k0), (n1c, o1, k1) = convs[0], (convs[1] if len(convs) > 1 else (None, None, 0))
+        lib.deepim_conv3x3_fewout_f16_forward(self.ctx.handle, A[o0], k0, A[o1] if o1 else None, k1, src, self.packed_dec16[key],
+                                              P[n0c + "_bias"], P[n1c + "_bias"] if n1c else None, self.B, hh, ww, ctotal, ctotal)
+
+    def decoder_fp16(self):
+        """FlowNetS refinement (deepIM_flownet.py:120-167) on NHWC fp16: Concat2 = [conv5_1 | lrelu(deconv5) | upsample_flow6to5 | 0],
+        Concat3 = [conv4_1 | lrelu(deconv4) | upsample_flow5to4 | 0]; flow6 / flow5 fp32 NCHW."""
+        A, h, B, P = self.act, self.ctx.handle, self.B, self.params
+        c2, c3, f = self.CONCAT2_H, self.CONCAT3_H, ctypes.c_float
+        self._fewout16("Convolution1", [("Convolution1", "flow6", 2)], A["conv6_1_h"], 1024, 8, 10)
+        lib.deepim_copy_channels_nhwc_f16(h, A["Concat2_h"], c2, 0, A["conv5_1_h"], 512, 0, 512, B * 15 * 20)
+        lib.deepim_deconv4x4s2_crop_f16_forward(h, A["Concat2_h"], A["conv6_1_h"], self.packed_dec16["deconv5"], P["deconv5_bias"], B,
+                                                1024, 1024, 8, 10, 512, 15, 20, f(SLOPE), c2, 512)
+        lib.deepim_upsample_flow_f16_forward(h, A["Concat2_h"], A["flow6"], P["upsample_flow6to5_weight"],
+                                             P["upsample_flow6to5_bias"], B, 8, 10, 15, 20, c2, 1024)
+        self._fewout16("Convolution2", [("Convolution2", "flow5", 2)], A["Concat2_h"], c2, 15, 20)
+        lib.deepim_copy_channels_nhwc_f16(h, A["Concat3_h"], c3, 0, A["conv4_1_h"], 512, 0, 512, B * 30 * 40)
+        lib.deepim_deconv4x4s2_crop_f16_forward(h, A["Concat3_h"], A["Concat2_h"], self.packed_dec16["deconv4"], P["deconv4_bias"], B,
+                                                c2, c2, 15, 20, 256, 30, 40, f(SLOPE), c3, 512)
+        lib.deepim_upsample_flow_f16_forward(h, A["Concat3_h"], A["flow5"], P["upsample_flow5to4_weight"],
+                                             P["upsample_flow5to4_bias"], B, 15, 20, 30, 40, c3, 768)
 
     # ------------------------------------------------------------------ forward pieces
     def _conv(self, name, src, dst, B, cin, h, w, cout, k, s, p, slope, ctotal=0, coff=0):
@@ -557,6 +615,10 @@ class deepIM_flownet(object):
         """Encoder activation `name` as an NCHW device array (a converted copy when the encoder ran channel-blocked)."""
         a = self.act[name]
         names = [g[0] for g in self.enc_geom]
+        if self.fp16_conv and name in names[:-1]:
+            # the fp16 encoder wrote only the NHWC fp16 tensor: its values as NCHW fp32 (the fp32 decoder's skip inputs)
+            lib.deepim_nhwc_f16_to_nchw_f32(self.ctx.handle, a, self.act[name + "_h"], a.shape[0], a.shape[1], a.shape[2], a.shape[3])
+            return a
         if getattr(self, "act_layout", "nchw") == "x3" and name in names[:-1]:
             lib.deepim_split16_to_nchw_f32(self.ctx.handle, a, self.act[name + "_x"], a.shape[0], a.shape[1], a.shape[2],
                                            a.shape[3], ctypes.c_float(1.0 / self.X3_ACT_SCALE))
@@ -631,6 +693,8 @@ class deepIM_flownet(object):
 
     def decoder(self):
         """FlowNetS refinement (deepIM_flownet.py:120-167)."""
+        if getattr(self, "fp16_decoder", False):
+            return self.decoder_fp16()
         A, h, B = self.act, self.ctx.handle, self.B
         self._conv("Convolution1", A["conv6_1"], A["flow6"], B, 1024, 8, 10, 2, 3, 1, 1, 1.0)
         self._skip_into("Concat2", 1026, "conv5_1", 512, 15 * 20)
@@ -645,10 +709,13 @@ class deepIM_flownet(object):
         A, P, h, B, H, W = self.act, self.params, self.ctx.handle, self.B, self.H, self.W
         # both predictors stream the same 770-channel Concat3: back to back, so that the second finds it where the first left it (the
         # Infinity Cache) instead of behind the 120 MB the first head's upsampling + inverse zoom move (round 6 trace: 62 -> 40 us at B = 32)
-        if self.with_mask_head:  # deepIM_flownet.py:627-666
-            self._conv("mask_conv3", A["Concat3"], A["mask_lowres"], B, 770, 30, 40, 1, 3, 1, 1, 1.0)
-        if self.with_flow_head:  # deepIM_flownet.py:677-713
-            self._conv("Convolution3", A["Concat3"], A["flow_lowres"], B, 770, 30, 40, 2, 3, 1, 1, 1.0)
+        if getattr(self, "fp16_decoder", False):   # fp16 Concat3: both predictors in ONE pass over it
+            self._fewout16("heads", self.heads16, A["Concat3_h"], self.CONCAT3_H, 30, 40)
+        else:
+            if self.with_mask_head:  # deepIM_flownet.py:627-666
+                self._conv("mask_conv3", A["Concat3"], A["mask_lowres"], B, 770, 30, 40, 1, 3, 1, 1, 1.0)
+            if self.with_flow_head:  # deepIM_flownet.py:677-713
+                self._conv("Convolution3", A["Concat3"], A["flow_lowres"], B, 770, 30, 40, 2, 3, 1, 1, 1.0)
         if self.with_mask_head:
             lib.deepim_upsample16_crop_forward(h, A["mask_logits"], A["mask_lowres"], P["mask_upsampling_weight"], B, 1,
                                                30, 40, H, W, 8, 8, ctypes.c_float(1.0))
