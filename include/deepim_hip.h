@@ -676,6 +676,51 @@ int deepim_sgd_mom_update(deepim_ctx* ctx, float* w, float* mom, const float* g,
 int deepim_sgd_mom_update_multi(deepim_ctx* ctx, const unsigned long long* table, int rows, int total_blocks, float lr,
                                 float momentum, float rescale, float clip);
 
+/* ---------------------------- mixed-precision training of the encoder (network.FP16_CONV in the training graph) -- */
+/* csrc/train_f16.hip; DESIGN.md §8f-4c. q(v) = round to fp16 (RNE) and back; S = the loss scale, a power of two. Forward = the
+ * FP16_CONV encoder; the backward of encoder layer l (conv6_1 down to flow_conv1) is
+ *   e_l   = S·(fc6 data gradient + d_dec61) at conv6_1 (fp32), d_l [+ S·skip_l] below (skip: fp32 decoder gradient of conv5_1 / conv4_1)
+ *   dz_l  = q(lrelu'(y_l)·e_l)                          NHWC fp16, lrelu' from the stored fp16 y_l
+ *   db_l  = Σ dz_l / S                                  fp32 sums
+ *   dW_l  = Σ_pix dz_l ⊗ im2col(y_{l-1}) / S             exact fp16 products, fp32 sums, fp32 result
+ *   d_l-1 = q(conv_transpose(dz_l, q(w_l)))              NHWC fp16 (not for flow_conv1)
+ * Loss-scale state (device, 4 x 32 bit): {float scale, float inv_scale, uint overflow, uint good_steps}. Every kernel below reads the
+ * scale from it; a non-finite dz / dW / db sets `overflow` (a non-finite d shows up in the dz it feeds). */
+
+/* dz (B,H,W,C NHWC fp16; may be d) and db (C fp32) of one layer: e = [d (NHWC fp16)] + [S·add (NCHW fp32)] (at least one of them),
+ * dz = q(lrelu'(y)·e) with y the layer's stored NHWC fp16 output, db = Σ dz · inv_scale. C % 64 == 0. Deterministic (fixed slices,
+ * fixed-order sums). */
+int deepim_lrelu_bias_backward_f16(deepim_ctx* ctx, void* dz_nhwc_f16, float* db, const void* d_nhwc_f16, const float* add_nchw,
+                                   const void* y_nhwc_f16, unsigned* state, float slope, int B, int C, int H, int W);
+/* Weight gradient of a conv layer (Cout, Cin, k, k; stride, pad) from its NHWC fp16 input x (B,H,W,Cin_pad; channels >= Cin zero)
+ * and dz (B,Ho,Wo,Cout): a GEMM with M = Cout, N = k*k*Cin_pad, K = B*Ho*Wo on v_mfma_f32_32x32x16_f16 (LDS-staged, operands read
+ * with ds_read_b64_tr_b16). Fixed split-K slices, fixed-order second pass; the epilogue multiplies by inv_scale, raises the
+ * overflow word on a non-finite value and writes the Cin real channels only: layout 0 = natural (Cout,Cin,k,k), 1 = tap-major
+ * (Cout,k*k,Cin), the layout deepim_sgd_mom_update_multi reads with layout word Cin | k*k << 32. Cin_pad % 8 == 0, Cout % 8 == 0. */
+int deepim_conv2d_wgrad_f16(deepim_ctx* ctx, float* dw, const void* x_nhwc_f16, const void* dz_nhwc_f16, unsigned* state, int B, int Cin,
+                            int Cin_pad, int H, int W, int Cout, int k, int stride, int pad, int layout);
+/* fp16 weights of the convolution that is the data gradient of layer (Co_l, Ci_l, k, k), in deepim_conv2d_f16_forward's packed
+ * order (Cout = Ci_l, Cin_pad = Co_l, kernel nky x nkx; deepim_conv_f16_packed_size(Ci_l, Co_l, nky, nkx) bytes): tap (a, b) =
+ * q(layer tap (ky0 + st (nky-1-a), kx0 + st (nkx-1-b))) — st = 1 with the full kernel: transposed and flipped; st = 2: one output
+ * parity class of a stride-2 layer. Co_l % 8 == 0. */
+int deepim_conv_f16_pack_dgrad(deepim_ctx* ctx, void* packed, const float* w_layer, int Co_l, int Ci_l, int k, int ky0, int kx0,
+                               int st, int nky, int nkx);
+/* Data gradient dx (B,Hd,Wd,Ci_l NHWC fp16) = q(conv_transpose(dz, q(w))) of a conv layer (Co_l,Ci_l,k,k; stride 1 or 2, pad) from
+ * dz (B,Ho,Wo,Co_l NHWC fp16) and the layer's fp32 weights. Stride 1: deepim_conv_f16_pack_dgrad + deepim_conv2d_f16_forward
+ * (slope 1, no bias, pad k-1-pad). Stride 2: the four output parity classes of the un-dilated dz (the ideal multiply-adds, as
+ * deepim_conv2d_dgrad_s2), each a stride-1 fp16 convolution into a class buffer whose window is stitched onto its parity positions.
+ * ws: deepim_conv_dgrad_f16_workspace_size bytes (packed weights + class buffer). */
+size_t deepim_conv_dgrad_f16_workspace_size(int B, int Ci_l, int Hd, int Wd, int Co_l, int k, int stride, int pad);
+int deepim_conv2d_dgrad_f16(deepim_ctx* ctx, void* dx_nhwc_f16, const void* dz_nhwc_f16, const float* w_layer, void* ws, int B,
+                            int Ci_l, int Hd, int Wd, int Co_l, int k, int stride, int pad);
+/* deepim_sgd_mom_update_multi (the same kernel) guarded by the loss-scale state: while its overflow word is set no weight and no
+ * momentum moves. Run deepim_amp_scale_update after it. */
+int deepim_sgd_mom_update_multi_amp(deepim_ctx* ctx, const unsigned long long* table, int rows, int total_blocks, float lr,
+                                    float momentum, float rescale, float clip, const unsigned* amp_state);
+/* the loss-scale step after an update: overflow → scale = max(1, scale / 2), good_steps = 0; else good_steps + 1, and at `window`
+ * scale = min(2^24, 2 scale), good_steps = 0. inv_scale follows, the overflow word is cleared. */
+int deepim_amp_scale_update(deepim_ctx* ctx, unsigned* state, int window);
+
 /* ------------------------------------- R-group: re-render between iterations -- */
 /* Replaces Render_Py.render (lib/render_glumpy/render_py_multi.py:101-129: OpenGL draw + glReadPixels +
  * depth linearisation) and the tensor packing that follows it in the batch updater

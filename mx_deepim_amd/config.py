@@ -22,6 +22,11 @@ class AttrDict(dict):
         return AttrDict({k: copy.deepcopy(v, memo) for k, v in self.items()})
 
 
+# Loss-scale defaults of the fp16 training graph, from the gradient magnitudes of the synthetic batch
+FP16_LOSS_SCALE_DEFAULT = 1024.0
+FP16_SCALE_WINDOW_DEFAULT = 1000
+
+
 def default_config():
     cfg = AttrDict()
     cfg.dataset = AttrDict(
@@ -44,7 +49,9 @@ def default_config():
         TRAIN_ITER=True, TRAIN_ITER_SIZE=4,   # yaml :57-58 — refinement iterations inside one training step (module.py:1131-1137)
         X3_CONV=False,     # split-fp16 conv path: fp32-grade accuracy (≈1e-6) on the fp16 matrix cores (not a reference key)
         FP16_CONV=False,   # BASELINE config 5: fp16 conv path (not a reference key; the reference is fp32 only)
-        FP16_DECODER=True,  # with FP16_CONV and the decoder in the graph: decoder + flow / mask predictors in fp16 too (False: fp32 decoder)
+        # with FP16_CONV and the decoder in the test graph: decoder + flow / mask predictors in fp16 too (False: fp32 decoder). The
+        # training graph ignores it: there the decoder and heads always run in fp32 on the fp16 encoder's activations
+        FP16_DECODER=True,
     )
     cfg.train_iter = AttrDict(SE3_PM_LOSS=True, SE3_PM_LOSS_TYPE="L1", LW_PM=0.1, LW_FLOW=0.25, LW_MASK=0.03,
                               NUM_3D_SAMPLE=3000, SE3_PM_SL1_SCALAR=1.0, SE3_DIST_LOSS=False,
@@ -52,7 +59,10 @@ def default_config():
     # experiments/deepim/cfgs/deepim_flownet_LM_SIXD_v1_ape_RFMx4_8epoch.yaml:76-92 (keys the label generation reads)
     # (the yaml also sets MASK_DILATE: True — a random cv2 dilation, i.e. loader-side augmentation, not built here)
     cfg.TRAIN = AttrDict(INIT_MASK="box_gt", FLOW_WEIGHT_TYPE="viz", MASK_DILATE=False,
-                         optimizer="sgd", lr=0.0001, momentum=0.975, wd=0.0005)   # config.py:68-77
+                         optimizer="sgd", lr=0.0001, momentum=0.975, wd=0.0005,   # config.py:68-77
+                         # mixed-precision training (network.FP16_CONV in the training graph; not reference keys): the initial loss
+                         # scale (a power of two) and the number of overflow-free steps after which it doubles
+                         FP16_LOSS_SCALE=FP16_LOSS_SCALE_DEFAULT, FP16_SCALE_WINDOW=FP16_SCALE_WINDOW_DEFAULT)
     cfg.TEST = AttrDict(test_iter=4, FAST_TEST=True, UPDATE_MASK="box_rendered", INIT_MASK="box_rendered")
     cfg.SCALES = [(480, 640)]
     return cfg

@@ -736,9 +736,11 @@ __global__ __launch_bounds__(256) void sgd_mom_kernel(float* __restrict__ w, flo
 }
 
 // every parameter in one launch: row r of the table = {w, mom, g, n, wd bits | first block << 32, Cin | kh*kw << 32 (0: natural g)}; a block finds its row with a
-// ballot over the rows' first blocks
+// ballot over the rows' first blocks. amp (mixed-precision training's loss-scale state, NULL otherwise): nothing moves while its
+// overflow word is set
 __global__ __launch_bounds__(256) void sgd_mom_multi_kernel(const unsigned long long* __restrict__ table, int rows, float lr,
-                                                            float momentum, float rescale, float clip) {
+                                                            float momentum, float rescale, float clip, const unsigned* __restrict__ amp) {
+  if (amp && amp[2]) return;
   const unsigned b = blockIdx.x;
   // row = number of rows that start at or before this block, minus one: every wave counts them 64 at a time with one load + ballot
   // (a serial walk of the table cost the late rows ~40 dependent loads)
@@ -814,7 +816,19 @@ extern "C" int deepim_sgd_mom_update_multi(deepim_ctx* ctx, const unsigned long 
   DI_DEVICE(ctx);
   DI_REQUIRE(rows >= 0 && table != nullptr, "sgd_mom_update_multi: no table");   // (w, mom, g 16-byte aligned: unchecked, device-side data)
   if (rows == 0 || total_blocks <= 0) return 0;
-  hipLaunchKernelGGL(sgd_mom_multi_kernel, dim3(total_blocks), dim3(256), 0, ctx->stream, table, rows, lr, momentum, rescale, clip);
+  hipLaunchKernelGGL(sgd_mom_multi_kernel, dim3(total_blocks), dim3(256), 0, ctx->stream, table, rows, lr, momentum, rescale, clip,
+                     (const unsigned*)nullptr);
+  DI_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int deepim_sgd_mom_update_multi_amp(deepim_ctx* ctx, const unsigned long long* table, int rows, int total_blocks, float lr,
+                                               float momentum, float rescale, float clip, const unsigned* amp_state) {
+  DI_DEVICE(ctx);
+  DI_REQUIRE(rows >= 0 && table != nullptr && amp_state != nullptr, "sgd_mom_update_multi_amp: no table / no loss-scale state");
+  if (rows == 0 || total_blocks <= 0) return 0;
+  hipLaunchKernelGGL(sgd_mom_multi_kernel, dim3(total_blocks), dim3(256), 0, ctx->stream, table, rows, lr, momentum, rescale, clip,
+                     amp_state);
   DI_LAUNCH_CHECK();
   return 0;
 }

@@ -1116,6 +1116,33 @@ __global__ void pack_f16_kernel(_Float16* __restrict__ packed, const float* __re
   packed[i] = (_Float16)v;
 }
 
+// The packed layout above for the convolution that is a layer's DATA GRADIENT, read straight from the layer's raw weights
+// w_layer (Co_l, Ci_l, kh_l, kw_l): Cout = Ci_l, Cin = Co_l (a multiple of 8), an nky x nkx kernel whose tap (a, b) is layer tap
+// (ky0 + st (nky-1-a), kx0 + st (nkx-1-b)) — st = 1: the transposed, flipped kernel; st = 2: one output parity class
+__global__ void pack_f16_dgrad_kernel(_Float16* __restrict__ packed, const float* __restrict__ w, int Co_l, int Ci_l, int kh_l, int kw_l,
+                                      int ky0, int kx0, int st, int nky, int nkx, int nchunk, int BM, long total) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  const int h = (int)(i & 7);
+  const long r1 = i >> 3;
+  const int m = (int)(r1 % BM);
+  const long r2 = r1 / BM;
+  const int o = (int)(r2 & 7);
+  const long r3 = r2 >> 3;
+  const int kc = (int)(r3 % nchunk);
+  const int mt = (int)(r3 / nchunk);
+  int tap, ci0;
+  f16_octet(kc * HOCT + o, Co_l, nky * nkx, &tap, &ci0);
+  const int co_l = ci0 + h, ci_l = mt * BM + m;      // this convolution's input channel = the layer's output channel
+  float v = 0.f;
+  if (ci_l < Ci_l && co_l < Co_l && tap < nky * nkx) {
+    const int a = tap / nkx, b = tap % nkx;
+    const int ky = ky0 + st * (nky - 1 - a), kx = kx0 + st * (nkx - 1 - b);
+    v = w[(((long)co_l * Ci_l + ci_l) * kh_l + ky) * kw_l + kx];
+  }
+  packed[i] = (_Float16)v;
+}
+
 __global__ void build_f16_tab_kernel(int2* __restrict__ tab, int noct, int noct_pad, int Cin_pad, int kh, int kw, int W) {
   const int q = blockIdx.x * blockDim.x + threadIdx.x;
   if (q >= noct_pad) return;
@@ -1616,6 +1643,21 @@ extern "C" int deepim_conv_f16_pack_weights(deepim_ctx* ctx, void* packed, const
   const long total = (long)di_div_up(Cout, BM) * nchunk * HOCT * BM * 8;
   hipLaunchKernelGGL(pack_f16_kernel, dim3(di_div_up(total, 256)), dim3(256), 0, ctx->stream, (_Float16*)packed, w, Cout,
                      Cin, Cin_pad, kh, kw, nchunk, BM, total);
+  DI_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int deepim_conv_f16_pack_dgrad(deepim_ctx* ctx, void* packed, const float* w_layer, int Co_l, int Ci_l, int k, int ky0,
+                                          int kx0, int st, int nky, int nkx) {
+  DI_DEVICE(ctx);
+  DI_REQUIRE((Co_l & 7) == 0 && (st == 1 || st == 2) && ky0 >= 0 && kx0 >= 0 && nky >= 1 && nkx >= 1 && ky0 + st * (nky - 1) < k &&
+                 kx0 + st * (nkx - 1) < k,
+             "conv_f16_pack_dgrad: Co_l % 8 must be 0 and the taps inside the layer's kernel");
+  const int nchunk = f16_chunks(Co_l, nky, nkx);
+  const int BM = f16_bm(Ci_l);
+  const long total = (long)di_div_up(Ci_l, BM) * nchunk * HOCT * BM * 8;
+  hipLaunchKernelGGL(pack_f16_dgrad_kernel, dim3(di_div_up(total, 256)), dim3(256), 0, ctx->stream, (_Float16*)packed, w_layer, Co_l,
+                     Ci_l, k, k, ky0, kx0, st, nky, nkx, nchunk, BM, total);
   DI_LAUNCH_CHECK();
   return 0;
 }

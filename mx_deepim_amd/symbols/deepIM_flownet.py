@@ -137,16 +137,31 @@ class deepIM_flownet(object):
         self.trans_loss_type = str(t.get("TRANS_LOSS_TYPE", "L2"))
         if self.se3_dist_loss and self.trans_loss_type not in ("L2", "smooth_L1", "L1"):
             raise Exception("Does not support small_cfg.TRANS_LOSS_TYPE: {}".format(self.trans_loss_type))      # :258-259
-        if getattr(n, "FP16_CONV", False) or getattr(n, "X3_CONV", False):
-            # encoder_fp16 / encoder_x3 fill only the fp16 / split16 activations; backward() reads the NCHW fp32 ones
-            raise NotImplementedError("training graph runs the fp32 convolutions only (network.FP16_CONV / X3_CONV unset)")
+        if getattr(n, "X3_CONV", False):
+            # encoder_x3 fills only the split16 activations and no backward reads them
+            raise NotImplementedError("training graph runs the fp32 or the fp16 convolutions only (network.X3_CONV unset)")
+        if getattr(n, "FP16_CONV", False):
+            # mixed precision: fp16 encoder forward and backward with a device-resident loss scale
+            tr = cfg.TRAIN
+            self.loss_scale_init = self._check_loss_scale(tr.get("FP16_LOSS_SCALE", 1024.0))
+            self.loss_scale_window = int(tr.get("FP16_SCALE_WINDOW", 1000))
+            if self.loss_scale_window < 1:
+                raise ValueError("TRAIN.FP16_SCALE_WINDOW must be >= 1, got {}".format(self.loss_scale_window))
         self.get_test_symbol_share(cfg)
+        self.fp16_decoder = False  # network.FP16_DECODER governs the test graph only: the training decoder and heads are fp32
         self.is_train = True
         self.nc8 = False          # NCHW activations: what the backward kernels read
         self.two_streams = False  # backward(): weight gradients on a second stream next to the data gradients (False: one stream)
         self.with_mask_head, self.with_flow_head = bool(n.PRED_MASK), bool(n.PRED_FLOW)    # :183, :314
         self.with_decoder = self.with_mask_head or self.with_flow_head
         return self
+
+    @staticmethod
+    def _check_loss_scale(scale):
+        v = float(scale)
+        if not (v >= 1.0 and v <= 2.0 ** 24 and np.isfinite(v) and np.frexp(v)[0] == 0.5):
+            raise ValueError("TRAIN.FP16_LOSS_SCALE must be a power of two in [1, 2^24], got {}".format(scale))
+        return v
 
     def get_test_symbol_share(self, cfg):
         n = cfg.network
@@ -845,12 +860,72 @@ def _train_methods():
         self.ws["d_points"] = ctx.empty((B, 3, num_points))
         self.ws["d_rot_norm"], self.ws["d_trans_est"] = ctx.empty((B, 4)), ctx.empty((B, 3))
         self.ws["d_rot"], self.ws["d_trans"] = ctx.empty((B, 4)), ctx.empty((B, 3))
+        if self.fp16_conv:
+            self._bind_train_fp16()
         if self.se3_dist_loss:            # deepIM_flownet.py:238-262
             A["zoom_trans_gt"], A["rot_loss"] = ctx.empty((B, 3)), ctx.empty((B,))
             A["trans_loss"], A["trans_loss_sum"] = ctx.empty((B, 3, 1)), ctx.empty((1,))
             self.ws["d_rot_norm_dist"], self.ws["d_zoom_trans_dist"] = ctx.empty((B, 4)), ctx.empty((B, 3, 1))
         ctx.sync()
         return self
+
+    def _bind_train_fp16(self):
+        """Buffers of the fp16 encoder backward: two NHWC fp16 gradient buffers (ping-pong, sized for the largest activation), the
+        dgrad workspace (packed weights + parity-class buffer), and the loss-scale state {scale, inv_scale, overflow, good_steps}."""
+        ctx, B = self.ctx, self.B
+        big = max(B * _out_hw(hh, ww, k, s_, p_)[0] * _out_hw(hh, ww, k, s_, p_)[1] * cout
+                  for _n, _ci, hh, ww, cout, k, s_, p_ in self.enc_geom)
+        self.ws["g16a"] = ctx.empty((big,), dtype=np.float16)
+        self.ws["g16b"] = ctx.empty((big,), dtype=np.float16)
+        nb = max(lib.load().deepim_conv_dgrad_f16_workspace_size(B, cin, hh, ww, cout, k, s_, p_)
+                 for _n, cin, hh, ww, cout, k, s_, p_ in self.enc_geom[1:])
+        self.ws["dgrad16"] = ctx.empty(((nb + 1) // 2,), dtype=np.float16)
+        self.amp_state = ctx.empty((4,), dtype=np.uint32)
+        self.set_loss_scale(self.loss_scale_init)
+
+    def set_loss_scale(self, scale, good_steps=0):
+        """Overwrite the device loss-scale state: scale (a power of two), overflow cleared."""
+        v = self._check_loss_scale(scale)
+        st = np.zeros(4, np.uint32)
+        st[:2] = np.array([v, 1.0 / v], np.float32).view(np.uint32)
+        st[3] = int(good_steps)
+        self.amp_state.copyfrom(st)
+
+    def loss_scale(self):
+        """The device loss-scale state as a dict (for logging and tests). The only call of the fp16 training graph that syncs."""
+        st = self.amp_state.asnumpy()
+        f = st[:2].view(np.float32)
+        return {"scale": float(f[0]), "inv_scale": float(f[1]), "overflow": bool(st[2]), "good_steps": int(st[3])}
+
+    def _encoder_backward_f16(self, e61):
+        """Backward of the fp16 encoder, last layer first: dz = q(lrelu'(y)·e) and db in one walk, dW on the fp16
+        matrix cores, d = q(conv_transpose(dz, q(w))) into the other NHWC fp16 buffer. e61: the fp32 NCHW gradient reaching
+        conv6_1 (fc6 data gradient + d_dec61), scaled by S inside the first walk."""
+        A, P, G, W_, h, B = self.act, self.params, self.grad, self.ws, self.ctx.handle, self.B
+        st = self.amp_state
+        skips = {"conv5_1": W_["d_skip5"], "conv4_1": W_["d_skip4"]} if self.with_decoder else {}
+        x_, y_ = W_["g16a"], W_["g16b"]
+        for li in range(len(self.enc_geom) - 1, -1, -1):
+            name, cin_, hh_, ww_, cout_, k_, s_, p_ = self.enc_geom[li]
+            ho_, wo_ = _out_hw(hh_, ww_, k_, s_, p_)
+            last = li == len(self.enc_geom) - 1
+            lib.deepim_lrelu_bias_backward_f16(h, x_, G[name + "_bias"], None if last else x_, e61 if last else skips.get(name),
+                                               A[name + "_h"], st, ctypes.c_float(SLOPE), B, cout_, ho_, wo_)
+            cpad = (cin_ + 7) // 8 * 8
+            if li == 0:      # conv1's input as NHWC fp16 (the training zoom wrote NCHW fp32)
+                lib.deepim_nchw_f32_to_nhwc_f16(h, A["net_input_h"], A["net_input"], B, cin_, hh_, ww_, cpad)
+                src = A["net_input_h"]
+            else:
+                src = A[self.enc_geom[li - 1][0] + "_h"]
+            if name + "_weight" in G.tm:
+                dw, layout = G.tm[name + "_weight"][0], 1
+            else:
+                dw, layout = dict.__getitem__(G, name + "_weight"), 0
+            lib.deepim_conv2d_wgrad_f16(h, dw, src, x_, st, B, cin_, cpad, hh_, ww_, cout_, k_, s_, p_, layout)
+            if li > 0:
+                lib.deepim_conv2d_dgrad_f16(h, y_, x_, P[name + "_weight"], W_["dgrad16"], B, cin_, hh_, ww_, cout_, k_, s_, p_)
+            x_, y_ = y_, x_
+        return G
 
     def forward_train(self, data, label):
         """data: image_observed, image_rendered, mask_observed, mask_rendered [, depth_*], src_pose; label:
@@ -1023,6 +1098,10 @@ def _train_methods():
         ga, gb = W_["ga"], W_["gb"]
         lib.deepim_fc_backward(h, ga, G["fc6_weight"], G["fc6_bias"], W_["g256b"], A["conv6_1"].reshape((B, n6)),
                                P["fc6_weight"], B, n6, 256)
+        if self.fp16_conv:
+            if self.with_decoder:
+                lib.deepim_axpy(h, ga, W_["d_dec61"], c(1.0), B * n6)
+            return self._encoder_backward_f16(ga)
         skips = {"conv5_1": "d_skip5", "conv4_1": "d_skip4"} if self.with_decoder else {}
         # encoder, last layer first: dz = lrelu'(y)·(dy [+ the gradient over the layer's skip connection]) and the bias gradient in
         # one fused walk, in place over dy; dx into the other buffer. (_dgrad can apply the activation gradient of the layer below
@@ -1078,12 +1157,22 @@ def _train_methods():
             dev = self.ctx.empty((len(rows), 6), np.uint64)
             dev.copyfrom(np.array(rows, dtype=np.uint64))
             tab = self._sgd_table = (float(wd), dev, len(rows), block)
-        lib.deepim_sgd_mom_update_multi(h, tab[1], tab[2], tab[3], c(lr), c(momentum), c(rescale_grad), c(clip_gradient or 0.0))
+        if self.fp16_conv:
+            # mixed precision: no parameter moves on a step whose gradients overflowed; then the loss-scale step
+            lib.deepim_sgd_mom_update_multi_amp(h, tab[1], tab[2], tab[3], c(lr), c(momentum), c(rescale_grad), c(clip_gradient or 0.0),
+                                                self.amp_state)
+            lib.deepim_amp_scale_update(h, self.amp_state, self.loss_scale_window)
+            self._repack_f16()
+        else:
+            lib.deepim_sgd_mom_update_multi(h, tab[1], tab[2], tab[3], c(lr), c(momentum), c(rescale_grad), c(clip_gradient or 0.0))
         orders = self._train_pack_orders()
+        enc = {g[0] for g in self.enc_geom}
         for name, shape in self.arg_shape_dict().items():
             if not name.endswith("_weight") or len(shape) != 4 or name.endswith("upsampling_weight"):
                 continue
             base = name[: -len("_weight")]
+            if self.fp16_conv and base in enc:      # the fp16 encoder reads packed_f16 only
+                continue
             if base.startswith("deconv") or base.startswith("upsample_flow"):
                 lib.deepim_deconv_pack_weights(h, self.packed[base], self.params[name], shape[0], shape[1])
             else:
@@ -1091,6 +1180,20 @@ def _train_methods():
                                                 orders.get(base, 3))
         if self.B > self.FC6_PLAIN_MAX_BATCH:      # small batches read fc6's raw weights (_fc6)
             lib.deepim_fc_pack_weights(h, self.packed["fc6"], self.params["fc6_weight"], 256, 1024 * 8 * 10)
+
+    def _repack_f16(self):
+        """The fp16 weights the fp16 encoder reads (packed_f16, conv1's patch-kernel pack included), from the fp32 masters."""
+        h, P = self.ctx.handle, self.params
+        cin = self.cin
+        for name, cout, k, s_, p_ in ENCODER:
+            lib.deepim_conv_f16_pack_weights(h, self.packed_f16[name], P[name + "_weight"], cout, cin, (cin + 7) // 8 * 8, k, k)
+            cin = cout
+        if "conv1_patch" in self.packed_f16:
+            w1 = P[ENCODER[0][0] + "_weight"]
+            if self.cin == 10:
+                lib.deepim_conv1_f16_c10_pack_weights(h, self.packed_f16["conv1_patch"], w1)
+            else:
+                lib.deepim_conv1_x3_pack_weights(h, self.packed_f16["conv1_patch"], w1, ctypes.c_float(1.0))
 
     def train_step(self, data, label, updater, iters=None, lr=None, wd=None, momentum=None, on_iter=None):
         """ONE training step as the reference runs it (deepim/core/module.py:1131-1137 with network.TRAIN_ITER_SIZE = 4, yaml
@@ -1134,7 +1237,8 @@ def _train_methods():
                     "Convolution3": (770, 30, 40, 2, 3, 1, 1), "mask_conv3": (770, 30, 40, 1, 3, 1, 1)})
         return {n: order(h, B, cin, hh, ww, cout, k, k, s_, p_) for n, (cin, hh, ww, cout, k, s_, p_) in geo.items()}
 
-    return dict(bind_train=bind_train, forward_train=forward_train, _dgrad=_dgrad,
+    return dict(bind_train=bind_train, _bind_train_fp16=_bind_train_fp16, set_loss_scale=set_loss_scale, loss_scale=loss_scale,
+                _encoder_backward_f16=_encoder_backward_f16, _repack_f16=_repack_f16, forward_train=forward_train, _dgrad=_dgrad,
                 _small_conv_backward=_small_conv_backward, _head_conv_backward=_head_conv_backward,
                 _deconv_backward=_deconv_backward, _decoder_backward=_decoder_backward, backward=backward, update=update, train_step=train_step,
                 _train_pack_orders=_train_pack_orders)

@@ -1,5 +1,6 @@
 """Dev probe: time one training-style iteration (forward_train + backward + update) and its pieces.
-usage: bench_train.py [B] [heads] [step4] [json]   — `heads` adds the refinement decoder with the flow and mask losses; `step4`
+usage: bench_train.py [B] [heads] [fp16] [step4] [json]   — `heads` adds the refinement decoder with the flow and mask losses; `fp16`
+trains with network.FP16_CONV (fp16 encoder forward and backward, loss scaling); `step4`
 times the reference's whole training step instead (module.py:1131-1137: TRAIN_ITER_SIZE = 4 iterations with the device batch
 updater — RT_transform, re-render, calc_RT_delta, K·T, lib/flow_c labels, depth > 0.2 mask — between them: net.train_step);
 `json` prints one JSON line instead of the sentence (bench.py's other_configs["training_iteration_*" / "training_step_x4_*"])."""
@@ -15,6 +16,9 @@ ctx = Context.get(0)
 d = synthetic.make_batch(B, seed=910, n_frames=1)
 HEADS = "heads" in sys.argv[2:]
 cfg = default_config(); cfg.network.PRED_FLOW = cfg.network.PRED_MASK = HEADS
+FP16 = "fp16" in sys.argv[2:]
+cfg.network.FP16_CONV = FP16
+DTYPE = "f16" if FP16 else "f32"
 net = deepIM_flownet().get_symbol(cfg, is_train=True)
 net.bind_train(ctx, B, net.init_weights(cfg, seed=91))
 gt = (d["depth_gt_observed"] > 0).astype(np.float32)
@@ -59,7 +63,7 @@ if STEP4:
     import json
     rec = {"value": 1e3 / step_ms, "unit": "training steps/s (x%d iterations: forward + backward + SGD step each, device batch updater between them, batch %d)" % (NIT, B),
            "step_ms": step_ms, "iterations_per_s": NIT * 1e3 / step_ms, "pairs_per_s": B * 1e3 / step_ms,
-           "batch_updater_ms_per_call": upd_ms, "batch_updater_share": (NIT - 1) * upd_ms / step_ms, "dtype": "f32",
+           "batch_updater_ms_per_call": upd_ms, "batch_updater_share": (NIT - 1) * upd_ms / step_ms, "dtype": DTYPE,
            "workload": "deepim/core/module.py:1131-1137 with TRAIN_ITER_SIZE = %d, %s, 480x640, synthetic pairs, closed loop on the device "
                        "(RT_transform, HIP re-render, calc_RT_delta, K·T + flow labels, mask)" % (
                            NIT, "full graph: encoder + refinement decoder + flow and mask heads + point-matching loss" if HEADS else
@@ -84,10 +88,12 @@ if "json" in sys.argv[2:]:
     import json
     print(json.dumps({"value": 1e3 / (fwd + bwd + upd), "unit": "training iterations/s (forward + backward + SGD step, batch %d)" % B,
                       "forward_ms": fwd, "backward_ms": bwd, "update_repack_ms": upd, "pairs_per_s": B * 1e3 / (fwd + bwd + upd),
-                      "backward_tflops_on_ideal_flops": 2 * gf / bwd / 1e9, "dtype": "f32",
+                      "backward_tflops_on_ideal_flops": 2 * gf / bwd / 1e9, "dtype": DTYPE,
                       "workload": "SURVEY 8f-4: one training-style iteration, %s, 480x640, synthetic pairs" % (
                           "full graph: encoder + refinement decoder + flow and mask heads + point-matching loss" if HEADS else
                           "pose branch: encoder + fc + point-matching loss")}))
     sys.exit(0)
-print(("heads " if HEADS else "pose ") + "B=%d: forward %.2f ms (%.0f TF), backward %.2f ms (%.0f TF on 2x forward FLOPs), update+repack %.2f ms; %.1f training iterations/s (pairs/s %.0f)"
+if FP16:
+    print("loss scale after the run: %s" % net.loss_scale())
+print(("heads " if HEADS else "pose ") + ("fp16 " if FP16 else "") + "B=%d: forward %.2f ms (%.0f TF), backward %.2f ms (%.0f TF on 2x forward FLOPs), update+repack %.2f ms; %.1f training iterations/s (pairs/s %.0f)"
       % (B, fwd, gf / fwd / 1e9, bwd, 2 * gf / bwd / 1e9, upd, 1e3 / (fwd + bwd + upd), B * 1e3 / (fwd + bwd + upd)))
