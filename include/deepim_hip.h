@@ -59,8 +59,7 @@ void* deepim_stream(deepim_ctx* ctx);           /* hipStream_t, for interop */
  * "conv_xcd_swizzle": 1 (default) = XCD-aware tile order, 0 = plain block order.
  * "conv_autotune": 0 (default) = the split-K factor of an under-filled conv grid comes from a deterministic cost
  * model (same geometry → same summation order in every run, process and rank); 1 = on the first call of a conv
- * geometry, time a few split-K factors and keep the fastest (plans then depend on timing noise). "conv_tile256": 1 = 256x128 tiles on 512-thread blocks when
- * Cout % 256 == 0 (default 0: measured no faster than 128x128). "wgrad_lds": 1 (default) = LDS-staged weight-gradient kernel
+ * geometry, time a few split-K factors and keep the fastest (plans then depend on timing noise). "wgrad_lds": 1 (default) = LDS-staged weight-gradient kernel
  * (and the few-filter stream kernel for Cout <= 4), 0 = the round-2 register-fed kernel; "dgrad_group": 1 (default) = the four
  * parity classes of deepim_conv2d_dgrad_s2 share one launch, 0 = class by class (A/B measurements). "wino_two_wave": 0 (default) =
  * the Winograd layers on the one-wave-per-SIMD kernel (16 positions per wave), 1 = the two-wave form (8 positions per wave, LDS
@@ -86,7 +85,8 @@ void* deepim_stream(deepim_ctx* ctx);           /* hipStream_t, for interop */
  * stride-1 pad-1 convolutions with Cout <= 4 and W % 4 == 0 (flow / mask predictors) compute four pixels per lane, 0 = one;
  * "conv_fewout_blocks": the grid those few-filter convolutions slice their input channels for — 0 (default) = ~1024 blocks where the pixels
  * alone give >= 32 blocks, ~512 below (measured, profiles/r06_heads.md), n = about n blocks; "conv_fewout_minc": the smallest channel slice
- * (default 32). Unknown names fail. */
+ * (default 32). "f16_dev_flags": 0 (default), or 16 = the fp16 convolutions never take the ping-pong kernel, all LDS-DMA layers run on
+ * the 4-wave kernel (same products in the same order: the tests' bit-exact reference); other values fail. Unknown names fail. */
 int deepim_set_option(deepim_ctx* ctx, const char* name, int value);
 /* *value = the current setting of an option deepim_set_option knows (host code that has to follow the context's kernel selection —
  * e.g. which weight-gradient layout the training graph registers — reads it here). Unknown names fail. */

@@ -18,11 +18,8 @@ constexpr int DI_STATUS_GROUP_RANGE = 2;      // GroupPicker index out of range
 constexpr int DI_STATUS_X3_SATURATED = 8;     // split-fp16 conv: a value left fp16's range after scaling and was clamped (results invalid)
 constexpr int DI_STATUS_MASK_BOX_EMPTY = 4;   // mask_box / fused re-render: empty mask (data_pair.py:98 np.min raises)
 
-// deepim_set_option(ctx, "f16_dev_flags", bits): measurement switches of csrc/conv_f16.hip
-constexpr int DI_F16_TN4 = 1;      // 128x128 wave tiles, one block per CU (the round-2 starting point)
-constexpr int DI_F16_W8 = 2;       // one 8-wave block per CU on a 256x256 tile
-constexpr int DI_F16_NO_TAIL = 4;  // no tail split of the under-filled last round
-constexpr int DI_F16_NO_DMA = 8;   // register-staged kernel instead of the LDS-DMA ring
+// deepim_set_option(ctx, "f16_dev_flags", 0 or DI_F16_NO_PP): the 4-wave kernel of csrc/conv_f16.hip is the ping-pong kernel's
+// bit-exact reference in the tests
 constexpr int DI_F16_NO_PP = 16;   // no ping-pong kernel (round 4): every LDS-DMA layer on the 4-wave kernel, as in round 3
 #ifndef DI_PP_MIN_TILES
 #define DI_PP_MIN_TILES 64
@@ -61,11 +58,9 @@ struct deepim_ctx {
   std::vector<ConvTab> conv_tabs;
   std::vector<ConvPlan> conv_plans;
   int conv_direct;    // LDS-free register-fed kernel for 128x128-tiled convs: 0 off, 1 (default) unless conv_max_split == 1, 2 always
-  int fc_slices;        // dev: K slices of the FC GEMV (0 = enough for ~1024 blocks)
   int conv_tail_split;  // 1: let the autotuner consider tail splits (default 0, see launch_conv)
   int conv_force_plan;  // dev: 0 = off, n > 0 = uniform split-K n, n < 0 = tail split with -n slices
   int conv_tail_slots;  // resident 128x128 blocks of the LDS-free kernel on the whole chip (256 CUs x 4): round size for the tail split
-  int conv_tile256;   // 1: 256x128 tiles (512-thread blocks) when Cout % 256 == 0 (default 0)
   int conv_autotune;  // 1: time split-K candidates on the first call of a geometry (default 0: deterministic cost-model plan)
   int conv_max_split;  // 0 auto, 1 off, n cap
   int conv_xcd_swizzle;  // 1: XCD-aware tile order (default), 0: plain
@@ -84,7 +79,7 @@ struct deepim_ctx {
   void* wino_counters;   // arrival counters of the Winograd kernels' in-kernel finish, one per tile block (deepim_create; zero between launches)
   int wino_persistent;   // 1 (default): the shared-transform kernel's grid is one block per resident slot, each walking its share of the tiles; 0: one block per tile block
   int wino_two_wave;     // 0 (default): Winograd layers on the one-wave 16-position kernel; 1: the two-waves-per-SIMD kernel (measured slower on the big layers)
-  int f16_dev_flags;     // dev: DI_F16_* bits — alternative tilings of the fp16 / x3 conv kernels (default 0)
+  int f16_dev_flags;     // 0 (default) or DI_F16_NO_PP: fp16 layers stay off the ping-pong kernel
   std::vector<const void*> attr_done;  // hipFuncSetAttribute groups already applied on THIS context's device (di_attr_needed)
 };
 

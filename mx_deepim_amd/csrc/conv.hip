@@ -125,13 +125,12 @@ __device__ __forceinline__ bool remap_pixel(const Remap& m, int r, int hw, long&
   return true;
 }
 
-template <int BM, int BN, int MODE, int NT = 256>
-__global__ __launch_bounds__(NT, 4) void conv_mfma_kernel(ConvParams p) {
-  constexpr int WM = BM / (NT / 128), WN = BN / 2;  // wave tile: waves form a (NT/128) x 2 grid over the block tile
+template <int BM, int BN, int MODE>
+__global__ __launch_bounds__(256, 4) void conv_mfma_kernel(ConvParams p) {
+  constexpr int WM = BM / 2, WN = BN / 2;  // wave tile: the 4 waves form a 2 x 2 grid over the block tile
   constexpr int TM = WM / 32, TN = WN / 32;
-  constexpr int NG = BM / GRAN;            // weight granules per block
-  constexpr int NGT = NG * 256 / NT;       // ... of which each thread copies this many (one dwordx4 each)
-  constexpr int EB = KT * BN / NT;         // gathered elements per thread per chunk (consecutive k rows)
+  constexpr int NG = BM / GRAN;            // weight granules per block, each thread copies one dwordx4 of each
+  constexpr int EB = KT * BN / 256;        // gathered elements per thread per chunk (consecutive k rows)
   constexpr int KS = KT / 2;               // MFMA k-steps per chunk
   constexpr int MPS = TM * TN;             // MFMAs per k-step
   constexpr int Q = KS * MPS;              // issue slots per chunk (one per MFMA)
@@ -216,7 +215,9 @@ __global__ __launch_bounds__(NT, 4) void conv_mfma_kernel(ConvParams p) {
   const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
       (void*)((const char*)p.in - p.pad_bytes), 0, (int)(p.in_bytes + (unsigned)p.pad_bytes), 0x00020000);
 
-  const int gt0 = (tid >> 8) * NGT, ta = tid & 255;   // this thread's first granule and its dwordx4 slot in the slab
+  // this thread's first granule and its dwordx4 slot in the slab; gt0 is 0 in a 256-thread block, but written without the
+  // shift the compiler schedules this kernel differently
+  const int gt0 = (tid >> 8) * NG, ta = tid & 255;
   const float* wblk = p.wp + ((long)mb * NG + gt0) * p.nchunk * (KT * GRAN) + ta * 4;
   if (MODE == MODE_DECONV) wblk += (long)zz * p.ngran * p.nchunk * (KT * GRAN);
   const int kc_begin = split * p.chunks_per_split;
@@ -261,9 +262,9 @@ __global__ __launch_bounds__(NT, 4) void conv_mfma_kernel(ConvParams p) {
 #pragma unroll
     for (int e = 0; e < EB; ++e) GATHER(e, tq)
     ALOAD0(kc_begin)
-    if (NGT == 2) ALOAD1(kc_begin)
+    if (NG == 2) ALOAD1(kc_begin)
     *reinterpret_cast<float4*>(&As[0][a_st]) = areg0;
-    if (NGT == 2) *reinterpret_cast<float4*>(&As[0][a_st + GRAN]) = areg1;
+    if (NG == 2) *reinterpret_cast<float4*>(&As[0][a_st + GRAN]) = areg1;
 #pragma unroll
     for (int e = 0; e < EB; ++e) Bs[0][b_st + e * BN] = BSEL(e);
     const int k1 = min(kc_begin + 1, kc_last);
@@ -273,7 +274,7 @@ __global__ __launch_bounds__(NT, 4) void conv_mfma_kernel(ConvParams p) {
 #pragma unroll
     for (int e = 0; e < EB; ++e) GATHER(e, tq)
     ALOAD0(k1)
-    if (NGT == 2) ALOAD1(k1)
+    if (NG == 2) ALOAD1(k1)
     const int2* tp2 = p.tab + min(kc_begin + 2, kc_last) * KT + krow0;
 #pragma unroll
     for (int e = 0; e < EB; ++e) tq[e] = tp2[e];
@@ -326,8 +327,8 @@ __global__ __launch_bounds__(NT, 4) void conv_mfma_kernel(ConvParams p) {
         }
         if (q == (ROOMY ? 3 : 2)) *reinterpret_cast<float4*>(asn) = areg0;
         if (q == (ROOMY ? 7 : 2)) ALOAD0(kg)
-        if (NGT == 2 && q == (ROOMY ? 11 : 6)) *reinterpret_cast<float4*>(asn + GRAN) = areg1;
-        if (NGT == 2 && q == (ROOMY ? 15 : 6)) ALOAD1(kg)
+        if (NG == 2 && q == (ROOMY ? 11 : 6)) *reinterpret_cast<float4*>(asn + GRAN) = areg1;
+        if (NG == 2 && q == (ROOMY ? 15 : 6)) ALOAD1(kg)
         if (q == Q - 1) {
 #pragma unroll
           for (int e = 0; e < EB; ++e) tq[e] = tpn[e];
@@ -1516,10 +1517,9 @@ int plan_ksplit(long tiles, int nchunk) {
   }
   return best_s;
 }
-TileChoice choose_tile(const deepim_ctx* ctx, int Cout, long npix, int nchunk, int classes, bool wide64 = false) {
+TileChoice choose_tile(int Cout, long npix, int nchunk, int classes, bool wide64 = false) {
   int bm = 128, bn = 128;
   if (Cout <= 64) { bm = 64; bn = (wide64 || npix >= 256L * 1024) ? 256 : 128; }   // wide64: the only 64-row LDS-free shape
-  else if (ctx->conv_tile256 && Cout % 256 == 0) bm = 256;   // 8-wave block: every gathered activation feeds 256 channels
   const long tiles = (long)di_div_up(Cout, bm) * di_div_up(npix, bn) * classes;
   return {bm, bn, plan_ksplit(tiles, nchunk), 0};
 }
@@ -1579,8 +1579,6 @@ int launch_one(deepim_ctx* ctx, ConvParams p, int classes, TileChoice t) {
     hipLaunchKernelGGL(conv_direct_kernel<2>, grid, dim3(256), 0, ctx->stream, p);
   else if (MODE == MODE_CONV && t.bm == 64 && t.bn == 256 && p.tab2 != nullptr)
     hipLaunchKernelGGL(conv_direct_kernel<1>, grid, dim3(256), 0, ctx->stream, p);
-  else if (t.bm == 256)
-    hipLaunchKernelGGL((conv_mfma_kernel<256, 128, MODE, 512>), grid, dim3(512), 0, ctx->stream, p);
   else if (t.bm == 128)
     hipLaunchKernelGGL((conv_mfma_kernel<128, 128, MODE>), grid, dim3(256), 0, ctx->stream, p);
   else if (t.bn == 256)
@@ -1607,9 +1605,9 @@ int launch_one(deepim_ctx* ctx, ConvParams p, int classes, TileChoice t) {
 // idempotent, so the trial launches only rewrite `out`.
 template <int MODE>
 int launch_conv(deepim_ctx* ctx, const ConvParams& p, int classes) {
-  TileChoice t = choose_tile(ctx, p.Cout, p.npix, p.nchunk, classes, p.out_nc8 != 0);
+  TileChoice t = choose_tile(p.Cout, p.npix, p.nchunk, classes, p.out_nc8 != 0);
   const ConvPlanKey key = {MODE, p.B, p.Cin, p.H, p.W, p.Cout, p.Ho, p.Wo, p.stride, p.pad, p.nchunk,
-                           ctx->conv_tail_split * 8 + ctx->conv_tile256 * 4 + (p.tab2 != nullptr ? ctx->conv_direct : 0) + 1024 * (p.in_nc8 * 2 + p.out_nc8),
+                           ctx->conv_tail_split * 8 + (p.tab2 != nullptr ? ctx->conv_direct : 0) + 1024 * (p.in_nc8 * 2 + p.out_nc8),
                            0};
   if (ctx->conv_autotune && ctx->conv_max_split != 1) {
     bool found = false;
@@ -1780,8 +1778,7 @@ extern "C" int deepim_conv_weight_order(deepim_ctx* ctx, int B, int Cin, int H, 
   if (Cout <= 4 && ctx->conv_max_split != 1) return 1;
   const bool direct = ctx->conv_direct == 2 || (ctx->conv_direct == 1 && ctx->conv_max_split != 1);
   if (!(direct && (Cin & 1) == 0 && (Cout > 64 || npix >= 256L * 1024))) return 1;
-  if (Cout <= 64) return 2;                                   // 64x256 tiles of the register-fed kernel
-  return (ctx->conv_tile256 && Cout % 256 == 0) ? 1 : 2;      // 256-row tiles exist in the LDS kernel only
+  return 2;                                                   // 128x128 or 64x256 tiles of the register-fed kernel
 }
 
 extern "C" int deepim_conv2d_forward(deepim_ctx* ctx, float* out, const float* in, const float* packed_w,
@@ -1973,7 +1970,7 @@ static int conv2d_dgrad_s2_impl(deepim_ctx* ctx, float* dx, const float* dz, con
   const int* ord = L.ord;
   const bool direct = ctx->conv_direct == 2 || (ctx->conv_direct == 1 && ctx->conv_max_split != 1);
   const size_t in_bytes = (size_t)B * Co_l * Ho * Wo * 4;
-  const bool grouped = fw != nullptr || (ctx->dgrad_group && direct && (Co_l & 1) == 0 && !(ctx->conv_tile256 && Ci_l % 256 == 0) &&
+  const bool grouped = fw != nullptr || (ctx->dgrad_group && direct && (Co_l & 1) == 0 &&
                                          in_bytes + (size_t)(4 * Wo + 4) * 4 < 0x7fffffffUL);
   // tile of the register-fed kernel: 128 x 128, or 64 rows x 256 pixels when dx has at most 64 channels (conv2's data gradient)
   const int bm = Ci_l <= 64 ? 64 : 128, bn = Ci_l <= 64 ? 256 : 128;
@@ -2274,7 +2271,7 @@ extern "C" int deepim_deconv4x4s2_crop_forward(deepim_ctx* ctx, float* out, cons
   // 64-77 TFLOP/s (profiles/r03_heads_b4_iteration_trace.txt). Not in the bit-exact configuration (conv_max_split = 1 keeps the
   // canonical (ci,ky,kx) order of the LDS kernel, as for the encoder).
   const bool direct = ctx->conv_direct == 2 || (ctx->conv_direct == 1 && ctx->conv_max_split != 1);
-  if (direct && crop_y == 1 && crop_x == 1 && deconv_direct_ok(Cin, Cout) && !ctx->conv_tile256 &&
+  if (direct && crop_y == 1 && crop_x == 1 && deconv_direct_ok(Cin, Cout) &&
       (size_t)B * Cin * H * W * 4 + (size_t)(4 * W + 4) * 4 < 0x7fffffffUL) {
     const S2Forward fw = {H, W, bias, slope, out_ctotal > 0 ? out_ctotal : Cout, out_coff, true};
     return conv2d_dgrad_s2_impl(ctx, out, in, nullptr, const_cast<float*>(packed_w) + deconv_lds_pack_floats(Cin, Cout), B, Cout, Ho, Wo,

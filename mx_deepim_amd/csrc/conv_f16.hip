@@ -37,15 +37,9 @@ constexpr int HOCT = 8;   // octets per chunk (K chunk = 8 octets x 8 halves = 6
 //   Cout % 256 != 0 (conv2)   waves 2x2, wave tile 2x4: 128 x 256 block
 //   Cout % 256 == 0           waves 2x2, wave tile 4x4: 256 x 256 block (256 accumulator registers, one wave per SIMD)
 inline int f16_bm(int Cout) { return Cout <= 64 ? 64 : ((Cout & 255) == 0 ? 256 : 128); }
-// DMA kernel: 128x64 wave tiles, two blocks per CU (DEEPIM_F16_TN4=1 restores the 128x128 wave tiles, one block per CU)
-// Dev switches live in the context (deepim_set_option "f16_dev_flags", DI_F16_*), never in the process environment:
-// tiling decides the summation order, and every rank must take the same plan.
-inline int f16_bn(int Cout, bool dma, int dev) {
-  if (!dma) return 256;
-  const bool tn4 = (dev & DI_F16_TN4) != 0;
-  if (f16_bm(Cout) == 256) return (tn4 || (dev & DI_F16_W8)) ? 256 : 128;
-  return f16_bm(Cout) == 128 ? (tn4 ? 512 : 256) : 256;
-}
+// DMA kernel: 128x64 wave tiles, two blocks per CU. Tiling decides the summation order, so it follows from the geometry
+// alone: every rank takes the same plan.
+inline int f16_bn(int Cout, bool dma) { return dma && f16_bm(Cout) == 256 ? 128 : 256; }
 
 struct ConvF16Params {
   const void* in;       // NHWC fp16 (B,H,W,Cin)
@@ -275,30 +269,27 @@ __global__ __launch_bounds__(256, 1) void conv_f16_kernel(ConvF16Params p) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// 256x256 tiles with LDS-DMA and a 4-stage ring (layers with Cout % 256 == 0 and Cin_pad % 64 == 0: conv3 … conv6_1).
+// LDS-DMA kernel (layers with Cout >= 128 and Cin_pad % 64 == 0 below the ping-pong kernel's grid size, and the x3 layers).
 // Register staging keeps exactly one K chunk of loads in flight per wave and every chunk then ends in "wait for the loads,
 // ds_write, barrier": measured, the kernel above spends about half its time in that wait (MFMAs removed: 20 % faster; loads
 // issued but never waited for: as fast as with no loads at all). Here the loads go global → LDS directly
 // (`buffer_load_dwordx4 … lds`, 1 KB per wave-instruction, hardware zero fill for padding taps), no staging registers and
-// no ds_write pass; a K chunk is 32 (4 octets: 16 KB of weights + 16 KB of activations), the ring holds 4 chunks, so three
-// chunks (3072 MFMA cycles) of loads are in flight behind the one being multiplied. The DMA is issued from inline asm:
+// no ds_write pass; a K chunk is 32 (4 octets of BM weight rows + BN pixels), the ring holds NSTAGE chunks, so NSTAGE - 1
+// chunks of loads are in flight behind the one being multiplied. The DMA is issued from inline asm:
 // through the builtin the compiler cannot tell the ring stages apart and drains vmcnt(0) before every ds_read.
-//   weights     stage image [octet 0..3][row 0..255][8 halves]  = 16 KB contiguous in the packed buffer (chunk32 c at c·16 KB)
-//   activations stage image [pixel 0..255][slot 0..3][8 halves], slot = octet ^ ((pixel >> 2) & 3): the DMA writes lanes
+//   weights     stage image [octet 0..3][row 0..BM-1][8 halves] = BM·64 B contiguous in the packed buffer (chunk32 c at c·BM·64 B)
+//   activations stage image [pixel 0..BN-1][slot 0..3][8 halves], slot = octet ^ ((pixel >> 2) & 3): the DMA writes lanes
 //               linearly, so the swizzle is applied to WHICH 16 bytes of the pixel's 64-byte run a lane fetches; a
 //               ds_read_b128 lane group (16 pixels, one octet) then covers all 64 banks once.
-// WGM x WGN waves of 128x128 (4x4 MFMA tiles) each: <2,2> = 256x256 block, 4 ring stages of 32 KB; <1,4> = 128x512 block for
-// Cout == 128 (conv2), 3 stages of 40 KB.
-template <int WGM, int WGN, int NSTAGE, bool X3 = false, int TN = 4>
-__global__ __launch_bounds__(WGM * WGN * 64, TN == 2 ? 2 : 1) void conv_f16_dma_kernel(ConvF16Params p) {
-  // TN = 2: 128x64 wave tiles (128 accumulator registers) so that two blocks share a CU, i.e. two waves per SIMD — one wave
-  // alone issues MFMAs at 71 % of the pipe's rate (tools/mfma_f16_probe.hip) and nothing covers its waits
-  // WGM * WGN = 8 (512 threads, TN = 2): eight 128x64 wave tiles share ONE 256x256 LDS image — two waves per SIMD as with two
-  // 4-wave blocks, but a third fewer DMA bytes per MFMA and a 4-stage ring
-  constexpr int BM = WGM * 128, BN = WGN * TN * 32, TM = 4, NW = WGM * WGN;
+// WGM x WGN = 4 waves of 128x64 (4x2 MFMA tiles) each: <2,2> = 256x128 block, <1,4> = 128x256 block for Cout == 128 (conv2),
+// 3 ring stages of 24 KB. 128 accumulator registers let two blocks share a CU, i.e. two waves per SIMD — one wave alone issues
+// MFMAs at 71 % of the pipe's rate (tools/mfma_f16_probe.hip) and nothing covers its waits.
+template <int WGM, int WGN, int NSTAGE, bool X3 = false>
+__global__ __launch_bounds__(256, 2) void conv_f16_dma_kernel(ConvF16Params p) {
+  constexpr int BM = WGM * 128, TN = 2, BN = WGN * TN * 32, TM = 4, NW = 4;
   constexpr int NPA = BM / (16 * NW), NPB = BN / (16 * NW), NP = NPA + NPB;   // 1 KB DMA pieces per wave per chunk: weights, activations
   constexpr int STAGE = (BM + BN) * 4;     // h8 per stage: BM*4 weights + BN*4 activations
-  static_assert((NW == 4 || NW == 8) && NPA >= 1 && NPB >= 1 && NSTAGE * STAGE * 16 <= 160 * 1024, "tile shape");
+  static_assert(WGM * WGN == NW && NPA >= 1 && NPB >= 1 && NSTAGE * STAGE * 16 <= 160 * 1024, "tile shape");
   extern __shared__ __attribute__((aligned(16))) h8 smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -474,7 +465,7 @@ __global__ __launch_bounds__(WGM * WGN * 64, TN == 2 ? 2 : 1) void conv_f16_dma_
 #undef DMA
 
   float amax = 0.f;
-  if constexpr (TN == 2) if (tail_slot >= 0 || p.partial) {
+  if (tail_slot >= 0 || p.partial) {
     // Raw fp32 partial sums (a tail slice: tile-local [pixel][BM channels]; a split-K slice: [slice][pixel][Cout]) through the
     // same LDS staging as the final tiles below: a pixel's 128 channels of this wave are 512 contiguous bytes
     constexpr int PITCH = 512 + 16;
@@ -505,25 +496,13 @@ __global__ __launch_bounds__(WGM * WGN * 64, TN == 2 ? 2 : 1) void conv_f16_dma_
     }
     return;
   }
-  if (tail_slot >= 0) {   // raw fp32 partial sums of a tail slice, tile-local [pixel][channel]
-    float* tp = p.tail_partial + (long)tail_slot * (BM * BN);
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int g = 0; g < 4; ++g)
-          *reinterpret_cast<float4*>(tp + (wn0 + j * 32 + lcol) * BM + wm0 + i * 32 + 8 * g + 4 * lrow) =
-              make_float4(acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]);
-    return;
-  }
-  if constexpr (TN == 2) if (!p.partial && (p.Cout & 127) == 0) {
+  if ((p.Cout & 127) == 0) {
     // Final output, whole 128-channel wave tiles: stage the tile through LDS (the ring is free once every wave has left the
     // K loop) so that a wave writes each pixel's run of its 128 channels — 256 B of fp16, 512 B of split16 records — as
     // contiguous 16-byte pieces, 1 KB per store instruction. The direct form below (8-byte quads, 64 different cache lines
     // per instruction) cost 10-12 % of the kernel (measured with the stores removed).
     constexpr int RUN = X3 ? 512 : 256, PITCH = RUN + 16, CPP = RUN / 16, PPI = 64 / CPP;
-    static_assert(4 * 32 * PITCH <= NSTAGE * STAGE * 16 || NW != 4, "staging area");
+    static_assert(4 * 32 * PITCH <= NSTAGE * STAGE * 16, "staging area");
     __syncthreads();
     char* stage = reinterpret_cast<char*>(smem) + wave * (32 * PITCH);
     const int cw0 = mb * BM + wm0;                                     // first channel of this wave's tile
@@ -582,16 +561,12 @@ __global__ __launch_bounds__(WGM * WGN * 64, TN == 2 ? 2 : 1) void conv_f16_dma_
     const long op = n0 + wn0 + j * 32 + lcol;
     if (op >= p.npix) continue;
     _Float16* orow = p.out + op * p.Cout;
-    float* prow = p.partial ? p.partial + ((long)split * p.npix + op) * p.Cout : nullptr;
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const int co0 = mb * BM + wm0 + i * 32 + 8 * g + 4 * lrow;
-        if (co0 < p.Cout && prow) {
-          *reinterpret_cast<float4*>(prow + co0) =
-              make_float4(acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]);
-        } else if (co0 < p.Cout && X3) {   // split16 output: record of 16 channels = [hi 16 | lo 16]
+        if (co0 < p.Cout && X3) {   // split16 output: record of 16 channels = [hi 16 | lo 16]
           h4 vh, vl;
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
@@ -1663,37 +1638,45 @@ extern "C" int deepim_conv_f16_pack_dgrad(deepim_ctx* ctx, void* packed, const f
 }
 
 namespace {
-// Plan + launch of the LDS-DMA kernel (fp16 or X3). One 256-thread block per CU. Plans, in units of one 64-wide K chunk:
-//   uniform split-K s:   ceil(blocks·s / 256) · ceil(nchunk / s)                      + reduce(blocks·s)
-//   tail split ts:       floor(blocks / 256) · nchunk + ceil(R·ts / 256) · ceil(nchunk / ts) + reduce(R·ts),  R = blocks mod 256
-// reduce(n) = c0 + c1·n·(BM·BN/16384): fp32 partial tiles written and read once; deterministic, no timing involved.
-template <bool X3>
-int launch_f16_dma(deepim_ctx* ctx, ConvF16Params p, int BM, int BN, float c0, float c1, bool pp = false) {
-  const int blocks = p.gx * p.gy;
-  const bool w8 = !pp && BM == 256 && BN == 256 && (ctx->f16_dev_flags & DI_F16_W8) != 0;   // dev: one 8-wave block per CU on a 256x256 tile
-  const bool tn2 = !pp && ((BM == 256 && BN == 128) || (BM == 128 && BN == 256));       // 128x64 wave tiles, two blocks per CU
-  const int slots = tn2 ? 512 : 256;            // resident blocks on the chip (the ping-pong kernel: one 8-wave block per CU)
-  int ks = 1, ts = 0;
+// Split-K plan of an fp16 / X3 conv launch with `slots` resident blocks on the chip. Plans, in units of one 64-wide K chunk:
+//   uniform split-K s:   ceil(blocks·s / slots) · ceil(nchunk / s)                          + reduce(blocks·s)
+//   tail split ts:       floor(blocks / slots) · nchunk + ceil(R·ts / slots) · ceil(nchunk / ts) + reduce(R·ts),  R = blocks mod slots
+// reduce(n) = c0 + c1·n·(BM·BN/16384): fp32 partial tiles written and read once; deterministic, no timing involved. Returns
+// the uniform split factor; tail splits are considered only for a kernel that has them (ts != nullptr: *ts = slices, 0 = none).
+int f16_plan_split(const deepim_ctx* ctx, int blocks, int nchunk, int BM, int BN, int slots, float c0, float c1, int* ts = nullptr) {
+  int ks = 1;
+  if (ts) *ts = 0;
   if (ctx->conv_max_split != 1) {
     float best = 1e30f;
     const float tile_w = (float)(BM * BN) / 16384.f;
     for (int s_ : {1, 2, 3, 4, 6, 8, 12, 16}) {
-      if (s_ > 1 && ((long)blocks * s_ > 2048 || s_ > max(1, p.nchunk / 4))) continue;
-      const float cost = (float)di_div_up((long)blocks * s_, slots) * (float)di_div_up(p.nchunk, s_) +
+      if (s_ > 1 && ((long)blocks * s_ > 2048 || s_ > max(1, nchunk / 4))) continue;
+      const float cost = (float)di_div_up((long)blocks * s_, slots) * (float)di_div_up(nchunk, s_) +
                          (s_ > 1 ? c0 + c1 * (float)((long)blocks * s_) * tile_w : 0.f);
       if (cost < best * 0.985f) { best = cost; ks = s_; }
     }
     const int R = blocks % slots;
-    if (blocks > slots && R > 0 && ctx->conv_max_split == 0 && !(ctx->f16_dev_flags & DI_F16_NO_TAIL)) {
+    if (ts && blocks > slots && R > 0 && ctx->conv_max_split == 0) {
       for (int t_ : {2, 3, 4, 5, 6, 8}) {
-        if (t_ > max(1, p.nchunk / 4)) continue;
-        const float cost = (float)(blocks / slots) * (float)p.nchunk + (float)di_div_up(R * t_, slots) * (float)di_div_up(p.nchunk, t_) +
+        if (t_ > max(1, nchunk / 4)) continue;
+        const float cost = (float)(blocks / slots) * (float)nchunk + (float)di_div_up(R * t_, slots) * (float)di_div_up(nchunk, t_) +
                            c0 + c1 * (float)(R * t_) * tile_w;
-        if (cost < best * 0.97f) { best = cost; ts = t_; ks = 1; }
+        if (cost < best * 0.97f) { best = cost; *ts = t_; ks = 1; }
       }
     }
   }
   if (ctx->conv_max_split > 1) ks = min(ks, ctx->conv_max_split);
+  return ks;
+}
+
+// Plan + launch of the LDS-DMA kernels (fp16 or X3): the 4-wave kernel on 128x64 wave tiles, two blocks per CU, or (pp, fp16
+// only) the ping-pong kernel, one 8-wave block per CU.
+template <bool X3>
+int launch_f16_dma(deepim_ctx* ctx, ConvF16Params p, int BM, int BN, float c0, float c1, bool pp = false) {
+  const int blocks = p.gx * p.gy;
+  const int slots = pp ? 256 : 512;   // resident blocks on the chip
+  int ts;
+  const int ks = f16_plan_split(ctx, blocks, p.nchunk, BM, BN, slots, c0, c1, &ts);
   p.chunks_per_split = di_div_up(p.nchunk, ks);
   p.ksplit = di_div_up(p.nchunk, p.chunks_per_split);
   p.partial = nullptr;
@@ -1717,14 +1700,10 @@ int launch_f16_dma(deepim_ctx* ctx, ConvF16Params p, int BM, int BN, float c0, f
   }
   static const char attr_tag = 0;   // function attributes are per DEVICE: remember them per context
   if (di_attr_needed(ctx, &attr_tag)) {
-    DI_CHECK(hipFuncSetAttribute((const void*)conv_f16_dma_kernel<2, 2, 4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072));
-    DI_CHECK(hipFuncSetAttribute((const void*)conv_f16_dma_kernel<1, 4, 3, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 122880));
-    DI_CHECK(hipFuncSetAttribute((const void*)conv_f16_dma_kernel<2, 2, 3, false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 73728));
-    DI_CHECK(hipFuncSetAttribute((const void*)conv_f16_dma_kernel<2, 2, 3, true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 73728));
-    DI_CHECK(hipFuncSetAttribute((const void*)conv_f16_dma_kernel<1, 4, 3, false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 73728));
-    DI_CHECK(hipFuncSetAttribute((const void*)conv_f16_dma_kernel<1, 4, 3, true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 73728));
-    DI_CHECK(hipFuncSetAttribute((const void*)conv_f16_dma_kernel<2, 4, 4, false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072));
-    DI_CHECK(hipFuncSetAttribute((const void*)conv_f16_dma_kernel<2, 4, 4, true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072));
+    DI_CHECK(hipFuncSetAttribute((const void*)conv_f16_dma_kernel<2, 2, 3, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 73728));
+    DI_CHECK(hipFuncSetAttribute((const void*)conv_f16_dma_kernel<2, 2, 3, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 73728));
+    DI_CHECK(hipFuncSetAttribute((const void*)conv_f16_dma_kernel<1, 4, 3, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 73728));
+    DI_CHECK(hipFuncSetAttribute((const void*)conv_f16_dma_kernel<1, 4, 3, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 73728));
     DI_CHECK(hipFuncSetAttribute((const void*)conv_f16_pp_kernel<2, 4, 5>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840));
 #if DI_PP_TRACE
     DI_CHECK(hipFuncSetAttribute((const void*)conv_f16_pp_kernel<2, 4, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 135168 + 8192));
@@ -1745,15 +1724,8 @@ int launch_f16_dma(deepim_ctx* ctx, ConvF16Params p, int BM, int BN, float c0, f
     } else {
       DI_REQUIRE(false, "conv2d_x3: no ping-pong kernel");
     }
-  } else if (BM == 128 && tn2) hipLaunchKernelGGL((conv_f16_dma_kernel<1, 4, 3, X3, 2>), dim3(grid), dim3(256), 73728, ctx->stream, p);
-  else if (w8) hipLaunchKernelGGL((conv_f16_dma_kernel<2, 4, 4, X3, 2>), dim3(grid), dim3(512), 131072, ctx->stream, p);
-  else if (tn2) hipLaunchKernelGGL((conv_f16_dma_kernel<2, 2, 3, X3, 2>), dim3(grid), dim3(256), 73728, ctx->stream, p);
-  else if constexpr (!X3) {   // 128x128 wave tiles, one block per CU (DEEPIM_F16_TN4=1; plain fp16 only)
-    if (BM == 128) hipLaunchKernelGGL((conv_f16_dma_kernel<1, 4, 3, false>), dim3(grid), dim3(256), 122880, ctx->stream, p);
-    else hipLaunchKernelGGL((conv_f16_dma_kernel<2, 2, 4, false>), dim3(grid), dim3(256), 131072, ctx->stream, p);
-  } else {
-    DI_REQUIRE(false, "conv2d_x3: tile shape not built");
-  }
+  } else if (BM == 128) hipLaunchKernelGGL((conv_f16_dma_kernel<1, 4, 3, X3>), dim3(grid), dim3(256), 73728, ctx->stream, p);
+  else hipLaunchKernelGGL((conv_f16_dma_kernel<2, 2, 3, X3>), dim3(grid), dim3(256), 73728, ctx->stream, p);
   if (p.ksplit > 1) {
     const long total4 = p.npix * p.Cout / 4;
     if (X3)
@@ -1806,13 +1778,13 @@ extern "C" int deepim_conv2d_f16_forward(deepim_ctx* ctx, void* out_nhwc_f16, co
   p.tab = tab;
   const bool ut = ((Cin_pad >> 3) & 7) == 0;
   const int BM = f16_bm(Cout);
-  int BN = f16_bn(Cout, ut && !(ctx->f16_dev_flags & DI_F16_NO_DMA), ctx->f16_dev_flags);
+  int BN = f16_bn(Cout, ut);
   p.n_full = 0; p.tail_s = 0; p.tail_cps = 0; p.tail_partial = nullptr; p.acc_scale = p.out_scale = 1.f; p.status = ctx->status;
   // Ping-pong kernel (one 8-wave block per CU, 256x256 / 128x512 tiles) from DI_F16_PP_MIN_TILES tiles on: conv2 … conv5_1 at
   // B = 32, conv2 … conv4_1 at B = 8 (150-tile layers run 1.2x faster on it than on the 4-wave kernel even half filled). Smaller
   // grids keep the 4-wave kernel on 256x128 tiles (two blocks per CU: twice the blocks for the same split factor). Fixed by the
   // geometry: the same plan on every rank.
-  if (ut && BM >= 128 && (Cout % 128) == 0 && !(ctx->f16_dev_flags & (DI_F16_NO_DMA | DI_F16_NO_PP | DI_F16_TN4 | DI_F16_W8))) {
+  if (ut && BM >= 128 && (Cout % 128) == 0 && !(ctx->f16_dev_flags & DI_F16_NO_PP)) {
     const int bn_pp = BM == 256 ? 256 : 512;
     const long tiles_pp = (long)di_div_up(p.npix, bn_pp) * di_div_up(Cout, BM);
     if (tiles_pp >= DI_F16_PP_MIN_TILES) {
@@ -1822,21 +1794,11 @@ extern "C" int deepim_conv2d_f16_forward(deepim_ctx* ctx, void* out_nhwc_f16, co
     }
   }
   p.gx = di_div_up(p.npix, BN); p.gy = di_div_up(Cout, BM);
-  if (ut && BM >= 128 && !(ctx->f16_dev_flags & DI_F16_NO_DMA)) return launch_f16_dma<false>(ctx, p, BM, BN, 1.5f, 0.009f);
+  if (ut && BM >= 128) return launch_f16_dma<false>(ctx, p, BM, BN, 1.5f, 0.009f);
+  // register-staged kernel (Cout <= 64, or Cin_pad % 64 != 0): one 256-thread block per CU (the LDS double buffer and the 256
+  // accumulator registers leave room for one), uniform split-K only
   const int blocks = p.gx * p.gy;
-  // one 256-thread block per CU (the LDS double buffer and the 256 accumulator registers leave room for one): split K when
-  // the grid cannot fill the 256 CUs; deterministic (cost model of csrc/conv.hip's plan_ksplit, one slot per CU)
-  int ks = 1;
-  if (ctx->conv_max_split != 1) {
-    float best = 1e30f;
-    for (int s_ : {1, 2, 3, 4, 6, 8, 12, 16}) {
-      if (s_ > 1 && ((long)blocks * s_ > 2048 || s_ > max(1, p.nchunk / 4))) continue;
-      const float cost = (float)di_div_up((long)blocks * s_, 256) * (float)di_div_up(p.nchunk, s_) +
-                         (s_ > 1 ? 1.5f + 0.009f * (float)((long)blocks * s_) * (float)(BM * BN) / 16384.f : 0.f);   // reduce: 8 B of fp32 partials written + read per output per slice
-      if (cost < best * 0.985f) { best = cost; ks = s_; }
-    }
-  }
-  if (ctx->conv_max_split > 1) ks = min(ks, ctx->conv_max_split);
+  const int ks = f16_plan_split(ctx, blocks, p.nchunk, BM, BN, 256, 1.5f, 0.009f);
   p.chunks_per_split = di_div_up(p.nchunk, ks);
   p.ksplit = di_div_up(p.nchunk, p.chunks_per_split);
   p.partial = nullptr;
@@ -1849,34 +1811,16 @@ extern "C" int deepim_conv2d_f16_forward(deepim_ctx* ctx, void* out_nhwc_f16, co
   const size_t lds = (size_t)2 * HOCT * (BM + BN) * 16;
   static const char attr_set_tag = 0;   // function attributes are per DEVICE: remember them per context
   if (di_attr_needed(ctx, &attr_set_tag)) {
-#define DI_F16_ATTR(A, B2, C, D, BMv, BNv)                                                                                  \
-  DI_CHECK(hipFuncSetAttribute((const void*)conv_f16_kernel<A, B2, C, D, true>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                               2 * HOCT * (BMv + BNv) * 16));                                                              \
-  DI_CHECK(hipFuncSetAttribute((const void*)conv_f16_kernel<A, B2, C, D, false>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                               2 * HOCT * (BMv + BNv) * 16));
-    DI_F16_ATTR(1, 4, 2, 2, 64, 256)
-    DI_F16_ATTR(2, 2, 2, 4, 128, 256)
-    DI_F16_ATTR(2, 2, 4, 4, 256, 256)
-#undef DI_F16_ATTR
+    DI_CHECK(hipFuncSetAttribute((const void*)conv_f16_kernel<1, 4, 2, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * HOCT * (64 + 256) * 16));
+    DI_CHECK(hipFuncSetAttribute((const void*)conv_f16_kernel<1, 4, 2, 2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * HOCT * (64 + 256) * 16));
+    DI_CHECK(hipFuncSetAttribute((const void*)conv_f16_kernel<2, 2, 2, 4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * HOCT * (128 + 256) * 16));
+    DI_CHECK(hipFuncSetAttribute((const void*)conv_f16_kernel<2, 2, 4, 4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * HOCT * (256 + 256) * 16));
   }
   const dim3 grid(blocks * p.ksplit);
-#define DI_F16_LAUNCH(A, B2, C, D)                                                                                 \
-  {                                                                                                                \
-    if (ut) hipLaunchKernelGGL((conv_f16_kernel<A, B2, C, D, true>), grid, dim3(256), lds, ctx->stream, p);         \
-    else hipLaunchKernelGGL((conv_f16_kernel<A, B2, C, D, false>), grid, dim3(256), lds, ctx->stream, p);           \
-  }
-  static const char dma_attr_tag = 0;   // function attributes are per DEVICE: remember them per context
-  if (di_attr_needed(ctx, &dma_attr_tag)) {
-    DI_CHECK(hipFuncSetAttribute((const void*)conv_f16_dma_kernel<2, 2, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072));
-    DI_CHECK(hipFuncSetAttribute((const void*)conv_f16_dma_kernel<1, 4, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 122880));
-  }
-  const bool dma = ut && !(ctx->f16_dev_flags & DI_F16_NO_DMA);
-  if (BM == 64) DI_F16_LAUNCH(1, 4, 2, 2)
-  else if (BM == 128 && dma) hipLaunchKernelGGL((conv_f16_dma_kernel<1, 4, 3>), grid, dim3(256), 122880, ctx->stream, p);
-  else if (BM == 128) DI_F16_LAUNCH(2, 2, 2, 4)
-  else if (dma) hipLaunchKernelGGL((conv_f16_dma_kernel<2, 2, 4>), grid, dim3(256), 131072, ctx->stream, p);
-  else DI_F16_LAUNCH(2, 2, 4, 4)
-#undef DI_F16_LAUNCH
+  if (BM == 64 && ut) hipLaunchKernelGGL((conv_f16_kernel<1, 4, 2, 2, true>), grid, dim3(256), lds, ctx->stream, p);
+  else if (BM == 64) hipLaunchKernelGGL((conv_f16_kernel<1, 4, 2, 2, false>), grid, dim3(256), lds, ctx->stream, p);
+  else if (BM == 128) hipLaunchKernelGGL((conv_f16_kernel<2, 2, 2, 4, false>), grid, dim3(256), lds, ctx->stream, p);
+  else hipLaunchKernelGGL((conv_f16_kernel<2, 2, 4, 4, false>), grid, dim3(256), lds, ctx->stream, p);
   if (p.ksplit > 1) {
     const long total4 = p.npix * Cout / 4;
     hipLaunchKernelGGL(splitk_f16_reduce_kernel, dim3(di_div_up(total4, 256)), dim3(256), 0, ctx->stream, p.out,
@@ -1968,7 +1912,7 @@ extern "C" int deepim_conv2d_x3_forward(deepim_ctx* ctx, void* out_split16, cons
   const size_t in_bytes = (size_t)B * H * W * Cv * 2;
   DI_REQUIRE(in_bytes + p.pad_bytes < 0x7fffffffUL, "conv2d_x3: input tensor must be < 2 GiB per launch");
   p.in_bytes = (unsigned)in_bytes;
-  const int BM = f16_bm(Cout), BN = (ctx->f16_dev_flags & DI_F16_W8) && BM == 256 ? 256 : (BM == 256 ? 128 : 256);   // 128x64 wave tiles
+  const int BM = f16_bm(Cout), BN = BM == 256 ? 128 : 256;   // 128x64 wave tiles
   p.gx = di_div_up(p.npix, BN); p.gy = di_div_up(Cout, BM);
   // the plan model of the fp16 path with a chunk 1.5x as long (96 instead of 64 MFMAs per wave)
   return launch_f16_dma<true>(ctx, p, BM, BN, 1.0f, 0.006f);

@@ -255,7 +255,7 @@ extern "C" int deepim_fc_forward(deepim_ctx* ctx, float* out, const float* in, c
   DI_REQUIRE((I & 3) == 0, "fc: input width must be a multiple of 4");
   const int rowblocks = di_div_up(O, FC_ROWS);
   // enough K slices to fill the chip (~512 blocks of 2 waves/SIMD), each a multiple of 256 elements
-  int S = ctx->fc_slices > 0 ? ctx->fc_slices : di_div_up(512, rowblocks);   // measured best at fc6: 8 row blocks x 64 slices
+  int S = di_div_up(512, rowblocks);   // measured best at fc6: 8 row blocks x 64 slices
   int slice = di_div_up(di_div_up(I, S), 256) * 256;
   S = di_div_up(I, slice);
   void* scratch;

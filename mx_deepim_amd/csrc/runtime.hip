@@ -42,9 +42,7 @@ void deepim_ctx_default_options(deepim_ctx* c) {
   c->conv_direct = 1;
   c->conv_tail_slots = 1024;
   c->conv_force_plan = 0;
-  c->fc_slices = 0;
   c->conv_tail_split = 0;
-  c->conv_tile256 = 0;   // measured: 113.1 vs 113.7 TF for 128x128 — kept as an option, off by default
 }
 
 extern "C" int deepim_create(int device_id, deepim_ctx** out) {
@@ -226,11 +224,9 @@ extern "C" int deepim_set_option(deepim_ctx* ctx, const char* name, int value) {
     return 0;
   }
   if (strcmp(name, "conv_direct") == 0) { ctx->conv_direct = value < 0 ? 0 : (value > 2 ? 2 : value); return 0; }
-  if (strcmp(name, "fc_slices") == 0) { ctx->fc_slices = value > 0 ? value : 0; return 0; }
   if (strcmp(name, "conv_tail_split") == 0) { ctx->conv_tail_split = value ? 1 : 0; return 0; }
   if (strcmp(name, "conv_force_plan") == 0) { ctx->conv_force_plan = value; return 0; }
   if (strcmp(name, "conv_tail_slots") == 0) { DI_REQUIRE(value >= 8 && value % 8 == 0, "conv_tail_slots must be a positive multiple of 8"); ctx->conv_tail_slots = value; return 0; }
-  if (strcmp(name, "conv_tile256") == 0) { ctx->conv_tile256 = value ? 1 : 0; return 0; }
   if (strcmp(name, "conv_autotune") == 0) { ctx->conv_autotune = value ? 1 : 0; return 0; }
   if (strcmp(name, "dgrad_group") == 0) { ctx->dgrad_group = value ? 1 : 0; return 0; }
   if (strcmp(name, "wgrad_lds") == 0) { ctx->wgrad_lds = value ? 1 : 0; return 0; }
@@ -245,7 +241,7 @@ extern "C" int deepim_set_option(deepim_ctx* ctx, const char* name, int value) {
   if (strcmp(name, "wino_wide") == 0) { ctx->wino_wide = (value >= 0 && value <= 3) ? value : 1; return 0; }
   if (strcmp(name, "wino_shared") == 0) { ctx->wino_shared = value ? 1 : 0; return 0; }
   if (strcmp(name, "wino_s2d_skip") == 0) { ctx->wino_s2d_skip = value ? 1 : 0; return 0; }
-  if (strcmp(name, "f16_dev_flags") == 0) { DI_REQUIRE(value >= 0 && value < 32, "f16_dev_flags: bits 0..4"); ctx->f16_dev_flags = value; return 0; }
+  if (strcmp(name, "f16_dev_flags") == 0) { DI_REQUIRE(value == 0 || value == DI_F16_NO_PP, "f16_dev_flags: 0 or 16"); ctx->f16_dev_flags = value; return 0; }
   if (strcmp(name, "conv_xcd_swizzle") == 0) {
     ctx->conv_xcd_swizzle = value ? 1 : 0;
     return 0;
@@ -258,9 +254,9 @@ extern "C" int deepim_set_option(deepim_ctx* ctx, const char* name, int value) {
 extern "C" int deepim_get_option(deepim_ctx* ctx, const char* name, int* value) {
   DI_REQUIRE(ctx != nullptr && name != nullptr && value != nullptr, "deepim_get_option: NULL argument");
   const struct { const char* n; int v; } opts[] = {
-      {"conv_max_split", ctx->conv_max_split}, {"conv_direct", ctx->conv_direct}, {"fc_slices", ctx->fc_slices},
+      {"conv_max_split", ctx->conv_max_split}, {"conv_direct", ctx->conv_direct},
       {"conv_tail_split", ctx->conv_tail_split}, {"conv_force_plan", ctx->conv_force_plan}, {"conv_tail_slots", ctx->conv_tail_slots},
-      {"conv_tile256", ctx->conv_tile256}, {"conv_autotune", ctx->conv_autotune}, {"dgrad_group", ctx->dgrad_group},
+      {"conv_autotune", ctx->conv_autotune}, {"dgrad_group", ctx->dgrad_group},
       {"wgrad_lds", ctx->wgrad_lds}, {"wino_two_wave", ctx->wino_two_wave}, {"wino_shared", ctx->wino_shared}, {"wino_wide", ctx->wino_wide}, {"wino_split", ctx->wino_split}, {"wino_persistent", ctx->wino_persistent}, {"wino_streamk", ctx->wino_streamk}, {"wino_fin", ctx->wino_fin}, {"conv_fewout_quad", ctx->conv_fewout_quad}, {"conv_fewout_blocks", ctx->conv_fewout_blocks}, {"conv_fewout_minc", ctx->conv_fewout_minc}, {"wino_s2d_skip", ctx->wino_s2d_skip}, {"f16_dev_flags", ctx->f16_dev_flags}, {"conv_xcd_swizzle", ctx->conv_xcd_swizzle}};
   for (const auto& o : opts)
     if (strcmp(name, o.n) == 0) { *value = o.v; return 0; }

@@ -32,8 +32,11 @@ def test_error_returns_are_raised_not_printed(ctx):
     h, d = ctx.handle, ctx.empty((16,))
     with pytest.raises(RuntimeError, match="multiple of 4"):
         lib.deepim_fc_forward(h, d, d, d, None, 1, 7, 2, cf(1.0))
-    with pytest.raises(RuntimeError, match="unknown option"):
-        lib.deepim_set_option(h, b"no_such_knob", 1)
+    for name in (b"no_such_knob", b"conv_tile256", b"fc_slices"):
+        with pytest.raises(RuntimeError, match="unknown option"):
+            lib.deepim_set_option(h, name, 1)
+    with pytest.raises(RuntimeError, match="f16_dev_flags"):   # only 0 and 16 (no ping-pong kernel) remain
+        lib.deepim_set_option(h, b"f16_dev_flags", 1)
     with pytest.raises(RuntimeError, match="rot_coord"):
         lib.deepim_rt_transform(h, d, None, d, d, None, None, 9, 1)
     with pytest.raises(RuntimeError, match="larger than 7"):

@@ -1,6 +1,6 @@
 """Dev probe: per-layer timing of the fp16 conv path (NHWC fp16 in/out) at the encoder geometries, on RANDOM operands (zero-filled
 operands clock 15-20 % higher: cdna_hip_programming.md §5.4 rule 25), variants interleaved in one process (rule 24).
-usage: bench_layers_f16.py [B] [cin0] [flags,flags,...]     — each `flags` = a value of deepim_set_option("f16_dev_flags")
+usage: bench_layers_f16.py [B] [cin0] [flags,flags,...]     — each `flags` = 0 or 16, a value of deepim_set_option("f16_dev_flags")
        (0 = default: ping-pong kernel where the grid fills the chip; 16 = round 3's 4-wave kernel everywhere)"""
 import ctypes, os, sys
 import numpy as np
