@@ -315,6 +315,8 @@ int deepim_relayout_nc8(deepim_ctx* ctx, float* dst, const float* src, int B, in
 /* The same conversion (NC8 -> NCHW) written into channels [dst_coff, dst_coff + C) of a dst_ctotal-channel NCHW tensor: the encoder
  * skip connections of the refinement decoder (Concat, deepim/symbols/deepIM_flownet.py:128-131, :143-146) in one pass. */
 int deepim_relayout_nc8_slice(deepim_ctx* ctx, float* dst, int dst_ctotal, int dst_coff, const float* src_nc8, int B, int C, size_t hw);
+/* the same from an NC8 tensor in space-to-depth order ((B, C, H, W), even H and W; see deepim_relayout_nc8_s2d) */
+int deepim_relayout_nc8_s2d_slice(deepim_ctx* ctx, float* dst, int dst_ctotal, int dst_coff, const float* src_s2d, int B, int C, int H, int W);
 /* The encoder's 3x3 stride-1 pad-1 layers (conv3_1 / conv4_1 / conv5_1 / conv6_1, deepIM_flownet.py:69-101) as fp32 Winograd
  * F(2x2,3x3): the same fp32 arithmetic with 2.25x fewer multiplies, a different summation (NOT the direct kernels' fmaf chain:
  * within 1e-5 of the layer's range, tests/test_gpu_wino.py). `in` is NC8; `out` NC8 (out_nc8 = 1) or channels [out_coff,
@@ -351,6 +353,18 @@ int deepim_conv_wino_pack_weights_s2d(deepim_ctx* ctx, float* packed_w, const fl
  * that order (2e-6 of range from the one-wave kernel's natural order). */
 int deepim_conv2d_wino_forward_s2d(deepim_ctx* ctx, float* out, const float* in_s2d, const float* packed_w, const float* bias,
                                    int B, int Cin, int H, int W, int Cout, float slope, int out_nc8, int out_ctotal, int out_coff);
+/* The 3x3 stride-2 pad-1 layers (conv4 / conv5) over the same space-to-depth input: the 3x3 kernel is taps 1..3 of a 5x5 stride-2
+ * pad-2 one, so phase (py, px) carries tap (a, b) = w[2a+py-1][2b+px-1] (zero where an index leaves 0..2). An even phase keeps only
+ * the middle tap along that axis (live positions 1, 2), an odd one taps 0 and 2 (positions 0, 1, 2); position 3 is dead everywhere:
+ * 25 of the 64 (phase, position) GEMMs remain, 1.44x fewer multiplies than the direct sum, dropped at compile time by the
+ * shared-transform kernel's phase walk. _pack_weights_s2d3 takes the layer's own (Cout, Cin, 3, 3) weights (size
+ * deepim_conv_wino_packed_size(Cout, 4*Cin)); _forward_s2d3 the (B, Cin, H, W) input's space-to-depth NC8 form (even H and W), output
+ * (B, Cout, H/2, W/2). _preferred_s2d3 is 0 under "conv_max_split" = 1, without the shared-transform kernel (Cout % 64, Cin % 16,
+ * "wino_shared" / "wino_two_wave"), for odd H or W, and below the measured batch threshold. deepim_conv_wino_plan takes s2d = 2. */
+int deepim_conv_wino_preferred_s2d3(deepim_ctx* ctx, int B, int Cin, int H, int W, int Cout);
+int deepim_conv_wino_pack_weights_s2d3(deepim_ctx* ctx, float* packed_w, const float* w /*Cout,Cin,3,3 dev*/, int Cout, int Cin);
+int deepim_conv2d_wino_forward_s2d3(deepim_ctx* ctx, float* out, const float* in_s2d, const float* packed_w, const float* bias,
+                                    int B, int Cin, int H, int W, int Cout, float slope, int out_nc8, int out_ctotal, int out_coff);
 int deepim_relayout_nc8_s2d(deepim_ctx* ctx, float* dst, const float* src, int B, int C, int H, int W, int to_s2d);
 int deepim_conv2d_wino_forward(deepim_ctx* ctx, float* out, const float* in, const float* packed_w, const float* bias,
                                int B, int Cin, int H, int W, int Cout, float slope, int out_nc8, int out_ctotal, int out_coff);

@@ -2322,8 +2322,9 @@ extern "C" int deepim_upsample16_crop_forward(deepim_ctx* ctx, float* out, const
 }
 
 // NC8 in space-to-depth order <-> NCHW: (B, C, H, W) <-> [n][(phase*C + c)/8][H/2][W/2][8], phase = (y&1)*2 + (x&1)
+// (NCHW side: channels [coff, coff + C) of a ctotal-channel tensor)
 __global__ __launch_bounds__(256) void relayout_s2d_kernel(float* __restrict__ dst, const float* __restrict__ src, int C, int H, int W,
-                                                           long total, int to_s2d) {
+                                                           long total, int to_s2d, int ctotal, int coff) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;   // index in the space-to-depth tensor
   if (i >= total) return;
   const int q = (int)(i & 7), hw4 = (H >> 1) * (W >> 1), C8 = C >> 3;
@@ -2332,7 +2333,7 @@ __global__ __launch_bounds__(256) void relayout_s2d_kernel(float* __restrict__ d
   const long n = plane / (4 * C8);
   const int r = (int)(plane % (4 * C8)), ph = r / C8, c = (r % C8) * 8 + q;
   const int y = 2 * (pix / (W >> 1)) + (ph >> 1), x = 2 * (pix % (W >> 1)) + (ph & 1);
-  const long j = ((n * C + c) * H + y) * W + x;
+  const long j = ((n * ctotal + coff + c) * H + y) * W + x;
   if (to_s2d) dst[i] = src[j]; else dst[j] = src[i];
 }
 extern "C" int deepim_relayout_nc8_s2d(deepim_ctx* ctx, float* dst, const float* src, int B, int C, int H, int W, int to_s2d) {
@@ -2340,7 +2341,21 @@ extern "C" int deepim_relayout_nc8_s2d(deepim_ctx* ctx, float* dst, const float*
   if (B == 0 || C == 0) return 0;
   DI_REQUIRE((C & 7) == 0 && ((H | W) & 1) == 0, "relayout_nc8_s2d: C % 8 == 0, even H and W");
   const long total = (long)B * C * H * W;
-  hipLaunchKernelGGL(relayout_s2d_kernel, dim3(di_div_up(total, 256)), dim3(256), 0, ctx->stream, dst, src, C, H, W, total, to_s2d);
+  hipLaunchKernelGGL(relayout_s2d_kernel, dim3(di_div_up(total, 256)), dim3(256), 0, ctx->stream, dst, src, C, H, W, total, to_s2d, C, 0);
+  DI_LAUNCH_CHECK();
+  return 0;
+}
+
+// the same from an NC8 tensor in space-to-depth order (a skip whose layer feeds a stride-2 Winograd layer): one pass, as above
+extern "C" int deepim_relayout_nc8_s2d_slice(deepim_ctx* ctx, float* dst, int dst_ctotal, int dst_coff, const float* src_s2d, int B, int C,
+                                             int H, int W) {
+  DI_DEVICE(ctx);
+  if (B == 0 || C == 0) return 0;
+  DI_REQUIRE((C & 7) == 0 && ((H | W) & 1) == 0 && dst_ctotal >= dst_coff + C && dst_coff >= 0,
+             "relayout_nc8_s2d_slice: C % 8 == 0, even H and W, the slice inside the tensor");
+  const long total = (long)B * C * H * W;
+  hipLaunchKernelGGL(relayout_s2d_kernel, dim3(di_div_up(total, 256)), dim3(256), 0, ctx->stream, dst, src_s2d, C, H, W, total, 0,
+                     dst_ctotal, dst_coff);
   DI_LAUNCH_CHECK();
   return 0;
 }

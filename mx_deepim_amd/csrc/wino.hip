@@ -701,26 +701,35 @@ __device__ __forceinline__ void wino8_body(const WinoParams& p, char* smem, cons
   // so that stage s has phase (s >> 1) & 3 — a compile-time constant at every place of the eight-step loop body.
   const int npb = S2D ? (c8n >> 2) : 0;
 #define W8_CB(s) (S2D ? (((s) >> 1) & 3) * npb + (((s) >> 3) << 1) + ((s) & 1) : (s))
-// position i of this wave in a stage of phase P (compile-time)
-#define W8_ACT(i, P) (!S2D || !((((P) & 1) && ((i) & 3) == 3) || (((P) >> 1) && ph && (i) >= 4)))
+// live rows xi / columns nu of U in a stage of phase P (compile-time). S2D 1 (5x5 stride 2): an odd phase drops position 3. S2D 2 (3x3
+// stride 2 pad 1 read as taps 1..3 of 5x5 stride 2 pad 2): position 3 is dead in every phase, and an even phase keeps only the middle
+// tap, whose G column (0, 1/2, 1/2, 0) also kills position 0 — 25 of the 64 (phase, position) pairs are left.
+#define W8_XLIVE(xi, P) (S2D == 0 || (S2D == 1 ? !(((P) >> 1) && (xi) == 3) : ((xi) != 3 && (((P) >> 1) || (xi) != 0))))
+#define W8_NLIVE(nu, P) (S2D == 0 || (S2D == 1 ? !(((P) & 1) && (nu) == 3) : ((nu) != 3 && (((P) & 1) || (nu) != 0))))
+// position i of this wave (xi = 2 ph + i / 4, nu = i % 4)
+#define W8_ACT(i, P) (W8_XLIVE(2 * ph + ((i) >> 2), P) && W8_NLIVE((i) & 3, P))
+// patch row r feeds rows xi = 0 (r = 0, 2), 1 and 2 (r = 1, 2), 3 (r = 1, 3) of the row pass
+#define W8_RLIVE(r, P) ((W8_XLIVE(0, P) && ((r) == 0 || (r) == 2)) || ((W8_XLIVE(1, P) || W8_XLIVE(2, P)) && ((r) == 1 || (r) == 2)) || \
+                        (W8_XLIVE(3, P) && ((r) == 1 || (r) == 3)))
 #define W8_LDS4(off) (*reinterpret_cast<f32x4*>(smem + (off)))
-// the 4 pixel loads of this lane's patch column for stage `stage` of phase P. S2D: patch row 3 feeds only xi = 3 — where the phase drops
-// those positions neither the load, nor that row of the row pass, nor its column pass and store are issued (compile-time).
+// the 4 pixel loads of this lane's patch column for stage `stage` of phase P. S2D: a patch row that feeds only rows xi the phase drops
+// (row 3 -> xi = 3; S2D 2, even phase: row 0 -> xi = 0 as well) is neither loaded, nor passed, nor column-passed and stored (compile-time).
 // (Column 3 feeds only nu = 3 as well; masking those lanes would cost 4 vector ORs per step, more than their L1 hits.)
 #define W8_PIX(stage, P)                                                                              \
   if (!(W8_ABL & 4)) {                                                                                \
     const int st_ = min((stage), ke - 1);                                                             \
     const int so_ = __builtin_amdgcn_readfirstlane(W8_CB(st_) * hw32);                                \
     _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_)                                                  \
-      if (i_ < 3 || !(S2D && ((P) >> 1))) {                                                           \
+      if (W8_RLIVE(i_, P)) {                                                                          \
         if constexpr (WIDE) raw[i_] = __builtin_bit_cast(tvec, __builtin_amdgcn_raw_buffer_load_b64(rsrc, voffT[i_], so_, 0)); \
         else raw[i_] = __builtin_bit_cast(tvec, __builtin_amdgcn_raw_buffer_load_b128(rsrc, voffT[i_], so_, 0)); \
       }                                                                                               \
   }
 #define W8_ROW(P)                                                                                     \
   {                                                                                                   \
-    T[0] = raw[0] - raw[2]; T[1] = raw[1] + raw[2]; T[2] = raw[2] - raw[1];                           \
-    if (!(S2D && ((P) >> 1))) T[3] = raw[1] - raw[3];                                                 \
+    if (W8_XLIVE(0, P)) T[0] = raw[0] - raw[2];                                                       \
+    T[1] = raw[1] + raw[2]; T[2] = raw[2] - raw[1];                                                   \
+    if (W8_XLIVE(3, P)) T[3] = raw[1] - raw[3];                                                       \
   }
 // column pass of row xi across the quad, IN PLACE: lane j holds t_j and needs (t0 - t2, t1 + t2, t2 - t1, t3 - t1)[j] (nu = 3 negated, as
 // packed) = self + sgn * T[lane (2, 2, 1, 1)[j]], sgn = (-1, +1, -1, -1): one v_fmac_f32 with a DPP quad_perm source per value.
@@ -784,7 +793,7 @@ __device__ __forceinline__ void wino8_body(const WinoParams& p, char* smem, cons
 // pixel loads of stage xst_ + 1 (phase xpp_); xtp_ = the phase of stage xst_
 #define W8_XWORK(sl)                                                                                  \
       if (sl == 0 && !(W8_ABL & 4)) { W8_ROW(xtp_) }                                                  \
-      if (sl >= 1 && sl <= 4 && !(W8_ABL & 4) && !(S2D && sl == 4 && (xtp_ >> 1))) { W8_COL(sl - 1, xsl_) } \
+      if (sl >= 1 && sl <= 4 && !(W8_ABL & 4) && W8_XLIVE(sl - 1, xtp_)) { W8_COL(sl - 1, xsl_) }      \
       if (sl == 5) { W8_PIX(xst_ + 1, xpp_) }
 
   // ---- prologue: stage 0 into slot 0 and into the operand registers; the top wave also transforms stage 1 into slot 1 and loads the
@@ -801,7 +810,8 @@ __device__ __forceinline__ void wino8_body(const WinoParams& p, char* smem, cons
   W8_ROW(0)
   W8_PIX(kb + 1, 0)
 #pragma unroll
-  for (int xi = 0; xi < 4; ++xi) W8_COL(xi, 0)
+  for (int xi = 0; xi < 4; ++xi)
+    if (W8_XLIVE(xi, 0)) W8_COL(xi, 0)
   W8_SYNC()
   W8_STAMP(5)
   {
@@ -813,7 +823,8 @@ __device__ __forceinline__ void wino8_body(const WinoParams& p, char* smem, cons
     W8_ROW(0)
     W8_PIX(kb + 2, 1)
 #pragma unroll
-    for (int xi = 0; xi < 4; ++xi) W8_COL(xi, 1)
+    for (int xi = 0; xi < 4; ++xi)
+      if (W8_XLIVE(xi, 0)) W8_COL(xi, 1)
   }
   __builtin_amdgcn_sched_barrier(0);
 
@@ -890,6 +901,9 @@ __device__ __forceinline__ void wino8_body(const WinoParams& p, char* smem, cons
 #undef W8_ROW
 #undef W8_PIX
 #undef W8_ACT
+#undef W8_RLIVE
+#undef W8_NLIVE
+#undef W8_XLIVE
 #undef W8_CB
 
   W8_STAMP(2)
@@ -1215,8 +1229,10 @@ static int wino8_streamk_plan(long grid, int nK, int step_granule, int slots, do
 }
 
 // U = G g G^T in double, rounded once; packed [Cout/32][Cin/8][position][lane = h*32 + row][4] with channel 8(c/8) + 4h + s (s = 0, 1: body 0; 2, 3: body 1)
-// s2d: `w` is a (Cout, Cin/4, 5, 5) stride-2 pad-2 kernel read as the 3x3 stride-1 pad-1 kernel over the 4 input phases it is
-// equivalent to — channel phase*(Cin/4) + c, phase = py*2 + px, tap (a, b) = w[2a + py][2b + px] (zero where 2a + py or 2b + px = 5)
+// s2d 1: `w` is a (Cout, Cin/4, 5, 5) stride-2 pad-2 kernel read as the 3x3 stride-1 pad-1 kernel over the 4 input phases it is
+// equivalent to — channel phase*(Cin/4) + c, phase = py*2 + px, tap (a, b) = w[2a + py][2b + px] (zero where 2a + py or 2b + px = 5).
+// s2d 2: `w` is a (Cout, Cin/4, 3, 3) stride-2 pad-1 kernel, i.e. taps 1..3 of a 5x5 stride-2 pad-2 one: tap (a, b) of phase (py, px) =
+// w[2a + py - 1][2b + px - 1] where both indices lie in 0..2, else zero
 __global__ void pack_wino_kernel(float* __restrict__ packed, const float* __restrict__ w, int Cout, int Cin, long total, int s2d) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= total) return;
@@ -1228,7 +1244,15 @@ __global__ void pack_wino_kernel(float* __restrict__ packed, const float* __rest
   const int xi = q >> 2, nu = q & 3;
   const double G[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
   double u = 0;
-  if (s2d) {
+  if (s2d == 2) {
+    const int C0 = Cin >> 2, ph = ci / C0, py = ph >> 1, px = ph & 1;
+    const float* g = w + ((long)co * C0 + (ci - ph * C0)) * 9;
+    for (int a = 0; a < 3; ++a)
+      for (int b = 0; b < 3; ++b) {
+        const int ky = 2 * a + py - 1, kx = 2 * b + px - 1;
+        if (ky >= 0 && ky < 3 && kx >= 0 && kx < 3) u += G[xi][a] * (double)g[ky * 3 + kx] * G[nu][b];
+      }
+  } else if (s2d) {
     const int C0 = Cin >> 2, ph = ci / C0, py = ph >> 1, px = ph & 1;
     const float* g = w + ((long)co * C0 + (ci - ph * C0)) * 25;
     for (int a = 0; a < 3; ++a)
@@ -1285,6 +1309,20 @@ extern "C" int deepim_conv_wino_preferred_s2d(deepim_ctx* ctx, int B, int Cin, i
   if ((size_t)B * Cin * H * W * 4 >= (1ull << 31) || (size_t)B * Cout * (H / 2) * (W / 2) * 4 >= (1ull << 31)) return 0;
   return wino_pays(ctx, B, H / 2, W / 2, Cout, WINO_MIN_BLOCKS_S2D);
 }
+// ... and for a 3x3 stride-2 pad-1 layer with input (B, Cin, H, W), run over the same space-to-depth form (deepim_conv2d_wino_forward_s2d3).
+// Shared-transform kernel only (Cout % 64 == 0, an even number of 8-channel blocks per phase), even H and W (the producing layers write
+// no zero row for an odd plane), and where it was measured faster than the direct kernel: from WINO_S2D3_MIN_WORK output tiles x
+// 8-channel input blocks (profiles/r09_stride2_wino.md: conv4 / conv5 at B = 8 = 76 800 / 40 960 units gain 8 / 14 %, at B = 4 = 38 400 /
+// 20 480 units they are within noise of the direct kernel).
+#ifndef WINO_S2D3_MIN_WORK
+#define WINO_S2D3_MIN_WORK 40000
+#endif
+extern "C" int deepim_conv_wino_preferred_s2d3(deepim_ctx* ctx, int B, int Cin, int H, int W, int Cout) {
+  if (B <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0 || (Cout & 63) || (Cin & 15) || ((H | W) & 1)) return 0;
+  if ((size_t)B * Cin * H * W * 4 >= (1ull << 31) || (size_t)B * Cout * (H / 2) * (W / 2) * 4 >= (1ull << 31)) return 0;
+  if (ctx && (ctx->conv_max_split == 1 || !ctx->wino_shared || ctx->wino_two_wave)) return 0;
+  return (long)B * ((H / 2 + 1) / 2) * ((W / 2 + 1) / 2) * (Cin / 8) >= WINO_S2D3_MIN_WORK ? 1 : 0;
+}
 
 extern "C" int deepim_conv_wino_pack_weights(deepim_ctx* ctx, float* packed_w, const float* w, int Cout, int Cin) {
   DI_DEVICE(ctx);
@@ -1308,11 +1346,23 @@ extern "C" int deepim_conv_wino_pack_weights_s2d(deepim_ctx* ctx, float* packed_
   return 0;
 }
 
+// A 3x3 stride-2 pad-1 layer (conv4 / conv5) over the same space-to-depth form: w is the layer's own (Cout, Cin, 3, 3) tensor, packed as
+// taps 1..3 of a 5x5 stride-2 pad-2 kernel (size deepim_conv_wino_packed_size(Cout, 4 * Cin)); 25 of the 64 (phase, position) GEMMs are
+// non-zero: 1.44x fewer multiplies than the direct sum's 36 per 2x2 tile and channel pair.
+extern "C" int deepim_conv_wino_pack_weights_s2d3(deepim_ctx* ctx, float* packed_w, const float* w, int Cout, int Cin) {
+  DI_DEVICE(ctx);
+  DI_REQUIRE(Cout > 0 && Cin > 0 && (Cout & 31) == 0 && (Cin & 7) == 0, "conv_wino_pack_weights_s2d3: Cout % 32 == 0 and Cin % 8 == 0 required");
+  const long total = (long)Cout * Cin * 4 * 16;
+  pack_wino_kernel<<<di_div_up(total, 256), 256, 0, ctx->stream>>>(packed_w, w, Cout, Cin * 4, total, 2);
+  DI_LAUNCH_CHECK();
+  return 0;
+}
+
 // 3x3, stride 1, pad 1 convolution + bias + LeakyReLU(slope) from channel-blocked `in` (B, Cin/8, H, W, 8) into channel-blocked
 // `out` (out_nc8 = 1; 3 = channel-blocked in space-to-depth order, what a stride-2 layer on this kernel reads) or into channels
 // [out_coff, out_coff + Cout) of an NCHW tensor of out_ctotal channels (out_nc8 = 0).
 static int wino_forward_impl(deepim_ctx* ctx, float* out, const float* in, const float* packed_w, const float* bias, int B, int Cin,
-                             int H, int W, int Cout, float slope, int out_nc8, int out_ctotal, int out_coff, bool s2d,
+                             int H, int W, int Cout, float slope, int out_nc8, int out_ctotal, int out_coff, int s2d,
                              int* plan_only = nullptr) {
   if (!plan_only) DI_DEVICE(ctx);      // (the plan is host arithmetic)
   DI_REQUIRE(B >= 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0, "conv2d_wino_forward: bad shape");
@@ -1334,7 +1384,9 @@ static int wino_forward_impl(deepim_ctx* ctx, float* out, const float* in, const
   bool half = shared && ctx->wino_wide == 2;
   if (shared && ctx->wino_wide == 1) {
     const long wide_blocks = (long)di_div_up(p.ntiles, 32) * di_div_up(Cout, 128);
-    half = wide_blocks * (Cin / 8) <= 100L * 256 || (Cout & 127) != 0;
+    // the 3x3 stride-2 geometry (25 MFMA blocks per 8-step body, not 49 / 64): the wide blocks win at every batch measured (B = 4 / 8 / 32,
+    // tools/bench_wino.py; profiles/r09_stride2_wino.md)
+    half = (s2d != 2 && wide_blocks * (Cin / 8) <= 100L * 256) || (Cout & 127) != 0;
   }
   const bool wide = shared && !half && (Cout & 127) == 0 && ctx->wino_wide != 0;
   p.gx = di_div_up(p.ntiles, (wide || half) ? 32 : (two_wave || shared) ? 64 : 128);
@@ -1353,7 +1405,8 @@ static int wino_forward_impl(deepim_ctx* ctx, float* out, const float* in, const
     // block -> (channel block, tile block) as conv_wino8_kernel maps it: gy < 8 dividing 8 deals 8 / gy XCDs to each channel block
     if ((p.gy & 7) != 0 && (8 % p.gy) == 0) grid = 8 * di_div_up(p.gx, 8 / p.gy);
     // the zero positions are dropped along an interleaved walk of the four input phases: two 8-channel blocks of each per loop body
-    const bool ph8 = s2d && (Cin % 64) == 0 && ctx->wino_s2d_skip;
+    // (ph8 = the geometry: 1 the 5x5, 2 the 3x3 stride-2 layers)
+    const int ph8 = (s2d && (Cin % 64) == 0 && ctx->wino_s2d_skip) ? s2d : 0;
     // under-filled grids split the input channels (conv5_1 / conv6_1 at B = 32, every layer at the per-GPU shares of an 8-GPU node)
     const int nK = Cin / 8;
     const size_t out_elems = (size_t)B * Cout * H * W;
@@ -1402,7 +1455,9 @@ static int wino_forward_impl(deepim_ctx* ctx, float* out, const float* in, const
     if (half) conv_wino4_kernel<O, S><<<grid, 256, 0, ctx->stream>>>(p);                              \
     else if (wide) conv_wino8_kernel<O, S, 1><<<grid, 512, 0, ctx->stream>>>(p);                      \
     else conv_wino8_kernel<O, S, 0><<<grid, 512, 0, ctx->stream>>>(p);
-    if (ph8) {
+    if (ph8 == 2) {
+      if (out_nc8) { W8_LAUNCH(1, 2) } else { W8_LAUNCH(0, 2) }
+    } else if (ph8) {
       if (out_nc8) { W8_LAUNCH(1, 1) } else { W8_LAUNCH(0, 1) }
     } else {
       if (out_nc8) { W8_LAUNCH(1, 0) } else { W8_LAUNCH(0, 0) }
@@ -1419,7 +1474,8 @@ static int wino_forward_impl(deepim_ctx* ctx, float* out, const float* in, const
     return 0;
   }
   if (plan_only) return 0;
-  // phase-by-phase K loop with the zero positions skipped: needs an even number of 8-channel blocks per input phase
+  // phase-by-phase K loop with the zero positions skipped: needs an even number of 8-channel blocks per input phase (the 5x5 walk
+  // skips a subset of the 3x3 stride-2 geometry's zero positions: it serves both)
   const bool phases = s2d && (Cin % 64) == 0 && ctx->wino_s2d_skip;
   if (two_wave) {
     if (out_nc8) conv_wino2_kernel<1><<<grid, 256, 0, ctx->stream>>>(p);
@@ -1438,7 +1494,7 @@ static int wino_forward_impl(deepim_ctx* ctx, float* out, const float* in, const
 extern "C" int deepim_conv2d_wino_forward(deepim_ctx* ctx, float* out, const float* in, const float* packed_w, const float* bias,
                                           int B, int Cin, int H, int W, int Cout, float slope, int out_nc8, int out_ctotal,
                                           int out_coff) {
-  return wino_forward_impl(ctx, out, in, packed_w, bias, B, Cin, H, W, Cout, slope, out_nc8, out_ctotal, out_coff, false);
+  return wino_forward_impl(ctx, out, in, packed_w, bias, B, Cin, H, W, Cout, slope, out_nc8, out_ctotal, out_coff, 0);
 }
 
 // The 5x5 stride-2 pad-2 layer itself: `in` = the space-to-depth NC8 form (B, 4 Cin, H/2, W/2) of its (B, Cin, H, W) input, packed_w
@@ -1448,17 +1504,26 @@ extern "C" int deepim_conv2d_wino_forward_s2d(deepim_ctx* ctx, float* out, const
                                               int B, int Cin, int H, int W, int Cout, float slope, int out_nc8, int out_ctotal,
                                               int out_coff) {
   DI_REQUIRE(H > 0 && W > 0 && ((H | W) & 1) == 0, "conv2d_wino_forward_s2d: even H and W required");
-  return wino_forward_impl(ctx, out, in_s2d, packed_w, bias, B, 4 * Cin, H / 2, W / 2, Cout, slope, out_nc8, out_ctotal, out_coff, true);
+  return wino_forward_impl(ctx, out, in_s2d, packed_w, bias, B, 4 * Cin, H / 2, W / 2, Cout, slope, out_nc8, out_ctotal, out_coff, 1);
 }
 
-// The launch plan of the shared-transform kernel for a layer geometry (s2d: the arguments are the space-to-depth problem's, as
-// wino_forward_impl sees them) under the context's options; plan[6] as documented at the fill site. -1 where that kernel is not used.
+// The 3x3 stride-2 pad-1 layer: `in_s2d` as above (even H and W), packed_w from deepim_conv_wino_pack_weights_s2d3, output
+// (B, Cout, H/2, W/2); 25 of 64 MFMAs per (phase, position) walk.
+extern "C" int deepim_conv2d_wino_forward_s2d3(deepim_ctx* ctx, float* out, const float* in_s2d, const float* packed_w, const float* bias,
+                                               int B, int Cin, int H, int W, int Cout, float slope, int out_nc8, int out_ctotal,
+                                               int out_coff) {
+  DI_REQUIRE(H > 0 && W > 0 && ((H | W) & 1) == 0, "conv2d_wino_forward_s2d3: even H and W required");
+  return wino_forward_impl(ctx, out, in_s2d, packed_w, bias, B, 4 * Cin, H / 2, W / 2, Cout, slope, out_nc8, out_ctotal, out_coff, 2);
+}
+
+// The launch plan of the shared-transform kernel for a layer geometry (s2d 1: 5x5 stride 2, 2: 3x3 stride 2; the arguments are then the
+// space-to-depth problem's, as wino_forward_impl sees them) under the context's options; plan[6] as documented at the fill site. -1 where that kernel is not used.
 extern "C" int deepim_conv_wino_plan(deepim_ctx* ctx, int B, int Cin, int H, int W, int Cout, int out_nc8, int s2d, int* plan) {
   DI_REQUIRE(plan != nullptr, "conv_wino_plan: null plan");
   for (int i = 0; i < 9; ++i) plan[i] = -1;
   deepim_ctx defaults;                 // ctx == NULL: the plan under the default options (no device involved)
   if (!ctx) { deepim_ctx_default_options(&defaults); ctx = &defaults; }
-  return wino_forward_impl(ctx, nullptr, nullptr, nullptr, nullptr, B, Cin, H, W, Cout, 0.f, out_nc8, 0, 0, s2d != 0, plan);
+  return wino_forward_impl(ctx, nullptr, nullptr, nullptr, nullptr, B, Cin, H, W, Cout, 0.f, out_nc8, 0, 0, s2d == 2 ? 2 : s2d != 0, plan);
 }
 
 #if W8_TRACE

@@ -314,7 +314,7 @@ class deepIM_flownet(object):
                 pk = DeviceArray(ctx, (nb // 4,))
                 lib.deepim_conv_pack_weights(h, pk, self.params[name], cout, cin, kh, kw)
             self.packed[base] = pk
-        self.packed_wino, self.wino_s2d, self.wino_conv1 = {}, set(), None
+        self.packed_wino, self.wino_s2d, self.wino_conv1, self.wino_s2d3 = {}, set(), None, {}
         if self.nc8 and getattr(self, "winograd", False) and not (self.fp16_conv or self.x3_conv or getattr(self, "is_train", False)):
             hh, ww, cin = H, W, self.cin
             L = lib.load()
@@ -329,6 +329,13 @@ class deepIM_flownet(object):
                     lib.deepim_conv_wino_pack_weights_s2d(h, pk, self.params[name + "_weight"], cout, cin)
                     self.packed_wino[name] = pk
                     self.wino_s2d.add(name)
+                elif (k, s_, p_) == (3, 2, 1) and L.deepim_conv_wino_preferred_s2d3(h, B, cin, hh, ww, cout):
+                    # conv4 / conv5: the 3x3 kernel as taps 1..3 of a 5x5 stride-2 one over the same space-to-depth input (25 of the
+                    # 64 (phase, position) GEMMs live). A separate attribute, as for conv1: bench.py's accounting reads packed_wino /
+                    # wino_s2d as F(2x2,3x3) layers of 16 / 49 positions
+                    pk = DeviceArray(ctx, (L.deepim_conv_wino_packed_size(cout, 4 * cin) // 4,))
+                    lib.deepim_conv_wino_pack_weights_s2d3(h, pk, self.params[name + "_weight"], cout, cin)
+                    self.wino_s2d3[name] = pk
                 hh, ww = _out_hw(hh, ww, k, s_, p_)
                 cin = cout
             # conv1 (7x7 stride 2, 8 -> 64) as Winograd F(2x2,4x4) over its four input phases (csrc/wino_c1.hip). A separate
@@ -601,7 +608,10 @@ class deepIM_flownet(object):
         """One encoder conv (index into enc_geom) from `src` into its activation buffer, in the configured layout."""
         name, cin, h, w, cout, k, s, p = self.enc_geom[li]
         out_mode = self._enc_out_mode(li)
-        if self.nc8 and name in self.packed_wino:
+        if self._s2d3_live(li):
+            lib.deepim_conv2d_wino_forward_s2d3(self.ctx.handle, self.act[name], src, self.wino_s2d3[name], self.params[name + "_bias"],
+                                                self.B, cin, h, w, cout, ctypes.c_float(SLOPE), out_mode, 0, 0)
+        elif self.nc8 and name in self.packed_wino:
             fwd = lib.deepim_conv2d_wino_forward_s2d if name in self.wino_s2d else lib.deepim_conv2d_wino_forward
             fwd(self.ctx.handle, self.act[name], src, self.packed_wino[name], self.params[name + "_bias"],      # s2d: 5x5 stride 2 over
                 self.B, cin, h, w, cout, ctypes.c_float(SLOPE), out_mode, 0, 0)                                  # the space-to-depth tensor
@@ -618,13 +628,22 @@ class deepIM_flownet(object):
         else:
             self._conv(name, src, self.act[name], self.B, cin, h, w, cout, k, s, p, SLOPE)
 
+    def _s2d3_live(self, li):
+        """Whether encoder layer li (a 3x3 stride-2 layer bound in `wino_s2d3`) runs on the space-to-depth Winograd path now:
+        `preferred` is asked again per call, so a context switched to the canonical order after bind keeps it on the direct kernel."""
+        name, cin, h, w, cout = self.enc_geom[li][:5]
+        return (self.nc8 and name in getattr(self, "wino_s2d3", {})
+                and bool(lib.load().deepim_conv_wino_preferred_s2d3(self.ctx.handle, self.B, cin, h, w, cout)))
+
     def _enc_out_mode(self, li):
         """Output layout of encoder layer li on the channel-blocked path: 0 = NCHW (the last layer, for fc6), 3 = NC8 in
         space-to-depth order (the next layer is a stride-2 Winograd layer), 1 = NC8."""
         if li == len(self.enc_geom) - 1:
             return 0
         nxt = self.enc_geom[li + 1][0]
-        return 3 if self.nc8 and nxt in getattr(self, "wino_s2d", ()) and nxt in getattr(self, "packed_wino", {}) else 1
+        if self.nc8 and nxt in getattr(self, "wino_s2d", ()) and nxt in getattr(self, "packed_wino", {}):
+            return 3
+        return 3 if self._s2d3_live(li + 1) else 1
 
     def activation_nchw(self, name):
         """Encoder activation `name` as an NCHW device array (a converted copy when the encoder ran channel-blocked)."""
@@ -700,9 +719,12 @@ class deepIM_flownet(object):
         tensor where the encoder ran channel-blocked (one pass instead of relayout + 2-D blit), else a slice copy."""
         A, h, B = self.act, self.ctx.handle, self.B
         names = [g[0] for g in self.enc_geom]
-        if (getattr(self, "act_layout", "nchw") == "nc8" and not self.fp16_conv and name in names[:-1]
-                and self._enc_out_mode(names.index(name)) != 3):
-            lib.deepim_relayout_nc8_slice(h, A[cat], ctotal, 0, A[name], B, C, hw)
+        if getattr(self, "act_layout", "nchw") == "nc8" and not self.fp16_conv and name in names[:-1]:
+            if self._enc_out_mode(names.index(name)) == 3:   # written space-to-depth for the stride-2 layer after it
+                a = A[name]
+                lib.deepim_relayout_nc8_s2d_slice(h, A[cat], ctotal, 0, a, B, C, a.shape[2], a.shape[3])
+            else:
+                lib.deepim_relayout_nc8_slice(h, A[cat], ctotal, 0, A[name], B, C, hw)
         else:
             lib.deepim_copy_channels(h, A[cat], ctotal, 0, self.activation_nchw(name), C, B, hw)
 

@@ -113,3 +113,44 @@ for name, cin, H, W, cout in [("conv2", 64, 240, 320, 128), ("conv3", 128, 120, 
     fl = 2.0 * cout * cin * 25 * Ho * Wo * B
     print("%-8s B %2d: direct %.3f ms %5.1f TF | winograd over space-to-depth %.3f ms  %5.1f TF algorithmic | x%.2f | max diff %.1e of range | other block shape %.3f ms"
           % (name, B, d, fl / d / 1e9, wv, fl / wv / 1e9, d / wv, err, wf))
+# the 3x3 stride-2 layers: direct NC8 kernel vs the Winograd kernel over the space-to-depth input (taps 1..3 of a 5x5 stride-2 kernel,
+# 25 of 64 (phase, position) GEMMs), both timed with whatever split-K second pass their plans add
+for name, cin, H, W, cout in [("conv4", 256, 60, 80, 512), ("conv5", 512, 30, 40, 512)]:
+    if ONLY and name not in ONLY:
+        continue
+    n = B * cin * H * W
+    xn = ctx.array(np.resize(rng.standard_normal(min(n, 1 << 24)).astype(np.float32), n).reshape(B, cin, H, W))
+    x8, xs = ctx.empty((B, cin, H, W)), ctx.empty((B, 4 * cin, H // 2, W // 2))
+    lib.deepim_relayout_nc8(ctx.handle, x8, xn, B, cin, H * W, 1)
+    lib.deepim_relayout_nc8_s2d(ctx.handle, xs, xn, B, cin, H, W, 1)
+    del xn
+    w = (rng.standard_normal((cout, cin, 3, 3)) / np.sqrt(cin * 9)).astype(np.float32)
+    wd = ctx.array(w)
+    pk = DeviceArray(ctx, (lib.load().deepim_conv_packed_size(cout, cin, 3, 3) // 4,))
+    lib.deepim_conv_pack_weights(ctx.handle, pk, wd, cout, cin, 3, 3)
+    pw = DeviceArray(ctx, (lib.load().deepim_conv_wino_packed_size(cout, 4 * cin) // 4,))
+    lib.deepim_conv_wino_pack_weights_s2d3(ctx.handle, pw, wd, cout, cin)
+    bias = ctx.array(rng.standard_normal(cout).astype(np.float32))
+    Ho, Wo = H // 2, W // 2
+    o1, o2 = ctx.empty((B, cout, Ho, Wo)), ctx.empty((B, cout, Ho, Wo))
+    direct = lambda: lib.deepim_conv2d_forward_ex(ctx.handle, o1, x8, pk, bias, B, cin, H, W, cout, 3, 3, 2, 1, cf(0.1), 0, 0, 1, 1)
+    wino = lambda: lib.deepim_conv2d_wino_forward_s2d3(ctx.handle, o2, xs, pw, bias, B, cin, H, W, cout, cf(0.1), 1, 0, 0)
+    def wino_other():   # the other block shape
+        lib.deepim_set_option(ctx.handle, b"wino_wide", WIDE1); wino(); lib.deepim_set_option(ctx.handle, b"wino_wide", WIDE0)
+    direct(); wino()
+    a, b = o1.asnumpy(), o2.asnumpy()
+    err = float(np.abs(a - b).max() / max(1.0, np.abs(a).max()))
+    ts = {}
+    for r in range(ROUNDS):
+        for key, fn in (("direct", direct), ("wino", wino), ("other", wino_other)):
+            fn()
+            t = ctx.timer(); t.start()
+            for _ in range(REPS):
+                fn()
+            t.stop()
+            ts.setdefault(key, []).append(t.elapsed_ms() / REPS)
+    d, wv, wo = (float(np.median(ts[k])) for k in ("direct", "wino", "other"))
+    fl = 2.0 * cout * cin * 9 * Ho * Wo * B
+    fle = 2.0 * cout * cin * 25 * B * ((Ho + 1) // 2) * ((Wo + 1) // 2)
+    print("%-8s B %2d: direct %.3f ms %5.1f TF | winograd over space-to-depth %.3f ms  %5.1f TF algorithmic, %5.1f TF executed | x%.2f | max diff %.1e of range | other block shape %.3f ms"
+          % (name, B, d, fl / d / 1e9, wv, fl / wv / 1e9, fle / wv / 1e9, d / wv, err, wo))
