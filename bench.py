@@ -10,6 +10,11 @@ OpenGL window) + rendered-mask / observed-mask update (deepim/cor
 feeding the next iteration's ZoomMask.  `--prestaged` skips the re-render and feeds pre-staged frames instead.
 Inputs are resident in HBM before the timed region.
 
+A plain run sets up, warms up, times `--steps` steps, writes `--dump-outputs` and prints its line.  Everything else — the
+auxiliary steps behind `roofline_zoom` / `render_ms` / `allgather_us`, the per-layer timings, the oracle parity replay, the CPU
+baseline, the other configurations, at N>1 the weak-scaling figure and the all-gather checks — runs with `--full` only, after the
+timed region.
+
 N>1: one process per GPU (the driver launches them with torch.distributed.run; this file only reads the RANK /
 WORLD_SIZE / LOCAL_RANK / MASTER_* variables it sets and never imports torch).  Pairs are independent; after every
 refinement iteration the refined poses are all-gathered with ONE `ncclAllGather` (RCCL over xGMI, 48 B/pair)
@@ -513,7 +518,7 @@ def dry_run(args, rank, world, rdzv):
                        "devices_opened_by_rank": [json.loads(r.decode())["opened"] for r in recs]}
         out["roofline"] = None
         out["dry_run"] = True
-        print(json.dumps(out) if args.full else compact_line(out))
+        print(json.dumps(out) if args.full_record else compact_line(out))
         sys.stdout.flush()
     rdzv.close()
 
@@ -589,10 +594,12 @@ class Loop(object):
         # iteration — every event record costs the stream ~5 µs (profiles/r03_heads_b4_iteration_trace.txt: the gaps sit exactly at
         # the records), which is 1-2 % of a B = 4 iteration with six of them. The front end, the re-render and the pose gather are
         # timed by the same events over AUX_STEPS extra steps right after the timed region.
+        # AUX_STEPS run with --full only: a plain run times its steps and nothing else
+        aux = self.aux_steps = self.AUX_STEPS if args.full else 0
         self.enc_timers = [[ctx.timer() for _ in range(NIT)] for _ in range(max(steps, self.AUX_STEPS))]
-        self.zoom_timers = [[ctx.timer() for _ in range(NIT)] for _ in range(self.AUX_STEPS)]
-        self.render_timers = [[ctx.timer() for _ in range(NIT - 1)] for _ in range(self.AUX_STEPS)]
-        self.gather_timers = [[ctx.timer() for _ in range(NIT)] for _ in range(self.AUX_STEPS)] if world > 1 else None
+        self.zoom_timers = [[ctx.timer() for _ in range(NIT)] for _ in range(aux)]
+        self.render_timers = [[ctx.timer() for _ in range(NIT - 1)] for _ in range(aux)]
+        self.gather_timers = [[ctx.timer() for _ in range(NIT)] for _ in range(aux)] if world > 1 else None
         self.use_graph = args.graph == "on"
         self.enc_graph = None
         # "step": the whole step as hipGraph segments (auto: where the launches are short enough for the host gaps and the event records
@@ -743,20 +750,22 @@ class Loop(object):
         dt = time.perf_counter() - t0
         if self.args.dump_outputs:                # the last timed step's results, before the auxiliary steps below recompute them
             self.outputs = self.last_outputs()
-        for s_ in range(self.AUX_STEPS):          # outside the timed region: front end / re-render / pose gather, by HIP events
-            self.step(self.enc_timers[s_] if self.step_graphs else None, self.zoom_timers[s_], self.render_timers[s_],
-                      self.gather_timers[s_] if self.gather_timers else None)
-        self.fence()
+        if self.aux_steps:
+            for s_ in range(self.aux_steps):      # outside the timed region: front end / re-render / pose gather, by HIP events
+                self.step(self.enc_timers[s_] if self.step_graphs else None, self.zoom_timers[s_], self.render_timers[s_],
+                          self.gather_timers[s_] if self.gather_timers else None)
+            self.fence()
         if self.world > 1:
             dt_local = dt
             dt = self.comm.max_over_ranks(dt_local) if self.comm is not None else self.rdzv.max(dt_local)   # MAX over ranks
-            assert abs(dt - self.rdzv.max(dt_local)) < 1e-9, "device and host max-over-ranks disagree"
-            # the gather really delivered every rank's poses, in rank order
-            got = self.gather_out.asnumpy().reshape(self.world, self.Bmax, 12)
-            mine = self.rdzv.all_gather(self.pose_cur.asnumpy().reshape(self.B, 12))
-            for r in range(self.world):
-                assert np.array_equal(got[r, :len(mine[r])], mine[r]), "all-gather returned wrong poses for rank %d" % r
-        # sanity: poses finite, zoom status clean
+            if self.args.full:
+                assert abs(dt - self.rdzv.max(dt_local)) < 1e-9, "device and host max-over-ranks disagree"
+                # the gather really delivered every rank's poses, in rank order
+                got = self.gather_out.asnumpy().reshape(self.world, self.Bmax, 12)
+                mine = self.rdzv.all_gather(self.pose_cur.asnumpy().reshape(self.B, 12))
+                for r in range(self.world):
+                    assert np.array_equal(got[r, :len(mine[r])], mine[r]), "all-gather returned wrong poses for rank %d" % r
+        # sanity: poses finite, zoom status clean (a figure measured on broken poses is no figure)
         st = ctypes.c_int(0)
         lib.deepim_zoom_status(h, ctypes.byref(st))
         assert np.all(np.isfinite(self.pose_cur.asnumpy())) and st.value == 0, ("bad poses / zoom status", st.value)
@@ -777,7 +786,7 @@ class Loop(object):
 
     def means(self):
         m = lambda rows: float(np.mean([t.elapsed_ms() for row in rows for t in row])) if rows and rows[0] else None   # noqa: E731
-        return {"enc_ms": m(self.enc_timers[:self.AUX_STEPS] if self.step_graphs else self.enc_timers[:self.steps]), "zoom_ms": m(self.zoom_timers), "render_ms": m(self.render_timers),
+        return {"enc_ms": m(self.enc_timers[:self.aux_steps] if self.step_graphs else self.enc_timers[:self.steps]), "zoom_ms": m(self.zoom_timers), "render_ms": m(self.render_timers),
                 "gather_ms": m(self.gather_timers) if self.gather_timers else None}
 
 
@@ -789,13 +798,13 @@ def main():
     ap.add_argument("--batch", type=int, default=32, help="pairs in the batch (bs32 of BASELINE.json's metric): the GLOBAL batch, "
                     "sharded over the GPUs in contiguous blocks (strong scaling, BASELINE configs[2] as written) — per GPU with --weak")
     ap.add_argument("--global-batch", type=int, default=0, help="strong scaling with this many pairs in total (overrides --batch)")
-    ap.add_argument("--weak", action="store_true", help="weak scaling: --batch pairs PER GPU, N x batch in total (at N > 1 the default "
+    ap.add_argument("--weak", action="store_true", help="weak scaling: --batch pairs PER GPU, N x batch in total (at N > 1 a --full "
                     "run appends this figure to `other_configs` next to the strong-scaling headline)")
     ap.add_argument("--allow-comm-fallback", action="store_true", help="N > 1 only: if RCCL cannot be brought up on every rank, run "
                     "the pose exchange through the TCP rendezvous instead of exiting non-zero (the line then says "
                     "comm.backend = tcp-fallback; never an xGMI number)")
     ap.add_argument("--iters", type=int, default=4, help="refinement iterations per step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--fp16", action="store_true", help="BASELINE config 5 mode: conv stack on the fp16 matrix cores "
                     "(NOT the headline: reduced precision; reported with dtype f16)")
     ap.add_argument("--no-winograd", action="store_true", help="fp32 path: keep conv3_1 / conv4_1 / conv5_1 / conv6_1 on the direct "
@@ -805,11 +814,11 @@ def main():
     ap.add_argument("--x3", action="store_true", help="split-fp16 conv mode: conv2 … conv6_1 as hi·hi + hi·lo + lo·hi on the "
                     "fp16 matrix cores with fp32 accumulation — fp32-grade results (≈1e-6 of the fp32 path, inside north_star's "
                     "1e-4), not bit-exact; reported with dtype f16x3 next to the bit-exact fp32 headline")
-    ap.add_argument("--layers", action="store_true", help="also report per-layer conv timings")
+    ap.add_argument("--layers", action="store_true", help="with --full: also report the per-layer conv timings in the record")
     ap.add_argument("--heads", action="store_true", help="BASELINE config 4 mode: full test graph (FAST_TEST off) with the "
                     "FlowNetS decoder and the mask / flow heads in every iteration (NOT the headline)")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the short secondary runs of the other BASELINE "
-                    "configurations (B=16, B=4 share of config 3, config 4 heads, config 5 fp16) that the default N=1 run "
+    ap.add_argument("--no-other-configs", action="store_true", help="--full: skip the short secondary runs of the other BASELINE "
+                    "configurations (B=16, B=4 share of config 3, config 4 heads, config 5 fp16) that a default N=1 --full run "
                     "appends to its JSON line as `other_configs` (and, at N > 1, the weak-scaling figure)")
     ap.add_argument("--autotune", action="store_true", help="dev: let the library time split-K factors per conv geometry on "
                     "the first call instead of using the deterministic cost-model plan")
@@ -833,24 +842,30 @@ def main():
     ap.add_argument("--dry-run", action="store_true", help="launch rehearsal without a GPU: the same rank / rendezvous / shard / "
                     "per-iteration pose all-gather (host backend) / max-over-ranks / one-JSON-line-from-rank-0 code path with a "
                     "host stand-in for the refinement step; the line carries \"dry_run\": true and no roofline")
-    ap.add_argument("--verify", type=int, default=2, help="parity of THIS configuration, outside the timed region, N=1 only: "
+    ap.add_argument("--verify", type=int, default=2, help="--full: parity of THIS configuration, outside the timed region, N=1 only: "
                     "after the timed loop one more step is run and for this many sampled pairs every one of its refinement "
                     "iterations is replayed through the CPU oracle (fed the frames the GPU rendered) → `parity` in the JSON "
                     "line; 0 = off")
-    ap.add_argument("--no-layer-timings", action="store_true", help="skip the per-layer HIP-event timings after the timed region (6 extra launches per "
+    ap.add_argument("--no-layer-timings", action="store_true", help="--full: skip the per-layer HIP-event timings after the timed region (6 extra launches per "
                     "encoder layer; the rocprofv3 passes of tools/run_profiles.sh cut the trace by iteration count and must not see them)")
-    ap.add_argument("--full", action="store_true", help="print the full record (what bench_detail.json holds) as the final line instead "
-                    "of the compact one the driver parses (used by the secondary runs and the tests that read its fields)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also measure and check everything the headline does not "
+                    "need: the auxiliary steps (front end / re-render / pose gather times, roofline_zoom), the per-layer timings, the "
+                    "parity replay (--verify), the CPU baseline, the other configurations and, at N > 1, the weak-scaling figure and the "
+                    "all-gather checks. Without it a run sets up, warms up, times the steps, dumps its outputs and prints its line")
+    ap.add_argument("--full-record", action="store_true", help="print the full record (what bench_detail.json holds) as the final line "
+                    "instead of the compact one the driver parses (used by the secondary runs and the tests that read its fields)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step "
                     "computed as DIR/<name>.npy (float32): pose_est (the refined poses; every rank's at N > 1), se3 and zoom_factor of its "
                     "last iteration, and with --heads mask_observed_pred and flow_est; at most 64 MB in all (above that the per-pixel "
                     "arrays keep a fixed, seeded sample of pairs, listed in <name>_pairs.npy). Inputs and weights are seeded, so the same "
                     "arguments give the same inputs on every run")
-    ap.add_argument("--extras-budget", type=float, default=200.0, help="wall-clock budget in seconds for everything after the "
+    ap.add_argument("--extras-budget", type=float, default=200.0, help="--full: wall-clock budget in seconds for everything after the "
                     "timed region (parity, CPU baseline, other configs); what does not fit is reported as skipped")
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.layers and not args.full:
+        ap.error("--layers reports the per-layer timings of a --full run: pass --full too")
     args.lit = args.lit == "on" or (args.lit == "auto" and args.fp16 and args.depth)
 
     rank = int(os.environ.get("RANK", "0"))
@@ -928,11 +943,11 @@ def main():
     my_rec = comm_record(h)
     recs = [json.loads(r.decode()) for r in rdzv.all_gather(json.dumps(my_rec).encode())] if world > 1 else [my_rec]
 
-    # N > 1, default configuration: the weak-scaling figure (--batch pairs PER GPU) next to the strong-scaling headline — a
+    # N > 1, default configuration, --full: the weak-scaling figure (--batch pairs PER GPU) next to the strong-scaling headline — a
     # second, short timed run of the same loop on every rank
     weak = None
     plain = not (args.fp16 or args.x3 or args.heads or args.prestaged or args.layers or args.depth or args.weak)
-    if world > 1 and plain and not args.no_other_configs:
+    if args.full and world > 1 and plain and not args.no_other_configs:
         Lw = Loop(args, ctx, rdzv, comm, rank, world, args.batch, args.batch, world * args.batch, False, 8)
         dtw = Lw.time(2)
         mw = Lw.means()
@@ -947,9 +962,7 @@ def main():
         mm = L.means()
         enc_ms, zoom_ms = mm["enc_ms"], mm["zoom_ms"]
         flops = encoder_flops_per_pair(net.cin) * B
-        achieved = flops / (enc_ms * 1e-3) / 1e12
         wino_layers = sorted(getattr(net, "packed_wino", {}))
-        executed = encoder_executed_flops_per_pair(net) * B / (enc_ms * 1e-3) / 1e12
         peak = 2500.0 if args.fp16 else FP32_PEAK_TFLOPS   # dense fp16 MFMA peak, MI355X_MICROARCH.md
         if args.x3:   # three fp16 MFMA products per algorithmic multiply-add on conv2 … conv6_1: peak in algorithmic FLOPs
             peak = 2500.0 / 3.0
@@ -964,9 +977,11 @@ def main():
                  "encoder conv group: conv_f16_dma_kernel<X3> (3 fp16 MFMAs per product; peak = 2.5 PF / 3) + conv1_x3_kernel" if args.x3 else
                  "encoder conv group, 10 layers, fp32 MFMA: conv_direct, conv_nc8" +
                  (", conv_wino8/4 (F(2x2,3x3): %d layers)" % len(wino_layers) if wino_layers else "") + " kernels")
-        rl, rl_hbm = roofline_block(kname, flops, encoder_executed_flops_per_pair(net) * B, enc_ms, peak, wino_layers, traffic, traffic_src,
-                                    os.path.join(ROOT, "profiles", "per_kernel.json"), B,
-                                    plain=not (args.fp16 or args.x3 or args.heads or args.depth) and bool(wino_layers))
+        rl, rl_hbm = None, None       # no encoder times without --full when the timed steps replay whole-step graphs (no events inside)
+        if enc_ms is not None:
+            rl, rl_hbm = roofline_block(kname, flops, encoder_executed_flops_per_pair(net) * B, enc_ms, peak, wino_layers, traffic,
+                                        traffic_src, os.path.join(ROOT, "profiles", "per_kernel.json"), B,
+                                        plain=not (args.fp16 or args.x3 or args.heads or args.depth) and bool(wino_layers))
         out = headline(args, world, NIT, dt, pairs_total, scaling, args.steps, args.warmup, gbatch if scaling == "strong" else B)
         cback = "none" if world == 1 else ("rccl" if comm is not None else ("tcp-fallback" if backend == "rccl" else "tcp-host-requested"))
         out["comm"] = {
@@ -992,21 +1007,22 @@ def main():
                        "parallelism": ("%d process(es), one per GPU, contiguous pair blocks; one RCCL ncclAllGather of the poses per iteration" % world) if comm_note is None
                                       else "%d ranks; %s; poses through the TCP rendezvous" % (world, comm_note)},
             "roofline": rl,
-            "roofline_zoom": {"bound": "hbm", "kernel": "bbox + zoom_factor + resample (fused front end)",
-                              "achieved": zoom_bytes / (zoom_ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                              "frac": zoom_bytes / (zoom_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, "ms": zoom_ms,
-                              "note": "algorithmic bytes = read + write of every zoomed channel once (SURVEY 8d); the fused "
-                                      "front end keeps BilinearSampler's float/double blend bit for bit (VALU work ~ the "
-                                      "HBM time), see profiles/r03_zoom_ablation.md"},
         })
+        if zoom_ms is not None:           # the auxiliary steps of a --full run
+            out["roofline_zoom"] = {"bound": "hbm", "kernel": "bbox + zoom_factor + resample (fused front end)",
+                                    "achieved": zoom_bytes / (zoom_ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                    "frac": zoom_bytes / (zoom_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, "ms": zoom_ms,
+                                    "note": "algorithmic bytes = read + write of every zoomed channel once (SURVEY 8d); the fused "
+                                            "front end keeps BilinearSampler's float/double blend bit for bit (VALU work ~ the "
+                                            "HBM time), see profiles/r03_zoom_ablation.md"}
         if rl_hbm:
             out["roofline_hbm"] = rl_hbm      # the Z / H / F kernels SURVEY 8(d) lists, algorithmic bytes / recorded time / 8 TB/s each
-        if not args.prestaged and NIT > 1:
+        if not args.prestaged and NIT > 1 and mm["render_ms"] is not None:
             out["render_ms"] = mm["render_ms"]
         if weak is not None:
             out.setdefault("other_configs", {})["weak_scaling_batch%d_per_gpu" % args.batch] = weak
-        # ---- everything below is OUTSIDE the timed region and bounded by --extras-budget; the headline above is
-        # complete already, and is printed even if the process is told to stop while the extras run
+        # ---- everything below runs with --full only, OUTSIDE the timed region and bounded by --extras-budget; the headline
+        # above is complete already, and is printed even if the process is told to stop while the extras run
         emitted = [False]
 
         def emit(*_sig):
@@ -1017,7 +1033,7 @@ def main():
                         json.dump(out, f, indent=1)
                 except OSError:
                     pass
-                if args.full:
+                if args.full_record:
                     print(json.dumps(out))
                 else:
                     for row in detail_lines(out):
@@ -1026,38 +1042,39 @@ def main():
                 sys.stdout.flush()
             if _sig:
                 os._exit(0)
-        import signal
-        for sg in (signal.SIGTERM, signal.SIGINT):
-            signal.signal(sg, emit)
-        deadline = time.time() + args.extras_budget
-        sys.stderr.write("[bench] timed region complete; extras (parity, CPU baseline, other configs) run under a %.0f s budget\n"
-                         % args.extras_budget)
-        sys.stderr.flush()
+        if args.full:
+            import signal
+            for sg in (signal.SIGTERM, signal.SIGINT):
+                signal.signal(sg, emit)
+            deadline = time.time() + args.extras_budget
+            sys.stderr.write("[bench] timed region complete; extras (parity, CPU baseline, other configs) run under a %.0f s budget\n"
+                             % args.extras_budget)
+            sys.stderr.flush()
 
-        def left():
-            return deadline - time.time()
-        if not (args.fp16 or args.x3 or args.no_layer_timings):       # live, this run: every encoder layer alone -> the dominant kernel's own roofline fraction
-            lt = layer_timings(ctx, net, peak=peak)
-            dom = max(lt, key=lambda r: r["ms"])
-            fam = [r for r in lt if r["kernel"] == dom["kernel"]]
-            rl["layers_live"] = lt
-            rl["dominant_kernel"] = "%s (%s)" % (dom["kernel"], ", ".join(r["layer"] for r in fam))
-            rl["dominant_ms"] = sum(r["ms"] for r in fam)
-            rl["dominant_achieved"] = sum(r["tflops_executed"] * r["ms"] for r in fam) / rl["dominant_ms"]
-            rl["dominant_frac"] = rl["dominant_achieved"] / peak
-            if args.layers:
-                out["layers"] = lt
-        if world == 1 and args.verify > 0:
-            try:
-                out["parity"] = verify_parity(args, cfg, net, params, ctx, step, pose_cur, batch["K"], B)
-            except Exception as e:                       # a checker failure must not lose the measured line — but it is loud
-                out["parity"] = {"error": repr(e)[:300], "within_bar": False}
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(params, cfg, batch, with_depth=args.depth)
-        default_run = (world == 1 and plain and not args.global_batch
-                       and args.batch == 32 and not args.no_other_configs and not args.no_cpu_baseline)
-        if default_run:
-            out["other_configs"] = other_configs(left)
+            def left():
+                return deadline - time.time()
+            if not (args.fp16 or args.x3 or args.no_layer_timings):       # live, this run: every encoder layer alone -> the dominant kernel's own roofline fraction
+                lt = layer_timings(ctx, net, peak=peak)
+                dom = max(lt, key=lambda r: r["ms"])
+                fam = [r for r in lt if r["kernel"] == dom["kernel"]]
+                rl["layers_live"] = lt
+                rl["dominant_kernel"] = "%s (%s)" % (dom["kernel"], ", ".join(r["layer"] for r in fam))
+                rl["dominant_ms"] = sum(r["ms"] for r in fam)
+                rl["dominant_achieved"] = sum(r["tflops_executed"] * r["ms"] for r in fam) / rl["dominant_ms"]
+                rl["dominant_frac"] = rl["dominant_achieved"] / peak
+                if args.layers:
+                    out["layers"] = lt
+            if world == 1 and args.verify > 0:
+                try:
+                    out["parity"] = verify_parity(args, cfg, net, params, ctx, step, pose_cur, batch["K"], B)
+                except Exception as e:                       # a checker failure must not lose the measured line — but it is loud
+                    out["parity"] = {"error": repr(e)[:300], "within_bar": False}
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(params, cfg, batch, with_depth=args.depth)
+            default_run = (world == 1 and plain and not args.global_batch
+                           and args.batch == 32 and not args.no_other_configs and not args.no_cpu_baseline)
+            if default_run:
+                out["other_configs"] = other_configs(left)
         emit()
     if comm is not None:
         comm.close()
@@ -1107,8 +1124,8 @@ def other_configs(left=lambda: 1e9):
             res[name] = {"skipped": "extras budget spent"}
             continue
         try:
-            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--steps", "8", "--warmup", "2", "--no-cpu-baseline",
-                                "--no-other-configs", "--full"] + extra, capture_output=True, text=True, timeout=max(30.0, min(150.0, left())))
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--steps", "8", "--warmup", "2", "--full", "--no-cpu-baseline",
+                                "--no-other-configs", "--full-record"] + extra, capture_output=True, text=True, timeout=max(30.0, min(150.0, left())))
             j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
             res[name] = {"value": j["value"], "unit": j["unit"], "ms_per_step": j["ms_per_step"], "dtype": j["dtype"],
                          "workload": j["config"]["workload"], "conv_tflops_executed": j["roofline"]["achieved"],

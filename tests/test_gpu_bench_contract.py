@@ -24,7 +24,7 @@ def _last_json(out):
 
 
 def test_bench_line_single_gpu():
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "1", "--warmup", "1", "--batch", "2", "--no-cpu-baseline",
+    r = subprocess.run([sys.executable, "bench.py", "--steps", "1", "--warmup", "1", "--batch", "2", "--full", "--no-cpu-baseline",
                         "--verify", "0"], cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     last = r.stdout.strip().splitlines()[-1]
@@ -43,6 +43,27 @@ def test_bench_line_single_gpu():
     rf = d["roofline"]
     assert rf["bound"] == "mfma" and rf["unit"] == "TFLOP/s" and abs(rf["frac"] - rf["achieved"] / rf["peak"]) < 1e-4
     assert 0 < rf["frac"] < 1 and d["config"]["workload"]
+
+
+def test_plain_run_times_its_steps_and_nothing_else():
+    """Without --full a run sets up, warms up, times its steps and prints the line: the contract's keys and the encoder roofline
+    from the HIP events inside the timed steps, but no auxiliary steps (roofline_zoom, render_ms), no per-layer timings, no parity
+    replay, no CPU baseline and no other configurations."""
+    r = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--batch", "2"], cwd=ROOT, capture_output=True,
+                       text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    last = r.stdout.strip().splitlines()[-1]
+    assert len(last) < 4096, len(last)
+    d = json.loads(last)
+    for k in REQUIRED:
+        assert k in d, k
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["dtype"] == "f32" and d["higher_is_better"] is True
+    assert abs(d["value"] - 2 * 4 * 2 / (d["ms_per_step"] * 2e-3)) < 1e-6 * d["value"]
+    rf = d["roofline"]
+    assert 0 < rf["frac"] < 1 and abs(rf["frac"] - rf["achieved"] / rf["peak"]) < 1e-4 and "dominant_frac" not in rf
+    for k in ("roofline_zoom", "render_ms", "parity", "cpu_baseline", "other_configs"):
+        assert k not in d, k
+    assert "timed region complete" not in r.stderr and d["comm"]["allgather_us"] is None
 
 
 def test_bench_dump_outputs_of_the_last_timed_step(tmp_path):
@@ -72,7 +93,7 @@ def test_bench_reports_parity_of_the_timed_configuration(extra, bar):
     sampled pairs replayed through the CPU oracle.  Bars: pose and se3 <= 1e-4 relative, zoom factors / crop indices /
     net input bit-exact."""
     r = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-other-configs",
-                        "--full", "--verify", "2"] + extra, cwd=ROOT, capture_output=True, text=True, timeout=1500)
+                        "--full", "--full-record", "--verify", "2"] + extra, cwd=ROOT, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _last_json(r.stdout)
     p = d["parity"]
@@ -89,7 +110,7 @@ def test_bench_parity_heads_and_config5_modes():
     written (`--fp16 --depth`: RGB-D input, against the oracle's fp16 emulation, bars 1e-4 / 1e-3)."""
     for extra in (["--heads", "--batch", "4"], ["--fp16", "--depth", "--batch", "8"]):
         r = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-other-configs",
-                            "--full", "--verify", "1"] + extra, cwd=ROOT, capture_output=True, text=True, timeout=1500)
+                            "--full", "--full-record", "--verify", "1"] + extra, cwd=ROOT, capture_output=True, text=True, timeout=1500)
         assert r.returncode == 0, r.stderr[-2000:]
         d = _last_json(r.stdout)
         p = d["parity"]
@@ -106,7 +127,7 @@ def test_headline_survives_a_sigterm_during_the_extras():
     announces the end of the timed region on stderr; SIGTERM after that → exactly one JSON line on stdout, exit code 0."""
     import signal
     import time
-    p = subprocess.Popen([sys.executable, "bench.py", "--steps", "1", "--warmup", "1", "--batch", "2", "--verify", "2",
+    p = subprocess.Popen([sys.executable, "bench.py", "--steps", "1", "--warmup", "1", "--batch", "2", "--full", "--verify", "2",
                           "--no-other-configs"], cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
     t0 = time.time()
     seen = False
@@ -146,7 +167,7 @@ def test_bench_two_ranks_weak_scaling_dry_run():
 def test_bench_two_ranks_default_is_strong_scaling_of_the_global_batch():
     """What the driver passes is `--gpus N` only: the batch is then GLOBAL (here --batch 4 → 2 per rank), strong scaling, and the
     default run appends the weak-scaling figure (--batch per GPU) to other_configs."""
-    d = _run_two_ranks(29673, ["--batch", "4"])
+    d = _run_two_ranks(29673, ["--batch", "4", "--full-record"])
     assert d["n_gpus"] == 2 and d["scaling"] == "strong" and d["config"]["global_batch"] == 4 and d["config"]["shard_counts"] == [2, 2]
     assert abs(d["value"] - 4 * 4 * 1 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"] and "bs4" in d["metric"]
     w = d["other_configs"]["weak_scaling_batch4_per_gpu"]
@@ -172,7 +193,8 @@ def test_bench_two_ranks_default_backend_agrees_on_the_rendezvous_fallback():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     env.pop("DEEPIM_BENCH_BACKEND", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", "29679", "bench.py", "--gpus", "2", "--steps", "1", "--warmup", "1", "--batch", "4", "--no-other-configs", "--full"]
+           "--master-port", "29679", "bench.py", "--gpus", "2", "--steps", "1", "--warmup", "1", "--batch", "4", "--no-other-configs", "--full",
+           "--full-record"]
     if ndev.value < 2:
         r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1200)
         assert r.returncode != 0 and not [l for l in r.stdout.splitlines() if l.startswith("{")], (r.stdout[-1500:], r.stderr[-1500:])

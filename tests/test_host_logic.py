@@ -317,7 +317,7 @@ def test_eight_rank_launch_rehearsal(global_batch, counts):
     global_batch = global_batch or 32
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr",
                         "127.0.0.1", "--master-port", str(port), "bench.py", "--gpus", "8", "--steps", "2", "--warmup", "1",
-                        "--dry-run", "--full"] + extra, cwd=root, capture_output=True, text=True, timeout=900,
+                        "--dry-run", "--full-record"] + extra, cwd=root, capture_output=True, text=True, timeout=900,
                        env=dict(os.environ, MASTER_ADDR="127.0.0.1"))
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -553,6 +553,15 @@ def test_bench_dry_run_dumps_outputs(tmp_path):
     r = subprocess.run([sys.executable, "bench.py", "--dry-run", "--steps", "0"], cwd=root, capture_output=True, text=True,
                        timeout=300)
     assert r.returncode != 0 and "--steps" in r.stderr
+
+
+def test_bench_layers_needs_full():
+    """--layers adds the per-layer timings of a --full run to its record: alone it is refused, before anything runs."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, "bench.py", "--dry-run", "--layers"], cwd=root, capture_output=True, text=True, timeout=300)
+    assert r.returncode != 0 and "--full" in r.stderr
 
 
 def test_bench_roofline_block_is_physical(tmp_path):
