@@ -372,7 +372,8 @@ int deepim_conv2d_wino_forward(deepim_ctx* ctx, float* out, const float* in, con
  * (csrc/wino_c1.hip): 81 (phase, position) GEMMs over the 8 channels per 2x2 tile, 2.42x fewer multiplies than the direct sum,
  * within 1e-5 of the layer's range from it. `in` is the NCHW (B, 8, H, W) net input; `out` is NC8 (out_mode 1) or NC8 in
  * space-to-depth order (out_mode 3, even output height and width: what the stride-2 Winograd layer conv2 reads). packed_w from
- * deepim_conv1_wino_pack_weights (the layer's (64, 8, 7, 7) weights; size deepim_conv1_wino_packed_size() bytes). _preferred is 0
+ * deepim_conv1_wino_pack_weights (the layer's (64, 8, 7, 7) weights; size deepim_conv1_wino_packed_size() bytes, laid out for the
+ * shared-transform kernel's 32x32x2 MFMAs: [channel half][pair][lane][4 k-steps]; query the size, the layout may change). _preferred is 0
  * for any other geometry and on a context in the canonical-summation-order configuration ("conv_max_split" = 1). */
 size_t deepim_conv1_wino_packed_size(void);
 int deepim_conv1_wino_preferred(deepim_ctx* ctx, int B, int Cin, int H, int W, int Cout);
