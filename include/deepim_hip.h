@@ -366,6 +366,15 @@ int deepim_conv_wino_pack_weights_s2d3(deepim_ctx* ctx, float* packed_w, const f
 int deepim_conv2d_wino_forward_s2d3(deepim_ctx* ctx, float* out, const float* in_s2d, const float* packed_w, const float* bias,
                                     int B, int Cin, int H, int W, int Cout, float slope, int out_nc8, int out_ctotal, int out_coff);
 int deepim_relayout_nc8_s2d(deepim_ctx* ctx, float* dst, const float* src, int B, int C, int H, int W, int to_s2d);
+/* The DATA GRADIENT of a 3x3 stride-1 pad-1 layer on the same kernels: it is the same kind of convolution from the layer's Cout to its
+ * Cin channels on the transposed, flipped weights. _pack_weights_dgrad writes U' of that Cin <- Cout problem straight from the layer's
+ * raw (Cout, Cin, 3, 3) tensor (size deepim_conv_wino_packed_size(Cin, Cout); needs Cin % 32 == 0, Cout % 8 == 0) — bit-identical to
+ * deepim_conv_wino_pack_weights on deepim_conv_flip_weights of it, without the flip buffer. deepim_conv2d_wino_dgrad: dx (B, Cin, H, W)
+ * NCHW from the channel-blocked dz (B, Cout/8, H, W, 8), no bias, no activation; <= 1e-5 of the range from the direct sum. Worth it
+ * where deepim_conv_wino_preferred(ctx, B, Cout, H, W, Cin) says so. */
+int deepim_conv_wino_pack_weights_dgrad(deepim_ctx* ctx, float* packed_w, const float* w /*Cout,Cin,3,3 dev*/, int Cout, int Cin);
+int deepim_conv2d_wino_dgrad(deepim_ctx* ctx, float* dx, const float* dz_nc8, const float* packed_w, int B, int Cin, int H, int W,
+                             int Cout);
 int deepim_conv2d_wino_forward(deepim_ctx* ctx, float* out, const float* in, const float* packed_w, const float* bias,
                                int B, int Cin, int H, int W, int Cout, float slope, int out_nc8, int out_ctotal, int out_coff);
 /* conv1 (7x7 stride 2 pad 3, Cin 8, Cout 64, deepIM_flownet.py:63) as fp32 Winograd F(2x2,4x4) over its four input phases
@@ -609,6 +618,11 @@ int deepim_bias_grad(deepim_ctx* ctx, float* db, const float* dz, int B, int C, 
  * be dy; add may be NULL), db[c] = sum of dz — what the training graph needs per encoder layer */
 int deepim_lrelu_bias_backward(deepim_ctx* ctx, float* dz, float* db, const float* dy, const float* add, const float* y,
                                float slope, int B, int C, size_t hw);
+/* the same walk where the saved output lies channel-blocked: y_mode 1 = NC8 (B, C/8, H, W, 8), 3 = NC8 in space-to-depth order (even H
+ * and W), 0 = NCHW like the gradients (the last encoder layer: taken for its dz_nc8 output); C % 8 == 0. dy / add / dz stay NCHW and dz holds the same bits as above on the NCHW copy of y; dz_nc8 (may be NULL) receives
+ * the same dz values once more as plain NC8 records — the input of deepim_conv2d_wino_dgrad */
+int deepim_lrelu_bias_backward_nc8(deepim_ctx* ctx, float* dz, float* dz_nc8, float* db, const float* dy, const float* add,
+                                   const float* y_nc8, int y_mode, float slope, int B, int C, int H, int W);
 /* wt (Cin,Cout,kh,kw) = w (Cout,Cin,kh,kw) transposed and flipped: the weights with which the data gradient of a
  * convolution is itself a stride-1 convolution (pad kh-1-p) — run on deepim_conv2d_forward after deepim_conv_pack_weights */
 int deepim_conv_flip_weights(deepim_ctx* ctx, float* wt, const float* w, int Cout, int Cin, int kh, int kw);
@@ -671,6 +685,10 @@ int deepim_conv2d_wgrad(deepim_ctx* ctx, float* dw, const float* x, const float*
  * option "wgrad_lds" on. deepim_sgd_mom_update_multi reads it in place; deepim_weight_grad_to_natural gives (Cout,Cin,kh,kw). */
 int deepim_conv2d_wgrad_tm(deepim_ctx* ctx, float* dw_tm, const float* x, const float* dz, int B, int Cin, int H, int W, int Cout,
                            int kh, int kw, int stride, int pad);
+/* ... with a channel-blocked x operand (x_mode 1 = NC8, 3 = NC8 in space-to-depth order, even H and W): a thread's eight K rows are
+ * one 32-byte record of x. Only the loads differ: bit-identical to deepim_conv2d_wgrad_tm on the NCHW copy of the same tensor. */
+int deepim_conv2d_wgrad_tm_nc8(deepim_ctx* ctx, float* dw_tm, const float* x_nc8, int x_mode, const float* dz, int B, int Cin, int H,
+                               int W, int Cout, int kh, int kw, int stride, int pad);
 int deepim_weight_grad_to_natural(deepim_ctx* ctx, float* dw, const float* dw_tm, int Cout, int Cin, int khw);
 /* weight AND bias gradient of a layer (db[c] = sum of dz): one launch for the few-filter layers (Cout <= 4, 3x3 / 4x4: the
  * prediction heads), deepim_bias_grad + deepim_conv2d_wgrad otherwise */

@@ -62,7 +62,13 @@ def default_config():
                          optimizer="sgd", lr=0.0001, momentum=0.975, wd=0.0005,   # config.py:68-77
                          # mixed-precision training (network.FP16_CONV in the training graph; not reference keys): the initial loss
                          # scale (a power of two) and the number of overflow-free steps after which it doubles
-                         FP16_LOSS_SCALE=FP16_LOSS_SCALE_DEFAULT, FP16_SCALE_WINDOW=FP16_SCALE_WINDOW_DEFAULT)
+                         FP16_LOSS_SCALE=FP16_LOSS_SCALE_DEFAULT, FP16_SCALE_WINDOW=FP16_SCALE_WINDOW_DEFAULT,
+                         # fp32 training on the inference encoder's kernels (not a reference key): channel-blocked
+                         # forward activations with fp32 Winograd where the inference path uses it, a backward that reads them in
+                         # place, the 3x3 stride-1 data gradients on the Winograd kernels. Same fp32 arithmetic, another summation
+                         # order (<= 1e-5 of a layer's range). Ignored with network.FP16_CONV, as network.WINOGRAD_CONV is on the
+                         # fp16 inference path; needs the LDS-staged weight gradient (context option "wgrad_lds", the default)
+                         WINOGRAD_CONV=False)
     cfg.TEST = AttrDict(test_iter=4, FAST_TEST=True, UPDATE_MASK="box_rendered", INIT_MASK="box_rendered")
     cfg.SCALES = [(480, 640)]
     return cfg

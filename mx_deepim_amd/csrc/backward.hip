@@ -99,6 +99,116 @@ __global__ __launch_bounds__(256) void lrelu_bias_backward_kernel(double* __rest
   }
 }
 
+// The same walk where the saved output y lies channel-blocked ((B, C/8, H, W, 8): YM 1; in space-to-depth order: YM 3) while the
+// gradients stay NCHW (YM 0: y is NCHW too and read like dy — the last encoder layer, whose dz is still wanted channel-blocked).
+// Block = (8-channel block, pixel slice); one step = a tile of 8 channels x 128 pixels. A lane per pixel would use 4 bytes of
+// every 32-byte record of y, so the tile goes through LDS: lane t reads half a record (pixel t / 2, channels 4 (t & 1) …) as
+// one dwordx4 and stores it transposed ([channel][pixel], pitch 136: the two record halves of a wave land 32 banks apart); the lane
+// then takes channel t / 32, pixels 4 (t & 31) … of the NCHW streams as dwordx4 accesses, y's signs from LDS. dz_nc8 (ZOUT) takes the
+// same dz values back through LDS into plain channel-blocked records, again half a record per lane. db: float64 per lane over its
+// pixels in order, a fixed tree over the 32 lanes of a channel, slices added in order by bias_grad_final_kernel.
+constexpr int LB8_PIX = 128, LB8_P = 136;
+template <bool V4, int YM, bool ZOUT>
+__global__ __launch_bounds__(256) void lrelu_bias_backward_nc8_kernel(double* __restrict__ partial, float* dz, float* __restrict__ dz_nc8,
+                                                                      const float* dy, const float* add, const float* __restrict__ y,
+                                                                      float slope, int B, int C, int H, int W, int S, int per_slice,
+                                                                      float* __restrict__ db) {
+  __shared__ __attribute__((aligned(16))) float ys[8 * LB8_P];
+  __shared__ __attribute__((aligned(16))) float zs[ZOUT ? 8 * LB8_P : 4];
+  __shared__ double red[256];
+  const int cb = blockIdx.x, sl = blockIdx.y, tid = threadIdx.x;
+  const int HW = H * W, C8 = C >> 3;
+  const int lo = sl * per_slice, hi = min(HW, lo + per_slice);
+  const int rp = tid >> 1, rh = (tid & 1) * 4;        // record side: pixel of the tile, first channel of the half record
+  const int ch = tid >> 5, q4 = (tid & 31) * 4;       // NCHW side: channel of the block, first pixel of the quad
+  double acc = 0.0;
+  for (int n = 0; n < B; ++n) {
+    const long base = ((long)n * C + cb * 8 + ch) * HW;
+    for (int t0 = lo; t0 < hi; t0 += LB8_PIX) {
+      const int pr = t0 + rp;
+      float4 yv = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (YM != 0 && pr < hi) {
+        long rec;
+        if (YM == 3) {
+          const int py = pr / W, px = pr - py * W;
+          rec = ((long)(n * 4 + (py & 1) * 2 + (px & 1)) * C8 + cb) * (HW >> 2) + (py >> 1) * (W >> 1) + (px >> 1);
+        } else {
+          rec = ((long)n * C8 + cb) * HW + pr;
+        }
+        yv = *reinterpret_cast<const float4*>(y + rec * 8 + rh);
+      }
+      if (YM != 0) {
+        ys[(rh + 0) * LB8_P + rp] = yv.x; ys[(rh + 1) * LB8_P + rp] = yv.y;
+        ys[(rh + 2) * LB8_P + rp] = yv.z; ys[(rh + 3) * LB8_P + rp] = yv.w;
+      }
+      const int pq = t0 + q4;
+      float g[4] = {0.f, 0.f, 0.f, 0.f};
+      if (V4) {
+        if (pq < hi) {     // HW % 4 == 0 and slices of whole tiles: the quad is entirely inside or entirely outside
+          const float4 v = *reinterpret_cast<const float4*>(dy + base + pq);
+          g[0] = v.x; g[1] = v.y; g[2] = v.z; g[3] = v.w;
+          if (add) {
+            const float4 a = *reinterpret_cast<const float4*>(add + base + pq);
+            g[0] += a.x; g[1] += a.y; g[2] += a.z; g[3] += a.w;
+          }
+        }
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (pq + j < hi) {
+            g[j] = dy[base + pq + j];
+            if (add) g[j] += add[base + pq + j];
+          }
+      }
+      __syncthreads();
+      float4 ysg = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (YM != 0) {
+        ysg = *reinterpret_cast<const float4*>(&ys[ch * LB8_P + q4]);
+      } else if (V4) {
+        if (pq < hi) ysg = *reinterpret_cast<const float4*>(y + base + pq);
+      } else {
+        if (pq < hi) ysg.x = y[base + pq];
+        if (pq + 1 < hi) ysg.y = y[base + pq + 1];
+        if (pq + 2 < hi) ysg.z = y[base + pq + 2];
+        if (pq + 3 < hi) ysg.w = y[base + pq + 3];
+      }
+      g[0] = ysg.x > 0.f ? g[0] : g[0] * slope; g[1] = ysg.y > 0.f ? g[1] : g[1] * slope;
+      g[2] = ysg.z > 0.f ? g[2] : g[2] * slope; g[3] = ysg.w > 0.f ? g[3] : g[3] * slope;
+      if (V4) {
+        if (pq < hi) {
+          *reinterpret_cast<float4*>(dz + base + pq) = make_float4(g[0], g[1], g[2], g[3]);
+          acc += (double)g[0]; acc += (double)g[1]; acc += (double)g[2]; acc += (double)g[3];
+        }
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (pq + j < hi) {
+            dz[base + pq + j] = g[j];
+            acc += (double)g[j];
+          }
+      }
+      if (ZOUT) *reinterpret_cast<float4*>(&zs[ch * LB8_P + q4]) = make_float4(g[0], g[1], g[2], g[3]);
+      __syncthreads();
+      if (ZOUT && pr < hi) {
+        const float4 zv = make_float4(zs[(rh + 0) * LB8_P + rp], zs[(rh + 1) * LB8_P + rp], zs[(rh + 2) * LB8_P + rp],
+                                      zs[(rh + 3) * LB8_P + rp]);
+        *reinterpret_cast<float4*>(dz_nc8 + (((long)n * C8 + cb) * HW + pr) * 8 + rh) = zv;
+      }
+    }
+  }
+  red[tid] = acc;
+  __syncthreads();
+  for (int s = 16; s > 0; s >>= 1) {
+    if ((tid & 31) < s) red[tid] += red[tid + s];
+    __syncthreads();
+  }
+  if ((tid & 31) == 0) {
+    const int c = cb * 8 + ch;
+    if (S == 1) db[c] = (float)red[tid];     // a single slice is the sum itself: no second pass
+    else partial[(long)c * S + sl] = red[tid];
+  }
+}
+
 // Backward of [Concat slice → LeakyReLU → Crop] in front of a transposed convolution, in one walk: channels [coff, coff + C) of
 // the concat gradient (B,ctotal,ho,wo), times lrelu'(y) of the same slice of the saved concat output (y NULL: no activation),
 // placed at (off_y, off_x) of the un-cropped frame (B,C,hf,wf) with zeros around, and summed per channel (the bias gradient).
@@ -334,7 +444,11 @@ constexpr int WG_PIX = 16, WG_P = 20;
 // into the loads' scalar offset), and sixteen fewer registers. An ablation with the per-row range arithmetic removed ran 9 %
 // faster (19 % on conv1): that arithmetic, not memory, was what the waves were short of. The gradient then comes out as
 // dw_tm[co][tap][ci]; whoever reads it (the SGD kernel, deepim_weight_grad_to_natural) applies the permutation.
-template <int BM, bool TAPM = false>
+// XL (TAPM only): the layout of x. 0 = NCHW. 1 = channel-blocked (B, Cin/8, H, W, 8): a thread's eight rows (one tap of eight
+// consecutive channels) are ONE 32-byte record, two dwordx4 loads instead of eight dword loads. 3 = the same records in space-to-depth
+// order (pixel (y, x), channel c at channel ((y & 1) * 2 + (x & 1)) * Cin + c, position (y / 2, x / 2) of a (B, 4 Cin / 8, H / 2, W / 2, 8)
+// tensor; even H and W). Only the loads differ: the LDS tiles, and so every sum, are the same bits as with XL = 0.
+template <int BM, bool TAPM = false, int XL = 0>
 __global__ __launch_bounds__(256, 3) void wgrad_lds_kernel(WgradParams p) {   // 41 KB of LDS per block: three blocks per CU
   constexpr int TM = BM / 64, NA = BM / 64;          // MFMA row tiles per wave; dZ dwordx4 loads per thread and chunk
   __shared__ __attribute__((aligned(16))) float As[2][BM * WG_P];
@@ -376,9 +490,13 @@ __global__ __launch_bounds__(256, 3) void wgrad_lds_kernel(WgradParams p) {   //
     if (k0 < p.K) {
       const int t = k0 / p.Cin, ci0 = k0 - t * p.Cin;
       tm_ty = t / p.kw - p.pad; tm_tx = t % p.kw - p.pad;
-      tm_off = (ci0 * p.H * p.W + tm_ty * p.W + tm_tx) * 4;
+      tm_off = XL == 3 ? (ci0 * (p.H >> 1) * (p.W >> 1)) * 4
+               : XL == 1 ? (ci0 * p.H * p.W + (tm_ty * p.W + tm_tx) * 8) * 4
+                         : (ci0 * p.H * p.W + tm_ty * p.W + tm_tx) * 4;
     }
   }
+  static_assert(XL == 0 || TAPM, "a channel-blocked x needs the tap-major K order");
+  constexpr int NB = XL ? 2 : 8;                       // im2col loads per thread and chunk
   const int plane_bytes = p.H * p.W * 4;
   f32x16 acc[TM][2];
 #pragma unroll
@@ -423,7 +541,11 @@ __global__ __launch_bounds__(256, 3) void wgrad_lds_kernel(WgradParams p) {   //
     if (TAPM) {
       const int hi = hi0 + tm_ty, wi = wi0 + tm_tx;
       const int bad = pinv | hi | (Hm1 - hi) | wi | (Wm1 - wi);
-      offb[0] = ((unsigned)(baseb + tm_off) & 0x7fffffffu) | ((unsigned)bad & OOB);
+      int off = baseb + tm_off;
+      if (XL == 1) off = (n * p.Cin * p.H * p.W + (hi0 * p.W + wi0) * 8) * 4 + tm_off;
+      if (XL == 3)   // the record of (hi, wi): phase plane (hi & 1) * 2 + (wi & 1), position (hi / 2, wi / 2)
+        off = ((n * 4 + (hi & 1) * 2 + (wi & 1)) * p.Cin * (p.H >> 1) * (p.W >> 1) + ((hi >> 1) * (p.W >> 1) + (wi >> 1)) * 8) * 4 + tm_off;
+      offb[0] = ((unsigned)off & 0x7fffffffu) | ((unsigned)bad & OOB);
     }
 #pragma unroll
     for (int e = 0; e < (TAPM ? 0 : 8); ++e) {
@@ -441,8 +563,15 @@ __global__ __launch_bounds__(256, 3) void wgrad_lds_kernel(WgradParams p) {   //
 #endif
 #pragma unroll
     for (int r = 0; r < NA; ++r) ra[r] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_dz, (int)offa[r], 0, 0));
+    if (XL) {   // channels 0-3 and 4-7 of the record (the second half rides in the scalar offset)
 #pragma unroll
-    for (int e = 0; e < 8; ++e)   // TAPM: the channel plane rides in the scalar offset (not range-checked: bit 31 of the vector offset decides)
+      for (int v = 0; v < 2; ++v) {
+        const f32x4 q = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_x, (int)offb[0], v * 16, 0));
+        rb[4 * v] = q[0]; rb[4 * v + 1] = q[1]; rb[4 * v + 2] = q[2]; rb[4 * v + 3] = q[3];
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < (XL ? 0 : 8); ++e)   // TAPM: the channel plane rides in the scalar offset (not range-checked: bit 31 of the vector offset decides)
       rb[e] = __builtin_bit_cast(float, TAPM ? __builtin_amdgcn_raw_buffer_load_b32(rs_x, (int)offb[0], e * plane_bytes, 0)
                                              : __builtin_amdgcn_raw_buffer_load_b32(rs_x, (int)offb[e], 0, 0));
 #if !WG_INTERLEAVE
@@ -494,7 +623,7 @@ __global__ __launch_bounds__(256, 3) void wgrad_lds_kernel(WgradParams p) {   //
       __builtin_amdgcn_sched_group_barrier(0x002, 5, 0);                   // a few VALU (byte offsets)
       if (k < NA + 4) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);   // DS write (NA b128 + 4 write2)
       else if (k < NA + 4 + (TM + 2)) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);   // DS read: second-half fragments
-      else if (k < NA + 4 + (TM + 2) + NA + 8) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);   // VMEM read
+      else if (k < NA + 4 + (TM + 2) + NA + NB) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);   // VMEM read
     }
 #endif
     __syncthreads();
@@ -859,6 +988,43 @@ extern "C" int deepim_lrelu_bias_backward(deepim_ctx* ctx, float* dz, float* db,
   return 0;
 }
 
+// deepim_lrelu_bias_backward where the saved output lies channel-blocked: y_mode 1 = (B, C/8, H, W, 8), 3 = the same records in
+// space-to-depth order (even H and W); 0 = NCHW like the gradients (for its dz_nc8 output). dz (NCHW, may be dy) holds the same bits as deepim_lrelu_bias_backward on the NCHW copy of y;
+// dz_nc8, when not NULL, receives the same values once more as plain channel-blocked records (the Winograd data gradient's input).
+extern "C" int deepim_lrelu_bias_backward_nc8(deepim_ctx* ctx, float* dz, float* dz_nc8, float* db, const float* dy, const float* add,
+                                              const float* y_nc8, int y_mode, float slope, int B, int C, int H, int W) {
+  DI_DEVICE(ctx);
+  DI_REQUIRE(B >= 0 && C >= 0 && H >= 0 && W >= 0 && (C & 7) == 0, "lrelu_bias_backward_nc8: C % 8 == 0 required");
+  DI_REQUIRE(y_mode == 0 || y_mode == 1 || y_mode == 3, "lrelu_bias_backward_nc8: y_mode must be 0 (NCHW), 1 (NC8) or 3 (NC8, space-to-depth order)");
+  DI_REQUIRE(y_mode != 3 || ((H | W) & 1) == 0, "lrelu_bias_backward_nc8: the space-to-depth order needs even H and W");
+  DI_REQUIRE((size_t)H * W < (1ull << 30), "lrelu_bias_backward_nc8: plane too large");
+  if (C == 0) return 0;
+  const int hw = H * W;
+  if (B == 0 || hw == 0) {   // nothing to walk: the sum over no elements is zero
+    DI_CHECK(hipMemsetAsync(db, 0, (size_t)C * sizeof(float), ctx->stream));
+    return 0;
+  }
+  // pixel slices of whole tiles, enough of them that a layer of few channel blocks still fills the chip; fixed by the geometry
+  int S = (int)max(1L, min((long)di_div_up(4096, C / 8), (long)di_div_up(hw, LB8_PIX)));
+  const int per_slice = di_div_up(di_div_up(hw, S), LB8_PIX) * LB8_PIX;
+  S = di_div_up(hw, per_slice);
+  void* scratch;
+  int rc = deepim_scratch(ctx, (size_t)C * S * sizeof(double), &scratch);
+  if (rc) return rc;
+  const dim3 grid(C / 8, S);
+#define DI_LB8(V4, YS, ZO) hipLaunchKernelGGL((lrelu_bias_backward_nc8_kernel<V4, YS, ZO>), grid, dim3(256), 0, ctx->stream, (double*)scratch, \
+                                              dz, dz_nc8, dy, add, y_nc8, slope, B, C, H, W, S, per_slice, db)
+#define DI_LB8_Y(V4, ZO) if (y_mode == 3) DI_LB8(V4, 3, ZO); else if (y_mode == 1) DI_LB8(V4, 1, ZO); else DI_LB8(V4, 0, ZO)
+  if (hw % 4 == 0) { if (dz_nc8) { DI_LB8_Y(true, true); } else { DI_LB8_Y(true, false); } }
+  else { if (dz_nc8) { DI_LB8_Y(false, true); } else { DI_LB8_Y(false, false); } }
+#undef DI_LB8_Y
+#undef DI_LB8
+  if (S > 1)
+    hipLaunchKernelGGL(bias_grad_final_kernel, dim3(di_div_up(C, 256)), dim3(256), 0, ctx->stream, db, (const double*)scratch, C, S);
+  DI_LAUNCH_CHECK();
+  return 0;
+}
+
 extern "C" int deepim_slice_lrelu_bias_scatter(deepim_ctx* ctx, float* out, float* db, const float* dcat, const float* ycat, int B,
                                                int ctotal, int coff, int C, int ho, int wo, int hf, int wf, int off_y, int off_x,
                                                float slope) {
@@ -950,7 +1116,7 @@ extern "C" int deepim_extract_channels(deepim_ctx* ctx, float* dst, const float*
 }
 
 static int conv2d_wgrad_impl(deepim_ctx* ctx, float* dw, float* db, const float* x, const float* dz, int B, int Cin, int H, int W,
-                             int Cout, int kh, int kw, int stride, int pad, bool tap_major = false);
+                             int Cout, int kh, int kw, int stride, int pad, bool tap_major = false, int x_mode = 0);
 
 extern "C" int deepim_conv2d_wgrad(deepim_ctx* ctx, float* dw, const float* x, const float* dz, int B, int Cin, int H, int W,
                                    int Cout, int kh, int kw, int stride, int pad) {
@@ -971,6 +1137,18 @@ extern "C" int deepim_conv2d_wgrad_tm(deepim_ctx* ctx, float* dw_tm, const float
                                       int Cout, int kh, int kw, int stride, int pad) {
   DI_REQUIRE((Cin & 7) == 0 && Cout > 4 && ctx->wgrad_lds, "conv2d_wgrad_tm: needs Cin % 8 == 0, Cout > 4 and the LDS-staged kernel");
   return conv2d_wgrad_impl(ctx, dw_tm, nullptr, x, dz, B, Cin, H, W, Cout, kh, kw, stride, pad, true);
+}
+
+// deepim_conv2d_wgrad_tm with a channel-blocked x operand: x_mode 1 = (B, Cin/8, H, W, 8), 3 = the same records in space-to-depth order
+// (what an encoder layer in front of a stride-2 Winograd layer writes; even H and W). Only the im2col loads differ, so the result is
+// bit-identical to deepim_conv2d_wgrad_tm on the NCHW copy of the same tensor.
+extern "C" int deepim_conv2d_wgrad_tm_nc8(deepim_ctx* ctx, float* dw_tm, const float* x_nc8, int x_mode, const float* dz, int B, int Cin,
+                                          int H, int W, int Cout, int kh, int kw, int stride, int pad) {
+  DI_REQUIRE((Cin & 7) == 0 && Cout > 4 && ctx->wgrad_lds, "conv2d_wgrad_tm_nc8: needs Cin % 8 == 0, Cout > 4 and the LDS-staged kernel");
+  DI_REQUIRE(x_mode == 1 || x_mode == 3, "conv2d_wgrad_tm_nc8: x_mode must be 1 (NC8) or 3 (NC8, space-to-depth order)");
+  DI_REQUIRE(x_mode == 1 || (H > 0 && W > 0 && ((H | W) & 1) == 0), "conv2d_wgrad_tm_nc8: the space-to-depth order needs even H and W");
+  DI_REQUIRE((size_t)B * Cin * H * W * 4 < 0x7fffffffUL, "conv2d_wgrad_tm_nc8: x beyond the 2 GiB buffer range");
+  return conv2d_wgrad_impl(ctx, dw_tm, nullptr, x_nc8, dz, B, Cin, H, W, Cout, kh, kw, stride, pad, true, x_mode);
 }
 
 namespace {
@@ -997,7 +1175,7 @@ extern "C" int deepim_weight_grad_to_natural(deepim_ctx* ctx, float* dw, const f
 }
 
 static int conv2d_wgrad_impl(deepim_ctx* ctx, float* dw, float* db, const float* x, const float* dz, int B, int Cin, int H, int W,
-                             int Cout, int kh, int kw, int stride, int pad, bool tap_major) {
+                             int Cout, int kh, int kw, int stride, int pad, bool tap_major, int x_mode) {
   DI_DEVICE(ctx);
   if (B == 0) {   // a rank with an empty shard: the gradients are zero, not whatever the buffers held (update() applies them)
     if (dw) DI_CHECK(hipMemsetAsync(dw, 0, (size_t)Cout * Cin * kh * kw * sizeof(float), ctx->stream));
@@ -1056,7 +1234,12 @@ static int conv2d_wgrad_impl(deepim_ctx* ctx, float* dw, float* db, const float*
       p.partial = (float*)scratch;
     }
     const dim3 grid(p.ktiles * p.mtiles * p.S);
-    if (tap_major) {
+    if (tap_major && x_mode) {
+      if (bm == 64 && x_mode == 3) hipLaunchKernelGGL((wgrad_lds_kernel<64, true, 3>), grid, dim3(256), 0, ctx->stream, p);
+      else if (bm == 64) hipLaunchKernelGGL((wgrad_lds_kernel<64, true, 1>), grid, dim3(256), 0, ctx->stream, p);
+      else if (x_mode == 3) hipLaunchKernelGGL((wgrad_lds_kernel<128, true, 3>), grid, dim3(256), 0, ctx->stream, p);
+      else hipLaunchKernelGGL((wgrad_lds_kernel<128, true, 1>), grid, dim3(256), 0, ctx->stream, p);
+    } else if (tap_major) {
       if (bm == 64) hipLaunchKernelGGL((wgrad_lds_kernel<64, true>), grid, dim3(256), 0, ctx->stream, p);
       else hipLaunchKernelGGL((wgrad_lds_kernel<128, true>), grid, dim3(256), 0, ctx->stream, p);
     } else if (bm == 64) hipLaunchKernelGGL(wgrad_lds_kernel<64>, grid, dim3(256), 0, ctx->stream, p);

@@ -1233,6 +1233,8 @@ static int wino8_streamk_plan(long grid, int nK, int step_granule, int slots, do
 // equivalent to — channel phase*(Cin/4) + c, phase = py*2 + px, tap (a, b) = w[2a + py][2b + px] (zero where 2a + py or 2b + px = 5).
 // s2d 2: `w` is a (Cout, Cin/4, 3, 3) stride-2 pad-1 kernel, i.e. taps 1..3 of a 5x5 stride-2 pad-2 one: tap (a, b) of phase (py, px) =
 // w[2a + py - 1][2b + px - 1] where both indices lie in 0..2, else zero
+// s2d 3: `w` is the (Cin, Cout, 3, 3) tensor of the layer whose DATA GRADIENT this convolution is, read transposed and flipped in place:
+// tap (a, b) of (co, ci) = w[ci][co][2 - a][2 - b] (the view deepim_conv_flip_weights materialises; same sums in the same order)
 __global__ void pack_wino_kernel(float* __restrict__ packed, const float* __restrict__ w, int Cout, int Cin, long total, int s2d) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= total) return;
@@ -1252,6 +1254,10 @@ __global__ void pack_wino_kernel(float* __restrict__ packed, const float* __rest
         const int ky = 2 * a + py - 1, kx = 2 * b + px - 1;
         if (ky >= 0 && ky < 3 && kx >= 0 && kx < 3) u += G[xi][a] * (double)g[ky * 3 + kx] * G[nu][b];
       }
+  } else if (s2d == 3) {
+    const float* g = w + ((long)ci * Cout + co) * 9;
+    for (int a = 0; a < 3; ++a)
+      for (int b = 0; b < 3; ++b) u += G[xi][a] * (double)g[(2 - a) * 3 + 2 - b] * G[nu][b];
   } else if (s2d) {
     const int C0 = Cin >> 2, ph = ci / C0, py = ph >> 1, px = ph & 1;
     const float* g = w + ((long)co * C0 + (ci - ph * C0)) * 25;
@@ -1358,6 +1364,18 @@ extern "C" int deepim_conv_wino_pack_weights_s2d3(deepim_ctx* ctx, float* packed
   return 0;
 }
 
+// The data gradient of a 3x3 stride-1 pad-1 layer (Cout, Cin, 3, 3) is the same kind of convolution from its Cout to its Cin channels
+// on the transposed, flipped weights: U' of that Cin <- Cout problem straight from the layer's raw tensor `w` (no flip buffer), size
+// deepim_conv_wino_packed_size(Cin, Cout). Bit-identical to deepim_conv_wino_pack_weights on deepim_conv_flip_weights of `w`.
+extern "C" int deepim_conv_wino_pack_weights_dgrad(deepim_ctx* ctx, float* packed_w, const float* w, int Cout, int Cin) {
+  DI_DEVICE(ctx);
+  DI_REQUIRE(Cout > 0 && Cin > 0 && (Cin & 31) == 0 && (Cout & 7) == 0, "conv_wino_pack_weights_dgrad: Cin % 32 == 0 and Cout % 8 == 0 required");
+  const long total = (long)Cout * Cin * 16;
+  pack_wino_kernel<<<di_div_up(total, 256), 256, 0, ctx->stream>>>(packed_w, w, Cin, Cout, total, 3);
+  DI_LAUNCH_CHECK();
+  return 0;
+}
+
 // 3x3, stride 1, pad 1 convolution + bias + LeakyReLU(slope) from channel-blocked `in` (B, Cin/8, H, W, 8) into channel-blocked
 // `out` (out_nc8 = 1; 3 = channel-blocked in space-to-depth order, what a stride-2 layer on this kernel reads) or into channels
 // [out_coff, out_coff + Cout) of an NCHW tensor of out_ctotal channels (out_nc8 = 0).
@@ -1417,7 +1435,7 @@ static int wino_forward_impl(deepim_ctx* ctx, float* out, const float* in, const
     int skF = 0, skq = 0, skrem = 0;
     const int skG = (ctx->wino_split != 1 && ctx->wino_persistent && ctx->wino_streamk && out_nc8 && out_elems * 4 < (1ull << 31)) ? wino8_streamk_plan(grid, nK, gran, slots, &cost_sk, &skF, &skq, &skrem) : 0;
     // measured (bench.py A/B in one box): +1 % at B = 32 (4-18 whole rounds before the cut one), -1 % at B = 4 (one): from two whole rounds on
-    // (the arrival counters are allocated on the first such launch: not inside a graph capture — run the sequence once eagerly first)
+    // (the arrival counters are allocated with the context, deepim_create: nothing is allocated at launch time)
     const bool streamk = skG > 0 &&
                          (ctx->wino_streamk == 2 || (skF >= 2 && cost_sk < cost_split * 0.98));   // 2: wherever it applies (tests)
     if (streamk) { S = 1; ks = nK; }
@@ -1495,6 +1513,13 @@ extern "C" int deepim_conv2d_wino_forward(deepim_ctx* ctx, float* out, const flo
                                           int B, int Cin, int H, int W, int Cout, float slope, int out_nc8, int out_ctotal,
                                           int out_coff) {
   return wino_forward_impl(ctx, out, in, packed_w, bias, B, Cin, H, W, Cout, slope, out_nc8, out_ctotal, out_coff, 0);
+}
+
+// dx (B, Cin, H, W), NCHW, of a 3x3 stride-1 pad-1 layer from its channel-blocked dz (B, Cout/8, H, W, 8) and the U' of
+// deepim_conv_wino_pack_weights_dgrad: the forward kernels on the Cin <- Cout problem, no bias, no activation (K-split second pass included).
+extern "C" int deepim_conv2d_wino_dgrad(deepim_ctx* ctx, float* dx, const float* dz_nc8, const float* packed_w, int B, int Cin, int H,
+                                        int W, int Cout) {
+  return wino_forward_impl(ctx, dx, dz_nc8, packed_w, nullptr, B, Cout, H, W, Cin, 1.0f, 0, 0, 0, 0);
 }
 
 // The 5x5 stride-2 pad-2 layer itself: `in` = the space-to-depth NC8 form (B, 4 Cin, H/2, W/2) of its (B, Cin, H, W) input, packed_w

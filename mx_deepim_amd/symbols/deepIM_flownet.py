@@ -150,7 +150,10 @@ class deepIM_flownet(object):
         self.get_test_symbol_share(cfg)
         self.fp16_decoder = False  # network.FP16_DECODER governs the test graph only: the training decoder and heads are fp32
         self.is_train = True
-        self.nc8 = False          # NCHW activations: what the backward kernels read
+        # TRAIN.WINOGRAD_CONV: the forward of the inference encoder (channel-blocked activations, fp32 Winograd
+        # layers) with a backward that reads those activations in place. The fp16 graph ignores the key
+        self.train_winograd = bool(cfg.TRAIN.get("WINOGRAD_CONV", False)) and not self.fp16_conv
+        self.nc8 = self.train_winograd   # False: NCHW activations, what the default backward kernels read
         self.two_streams = False  # backward(): weight gradients on a second stream next to the data gradients (False: one stream)
         self.with_mask_head, self.with_flow_head = bool(n.PRED_MASK), bool(n.PRED_FLOW)    # :183, :314
         self.with_decoder = self.with_mask_head or self.with_flow_head
@@ -315,7 +318,9 @@ class deepIM_flownet(object):
                 lib.deepim_conv_pack_weights(h, pk, self.params[name], cout, cin, kh, kw)
             self.packed[base] = pk
         self.packed_wino, self.wino_s2d, self.wino_conv1, self.wino_s2d3 = {}, set(), None, {}
-        if self.nc8 and getattr(self, "winograd", False) and not (self.fp16_conv or self.x3_conv or getattr(self, "is_train", False)):
+        self.packed_wino_dgrad = {}     # training with TRAIN.WINOGRAD_CONV: U' of the 3x3 stride-1 data gradients (bind_train)
+        if self.nc8 and getattr(self, "winograd", False) and not (self.fp16_conv or self.x3_conv) and (
+                not getattr(self, "is_train", False) or getattr(self, "train_winograd", False)):
             hh, ww, cin = H, W, self.cin
             L = lib.load()
             for li, (name, cout, k, s_, p_) in enumerate(ENCODER):
@@ -833,6 +838,9 @@ def _train_methods():
         # deepim_conv2d_wgrad into the natural buffer and the SGD table reads that one (layout word 0).
         opt = ctypes.c_int(0)
         lib.deepim_get_option(ctx.handle, b"wgrad_lds", ctypes.byref(opt))
+        if self.train_winograd and not opt.value:
+            raise NotImplementedError("TRAIN.WINOGRAD_CONV needs the LDS-staged weight gradient (context option wgrad_lds = 1): the "
+                                      "register-fed kernel reads NCHW activations only")
         for gname, cin, _h, _w, cout, k, _s, _p in self.enc_geom:       # conv layers: (Cout, Cin, k, k)
             if opt.value and cin % 8 == 0:
                 self.grad.tm[gname + "_weight"] = (ctx.zeros((cout, k * k, cin)), cout, cin, k * k)
@@ -877,6 +885,18 @@ def _train_methods():
             self.ws["zm_a"], self.ws["zm_b"], self.ws["zm_f"] = ctx.empty((B, 1, H, W)), ctx.empty((B, 1, H, W)), ctx.empty((B, 4))
             self.ws["d_mask_hi"] = ctx.empty((B, 1, H, W))
         self.ws["dil"], self.ws["wt_packed"] = ctx.empty((dil,)), ctx.empty((pmax,))
+        if self.train_winograd:
+            # the 3x3 stride-1 data gradients on the Winograd kernels: U' per layer, and ONE channel-blocked dz buffer (the largest
+            # such layer's output) that the activation-gradient walk fills next to the NCHW dz
+            L, nz = lib.load(), 0
+            for name, cin, h, w, cout, k, s_, p_ in self.enc_geom[1:]:
+                if (k, s_, p_) == (3, 1, 1) and cin % 32 == 0 and L.deepim_conv_wino_preferred(ctx.handle, B, cout, h, w, cin):
+                    pk = DeviceArray(ctx, (L.deepim_conv_wino_packed_size(cin, cout) // 4,))
+                    lib.deepim_conv_wino_pack_weights_dgrad(ctx.handle, pk, self.params[name + "_weight"], cout, cin)
+                    self.packed_wino_dgrad[name] = pk
+                    nz = max(nz, B * cout * h * w)
+            if nz:
+                self.ws["dz_nc8"] = ctx.empty((nz,))
         self.ws["g256a"], self.ws["g256b"] = ctx.empty((B, 256)), ctx.empty((B, 256))
         self.ws["dy7"], self.ws["w7"], self.ws["dw7"], self.ws["db7"] = ctx.empty((B, 7)), w7, dw7, db7
         self.ws["d_points"] = ctx.empty((B, 3, num_points))
@@ -1138,16 +1158,29 @@ def _train_methods():
         for li in range(len(self.enc_geom) - 1, -1, -1):
             name, cin_, hh_, ww_, cout_, k_, s_, p_ = self.enc_geom[li]
             ho_, wo_ = _out_hw(hh_, ww_, k_, s_, p_)
-            lib.deepim_lrelu_bias_backward(h, ga, G[name + "_bias"], ga, W_[extra[name]] if name in extra else None, A[name],
-                                           c(SLOPE), B, cout_, ho_ * wo_)
+            add_ = W_[extra[name]] if name in extra else None
+            y_mode = self._enc_out_mode(li) if self.train_winograd else 0     # how forward_train left this layer's output
+            wdg = self.packed_wino_dgrad.get(name) if (self.train_winograd and li > 0) else None
+            if wdg is not None and not lib.load().deepim_conv_wino_preferred(h, B, cout_, hh_, ww_, cin_):
+                wdg = None    # (asked again per call: a context switched to the canonical order after bind takes the direct kernel)
+            if y_mode or wdg is not None:      # (conv6_1 wrote NCHW for fc6, y_mode 0: the same walk for its channel-blocked dz)
+                lib.deepim_lrelu_bias_backward_nc8(h, ga, W_["dz_nc8"] if wdg is not None else None, G[name + "_bias"], ga, add_, A[name],
+                                                   y_mode, c(SLOPE), B, cout_, ho_, wo_)
+            else:
+                lib.deepim_lrelu_bias_backward(h, ga, G[name + "_bias"], ga, add_, A[name], c(SLOPE), B, cout_, ho_ * wo_)
             lib.deepim_stream_wait(h, side)      # weight gradient of layer li+1 done: gb may be overwritten
             lib.deepim_stream_wait(side, h)      # dz of this layer ready
             src = A["net_input"] if li == 0 else A[self.enc_geom[li - 1][0]]
-            if name + "_weight" in G.tm:
+            x_mode = self._enc_out_mode(li - 1) if (self.train_winograd and li > 0) else 0
+            if x_mode:      # the producer's channel-blocked output, read in place (bind_train: wgrad_lds is on, Cin % 8 == 0)
+                lib.deepim_conv2d_wgrad_tm_nc8(side, G.tm[name + "_weight"][0], src, x_mode, ga, B, cin_, hh_, ww_, cout_, k_, k_, s_, p_)
+            elif name + "_weight" in G.tm:
                 lib.deepim_conv2d_wgrad_tm(side, G.tm[name + "_weight"][0], src, ga, B, cin_, hh_, ww_, cout_, k_, k_, s_, p_)   # tap-major: _Grads
             else:       # Cin % 8 != 0 (6- / 10-channel conv1) or wgrad_lds = 0: natural (Cout, Cin, k, k) gradient
                 lib.deepim_conv2d_wgrad(side, dict.__getitem__(G, name + "_weight"), src, ga, B, cin_, hh_, ww_, cout_, k_, k_, s_, p_)
-            if li > 0:
+            if li > 0 and wdg is not None:
+                lib.deepim_conv2d_wino_dgrad(h, gb, W_["dz_nc8"], wdg, B, cin_, hh_, ww_, cout_)
+            elif li > 0:
                 self._dgrad(gb, ga, P[name + "_weight"], B, cin_, hh_, ww_, cout_, k_, s_, p_, ho_, wo_)
             ga, gb = gb, ga
         lib.deepim_stream_wait(h, side)          # every gradient is in place when the main stream goes on (update)
@@ -1195,13 +1228,38 @@ def _train_methods():
             base = name[: -len("_weight")]
             if self.fp16_conv and base in enc:      # the fp16 encoder reads packed_f16 only
                 continue
+            if self.train_winograd and base in enc:  # channel-blocked encoder: _repack_train_winograd below
+                continue
             if base.startswith("deconv") or base.startswith("upsample_flow"):
                 lib.deepim_deconv_pack_weights(h, self.packed[base], self.params[name], shape[0], shape[1])
             else:
                 lib.deepim_conv_pack_weights_ex(h, self.packed[base], self.params[name], shape[0], shape[1], shape[2], shape[3],
                                                 orders.get(base, 3))
+        if self.train_winograd:
+            self._repack_train_winograd()
         if self.B > self.FC6_PLAIN_MAX_BATCH:      # small batches read fc6's raw weights (_fc6)
             lib.deepim_fc_pack_weights(h, self.packed["fc6"], self.params["fc6_weight"], 256, 1024 * 8 * 10)
+
+    def _repack_train_winograd(self):
+        """TRAIN.WINOGRAD_CONV: the encoder weights in exactly the forms this mode's forward and backward read — per layer the
+        Winograd U of the kernel encoder_layer() picks (asked the way it asks), else the direct kernel's operand order for
+        channel-blocked input (conv1 on the NCHW net input: the NCHW orders); and U' of the Winograd data gradients."""
+        L, h, P, B = lib.load(), self.ctx.handle, self.params, self.B
+        for li, (name, cin, hh, ww, cout, k, s_, p_) in enumerate(self.enc_geom):
+            w = P[name + "_weight"]
+            if self._s2d3_live(li):
+                lib.deepim_conv_wino_pack_weights_s2d3(h, self.wino_s2d3[name], w, cout, cin)
+            elif name in self.packed_wino and name in self.wino_s2d:
+                lib.deepim_conv_wino_pack_weights_s2d(h, self.packed_wino[name], w, cout, cin)
+            elif name in self.packed_wino:
+                lib.deepim_conv_wino_pack_weights(h, self.packed_wino[name], w, cout, cin)
+            elif li == 0 and self.wino_conv1 is not None and L.deepim_conv1_wino_preferred(h, B, cin, hh, ww, cout):
+                lib.deepim_conv1_wino_pack_weights(h, self.wino_conv1, w)
+            else:
+                lib.deepim_conv_pack_weights_ex(h, self.packed[name], w, cout, cin, k, k, 4 if li > 0 else 3)
+        for name, cin, hh, ww, cout, k, s_, p_ in self.enc_geom:
+            if name in self.packed_wino_dgrad:
+                lib.deepim_conv_wino_pack_weights_dgrad(h, self.packed_wino_dgrad[name], P[name + "_weight"], cout, cin)
 
     def _repack_f16(self):
         """The fp16 weights the fp16 encoder reads (packed_f16, conv1's patch-kernel pack included), from the fp32 masters."""
@@ -1254,7 +1312,8 @@ def _train_methods():
         deepim_conv_weight_order): the per-step re-pack writes only that one."""
         order = lib.load().deepim_conv_weight_order      # evaluated per update: follows the context's conv options
         h, B = self.ctx.handle, self.B
-        geo = {g[0]: g[1:] for g in self.enc_geom}
+        # (TRAIN.WINOGRAD_CONV: the encoder layers are re-packed by _repack_train_winograd in the orders the channel-blocked forward reads)
+        geo = {} if self.train_winograd else {g[0]: g[1:] for g in self.enc_geom}
         geo.update({"Convolution1": (1024, 8, 10, 2, 3, 1, 1), "Convolution2": (1026, 15, 20, 2, 3, 1, 1),
                     "Convolution3": (770, 30, 40, 2, 3, 1, 1), "mask_conv3": (770, 30, 40, 1, 3, 1, 1)})
         return {n: order(h, B, cin, hh, ww, cout, k, k, s_, p_) for n, (cin, hh, ww, cout, k, s_, p_) in geo.items()}
@@ -1262,6 +1321,7 @@ def _train_methods():
     return dict(bind_train=bind_train, _bind_train_fp16=_bind_train_fp16, set_loss_scale=set_loss_scale, loss_scale=loss_scale,
                 _encoder_backward_f16=_encoder_backward_f16, _repack_f16=_repack_f16, forward_train=forward_train, _dgrad=_dgrad,
                 _small_conv_backward=_small_conv_backward, _head_conv_backward=_head_conv_backward,
+                _repack_train_winograd=_repack_train_winograd,
                 _deconv_backward=_deconv_backward, _decoder_backward=_decoder_backward, backward=backward, update=update, train_step=train_step,
                 _train_pack_orders=_train_pack_orders)
 
