@@ -754,6 +754,58 @@ int deepim_sgd_mom_update_multi_amp(deepim_ctx* ctx, const unsigned long long* t
  * scale = min(2^24, 2 scale), good_steps = 0. inv_scale follows, the overflow word is cleared. */
 int deepim_amp_scale_update(deepim_ctx* ctx, unsigned* state, int window);
 
+/* Split-fp16 ("x3") training (TRAIN.X3_CONV): the encoder backward on the fp16 matrix cores at fp32 grade (csrc/train_x3.hip,
+ * DESIGN.md §8f-4e). split(v, s): hi = f16(clamp(v·s, ±60000)), lo = f16(clamp(v·s) − hi); a product of two pairs is hi·hi + hi·lo +
+ * lo·hi with fp32 accumulation. S = the gradient scale (a power of two), the stored activations y_l are split16 at scale 16:
+ *   e_l   S·(fc6 data gradient + d_dec61) at conv6_1; d_l [+ S·skip_l] below
+ *   dz_l  = split(lrelu'(y_l)·e_l, 1), lrelu' from the sign of y_l's hi half          split16 NHWC
+ *   db_l  = Σ dz_l / S                                                                 fp32 sums in a fixed order
+ *   dW_l  = Σ_pix dz_l ⊗ im2col(y_{l-1}) / (16·S)                                      fp32 result
+ *   d_l-1 = split(conv_transpose(dz_l, split(w_l, s_w)) / s_w, 1)                      split16 NHWC (not for flow_conv1)
+ * The scale state is the fp16 mode's {float scale, float inv_scale, uint overflow, uint good_steps}, updated by
+ * deepim_sgd_mom_update_multi_amp / deepim_amp_scale_update. A clamp in any split of the backward, or a non-finite value, sets
+ * `overflow`; underflow is not detected (a scaled maximum below about 2^-4 degrades towards fp16 grade). No call syncs the host. */
+
+/* dz (B,H,W,2C split16; may be d) and db (C fp32) of one layer: e = [d (split16, hi + lo)] + [S·add (NCHW fp32)] (at least one of
+ * them), dz = split(lrelu'(y)·e, 1) with y the layer's stored split16 output, db = Σ (dz.hi + dz.lo) · inv_scale. C % 64 == 0.
+ * Deterministic (fixed slices, fixed-order sums); the arguments of deepim_lrelu_bias_backward_f16. */
+int deepim_lrelu_bias_backward_x3(deepim_ctx* ctx, void* dz_split16, float* db, const void* d_split16, const float* add_nchw,
+                                  const void* y_split16, unsigned* state, float slope, int B, int C, int H, int W);
+/* Weight gradient of a conv layer (Cout, Cin, k, k; stride, pad) from its split16 input x (B,H,W,2 Cin; stored at x_scale) and the
+ * split16 dz (B,Ho,Wo,2 Cout): a GEMM with M = Cout, N = k*k*Cin, K = B*Ho*Wo, three v_mfma_f32_32x32x16_f16 per fragment pair
+ * (LDS-staged, operands read with ds_read_b64_tr_b16). Fixed split-K slices, fixed-order second pass; the epilogue multiplies by
+ * inv_scale / x_scale and raises the overflow word on a non-finite value. layout 0 = natural (Cout,Cin,k,k), 1 = tap-major
+ * (Cout,k*k,Cin), as deepim_conv2d_wgrad_f16. Cin % 16 == 0, Cout % 16 == 0 (whole records). */
+int deepim_conv2d_wgrad_x3(deepim_ctx* ctx, float* dw, const void* x_split16, const void* dz_split16, unsigned* state, int B, int Cin,
+                           int H, int W, int Cout, int k, int stride, int pad, int layout, float x_scale);
+/* Split-fp16 weights of the convolution that is the data gradient of layer (Co_l, Ci_l, k, k), in deepim_conv2d_x3_forward's packed
+ * order (Cout = Ci_l, Cin = Co_l, kernel nky x nkx; deepim_conv_x3_packed_size(Ci_l, Co_l, nky, nkx) bytes): tap (a, b) =
+ * split(layer tap (ky0 + st (nky-1-a), kx0 + st (nkx-1-b)), w_scale). With st = 1 and the full kernel it equals
+ * deepim_conv_x3_pack_weights of the transposed, flipped weights bit for bit; st = 2: one output parity class of a stride-2 layer.
+ * A weight that w_scale does not hold (|w·w_scale| > 60000) is clamped and sets the overflow word of `state`.
+ * Co_l % 32 == 0, Ci_l % 128 == 0. */
+int deepim_conv_x3_pack_dgrad(deepim_ctx* ctx, void* packed, const float* w_layer, unsigned* state, int Co_l, int Ci_l, int k, int ky0,
+                              int kx0, int st, int nky, int nkx, float w_scale);
+/* Data gradient dx (B,Hd,Wd,2 Ci_l split16 at scale 1) = split(conv_transpose(dz, split(w, w_scale)) / w_scale, 1) of a conv layer
+ * (Co_l,Ci_l,k,k; stride 1 or 2, pad) from the split16 dz (B,Ho,Wo,2 Co_l) and the layer's fp32 weights. Stride 1:
+ * deepim_conv_x3_pack_dgrad + deepim_conv2d_x3_forward (slope 1, no bias, pad k-1-pad). Stride 2: the four output parity classes
+ * of the un-dilated dz, each a stride-1 x3 convolution into a class buffer whose window is stitched onto its parity positions, as
+ * deepim_conv2d_dgrad_f16. A clamp of dx sets the overflow word of `state` (through deepim_x3_status_to_state).
+ * ws: deepim_conv_dgrad_x3_workspace_size bytes (packed weights + class buffer). Co_l % 32 == 0, Ci_l % 128 == 0. */
+size_t deepim_conv_dgrad_x3_workspace_size(int B, int Ci_l, int Hd, int Wd, int Co_l, int k, int stride, int pad);
+int deepim_conv2d_dgrad_x3(deepim_ctx* ctx, void* dx_split16, const void* dz_split16, const float* w_layer, void* ws, unsigned* state,
+                           int B, int Ci_l, int Hd, int Wd, int Co_l, int k, int stride, int pad, float w_scale);
+/* The split-fp16 kernels report a clamp through bit 3 of the context's status word. This moves the bit into the overflow word of
+ * `state` on the device and clears it in the status word (the scale state carries it from there on). */
+int deepim_x3_status_to_state(deepim_ctx* ctx, unsigned* state);
+/* deepim_split16_to_nchw_f32 with the device scale taken out as well: out = (hi + lo) · inv_scale · state.inv_scale. Feeds the
+ * fp32 kernels that take the two shapes the x3 kernels do not (conv1's weight gradient). */
+int deepim_split16_to_nchw_f32_unscaled(deepim_ctx* ctx, float* out, const void* in_split16, const unsigned* state, int B, int C, int H,
+                                        int W, float inv_scale);
+/* A weight tensor (n floats) against the scale its x3 pack uses: |w·w_scale| > 60000 (where the pack clamps) or a NaN sets the
+ * overflow word of `state`, so the step that would run on clamped weights is skipped and reported. */
+int deepim_x3_weight_range_check(deepim_ctx* ctx, const float* w, long n, float w_scale, unsigned* state);
+
 /* ------------------------------------- R-group: re-render between iterations -- */
 /* Replaces Render_Py.render (lib/render_glumpy/render_py_multi.py:101-129: OpenGL draw + glReadPixels +
  * depth linearisation) and the tensor packing that follows it in the batch updater

@@ -25,6 +25,10 @@ class AttrDict(dict):
 # Loss-scale defaults of the fp16 training graph, from the gradient magnitudes of the synthetic batch
 FP16_LOSS_SCALE_DEFAULT = 1024.0
 FP16_SCALE_WINDOW_DEFAULT = 1000
+# Gradient-scale defaults of the split-fp16 training graph (TRAIN.X3_CONV): the largest power of two that keeps every encoder
+# layer's scaled max |dz| of the synthetic batches at or below 3750 / 16 (profiles/r12_x3_train.md)
+X3_GRAD_SCALE_DEFAULT = 65536.0
+X3_SCALE_WINDOW_DEFAULT = 1000
 
 
 def default_config():
@@ -68,7 +72,12 @@ def default_config():
                          # place, the 3x3 stride-1 data gradients on the Winograd kernels. Same fp32 arithmetic, another summation
                          # order (<= 1e-5 of a layer's range). Ignored with network.FP16_CONV, as network.WINOGRAD_CONV is on the
                          # fp16 inference path; needs the LDS-staged weight gradient (context option "wgrad_lds", the default)
-                         WINOGRAD_CONV=False)
+                         WINOGRAD_CONV=False,
+                         # split-fp16 training (not a reference key): the x3 encoder forward with a backward on the
+                         # fp16 matrix cores at fp32 grade (three MFMAs per product), gradients carried at the power-of-two scale
+                         # X3_GRAD_SCALE, which halves on an overflow and doubles after X3_SCALE_WINDOW clean steps. Ignored with
+                         # network.FP16_CONV; excludes WINOGRAD_CONV. network.X3_CONV stays a test-graph key
+                         X3_CONV=False, X3_GRAD_SCALE=X3_GRAD_SCALE_DEFAULT, X3_SCALE_WINDOW=X3_SCALE_WINDOW_DEFAULT)
     cfg.TEST = AttrDict(test_iter=4, FAST_TEST=True, UPDATE_MASK="box_rendered", INIT_MASK="box_rendered")
     cfg.SCALES = [(480, 640)]
     return cfg

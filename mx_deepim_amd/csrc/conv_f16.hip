@@ -17,6 +17,7 @@
 // Roofline: at 128x128 tiles the arithmetic intensity towards L2 is 64 FLOP/B, i.e. this kernel is L1/L2-
 // bandwidth-bound, not MFMA-bound (2.5 PFLOP/s dense fp16 peak).
 #include "common.h"
+#include "x3_split.h"
 
 namespace {
 
@@ -64,27 +65,7 @@ struct ConvF16Params {
   float acc_scale, out_scale;    // X3 mode: accumulator → real units (2^-(s_act+s_w)), real units → stored activations (2^s_act)
 };
 
-// X3 ("split fp16") operands: a real value v is carried as the fp16 pair hi = f16(v·2^s), lo = f16(v·2^s − hi), i.e. 22
-// significand bits, and a product as hi·hi + hi·lo + lo·hi on the fp16 matrix cores with fp32 accumulation (the dropped
-// lo·lo term is 2^-22 relative): fp32-grade results at 16/3 of the fp32 MFMA rate. Tensors keep the NHWC fp16 machinery:
-// 16 real channels are one 32-half record [hi 0..15 | lo 0..15], so a tensor with C real channels looks like an fp16
-// tensor with 2C channels and the loaders below run unchanged; one 32-wide K chunk is then 16 real channels of a tap.
-struct X3Pair { _Float16 hi, lo; };
-__device__ __forceinline__ X3Pair x3_split(float x, float scale) {
-  float v = x * scale;
-  v = fminf(fmaxf(v, -60000.f), 60000.f);     // saturate instead of inf (fp16 max 65504)
-  const _Float16 h = (_Float16)v;
-  return {h, (_Float16)(v - (float)h)};
-}
-// the same, tracking the largest scaled magnitude in `amax` (one v_max per value): the caller reports a clamp once per thread
-// through bit DI_STATUS_X3_SATURATED of the context's status word — saturation is never silent
-__device__ __forceinline__ X3Pair x3_split(float x, float scale, float& amax) {
-  amax = fmaxf(amax, fabsf(x * scale));
-  return x3_split(x, scale);
-}
-__device__ __forceinline__ void x3_report(float amax, int* status) {
-  if (amax > 60000.f) atomicOr(status, DI_STATUS_X3_SATURATED);
-}
+// X3 ("split fp16") operands: X3Pair / x3_split / x3_report live in x3_split.h (shared with csrc/train_x3.hip)
 
 // validity of the (ky,kx) taps of a pixel as a 64-bit word (bit ky*8+kx), kh,kw <= 7: rows/columns hi0+k, wi0+k inside the frame
 __device__ __forceinline__ unsigned long long tap_mask64(int hi0, int wi0, int H, int W) {
@@ -1179,6 +1160,37 @@ __global__ void pack_x3_kernel(_Float16* __restrict__ packed, const float* __res
   packed[i] = (cv & 16) ? s2.lo : s2.hi;
 }
 
+// X3 weights of a data gradient: pack_x3_kernel's layout for the convolution pack_f16_dgrad_kernel describes (Cout = Ci_l, Cin =
+// Co_l, tap (a, b) = layer tap (ky0 + st (nky-1-a), kx0 + st (nkx-1-b))). A weight the scale does not hold is clamped AND raises
+// word 2 of the training scale state.
+__global__ void pack_x3_dgrad_kernel(_Float16* __restrict__ packed, const float* __restrict__ w, unsigned* __restrict__ state, int Co_l,
+                                     int Ci_l, int kh_l, int kw_l, int ky0, int kx0, int st, int nky, int nkx, int nchunk, int BM,
+                                     float w_scale, long total) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  const int h = (int)(i & 7);
+  const long r1 = i >> 3;
+  const int m = (int)(r1 % BM);
+  const long r2 = r1 / BM;
+  const int o = (int)(r2 & 7);
+  const long r3 = r2 >> 3;
+  const int kc = (int)(r3 % nchunk);
+  const int mt = (int)(r3 / nchunk);
+  int tap, cv0;
+  f16_octet(kc * HOCT + o, 2 * Co_l, nky * nkx, &tap, &cv0);
+  const int cv = cv0 + h, ci_l = mt * BM + m;
+  const int co_l = (cv >> 5) * 16 + (cv & 15);
+  X3Pair s2 = {(_Float16)0.f, (_Float16)0.f};
+  if (ci_l < Ci_l && co_l < Co_l && tap < nky * nkx) {
+    const int a = tap / nkx, b = tap % nkx;
+    const int ky = ky0 + st * (nky - 1 - a), kx = kx0 + st * (nkx - 1 - b);
+    const float v = w[(((long)co_l * Ci_l + ci_l) * kh_l + ky) * kw_l + kx];
+    if (!(fabsf(v * w_scale) <= 60000.f)) state[2] = 1u;
+    s2 = x3_split(v, w_scale);
+  }
+  packed[i] = (cv & 16) ? s2.lo : s2.hi;
+}
+
 // NCHW fp32 → split16 NHWC; one thread per (pixel, 4 channels): two 8-byte stores
 __global__ __launch_bounds__(256) void nchw_to_split16_kernel(_Float16* __restrict__ out, const float* __restrict__ in, int C,
                                                               long hw, float scale, long total, int* status) {
@@ -1869,6 +1881,21 @@ extern "C" int deepim_conv_x3_pack_weights(deepim_ctx* ctx, void* packed, const 
   const long total = (long)di_div_up(Cout, BM) * nchunk * HOCT * BM * 8;
   hipLaunchKernelGGL(pack_x3_kernel, dim3(di_div_up(total, 256)), dim3(256), 0, ctx->stream, (_Float16*)packed, w, Cout, Cin, kh,
                      kw, nchunk, BM, w_scale, total);
+  DI_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int deepim_conv_x3_pack_dgrad(deepim_ctx* ctx, void* packed, const float* w_layer, unsigned* state, int Co_l, int Ci_l,
+                                         int k, int ky0, int kx0, int st, int nky, int nkx, float w_scale) {
+  DI_DEVICE(ctx);
+  DI_REQUIRE((Co_l & 31) == 0 && (Ci_l & 127) == 0, "conv_x3_pack_dgrad: needs Co_l % 32 == 0 and Ci_l % 128 == 0");
+  DI_REQUIRE((st == 1 || st == 2) && ky0 >= 0 && kx0 >= 0 && nky >= 1 && nkx >= 1 && ky0 + st * (nky - 1) < k && kx0 + st * (nkx - 1) < k,
+             "conv_x3_pack_dgrad: the taps must lie inside the layer's kernel");
+  const int nchunk = f16_chunks(2 * Co_l, nky, nkx);
+  const int BM = f16_bm(Ci_l);
+  const long total = (long)di_div_up(Ci_l, BM) * nchunk * HOCT * BM * 8;
+  hipLaunchKernelGGL(pack_x3_dgrad_kernel, dim3(di_div_up(total, 256)), dim3(256), 0, ctx->stream, (_Float16*)packed, w_layer, state,
+                     Co_l, Ci_l, k, k, ky0, kx0, st, nky, nkx, nchunk, BM, w_scale, total);
   DI_LAUNCH_CHECK();
   return 0;
 }

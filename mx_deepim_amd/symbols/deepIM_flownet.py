@@ -20,7 +20,7 @@ import ctypes
 
 import numpy as np
 
-from ..config import ROT_COORD_CODE, default_config
+from ..config import ROT_COORD_CODE, X3_GRAD_SCALE_DEFAULT, X3_SCALE_WINDOW_DEFAULT, default_config
 from ..runtime import Context, DeviceArray, lib
 
 # name, Cout, kernel, stride, pad  (deepIM_flownet.py:63-107)
@@ -147,7 +147,21 @@ class deepIM_flownet(object):
             self.loss_scale_window = int(tr.get("FP16_SCALE_WINDOW", 1000))
             if self.loss_scale_window < 1:
                 raise ValueError("TRAIN.FP16_SCALE_WINDOW must be >= 1, got {}".format(self.loss_scale_window))
+        # TRAIN.X3_CONV: split-fp16 encoder forward and backward with a device-resident gradient scale. The fp16
+        # graph ignores the key, as it ignores TRAIN.WINOGRAD_CONV
+        train_x3 = bool(cfg.TRAIN.get("X3_CONV", False)) and not getattr(n, "FP16_CONV", False)
+        if train_x3:
+            tr = cfg.TRAIN
+            if tr.get("WINOGRAD_CONV", False):
+                raise ValueError("TRAIN.X3_CONV and TRAIN.WINOGRAD_CONV exclude each other: one encoder arithmetic per training graph")
+            self.loss_scale_init = self._check_loss_scale(tr.get("X3_GRAD_SCALE", X3_GRAD_SCALE_DEFAULT), "TRAIN.X3_GRAD_SCALE")
+            self.loss_scale_window = int(tr.get("X3_SCALE_WINDOW", X3_SCALE_WINDOW_DEFAULT))
+            if self.loss_scale_window < 1:
+                raise ValueError("TRAIN.X3_SCALE_WINDOW must be >= 1, got {}".format(self.loss_scale_window))
         self.get_test_symbol_share(cfg)
+        self.train_x3 = train_x3
+        if train_x3:
+            self.x3_conv = True    # the forward of the x3 test graph: encoder_x3() on packed_x3 and the split16 activations
         self.fp16_decoder = False  # network.FP16_DECODER governs the test graph only: the training decoder and heads are fp32
         self.is_train = True
         # TRAIN.WINOGRAD_CONV: the forward of the inference encoder (channel-blocked activations, fp32 Winograd
@@ -160,10 +174,10 @@ class deepIM_flownet(object):
         return self
 
     @staticmethod
-    def _check_loss_scale(scale):
+    def _check_loss_scale(scale, key="TRAIN.FP16_LOSS_SCALE"):
         v = float(scale)
         if not (v >= 1.0 and v <= 2.0 ** 24 and np.isfinite(v) and np.frexp(v)[0] == 0.5):
-            raise ValueError("TRAIN.FP16_LOSS_SCALE must be a power of two in [1, 2^24], got {}".format(scale))
+            raise ValueError("{} must be a power of two in [1, 2^24], got {}".format(key, scale))
         return v
 
     def get_test_symbol_share(self, cfg):
@@ -904,6 +918,8 @@ def _train_methods():
         self.ws["d_rot"], self.ws["d_trans"] = ctx.empty((B, 4)), ctx.empty((B, 3))
         if self.fp16_conv:
             self._bind_train_fp16()
+        if self.train_x3:
+            self._bind_train_x3()
         if self.se3_dist_loss:            # deepIM_flownet.py:238-262
             A["zoom_trans_gt"], A["rot_loss"] = ctx.empty((B, 3)), ctx.empty((B,))
             A["trans_loss"], A["trans_loss_sum"] = ctx.empty((B, 3, 1)), ctx.empty((1,))
@@ -925,6 +941,24 @@ def _train_methods():
         self.amp_state = ctx.empty((4,), dtype=np.uint32)
         self.set_loss_scale(self.loss_scale_init)
 
+    def _bind_train_x3(self):
+        """Buffers of the split-fp16 encoder backward (bind() already made packed_x3, conv1's pack included, and the split16
+        activations): two split16 gradient buffers (ping-pong, sized for the largest activation), the dgrad workspace (packed
+        weights + parity-class buffer) and the scale state {scale, inv_scale, overflow, good_steps}."""
+        ctx, B = self.ctx, self.B
+        if ENCODER[0][0] not in self.packed_x3:
+            raise NotImplementedError("TRAIN.X3_CONV needs the 8-channel network input with W % 4 == 0 (conv1 on the split-fp16 patch "
+                                      "kernel)")
+        big = max(B * _out_hw(hh, ww, k, s_, p_)[0] * _out_hw(hh, ww, k, s_, p_)[1] * cout
+                  for _n, _ci, hh, ww, cout, k, s_, p_ in self.enc_geom)
+        self.ws["gx3a"] = ctx.empty((2 * big,), dtype=np.float16)
+        self.ws["gx3b"] = ctx.empty((2 * big,), dtype=np.float16)
+        nb = max(lib.load().deepim_conv_dgrad_x3_workspace_size(B, cin, hh, ww, cout, k, s_, p_)
+                 for _n, cin, hh, ww, cout, k, s_, p_ in self.enc_geom[1:] if cin % 128 == 0)
+        self.ws["dgradx3"] = ctx.empty(((nb + 1) // 2,), dtype=np.float16)
+        self.amp_state = ctx.empty((4,), dtype=np.uint32)
+        self.set_loss_scale(self.loss_scale_init)
+
     def set_loss_scale(self, scale, good_steps=0):
         """Overwrite the device loss-scale state: scale (a power of two), overflow cleared."""
         v = self._check_loss_scale(scale)
@@ -934,7 +968,7 @@ def _train_methods():
         self.amp_state.copyfrom(st)
 
     def loss_scale(self):
-        """The device loss-scale state as a dict (for logging and tests). The only call of the fp16 training graph that syncs."""
+        """The device loss-scale state as a dict (for logging and tests). The only call of the fp16 / x3 training graphs that syncs."""
         st = self.amp_state.asnumpy()
         f = st[:2].view(np.float32)
         return {"scale": float(f[0]), "inv_scale": float(f[1]), "overflow": bool(st[2]), "good_steps": int(st[3])}
@@ -966,6 +1000,48 @@ def _train_methods():
             lib.deepim_conv2d_wgrad_f16(h, dw, src, x_, st, B, cin_, cpad, hh_, ww_, cout_, k_, s_, p_, layout)
             if li > 0:
                 lib.deepim_conv2d_dgrad_f16(h, y_, x_, P[name + "_weight"], W_["dgrad16"], B, cin_, hh_, ww_, cout_, k_, s_, p_)
+            x_, y_ = y_, x_
+        return G
+
+    def _encoder_backward_x3(self, e61):
+        """Backward of the split-fp16 encoder, last layer first: dz = split(lrelu'(y)·e, 1) and db in one walk, dW as
+        three fp16 MFMAs per fragment pair, d = split(conv_transpose(dz, split(w, s_w)) / s_w, 1) into the other split16 buffer.
+        e61: the fp32 NCHW gradient reaching conv6_1 (fc6 data gradient + d_dec61), scaled by S inside the first walk. The two
+        shapes the x3 kernels do not take run on the fp32 kernels over converted tensors: conv1's weight gradient (Cin = 8) and
+        conv2's data gradient (64 output channels); the fp32 ping-pong buffers are free for them once the first walk has read e61."""
+        A, P, G, W_, h, B = self.act, self.params, self.grad, self.ws, self.ctx.handle, self.B
+        c, st = ctypes.c_float, self.amp_state
+        lib.deepim_x3_status_to_state(h, st)      # a clamp in the forward: the step is skipped, as after one in the backward
+        skips = {"conv5_1": W_["d_skip5"], "conv4_1": W_["d_skip4"]} if self.with_decoder else {}
+        x_, y_ = W_["gx3a"], W_["gx3b"]
+        fa, fb = W_["ga"], W_["gb"]
+        for li in range(len(self.enc_geom) - 1, -1, -1):
+            name, cin_, hh_, ww_, cout_, k_, s_, p_ = self.enc_geom[li]
+            ho_, wo_ = _out_hw(hh_, ww_, k_, s_, p_)
+            last = li == len(self.enc_geom) - 1
+            lib.deepim_lrelu_bias_backward_x3(h, x_, G[name + "_bias"], None if last else x_, e61 if last else skips.get(name),
+                                              A[name + "_x"], st, c(SLOPE), B, cout_, ho_, wo_)
+            if name + "_weight" in G.tm:
+                dw, layout = G.tm[name + "_weight"][0], 1
+            else:
+                dw, layout = dict.__getitem__(G, name + "_weight"), 0
+            if li == 0:      # dz in real units as NCHW fp32, then the fp32 weight gradient from the NCHW net input
+                lib.deepim_split16_to_nchw_f32_unscaled(h, fa, x_, st, B, cout_, ho_, wo_, c(1.0))
+                if layout:
+                    lib.deepim_conv2d_wgrad_tm(h, dw, A["net_input"], fa, B, cin_, hh_, ww_, cout_, k_, k_, s_, p_)
+                else:
+                    lib.deepim_conv2d_wgrad(h, dw, A["net_input"], fa, B, cin_, hh_, ww_, cout_, k_, k_, s_, p_)
+                break
+            lib.deepim_conv2d_wgrad_x3(h, dw, A[self.enc_geom[li - 1][0] + "_x"], x_, st, B, cin_, hh_, ww_, cout_, k_, s_, p_, layout,
+                                       c(self.X3_ACT_SCALE))
+            if cin_ % 128 == 0:
+                lib.deepim_conv2d_dgrad_x3(h, y_, x_, P[name + "_weight"], W_["dgradx3"], st, B, cin_, hh_, ww_, cout_, k_, s_, p_,
+                                           c(self.x3_wscale[name]))
+            else:            # conv2: the scaled dz as NCHW fp32 → fp32 data gradient → split16 at scale 1
+                lib.deepim_split16_to_nchw_f32(h, fa, x_, B, cout_, ho_, wo_, c(1.0))
+                self._dgrad(fb, fa, P[name + "_weight"], B, cin_, hh_, ww_, cout_, k_, s_, p_, ho_, wo_)
+                lib.deepim_nchw_f32_to_split16(h, y_, fb, B, cin_, hh_, ww_, c(1.0))
+                lib.deepim_x3_status_to_state(h, st)
             x_, y_ = y_, x_
         return G
 
@@ -1144,6 +1220,10 @@ def _train_methods():
             if self.with_decoder:
                 lib.deepim_axpy(h, ga, W_["d_dec61"], c(1.0), B * n6)
             return self._encoder_backward_f16(ga)
+        if self.train_x3:
+            if self.with_decoder:
+                lib.deepim_axpy(h, ga, W_["d_dec61"], c(1.0), B * n6)
+            return self._encoder_backward_x3(ga)
         skips = {"conv5_1": "d_skip5", "conv4_1": "d_skip4"} if self.with_decoder else {}
         # encoder, last layer first: dz = lrelu'(y)·(dy [+ the gradient over the layer's skip connection]) and the bias gradient in
         # one fused walk, in place over dy; dx into the other buffer. (_dgrad can apply the activation gradient of the layer below
@@ -1212,12 +1292,15 @@ def _train_methods():
             dev = self.ctx.empty((len(rows), 6), np.uint64)
             dev.copyfrom(np.array(rows, dtype=np.uint64))
             tab = self._sgd_table = (float(wd), dev, len(rows), block)
-        if self.fp16_conv:
-            # mixed precision: no parameter moves on a step whose gradients overflowed; then the loss-scale step
+        if self.fp16_conv or self.train_x3:
+            # scaled gradients: no parameter moves on a step whose gradients overflowed; then the scale step
             lib.deepim_sgd_mom_update_multi_amp(h, tab[1], tab[2], tab[3], c(lr), c(momentum), c(rescale_grad), c(clip_gradient or 0.0),
                                                 self.amp_state)
             lib.deepim_amp_scale_update(h, self.amp_state, self.loss_scale_window)
-            self._repack_f16()
+            if self.fp16_conv:
+                self._repack_f16()
+            else:
+                self._repack_x3()
         else:
             lib.deepim_sgd_mom_update_multi(h, tab[1], tab[2], tab[3], c(lr), c(momentum), c(rescale_grad), c(clip_gradient or 0.0))
         orders = self._train_pack_orders()
@@ -1226,7 +1309,7 @@ def _train_methods():
             if not name.endswith("_weight") or len(shape) != 4 or name.endswith("upsampling_weight"):
                 continue
             base = name[: -len("_weight")]
-            if self.fp16_conv and base in enc:      # the fp16 encoder reads packed_f16 only
+            if (self.fp16_conv or self.train_x3) and base in enc:      # the fp16 / x3 encoder reads packed_f16 / packed_x3 only
                 continue
             if self.train_winograd and base in enc:  # channel-blocked encoder: _repack_train_winograd below
                 continue
@@ -1275,6 +1358,19 @@ def _train_methods():
             else:
                 lib.deepim_conv1_x3_pack_weights(h, self.packed_f16["conv1_patch"], w1, ctypes.c_float(1.0))
 
+    def _repack_x3(self):
+        """The split-fp16 weights the x3 encoder reads (packed_x3, conv1's patch-kernel pack included), from the fp32 masters at the
+        bind-time scales x3_wscale (recomputing them would sync the host). A weight that has outgrown its scale is clamped by the
+        pack: the range check raises the overflow word for it, so the next step is skipped and reported, not silently wrong."""
+        h, P, c, L = self.ctx.handle, self.params, ctypes.c_float, lib.load()
+        for li, (name, cin, hh, ww, cout, k, s_, p_) in enumerate(self.enc_geom):
+            w, sw = P[name + "_weight"], c(self.x3_wscale[name])
+            if li == 0:
+                lib.deepim_conv1_x3_pack_weights(h, self.packed_x3[name], w, sw)
+            else:
+                lib.deepim_conv_x3_pack_weights(h, self.packed_x3[name], w, cout, cin, k, k, sw)
+            lib.deepim_x3_weight_range_check(h, w, w.size, sw, self.amp_state)
+
     def train_step(self, data, label, updater, iters=None, lr=None, wd=None, momentum=None, on_iter=None):
         """ONE training step as the reference runs it (deepim/core/module.py:1131-1137 with network.TRAIN_ITER_SIZE = 4, yaml
         :57-58): for every refinement iteration forward_backward → preds (rot_est, trans_est) → update (SGD + re-pack), and between
@@ -1319,7 +1415,8 @@ def _train_methods():
         return {n: order(h, B, cin, hh, ww, cout, k, k, s_, p_) for n, (cin, hh, ww, cout, k, s_, p_) in geo.items()}
 
     return dict(bind_train=bind_train, _bind_train_fp16=_bind_train_fp16, set_loss_scale=set_loss_scale, loss_scale=loss_scale,
-                _encoder_backward_f16=_encoder_backward_f16, _repack_f16=_repack_f16, forward_train=forward_train, _dgrad=_dgrad,
+                _encoder_backward_f16=_encoder_backward_f16, _repack_f16=_repack_f16,
+                _bind_train_x3=_bind_train_x3, _encoder_backward_x3=_encoder_backward_x3, _repack_x3=_repack_x3, forward_train=forward_train, _dgrad=_dgrad,
                 _small_conv_backward=_small_conv_backward, _head_conv_backward=_head_conv_backward,
                 _repack_train_winograd=_repack_train_winograd,
                 _deconv_backward=_deconv_backward, _decoder_backward=_decoder_backward, backward=backward, update=update, train_step=train_step,

@@ -1,7 +1,8 @@
 """Dev probe: time one training-style iteration (forward_train + backward + update) and its pieces.
-usage: bench_train.py [B] [heads] [fp16] [wino] [step4] [json]   — `heads` adds the refinement decoder with the flow and mask losses; `fp16`
+usage: bench_train.py [B] [heads] [fp16] [wino] [x3] [step4] [json]   — `heads` adds the refinement decoder with the flow and mask losses; `fp16`
 trains with network.FP16_CONV (fp16 encoder forward and backward, loss scaling); `wino` sets TRAIN.WINOGRAD_CONV
-(fp32 training on the channel-blocked Winograd encoder; "winograd": true in the JSON); `step4`
+(fp32 training on the channel-blocked Winograd encoder; "winograd": true in the JSON); `x3` sets TRAIN.X3_CONV
+(split-fp16 encoder forward and backward with a gradient scale; "dtype": "x3" in the JSON); `step4`
 times the reference's whole training step instead (module.py:1131-1137: TRAIN_ITER_SIZE = 4 iterations with the device batch
 updater — RT_transform, re-render, calc_RT_delta, K·T, lib/flow_c labels, depth > 0.2 mask — between them: net.train_step);
 `json` prints one JSON line instead of the sentence (bench.py's other_configs["training_iteration_*" / "training_step_x4_*"])."""
@@ -19,9 +20,11 @@ HEADS = "heads" in sys.argv[2:]
 cfg = default_config(); cfg.network.PRED_FLOW = cfg.network.PRED_MASK = HEADS
 FP16 = "fp16" in sys.argv[2:]
 cfg.network.FP16_CONV = FP16
-DTYPE = "f16" if FP16 else "f32"
 WINO = "wino" in sys.argv[2:]
 cfg.TRAIN.WINOGRAD_CONV = WINO
+X3 = "x3" in sys.argv[2:] and not FP16
+cfg.TRAIN.X3_CONV = X3
+DTYPE = "f16" if FP16 else ("x3" if X3 else "f32")
 net = deepIM_flownet().get_symbol(cfg, is_train=True)
 net.bind_train(ctx, B, net.init_weights(cfg, seed=91))
 gt = (d["depth_gt_observed"] > 0).astype(np.float32)
@@ -97,7 +100,7 @@ if "json" in sys.argv[2:]:
                           "full graph: encoder + refinement decoder + flow and mask heads + point-matching loss" if HEADS else
                           "pose branch: encoder + fc + point-matching loss")}))
     sys.exit(0)
-if FP16:
+if FP16 or X3:
     print("loss scale after the run: %s" % net.loss_scale())
-print(("heads " if HEADS else "pose ") + ("fp16 " if FP16 else "") + ("wino " if WINO else "") + "B=%d: forward %.2f ms (%.0f TF), backward %.2f ms (%.0f TF on 2x forward FLOPs), update+repack %.2f ms; %.1f training iterations/s (pairs/s %.0f)"
+print(("heads " if HEADS else "pose ") + ("fp16 " if FP16 else "") + ("wino " if WINO else "") + ("x3 " if X3 else "") + "B=%d: forward %.2f ms (%.0f TF), backward %.2f ms (%.0f TF on 2x forward FLOPs), update+repack %.2f ms; %.1f training iterations/s (pairs/s %.0f)"
       % (B, fwd, gf / fwd / 1e9, bwd, 2 * gf / bwd / 1e9, upd, 1e3 / (fwd + bwd + upd), B * 1e3 / (fwd + bwd + upd)))
