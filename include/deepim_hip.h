@@ -67,7 +67,9 @@ void* deepim_stream(deepim_ctx* ctx);           /* hipStream_t, for interop */
  * whose transformed weights are identically zero, 0 = runs all 16 (A/B measurements). "wino_shared": 1 (default) = Winograd layers with
  * Cout % 64 == 0 run on the shared-transform kernel (8- or 4-wave blocks, the input transform computed once per block and handed over
  * through LDS), 0 = the round-4 one-wave kernel. "wino_wide": block shape of that kernel — 1 (default) = per layer by the work per CU,
- * 0 = 64 channels x 64 tiles, 3 = 128 x 32 (Cout % 128 == 0), 2 = 64 x 32 on four waves, two blocks per CU. "wino_split": its split
+ * 0 = 64 channels x 64 tiles, 3 = 128 x 32 (Cout % 128 == 0), 2 = 64 x 32 on four waves, two blocks per CU, 4 = 256 x 32 on nine
+ * accumulator tuples per wave where that shape exists (deepim_conv2d_wino_forward_s2d3 with "wino_s2d_skip" on, Cin % 16 == 0 and
+ * Cout % 256 == 0: the same bits as 3 for the same K slicing), anywhere else as 3. "wino_split": its split
  * over the input channels where the grid does not fill the chip — 0 (default) = the deterministic plan of the geometry, 1 = never
  * (one block walks all of Cin: the 3x3 layers are then bit-identical to the one-wave kernel), n = at most n slices. "wino_persistent": 1
  * (default) = its grid is one block per resident slot (256 of 8 waves, 512 of 4), each walking its share of the tile blocks, 0 = one
@@ -332,7 +334,7 @@ int deepim_conv_wino_preferred(deepim_ctx* ctx, int B, int Cin, int H, int W, in
 int deepim_conv_wino_preferred_s2d(deepim_ctx* ctx, int B, int Cin, int H, int W, int Cout);
 /* The launch plan the shared-transform kernel would use for a layer under the context's options (no launch; tests and docs read it):
  * arguments as deepim_conv2d_wino_forward sees them (s2d = 1: Cin, H, W of the space-to-depth problem). plan[0] block shape (0 = 64
- * channels x 64 tiles, 1 = 128 x 32, 2 = 64 x 32 on four waves), [1] grid, [2] K slices S, [3] K steps per slice, [4] stream-K granules
+ * channels x 64 tiles, 1 = 128 x 32, 2 = 64 x 32 on four waves, 3 = 256 x 32 on nine accumulator tuples), [1] grid, [2] K slices S, [3] K steps per slice, [4] stream-K granules
  * per tile block (0 = off: whole tile blocks per block), [5] granules of the last round per persistent block, [6] whole tile blocks
  * per persistent block before them, [7] tile blocks of the layer (incl. the padding of the XCD deal), [8] the first so many blocks of an
  * XCD take one granule more. All -1 where another kernel runs the layer. Host arithmetic only: ctx = NULL asks for the plan under
@@ -360,11 +362,18 @@ int deepim_conv2d_wino_forward_s2d(deepim_ctx* ctx, float* out, const float* in_
  * shared-transform kernel's phase walk. _pack_weights_s2d3 takes the layer's own (Cout, Cin, 3, 3) weights (size
  * deepim_conv_wino_packed_size(Cout, 4*Cin)); _forward_s2d3 the (B, Cin, H, W) input's space-to-depth NC8 form (even H and W), output
  * (B, Cout, H/2, W/2). _preferred_s2d3 is 0 under "conv_max_split" = 1, without the shared-transform kernel (Cout % 64, Cin % 16,
- * "wino_shared" / "wino_two_wave"), for odd H or W, and below the measured batch threshold. deepim_conv_wino_plan takes s2d = 2. */
+ * "wino_shared" / "wino_two_wave"), for odd H or W, and below the measured batch threshold. deepim_conv_wino_plan takes s2d = 2.
+ * _forward_s2d3_wide is the same layer on blocks of 256 channels x 32 tiles with nine accumulator tuples per wave, where that shape
+ * exists ("wino_wide" at its default, "wino_s2d_skip" on, Cin % 16 == 0, Cout % 256 == 0; anywhere else it is _forward_s2d3): the same
+ * bits for the same K slicing. _preferred_s2d3_wide says where it measured faster (and _preferred_s2d3 holds): from two whole rounds of
+ * such blocks on the chip's 256 CUs, or one round of 80 to 256. deepim_conv_wino_plan takes s2d = 3 for it and reports block shape 3. */
 int deepim_conv_wino_preferred_s2d3(deepim_ctx* ctx, int B, int Cin, int H, int W, int Cout);
+int deepim_conv_wino_preferred_s2d3_wide(deepim_ctx* ctx, int B, int Cin, int H, int W, int Cout);
 int deepim_conv_wino_pack_weights_s2d3(deepim_ctx* ctx, float* packed_w, const float* w /*Cout,Cin,3,3 dev*/, int Cout, int Cin);
 int deepim_conv2d_wino_forward_s2d3(deepim_ctx* ctx, float* out, const float* in_s2d, const float* packed_w, const float* bias,
                                     int B, int Cin, int H, int W, int Cout, float slope, int out_nc8, int out_ctotal, int out_coff);
+int deepim_conv2d_wino_forward_s2d3_wide(deepim_ctx* ctx, float* out, const float* in_s2d, const float* packed_w, const float* bias,
+                                         int B, int Cin, int H, int W, int Cout, float slope, int out_nc8, int out_ctotal, int out_coff);
 int deepim_relayout_nc8_s2d(deepim_ctx* ctx, float* dst, const float* src, int B, int C, int H, int W, int to_s2d);
 /* The DATA GRADIENT of a 3x3 stride-1 pad-1 layer on the same kernels: it is the same kind of convolution from the layer's Cout to its
  * Cin channels on the transposed, flipped weights. _pack_weights_dgrad writes U' of that Cin <- Cout problem straight from the layer's

@@ -68,7 +68,7 @@ struct deepim_ctx {
   int wgrad_lds;         // 1 (default): LDS-staged weight-gradient kernel; 0: the round-2 register-fed kernel (A/B measurements)
   int wino_s2d_skip;     // 1 (default): stride-2 Winograd layers skip the positions whose weights are identically zero; 0: all 16 (A/B measurements)
   int wino_shared;       // 1 (default): Winograd layers with Cout % 64 == 0 on the 8-wave shared-transform kernel (conv_wino8_kernel); 0: the round-4 one-wave kernel
-  int wino_wide;         // block shape of the shared-transform kernel: 1 (default) = per layer by the work per CU, 0 = 64 ch x 64 tiles, 3 = 128 x 32, 2 = 64 x 32 on four waves (two blocks per CU)
+  int wino_wide;         // block shape of the shared-transform kernel: 1 (default) = per layer by the work per CU, 0 = 64 ch x 64 tiles, 3 = 128 x 32, 2 = 64 x 32 on four waves (two blocks per CU), 4 = 256 x 32 on nine accumulator tuples (3x3 stride-2 walk, Cout % 256 == 0; elsewhere as 3)
   int wino_split;        // K-split of the shared-transform kernel: 0 (default) = the plan of wino8_split_plan, 1 = never, n = at most n slices
   int conv_fewout_blocks, conv_fewout_minc;   // few-filter heads: channel slices so that the grid has about this many blocks (0 = default: 1024 where the pixels alone give >= 32 blocks, else 512), of at least this many channels each (32)
   int conv_fewout_quad;  // 1 (default): the 3x3 stride-1 heads with W % 4 == 0 on the four-pixels-per-lane kernel; 0: one pixel per lane

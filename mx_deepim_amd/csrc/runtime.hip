@@ -238,7 +238,7 @@ extern "C" int deepim_set_option(deepim_ctx* ctx, const char* name, int value) {
   if (strcmp(name, "wino_fin") == 0) { ctx->wino_fin = value != 0; return 0; }
   if (strcmp(name, "wino_streamk") == 0) { ctx->wino_streamk = value < 0 ? 0 : value > 2 ? 2 : value; return 0; }
   if (strcmp(name, "wino_split") == 0) { ctx->wino_split = value < 0 ? 0 : value; return 0; }
-  if (strcmp(name, "wino_wide") == 0) { ctx->wino_wide = (value >= 0 && value <= 3) ? value : 1; return 0; }
+  if (strcmp(name, "wino_wide") == 0) { ctx->wino_wide = (value >= 0 && value <= 4) ? value : 1; return 0; }
   if (strcmp(name, "wino_shared") == 0) { ctx->wino_shared = value ? 1 : 0; return 0; }
   if (strcmp(name, "wino_s2d_skip") == 0) { ctx->wino_s2d_skip = value ? 1 : 0; return 0; }
   if (strcmp(name, "f16_dev_flags") == 0) { DI_REQUIRE(value == 0 || value == DI_F16_NO_PP, "f16_dev_flags: 0 or 16"); ctx->f16_dev_flags = value; return 0; }

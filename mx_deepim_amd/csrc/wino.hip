@@ -1014,6 +1014,265 @@ __device__ __forceinline__ void wino8_body(const WinoParams& p, char* smem, cons
 #undef W8_LDS4
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Nine-accumulator blocks for the 3x3 stride-2 walk (S2D = 2 only; "wino_wide" = 4; profiles/r13_s2d3_nine_tuples.md). Position 3 is
+// dead in every phase of that walk, so only the nine positions xi, nu in {0, 1, 2} ever accumulate: a wave that owns ALL nine of one
+// 32-channel x 32-tile sub-block needs nine f32x16 tuples = 144 registers, which fit at two waves per SIMD once the accumulators are
+// plain architectural registers (no "a" constraints: gfx950's file is unified, the MFMAs read and write v[...] in place) and the
+// operands come through short rings instead of whole-stage arrays. A 512-thread block is then 256 channels x 32 tiles:
+//   * wave w multiplies sub-block w: per eight-step body 4 4 6 6 6 6 9 9 = 50 live positions x 4 k-steps = 200 MFMAs, the same for
+//     every wave (the 128 x 32 block deals its SIMD's waves 15 : 10), twice the MFMAs per barrier, every V feeds 256 channels;
+//   * operands: U straight from global memory, W9_DU positions ahead (no barrier stands in its way), V from LDS W9_DV positions ahead.
+//     50 is a multiple of both depths, so a ring slot is a compile-time constant at every place of the body. All V reads of stage k
+//     lie between barriers k and k + 1: the barrier of a step sits in front of its last W9_DV positions' MFMAs, whose operands are in
+//     registers by then — a wave leaves the barrier with 8 MFMAs to issue while its first reads of the next stage are in flight;
+//   * transform role as in the 128 x 32 shape (32 tiles x 8 channels x 4 patch columns over the 512 lanes, two channels per lane, live
+//     patch rows only, DPP column pass, two V slots, one barrier per stage); the two waves of a SIMD do it at different places of the
+//     step: waves 0-3 in the step's first two positions (stage k + 1 into the other slot), waves 4-7 behind the barrier (stage k + 2
+//     into the slot whose reads the barrier has just closed);
+//   * output transform in the wave's own registers: the operations of W8_FINISH in its order with the terms that are identically
+//     zero (nu = 3, xi = 3) left out — for the same K slicing the results are bit-identical to the 128 x 32 shape's. No exchange
+//     through LDS, no second barrier.
+constexpr int W9_DU = 5, W9_DV = 2;
+constexpr int w9_n(int P) { return ((P >> 1) ? 3 : 2) * ((P & 1) ? 3 : 2); }                       // live positions of a stage of phase P
+constexpr int w9_xi(int P, int e) { return e / ((P & 1) ? 3 : 2) + ((P >> 1) ? 0 : 1); }           // ... its e-th one
+constexpr int w9_nu(int P, int e) { return e % ((P & 1) ? 3 : 2) + ((P & 1) ? 0 : 1); }
+constexpr int w9_g0(int J) { int g = 0; for (int j = 0; j < J; ++j) g += w9_n((j >> 1) & 3); return g; }   // entries of the body before step J
+constexpr int w9_step_of(int G) { int j = 0; while (G >= w9_n((j >> 1) & 3)) { G -= w9_n((j >> 1) & 3); ++j; } return j; }
+constexpr int w9_pos_of(int G) { int j = 0; while (G >= w9_n((j >> 1) & 3)) { G -= w9_n((j >> 1) & 3); ++j; } return G; }
+static_assert(w9_g0(8) % W9_DU == 0 && w9_g0(8) % W9_DV == 0, "ring slots must repeat from body to body");
+
+template <int OUT_NC8, int PH>
+__device__ __forceinline__ void wino9_body(const WinoParams& p, char* smem, const int wave, const int bid, const int kb, const int ke,
+                                           const int copy) {
+  constexpr int QS = W8_QSW, VSLOT = 16 * QS;
+  int tid = threadIdx.x;
+  asm volatile("" : "+v"(tid));   // per tile, as in wino8_body
+  const int lane = tid & 63;
+  const int lrow = lane >> 5, lcol = lane & 31;
+  int mb2, bx;
+  w8_block_coords(p, bid, mb2, bx);
+  if (bx >= p.gx) return;
+  int tpi = p.TY * p.TX, TXp = p.TX;
+  asm volatile("" : "+s"(tpi), "+s"(TXp));
+  const int c8n = p.Cin >> 3;
+  const int hw32 = p.H * p.W * 32;
+  const int npb = c8n >> 2;
+
+  // ---- transform role: lane = (tile Tl of 32, channel pair cg of the 8 channels, patch column j)
+  const int j = lane & 3, cg = (lane >> 2) & 3, Tl = wave * 4 + (lane >> 4);
+  int voffT[3];   // patch rows 0..2 (row 3 feeds only xi = 3)
+  {
+    const int tT = bx * 32 + Tl;
+    const bool tv = tT < p.ntiles;
+    const int n = tv ? tT / tpi : 0;
+    const int tr = tv ? tT - n * tpi : 0;
+    const int ty = tr / TXp, tx = tr - ty * TXp;
+    const int x = 2 * tx - 1 + j;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      const int y = 2 * ty - 1 + i;
+      const bool ok = tv && y >= 0 && y < p.H && x >= 0 && x < p.W;
+      voffT[i] = ok ? (((n * c8n) * p.H + y) * p.W + x) * 32 + cg * 8 : (int)0x80000000;
+    }
+  }
+  const float sgn = j == 1 ? 1.f : -1.f;
+  const unsigned vw = (unsigned)((cg >> 1) * W8_HS + (cg & 1) * 8 + Tl * 16 + j * QS);
+  // ---- multiply role: sub-block `wave` of the block's eight
+  const unsigned rb = (unsigned)(lrow * W8_HS + lcol * 16);
+  const int ra_g = lane * 16;
+  const int ra_s0 = ((mb2 * 8 + wave) * c8n) * 16384;
+  const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.in, 0, (int)p.in_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrw = __builtin_amdgcn_make_buffer_rsrc((void*)p.wd, 0, (int)p.wd_bytes, 0x00020000);
+
+  f32x16 acc[9];   // [xi * 3 + nu]
+  {
+    const float zf = 0.f;
+#pragma unroll
+    // zeroed by the matrix pipe (see wino8_body); the s_nop covers the v_mov that makes zf, which the hazard pass cannot see from here
+    for (int q = 0; q < 9; ++q) asm volatile("s_nop 4\n\tv_mfma_f32_32x32x2_f32 %0, %1, %1, 0" : "=&v"(acc[q]) : "v"(zf));
+  }
+  f32x2 raw[3], T[3];
+  f32x4 ua[W9_DU], va[W9_DV];
+
+#define W9_CB(s) ((((s) >> 1) & 3) * npb + (((s) >> 3) << 1) + ((s) & 1))
+#define W9_XLIVE(xi, P) ((xi) != 0 || ((P) >> 1))   /* rows xi = 0..2 of U in a stage of phase P; patch row 0 feeds xi = 0 only */
+#define W9_LDS4(off) (*reinterpret_cast<f32x4*>(smem + (off)))
+#define W9_PIX(stage, P)                                                                              \
+  {                                                                                                   \
+    const int st_ = min((stage), ke - 1);                                                             \
+    const int so_ = __builtin_amdgcn_readfirstlane(W9_CB(st_) * hw32);                                \
+    _Pragma("unroll") for (int i_ = 0; i_ < 3; ++i_)                                                  \
+      if (i_ != 0 || W9_XLIVE(0, P)) raw[i_] = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rsrc, voffT[i_], so_, 0)); \
+  }
+#define W9_ROW(P)                                                                                     \
+  {                                                                                                   \
+    if (W9_XLIVE(0, P)) T[0] = raw[0] - raw[2];                                                       \
+    T[1] = raw[1] + raw[2]; T[2] = raw[2] - raw[1];                                                   \
+  }
+// column pass of row xi across the quad (see W8_COL: the wait states and the DPP reads they protect are ONE asm statement)
+#define W9_DPPQ "quad_perm:[2,2,1,1] row_mask:0xf bank_mask:0xf"
+#define W9_COL(xi, slot_)                                                                             \
+  {                                                                                                   \
+    float c0_ = T[xi].x, c1_ = T[xi].y;                                                               \
+    asm volatile("s_nop 1\n\tv_fmac_f32_dpp %0, %0, %2 " W9_DPPQ "\n\tv_fmac_f32_dpp %1, %1, %2 " W9_DPPQ \
+                 : "+v"(c0_), "+v"(c1_) : "v"(sgn));                                                  \
+    f32x2 v_; v_.x = c0_; v_.y = c1_;                                                                 \
+    *reinterpret_cast<f32x2*>(smem + (vw + (unsigned)((slot_) * VSLOT + (xi) * 4 * QS))) = v_;        \
+  }
+#define W9_SYNC()                                                                                     \
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                  \
+  __builtin_amdgcn_s_barrier();                                                                       \
+  asm volatile("" ::: "memory");
+// operands of entry G_ (position E_ of step J_ of the body that starts at stage k; J_ may run into the next body)
+#define W9_RDU(G_, J_, E_, rsa_) \
+  ua[(G_) % W9_DU] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrw, ra_g + (w9_xi(((J_) >> 1) & 3, E_) * 4 + w9_nu(((J_) >> 1) & 3, E_)) * 1024, rsa_, 0));
+#define W9_RDV(G_, J_, E_) \
+  va[(G_) % W9_DV] = W9_LDS4(rb + (unsigned)(((J_) & 1) * VSLOT + (w9_xi(((J_) >> 1) & 3, E_) * 4 + w9_nu(((J_) >> 1) & 3, E_)) * QS));
+#define W9_RSA(s) __builtin_amdgcn_readfirstlane(ra_s0 + W9_CB(s) * 16384)
+
+  // ---- prologue: stage kb into slot 0 (waves 4-7: stage kb + 1 into slot 1 as well), then the rings' first entries
+  W9_PIX(kb, 0)
+  W9_ROW(0)
+  W9_PIX(kb + 1, 0)
+  W9_COL(1, 0)
+  W9_COL(2, 0)
+  if constexpr (PH == 1) {
+    W9_ROW(0)
+    W9_PIX(kb + 2, 1)
+    W9_COL(1, 1)
+    W9_COL(2, 1)
+  }
+  W9_SYNC()
+  {
+    const int r0_ = W9_RSA(kb), r1_ = W9_RSA(kb + 1);
+    W9_RDU(0, 0, 0, r0_) W9_RDU(1, 0, 1, r0_) W9_RDU(2, 0, 2, r0_) W9_RDU(3, 0, 3, r0_) W9_RDU(4, 1, 0, r1_)
+    W9_RDV(0, 0, 0) W9_RDV(1, 0, 1)
+  }
+  __builtin_amdgcn_sched_barrier(0);
+
+  // ---- entry (J, E): the four MFMAs of position E of step J, each with its share of the transform role behind it, then the refill of
+  // the two ring slots it has freed. The step's barrier stands in front of the MFMAs of its last W9_DV positions.
+#define W9_SLOT(J, E, S)                                                                              \
+    acc[a_] = __builtin_amdgcn_mfma_f32_32x32x2f32((S) == 0 ? ua[G_ % W9_DU].x : (S) == 1 ? ua[G_ % W9_DU].y : (S) == 2 ? ua[G_ % W9_DU].z : ua[G_ % W9_DU].w, \
+                                                   (S) == 0 ? va[G_ % W9_DV].x : (S) == 1 ? va[G_ % W9_DV].y : (S) == 2 ? va[G_ % W9_DV].z : va[G_ % W9_DV].w, acc[a_], 0, 0, 0); \
+    if constexpr ((E) == (PH == 0 ? 0 : n_ - 2)) {   /* transform of stage k + J + 1 (waves 0-3) / k + J + 2 (waves 4-7) */ \
+      constexpr int PT_ = (((J) + 1 + PH) >> 1) & 3, SLT_ = ((J) + 1 + PH) & 1;                        \
+      if constexpr ((S) == 0) { W9_ROW(PT_) }                                                         \
+      else if constexpr (W9_XLIVE((S) - 1, PT_)) { W9_COL((S) - 1, SLT_) }                            \
+    }                                                                                                 \
+    if constexpr ((E) == (PH == 0 ? 1 : n_ - 1) && (S) == 0) { W9_PIX(k + (J) + 2 + PH, ((((J) + 2 + PH) >> 1) & 3)) } \
+    __builtin_amdgcn_sched_barrier(0);
+#define W9_ENTRY(J, E)                                                                                \
+  if constexpr (PH >= 0 && (E) < w9_n(((J) >> 1) & 3)) {                                              \
+    constexpr int P_ = ((J) >> 1) & 3, n_ = w9_n(P_), G_ = w9_g0(J) + (E) + 0 * PH;   /* (+ 0 * PH: checked per instantiation only) */ \
+    constexpr int a_ = w9_xi(P_, E) * 3 + w9_nu(P_, E) + 0 * PH;                                      \
+    constexpr int GU_ = G_ + W9_DU, JU_ = w9_step_of(GU_), EU_ = w9_pos_of(GU_);                      \
+    constexpr int GV_ = G_ + W9_DV, JV_ = w9_step_of(GV_), EV_ = w9_pos_of(GV_);                      \
+    static_assert((E) >= n_ || (JU_ - (J) <= 2 && JV_ - (J) <= 1), "ring look-ahead");                               \
+    if constexpr ((E) == n_ - W9_DV) { W9_SYNC() }                                                    \
+    W9_SLOT(J, E, 0) W9_SLOT(J, E, 1) W9_SLOT(J, E, 2) W9_SLOT(J, E, 3)                               \
+    W9_RDU(G_, JU_, EU_, (JU_ == (J) ? rsa0_ : JU_ == (J) + 1 ? rsa1_ : rsa2_))                       \
+    W9_RDV(G_, JV_, EV_)                                                                              \
+    __builtin_amdgcn_sched_barrier(0);                                                                \
+  }
+#define W9_STEP(J)                                                                                    \
+  {                                                                                                   \
+    const int rsa0_ = W9_RSA(k + (J)), rsa1_ = W9_RSA(k + (J) + 1), rsa2_ = W9_RSA(k + (J) + 2);      \
+    W9_ENTRY(J, 0) W9_ENTRY(J, 1) W9_ENTRY(J, 2) W9_ENTRY(J, 3) W9_ENTRY(J, 4) W9_ENTRY(J, 5) W9_ENTRY(J, 6) W9_ENTRY(J, 7) W9_ENTRY(J, 8) \
+  }
+  // kb % 8 == 0 and (ke - kb) % 8 == 0 (the launcher checks): phases 0 0 1 1 2 2 3 3 per body. Past the last stage the look-ahead re-reads
+  // the last pixels, reads U of blocks inside the same sub-block and V nobody multiplies.
+  for (int k = kb; k < ke; k += 8) {
+    W9_STEP(0) W9_STEP(1) W9_STEP(2) W9_STEP(3) W9_STEP(4) W9_STEP(5) W9_STEP(6) W9_STEP(7)
+  }
+#undef W9_STEP
+#undef W9_ENTRY
+#undef W9_SLOT
+#undef W9_RSA
+#undef W9_RDV
+#undef W9_RDU
+#undef W9_COL
+#undef W9_DPPQ
+#undef W9_ROW
+#undef W9_PIX
+#undef W9_LDS4
+#undef W9_XLIVE
+#undef W9_CB
+
+  // ---- output transform, all in this wave: acc[xi * 3 + nu][r] = channel (r & 3) + 8 (r >> 2) + 4 lrow of the wave's 32, tile lcol.
+  // s[xi][0] = (m0 + m1) + m2, s[xi][1] = m1 - m2 (m3 = 0); Y[0][b] = ((s0 + s1) + s2) + bias, Y[1][b] = (s1 - s2) + bias (s3 = 0).
+  int bxe = __builtin_amdgcn_readfirstlane(bx), mb2e = __builtin_amdgcn_readfirstlane(mb2), tpie = __builtin_amdgcn_readfirstlane(tpi),
+      TXe = __builtin_amdgcn_readfirstlane(p.TX);
+  asm volatile("" : "+s"(bxe), "+s"(mb2e), "+s"(tpie), "+s"(TXe));   // computed HERE, not carried through the K loop (see wino8_body)
+  const int lanee = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+  const int lrow_e = lanee >> 5, lcol_e = lanee & 31;
+  const int t = bxe * 32 + lcol_e;
+  if (t >= p.ntiles) return;
+  const int n = t / tpie;
+  const int trm = t - n * tpie;
+  const int ty = trm / TXe, tx = trm - ty * TXe;
+  const int y0 = 2 * ty, x0 = 2 * tx;
+  const bool y1ok = y0 + 1 < p.H, x1ok = x0 + 1 < p.W;
+  const int mb = mb2e * 8 + wave;
+  float* const outp = copy >= 0 ? p.part + (long)copy * p.part_stride : p.out;
+  const float* const biasp = copy >= 0 ? nullptr : p.bias;
+  float slope_e = copy >= 0 ? 1.f : p.slope;
+  const bool through = copy >= 0 && p.sk_count != nullptr;
+  const __amdgpu_buffer_rsrc_t rsrp = __builtin_amdgcn_make_buffer_rsrc((void*)outp, 0, OUT_NC8 ? (int)p.out_bytes : 0, 0x00020000);
+  const int C8o = p.Cout >> 3, tpo = p.TY * TXe;
+  const int gstep = p.out_s2d ? tpo : p.H * p.W;
+  const int ab1 = p.out_s2d ? C8o * tpo : 1, ab2 = p.out_s2d ? 2 * C8o * tpo : p.W;
+  const int vo0 = ((p.out_s2d ? (n * 4 * C8o + mb * 4) * tpo + ty * TXe + tx : (n * C8o + mb * 4) * (p.H * p.W) + y0 * p.W + x0) * 32) + 16 * lrow_e;
+  asm volatile("" : "+v"(slope_e));
+  float4 bq[4];
+#pragma unroll
+  for (int g = 0; g < 4; ++g)
+    bq[g] = biasp ? *reinterpret_cast<const float4*>(biasp + mb * 32 + 8 * g + 4 * lrow_e) : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    float o[4][4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int r = 4 * g + e;
+      const float bv = e == 0 ? bq[g].x : e == 1 ? bq[g].y : e == 2 ? bq[g].z : bq[g].w;
+      float s[3][2];
+#pragma unroll
+      for (int xi = 0; xi < 3; ++xi) {
+        const float m0 = acc[xi * 3 + 0][r], m1 = acc[xi * 3 + 1][r], m2 = acc[xi * 3 + 2][r];
+        s[xi][0] = (m0 + m1) + m2;
+        s[xi][1] = m1 - m2;
+      }
+#pragma unroll
+      for (int b = 0; b < 2; ++b) {
+        float v0 = ((s[0][b] + s[1][b]) + s[2][b]) + bv;
+        float v1 = (s[1][b] - s[2][b]) + bv;
+        o[0 * 2 + b][e] = v0 > 0.f ? v0 : v0 * slope_e;
+        o[1 * 2 + b][e] = v1 > 0.f ? v1 : v1 * slope_e;
+      }
+    }
+#pragma unroll
+    for (int ab = 0; ab < 4; ++ab) {
+      const int a = ab >> 1, b = ab & 1;
+      if ((a && !y1ok) || (b && !x1ok)) continue;
+      if (OUT_NC8) {
+        const int so_ = (g * gstep + (ab == 0 ? 0 : ab == 1 ? ab1 : ab == 2 ? ab2 : ab1 + ab2)) * 32;
+        f32x4 ov; ov.x = o[ab][0]; ov.y = o[ab][1]; ov.z = o[ab][2]; ov.w = o[ab][3];
+        const auto od = __builtin_bit_cast(__attribute__((__vector_size__(4 * sizeof(unsigned)))) unsigned, ov);
+        if (through) __builtin_amdgcn_raw_buffer_store_b128(od, rsrp, vo0, so_, 17);   // a stream-K piece: straight to memory (sc0 sc1)
+        else __builtin_amdgcn_raw_buffer_store_b128(od, rsrp, vo0, so_, 0);
+      } else {
+        const long pix = (long)(y0 + a) * p.W + x0 + b;
+        const long c0 = (long)n * p.out_ctotal + p.out_coff + mb * 32 + 8 * g + 4 * lrow_e;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) outp[(c0 + e) * p.H * p.W + pix] = o[ab][e];
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+#undef W9_SYNC
+}
+
 // stream-K: which block's run holds granule u of the XCD's last-round granules (runs of sk_q + 1 for the first sk_rem blocks, sk_q after)
 __device__ __forceinline__ int w8_run_owner(const WinoParams& p, const int u) {
   const int big = p.sk_rem * (p.sk_q + 1);
@@ -1143,6 +1402,15 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   // waves w and w + 4 share a SIMD: a top and a bottom half each
   if (((wave >> 2) & 1) == 0) { W8_PERSIST((wino8_body<OUT_NC8, S2D, 0, SHAPE>(p, smem, wave, vb, bid, kb, ke, copy)), (SHAPE == 0 ? 64 : 32), (SHAPE == 1 ? 128 : 64)) }
   else { W8_PERSIST((wino8_body<OUT_NC8, S2D, 1, SHAPE>(p, smem, wave, vb, bid, kb, ke, copy)), (SHAPE == 0 ? 64 : 32), (SHAPE == 1 ? 128 : 64)) }
+}
+
+// The nine-accumulator blocks of the 3x3 stride-2 walk: 256 channels x 32 tiles, waves w and w + 4 share a SIMD
+template <int OUT_NC8>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv_wino9_kernel(WinoParams p) {
+  __shared__ __attribute__((aligned(16))) char smem[W8_LDS_HALF_BYTES];
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (((wave >> 2) & 1) == 0) { W8_PERSIST((wino9_body<OUT_NC8, 0>(p, smem, wave, bid, kb, ke, copy)), 32, 256) }
+  else { W8_PERSIST((wino9_body<OUT_NC8, 1>(p, smem, wave, bid, kb, ke, copy)), 32, 256) }
 }
 
 // SHAPE 2: four waves, two blocks per CU (the register file holds two waves of 256 registers per SIMD: one of each block)
@@ -1293,6 +1561,15 @@ extern "C" size_t deepim_conv_wino_packed_size(int Cout, int Cin) {
 #ifndef WINO_MIN_TILES
 #define WINO_MIN_TILES 64
 #endif
+// where deepim_conv_wino_preferred_s2d3_wide sends a 3x3 stride-2 layer to the nine-accumulator blocks: where they measured faster than the
+// 128 x 32 blocks (profiles/r13_s2d3_nine_tuples.md §3, nb = blocks of 256 channels x 32 tiles on 256 slots). From two whole rounds on
+// (conv4 at B = 32: nb = 600, -5 %), stream-K levels the rest; one partly filled round that covers a third of the chip or more (conv5 at
+// B = 32 / 16: nb = 160 / 80, -7 / -10 %; conv4 at B = 8: 150, -5 %) runs every block at once. Between one and two rounds the second
+// round is nearly empty (conv4 at B = 16: nb = 300, +6 %), and below 80 blocks too few CUs work (conv5 at B = 8: nb = 40, +3 %).
+#ifndef WINO_NINE_MIN_BLOCKS
+#define WINO_NINE_MIN_BLOCKS 80
+#endif
+static bool wino_nine_pays(long nb) { return nb >= 2 * 256 || (nb >= WINO_NINE_MIN_BLOCKS && nb <= 256); }
 static long wino_blocks(int B, int H, int W, int Cout) {
   const long tiles = (long)B * ((H + 1) / 2) * ((W + 1) / 2);
   return (long)di_div_up(tiles, 128) * (Cout / 32);
@@ -1328,6 +1605,16 @@ extern "C" int deepim_conv_wino_preferred_s2d3(deepim_ctx* ctx, int B, int Cin, 
   if ((size_t)B * Cin * H * W * 4 >= (1ull << 31) || (size_t)B * Cout * (H / 2) * (W / 2) * 4 >= (1ull << 31)) return 0;
   if (ctx && (ctx->conv_max_split == 1 || !ctx->wino_shared || ctx->wino_two_wave)) return 0;
   return (long)B * ((H / 2 + 1) / 2) * ((W / 2 + 1) / 2) * (Cin / 8) >= WINO_S2D3_MIN_WORK ? 1 : 0;
+}
+
+// Whether a layer that deepim_conv_wino_preferred_s2d3 accepts should go through deepim_conv2d_wino_forward_s2d3_wide: where the shape
+// exists under the context's options and measured faster (wino_nine_pays above)
+extern "C" int deepim_conv_wino_preferred_s2d3_wide(deepim_ctx* ctx, int B, int Cin, int H, int W, int Cout) {
+  if (!deepim_conv_wino_preferred_s2d3(ctx, B, Cin, H, W, Cout)) return 0;
+  if ((Cout & 255) || ((4 * Cin) % 64)) return 0;
+  if (ctx && (ctx->wino_wide != 1 || !ctx->wino_s2d_skip)) return 0;
+  const long tiles = (long)B * ((H / 2 + 1) / 2) * ((W / 2 + 1) / 2);
+  return wino_nine_pays((long)di_div_up(tiles, 32) * (Cout / 256)) ? 1 : 0;
 }
 
 extern "C" int deepim_conv_wino_pack_weights(deepim_ctx* ctx, float* packed_w, const float* w, int Cout, int Cin) {
@@ -1381,7 +1668,7 @@ extern "C" int deepim_conv_wino_pack_weights_dgrad(deepim_ctx* ctx, float* packe
 // [out_coff, out_coff + Cout) of an NCHW tensor of out_ctotal channels (out_nc8 = 0).
 static int wino_forward_impl(deepim_ctx* ctx, float* out, const float* in, const float* packed_w, const float* bias, int B, int Cin,
                              int H, int W, int Cout, float slope, int out_nc8, int out_ctotal, int out_coff, int s2d,
-                             int* plan_only = nullptr) {
+                             int* plan_only = nullptr, bool force_nine = false) {
   if (!plan_only) DI_DEVICE(ctx);      // (the plan is host arithmetic)
   DI_REQUIRE(B >= 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0, "conv2d_wino_forward: bad shape");
   DI_REQUIRE((Cout & 31) == 0 && (Cin & 7) == 0, "conv2d_wino_forward: Cout % 32 == 0 and Cin % 8 == 0 required");
@@ -1406,9 +1693,16 @@ static int wino_forward_impl(deepim_ctx* ctx, float* out, const float* in, const
     // tools/bench_wino.py; profiles/r09_stride2_wino.md)
     half = (s2d != 2 && wide_blocks * (Cin / 8) <= 100L * 256) || (Cout & 127) != 0;
   }
-  const bool wide = shared && !half && (Cout & 127) == 0 && ctx->wino_wide != 0;
-  p.gx = di_div_up(p.ntiles, (wide || half) ? 32 : (two_wave || shared) ? 64 : 128);
-  p.gy = wide ? Cout / 128 : shared ? Cout / 64 : Cout / 32;
+  // 4 = the nine-accumulator 256 x 32 blocks (conv_wino9_kernel) where they exist — the 3x3 stride-2 walk with its dead positions dropped
+  // and Cout % 256 == 0 —, anywhere else as 3. Under the default (1) this launcher keeps the 128 x 32 blocks for that walk; the caller
+  // that wants the new shape where it measured faster asks deepim_conv_wino_preferred_s2d3_wide and calls
+  // deepim_conv2d_wino_forward_s2d3_wide (force_nine), as the network does (profiles/r13_s2d3_nine_tuples.md)
+  const bool nine_ok = shared && s2d == 2 && (Cin % 64) == 0 && ctx->wino_s2d_skip && (Cout & 255) == 0;
+  const bool nine = nine_ok && (ctx->wino_wide == 4 || (force_nine && ctx->wino_wide == 1));
+  if (nine) half = false;
+  const bool wide = shared && !half && !nine && (Cout & 127) == 0 && ctx->wino_wide != 0;
+  p.gx = di_div_up(p.ntiles, (wide || half || nine) ? 32 : (two_wave || shared) ? 64 : 128);
+  p.gy = nine ? Cout / 256 : wide ? Cout / 128 : shared ? Cout / 64 : Cout / 32;
   p.in_bytes = (unsigned)in_bytes; p.wd_bytes = (unsigned)wd_bytes;
   p.out_bytes = (unsigned)std::min<size_t>((size_t)B * Cout * H * W * 4, 0x7fffffffu);
   p.out_ctotal = out_ctotal > 0 ? out_ctotal : Cout;
@@ -1465,15 +1759,18 @@ static int wino_forward_impl(deepim_ctx* ctx, float* out, const float* in, const
       if (!plan_only) p.sk_count = (int*)ctx->wino_counters;
       if (!out_nc8) { p.fin_nchw = 1; p.fin_ctotal = out_ctotal > 0 ? out_ctotal : Cout; p.fin_coff = out_coff; }
     }
-    if (plan_only) {   // {block shape 0 / 1 wide / 2 four-wave, grid, K slices, K steps per slice, stream-K granules per tile block (0: off), granules per run, whole tile blocks per block before the run, tile blocks of the layer (incl. the padding of the XCD deal), runs that are one granule longer}
-      plan_only[0] = half ? 2 : wide ? 1 : 0; plan_only[1] = grid; plan_only[2] = S; plan_only[3] = ks; plan_only[4] = p.sk_G; plan_only[5] = p.sk_q; plan_only[6] = p.sk_F; plan_only[7] = p.grid0; plan_only[8] = p.sk_rem;
+    if (plan_only) {   // {block shape 0 / 1 wide / 2 four-wave / 3 nine-accumulator 256 x 32, grid, K slices, K steps per slice, stream-K granules per tile block (0: off), granules per run, whole tile blocks per block before the run, tile blocks of the layer (incl. the padding of the XCD deal), runs that are one granule longer}
+      plan_only[0] = half ? 2 : nine ? 3 : wide ? 1 : 0; plan_only[1] = grid; plan_only[2] = S; plan_only[3] = ks; plan_only[4] = p.sk_G; plan_only[5] = p.sk_q; plan_only[6] = p.sk_F; plan_only[7] = p.grid0; plan_only[8] = p.sk_rem;
       return 0;
     }
 #define W8_LAUNCH(O, S)                                                                               \
     if (half) conv_wino4_kernel<O, S><<<grid, 256, 0, ctx->stream>>>(p);                              \
     else if (wide) conv_wino8_kernel<O, S, 1><<<grid, 512, 0, ctx->stream>>>(p);                      \
     else conv_wino8_kernel<O, S, 0><<<grid, 512, 0, ctx->stream>>>(p);
-    if (ph8 == 2) {
+    if (nine) {
+      if (out_nc8) conv_wino9_kernel<1><<<grid, 512, 0, ctx->stream>>>(p);
+      else conv_wino9_kernel<0><<<grid, 512, 0, ctx->stream>>>(p);
+    } else if (ph8 == 2) {
       if (out_nc8) { W8_LAUNCH(1, 2) } else { W8_LAUNCH(0, 2) }
     } else if (ph8) {
       if (out_nc8) { W8_LAUNCH(1, 1) } else { W8_LAUNCH(0, 1) }
@@ -1541,14 +1838,26 @@ extern "C" int deepim_conv2d_wino_forward_s2d3(deepim_ctx* ctx, float* out, cons
   return wino_forward_impl(ctx, out, in_s2d, packed_w, bias, B, 4 * Cin, H / 2, W / 2, Cout, slope, out_nc8, out_ctotal, out_coff, 2);
 }
 
-// The launch plan of the shared-transform kernel for a layer geometry (s2d 1: 5x5 stride 2, 2: 3x3 stride 2; the arguments are then the
+// The same layer through the nine-accumulator 256-channel x 32-tile blocks (conv_wino9_kernel) where that shape exists under the
+// context's options (block shape left at its default, "wino_s2d_skip" on, Cin % 16 == 0, Cout % 256 == 0); anywhere else exactly
+// deepim_conv2d_wino_forward_s2d3. For the same K slicing the same bits as the 128 x 32 blocks.
+extern "C" int deepim_conv2d_wino_forward_s2d3_wide(deepim_ctx* ctx, float* out, const float* in_s2d, const float* packed_w, const float* bias,
+                                                    int B, int Cin, int H, int W, int Cout, float slope, int out_nc8, int out_ctotal,
+                                                    int out_coff) {
+  DI_REQUIRE(H > 0 && W > 0 && ((H | W) & 1) == 0, "conv2d_wino_forward_s2d3_wide: even H and W required");
+  return wino_forward_impl(ctx, out, in_s2d, packed_w, bias, B, 4 * Cin, H / 2, W / 2, Cout, slope, out_nc8, out_ctotal, out_coff, 2, nullptr, true);
+}
+
+// The launch plan of the shared-transform kernel for a layer geometry (s2d 1: 5x5 stride 2, 2: 3x3 stride 2, 3: 3x3 stride 2 through
+// deepim_conv2d_wino_forward_s2d3_wide; the arguments are then the
 // space-to-depth problem's, as wino_forward_impl sees them) under the context's options; plan[6] as documented at the fill site. -1 where that kernel is not used.
 extern "C" int deepim_conv_wino_plan(deepim_ctx* ctx, int B, int Cin, int H, int W, int Cout, int out_nc8, int s2d, int* plan) {
   DI_REQUIRE(plan != nullptr, "conv_wino_plan: null plan");
   for (int i = 0; i < 9; ++i) plan[i] = -1;
   deepim_ctx defaults;                 // ctx == NULL: the plan under the default options (no device involved)
   if (!ctx) { deepim_ctx_default_options(&defaults); ctx = &defaults; }
-  return wino_forward_impl(ctx, nullptr, nullptr, nullptr, nullptr, B, Cin, H, W, Cout, 0.f, out_nc8, 0, 0, s2d == 2 ? 2 : s2d != 0, plan);
+  return wino_forward_impl(ctx, nullptr, nullptr, nullptr, nullptr, B, Cin, H, W, Cout, 0.f, out_nc8, 0, 0, (s2d == 2 || s2d == 3) ? 2 : s2d != 0, plan,
+                           s2d == 3);
 }
 
 #if W8_TRACE

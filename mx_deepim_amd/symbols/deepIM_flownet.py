@@ -628,8 +628,11 @@ class deepIM_flownet(object):
         name, cin, h, w, cout, k, s, p = self.enc_geom[li]
         out_mode = self._enc_out_mode(li)
         if self._s2d3_live(li):
-            lib.deepim_conv2d_wino_forward_s2d3(self.ctx.handle, self.act[name], src, self.wino_s2d3[name], self.params[name + "_bias"],
-                                                self.B, cin, h, w, cout, ctypes.c_float(SLOPE), out_mode, 0, 0)
+            # the 256-channel x 32-tile blocks where they measured faster (asked per call, as `_s2d3_live`: the options may change after bind)
+            wide = lib.load().deepim_conv_wino_preferred_s2d3_wide(self.ctx.handle, self.B, cin, h, w, cout)
+            fwd = lib.deepim_conv2d_wino_forward_s2d3_wide if wide else lib.deepim_conv2d_wino_forward_s2d3
+            fwd(self.ctx.handle, self.act[name], src, self.wino_s2d3[name], self.params[name + "_bias"],
+                self.B, cin, h, w, cout, ctypes.c_float(SLOPE), out_mode, 0, 0)
         elif self.nc8 and name in self.packed_wino:
             fwd = lib.deepim_conv2d_wino_forward_s2d if name in self.wino_s2d else lib.deepim_conv2d_wino_forward
             fwd(self.ctx.handle, self.act[name], src, self.packed_wino[name], self.params[name + "_bias"],      # s2d: 5x5 stride 2 over
