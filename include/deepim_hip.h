@@ -333,12 +333,15 @@ int deepim_conv_wino_preferred(deepim_ctx* ctx, int B, int Cin, int H, int W, in
 /* the same for a 5x5 stride-2 pad-2 layer (B, Cin, H, W) run over its space-to-depth form (one-wave kernel: from 256 blocks on) */
 int deepim_conv_wino_preferred_s2d(deepim_ctx* ctx, int B, int Cin, int H, int W, int Cout);
 /* The launch plan the shared-transform kernel would use for a layer under the context's options (no launch; tests and docs read it):
- * arguments as deepim_conv2d_wino_forward sees them (s2d = 1: Cin, H, W of the space-to-depth problem). plan[0] block shape (0 = 64
- * channels x 64 tiles, 1 = 128 x 32, 2 = 64 x 32 on four waves, 3 = 256 x 32 on nine accumulator tuples), [1] grid, [2] K slices S, [3] K steps per slice, [4] stream-K granules
- * per tile block (0 = off: whole tile blocks per block), [5] granules of the last round per persistent block, [6] whole tile blocks
- * per persistent block before them, [7] tile blocks of the layer (incl. the padding of the XCD deal), [8] the first so many blocks of an
- * XCD take one granule more. All -1 where another kernel runs the layer. Host arithmetic only: ctx = NULL asks for the plan under
- * the default options (no device needed). */
+ * arguments as deepim_conv2d_wino_forward sees them (s2d != 0: Cin, H, W of the space-to-depth problem; 1 = a 5x5 stride-2 layer, 2 = a
+ * 3x3 stride-2 one, 3 = that one through deepim_conv2d_wino_forward_s2d3_wide). The nine ints are fields of the planner's WinoPlan
+ * (csrc/wino_plan.h, documented there): plan[0] = shape, counted from the first shared-transform shape (0 = 64 channels x 64 tiles,
+ * 1 = 128 x 32, 2 = 64 x 32 on four waves, 3 = 256 x 32 on nine accumulator tuples), [1] = grid (blocks launched), [2] = S (K slices),
+ * [3] = ks (K steps per slice), [4] = sk_G (stream-K granules per tile block, 0 = off: whole tile blocks per block), [5] = sk_q (granules
+ * of the last round per persistent block), [6] = sk_F (whole tile blocks per persistent block before them), [7] = grid0 (tile blocks of
+ * the layer, incl. the padding of the XCD deal), [8] = sk_rem (the first so many blocks of an XCD take one granule more). All -1 (and
+ * return 0) where another kernel runs the layer, and for an empty batch. Host arithmetic only: ctx = NULL asks for the plan under the
+ * default options (no device needed). */
 int deepim_conv_wino_plan(deepim_ctx* ctx, int B, int Cin, int H, int W, int Cout, int out_nc8, int s2d, int* plan /*9, host*/);
 int deepim_conv_wino_pack_weights(deepim_ctx* ctx, float* packed_w, const float* w /*Cout,Cin,3,3 dev*/, int Cout, int Cin);
 /* The 5x5 stride-2 pad-2 layers (conv2 / conv3, deepIM_flownet.py:65-68) on the same kernel: a stride-2 convolution is a stride-1

@@ -10,6 +10,7 @@
 #include <type_traits>
 #include <algorithm>
 #include "../../include/deepim_hip.h"
+#include "wino_plan.h"
 
 constexpr int DI_MAX_BOX_SAMPLES = 4096;
 // bits of the sticky status word (deepim_zoom_status)
@@ -65,20 +66,13 @@ struct deepim_ctx {
   int conv_max_split;  // 0 auto, 1 off, n cap
   int conv_xcd_swizzle;  // 1: XCD-aware tile order (default), 0: plain
   int dgrad_group;       // 1 (default): the four parity classes of a stride-2 data gradient share one launch; 0: class by class
+  WinoOptions wino;      // the "wino_*" options of the fp32 Winograd kernels (csrc/wino_plan.h: fields and defaults)
   int wgrad_lds;         // 1 (default): LDS-staged weight-gradient kernel; 0: the round-2 register-fed kernel (A/B measurements)
-  int wino_s2d_skip;     // 1 (default): stride-2 Winograd layers skip the positions whose weights are identically zero; 0: all 16 (A/B measurements)
-  int wino_shared;       // 1 (default): Winograd layers with Cout % 64 == 0 on the 8-wave shared-transform kernel (conv_wino8_kernel); 0: the round-4 one-wave kernel
-  int wino_wide;         // block shape of the shared-transform kernel: 1 (default) = per layer by the work per CU, 0 = 64 ch x 64 tiles, 3 = 128 x 32, 2 = 64 x 32 on four waves (two blocks per CU), 4 = 256 x 32 on nine accumulator tuples (3x3 stride-2 walk, Cout % 256 == 0; elsewhere as 3)
-  int wino_split;        // K-split of the shared-transform kernel: 0 (default) = the plan of wino8_split_plan, 1 = never, n = at most n slices
   int conv_fewout_blocks, conv_fewout_minc;   // few-filter heads: channel slices so that the grid has about this many blocks (0 = default: 1024 where the pixels alone give >= 32 blocks, else 512), of at least this many channels each (32)
   int conv_fewout_quad;  // 1 (default): the 3x3 stride-1 heads with W % 4 == 0 on the four-pixels-per-lane kernel; 0: one pixel per lane
-  int wino_streamk;      // 1 (default): where a grid leaves a partly filled last round, the persistent blocks share the work granule by granule (stream-K; needs wino_persistent, off with wino_split = 1); 2: wherever it applies, whatever the cost model says; 0: never
   std::map<uintptr_t, size_t> allocs;   // deepim_malloc's live allocations (base -> bytes): deepim_d2d's residency test without a driver query
-  int wino_fin;          // 1: a K-split Winograd layer is finished inside the kernel by the block whose slice arrives last (no second pass); 0 (default): wino_reduce_kernel — the serial finish of the last slices costs more than the parallel second pass (profiles/r06_b4_share.md)
   std::mutex allocs_mu;  // guards `allocs`: a DeviceArray finalizer on another Python thread may free while the main thread copies (ctypes drops the GIL)
   void* wino_counters;   // arrival counters of the Winograd kernels' in-kernel finish, one per tile block (deepim_create; zero between launches)
-  int wino_persistent;   // 1 (default): the shared-transform kernel's grid is one block per resident slot, each walking its share of the tiles; 0: one block per tile block
-  int wino_two_wave;     // 0 (default): Winograd layers on the one-wave 16-position kernel; 1: the two-waves-per-SIMD kernel (measured slower on the big layers)
   int f16_dev_flags;     // 0 (default) or DI_F16_NO_PP: fp16 layers stay off the ping-pong kernel
   std::vector<const void*> attr_done;  // hipFuncSetAttribute groups already applied on THIS context's device (di_attr_needed)
 };
@@ -90,7 +84,6 @@ static inline bool di_attr_needed(deepim_ctx* ctx, const void* tag) {
   return true;
 }
 
-#define DI_WINO_COUNTERS 16384   /* arrival counters per context (64 KB): tile blocks of one Winograd launch that can finish in-kernel */
 void deepim_set_error(const char* where, hipError_t e);
 void deepim_set_error_msg(const char* msg);
 

@@ -18,7 +18,7 @@ extern "C" int deepim_device_count(int* n) {
   return 0;
 }
 
-// The option defaults of a fresh context (also what the host-arithmetic queries — deepim_conv_wino_plan — assume without a context)
+// The option defaults of a fresh context (the Winograd ones: WinoOptions' own — what the host-arithmetic queries assume without a context)
 void deepim_ctx_default_options(deepim_ctx* c) {
   c->capturing = false;
   c->conv_max_split = 0;
@@ -26,18 +26,11 @@ void deepim_ctx_default_options(deepim_ctx* c) {
   c->f16_dev_flags = 0;
   c->wgrad_lds = 1;
   c->dgrad_group = 1;
-  c->wino_two_wave = 0;
-  c->wino_shared = 1;
-  c->wino_persistent = 1;
-  c->wino_streamk = 1;
-  c->wino_fin = 0;   // measured slower than the second pass at every batch size (profiles/r06_b4_share.md)
   c->conv_fewout_quad = 1;
   c->conv_fewout_blocks = 0;     // 0 = by the grid (launch site)
   c->conv_fewout_minc = 32;
   c->wino_counters = nullptr;
-  c->wino_split = 0;
-  c->wino_wide = 1;
-  c->wino_s2d_skip = 1;
+  c->wino = WinoOptions();
   c->conv_autotune = 0;
   c->conv_direct = 1;
   c->conv_tail_slots = 1024;
@@ -230,17 +223,17 @@ extern "C" int deepim_set_option(deepim_ctx* ctx, const char* name, int value) {
   if (strcmp(name, "conv_autotune") == 0) { ctx->conv_autotune = value ? 1 : 0; return 0; }
   if (strcmp(name, "dgrad_group") == 0) { ctx->dgrad_group = value ? 1 : 0; return 0; }
   if (strcmp(name, "wgrad_lds") == 0) { ctx->wgrad_lds = value ? 1 : 0; return 0; }
-  if (strcmp(name, "wino_two_wave") == 0) { ctx->wino_two_wave = value ? 1 : 0; return 0; }
-  if (strcmp(name, "wino_persistent") == 0) { ctx->wino_persistent = value ? 1 : 0; return 0; }
+  if (strcmp(name, "wino_two_wave") == 0) { ctx->wino.two_wave = value ? 1 : 0; return 0; }
+  if (strcmp(name, "wino_persistent") == 0) { ctx->wino.persistent = value ? 1 : 0; return 0; }
   if (strcmp(name, "conv_fewout_blocks") == 0) { ctx->conv_fewout_blocks = value < 0 ? 0 : value; return 0; }
   if (strcmp(name, "conv_fewout_minc") == 0) { ctx->conv_fewout_minc = value < 1 ? 1 : value; return 0; }
   if (strcmp(name, "conv_fewout_quad") == 0) { ctx->conv_fewout_quad = value ? 1 : 0; return 0; }
-  if (strcmp(name, "wino_fin") == 0) { ctx->wino_fin = value != 0; return 0; }
-  if (strcmp(name, "wino_streamk") == 0) { ctx->wino_streamk = value < 0 ? 0 : value > 2 ? 2 : value; return 0; }
-  if (strcmp(name, "wino_split") == 0) { ctx->wino_split = value < 0 ? 0 : value; return 0; }
-  if (strcmp(name, "wino_wide") == 0) { ctx->wino_wide = (value >= 0 && value <= 4) ? value : 1; return 0; }
-  if (strcmp(name, "wino_shared") == 0) { ctx->wino_shared = value ? 1 : 0; return 0; }
-  if (strcmp(name, "wino_s2d_skip") == 0) { ctx->wino_s2d_skip = value ? 1 : 0; return 0; }
+  if (strcmp(name, "wino_fin") == 0) { ctx->wino.fin = value != 0; return 0; }
+  if (strcmp(name, "wino_streamk") == 0) { ctx->wino.streamk = value < 0 ? 0 : value > 2 ? 2 : value; return 0; }
+  if (strcmp(name, "wino_split") == 0) { ctx->wino.split = value < 0 ? 0 : value; return 0; }
+  if (strcmp(name, "wino_wide") == 0) { ctx->wino.wide = (value >= 0 && value <= 4) ? value : 1; return 0; }
+  if (strcmp(name, "wino_shared") == 0) { ctx->wino.shared = value ? 1 : 0; return 0; }
+  if (strcmp(name, "wino_s2d_skip") == 0) { ctx->wino.s2d_skip = value ? 1 : 0; return 0; }
   if (strcmp(name, "f16_dev_flags") == 0) { DI_REQUIRE(value == 0 || value == DI_F16_NO_PP, "f16_dev_flags: 0 or 16"); ctx->f16_dev_flags = value; return 0; }
   if (strcmp(name, "conv_xcd_swizzle") == 0) {
     ctx->conv_xcd_swizzle = value ? 1 : 0;
@@ -257,7 +250,7 @@ extern "C" int deepim_get_option(deepim_ctx* ctx, const char* name, int* value) 
       {"conv_max_split", ctx->conv_max_split}, {"conv_direct", ctx->conv_direct},
       {"conv_tail_split", ctx->conv_tail_split}, {"conv_force_plan", ctx->conv_force_plan}, {"conv_tail_slots", ctx->conv_tail_slots},
       {"conv_autotune", ctx->conv_autotune}, {"dgrad_group", ctx->dgrad_group},
-      {"wgrad_lds", ctx->wgrad_lds}, {"wino_two_wave", ctx->wino_two_wave}, {"wino_shared", ctx->wino_shared}, {"wino_wide", ctx->wino_wide}, {"wino_split", ctx->wino_split}, {"wino_persistent", ctx->wino_persistent}, {"wino_streamk", ctx->wino_streamk}, {"wino_fin", ctx->wino_fin}, {"conv_fewout_quad", ctx->conv_fewout_quad}, {"conv_fewout_blocks", ctx->conv_fewout_blocks}, {"conv_fewout_minc", ctx->conv_fewout_minc}, {"wino_s2d_skip", ctx->wino_s2d_skip}, {"f16_dev_flags", ctx->f16_dev_flags}, {"conv_xcd_swizzle", ctx->conv_xcd_swizzle}};
+      {"wgrad_lds", ctx->wgrad_lds}, {"wino_two_wave", ctx->wino.two_wave}, {"wino_shared", ctx->wino.shared}, {"wino_wide", ctx->wino.wide}, {"wino_split", ctx->wino.split}, {"wino_persistent", ctx->wino.persistent}, {"wino_streamk", ctx->wino.streamk}, {"wino_fin", ctx->wino.fin}, {"conv_fewout_quad", ctx->conv_fewout_quad}, {"conv_fewout_blocks", ctx->conv_fewout_blocks}, {"conv_fewout_minc", ctx->conv_fewout_minc}, {"wino_s2d_skip", ctx->wino.s2d_skip}, {"f16_dev_flags", ctx->f16_dev_flags}, {"conv_xcd_swizzle", ctx->conv_xcd_swizzle}};
   for (const auto& o : opts)
     if (strcmp(name, o.n) == 0) { *value = o.v; return 0; }
   deepim_set_error_msg("deepim_get_option: unknown option");

@@ -1453,49 +1453,6 @@ __global__ __launch_bounds__(256) void wino_reduce_kernel(float* __restrict__ ou
   }
 }
 
-// K-split plan of conv_wino8_kernel for a grid of `blocks` full-K blocks of nK steps on the chip's 256 CUs (one block per CU at a
-// time): S slices of ks steps each so that blocks x S fills whole rounds; cost model = rounds x (steps + per-block prologue/epilogue,
-// ~6 steps' worth) + the second pass (S + 1 passes over the output at ~4 TB/s, in steps of ~1.7 us). Deterministic: a function of
-// the geometry only. step_granule: 2 (slot parity) or 8 (the stride-2 form's loop body).
-static int wino8_split_plan(long blocks, int nK, int step_granule, double out_mb, int max_split, int* kslice, int slots = 256,
-                            double* cost_out = nullptr) {
-  int best = 1;
-  double best_cost = 1e30;
-  for (int S = 1; S <= 16; ++S) {
-    if (max_split > 0 && S > max_split) break;
-    int ks = di_div_up(di_div_up(nK, S), step_granule) * step_granule;
-    if (S > 1 && ks < 8) break;
-    const int Seff = di_div_up(nK, ks);
-    if (Seff != S) continue;
-    const double rounds = (double)di_div_up(blocks * S, slots);
-    double cost = rounds * (ks + 6.0);
-    if (S > 1) cost += (S + 1) * out_mb / 4000.0 / 1.7e-3 + 1.5;   // MB / (MB per ms) -> ms -> steps; + a launch boundary
-    if (cost < best_cost - 1e-9) { best_cost = cost; best = S; *kslice = ks; }
-  }
-  if (best == 1) *kslice = nK;
-  if (cost_out) *cost_out = best_cost;
-  return best;
-}
-
-// Stream-K of the last round of the same grid (WinoParams::sk_*): F whole tile blocks per persistent block, then every block an equal
-// run (+- 1) of the remaining tile blocks' granules — at the price of up to two more pieces per block and the read-back of the cut tile
-// blocks. Same cost unit as wino8_split_plan (steps). Returns the granules per tile block, 0 where it does not apply: the XCD deal
-// needs grid % 8 == 0, and no tile block is cut into more than W8_SK_MAX_COPIES pieces.
-#define W8_SK_MAX_COPIES 8
-#define W8_SK_MAX_TILE_BLOCKS DI_WINO_COUNTERS   /* counters per context (64 KB) */
-static int wino8_streamk_plan(long grid, int nK, int step_granule, int slots, double* cost, int* F, int* q, int* rem) {
-  if (grid % 8 != 0 || nK % step_granule != 0 || grid > W8_SK_MAX_TILE_BLOCKS) return 0;
-  const int G = nK / step_granule, nlb = slots / 8;
-  const long ltiles = grid / 8;
-  *F = (int)(ltiles / nlb);
-  const long units = (ltiles - (long)*F * nlb) * G;
-  if (units == 0) return 0;
-  *q = (int)(units / nlb); *rem = (int)(units % nlb);
-  if (*q < 1 || di_div_up(G, *q) + 1 > W8_SK_MAX_COPIES) return 0;
-  *cost = (double)*F * (nK + 6.0) + ((double)*q + (*rem ? 1 : 0)) * step_granule + 2 * 6.0 + 2.0;
-  return G;
-}
-
 // U = G g G^T in double, rounded once; packed [Cout/32][Cin/8][position][lane = h*32 + row][4] with channel 8(c/8) + 4h + s (s = 0, 1: body 0; 2, 3: body 1)
 // s2d 1: `w` is a (Cout, Cin/4, 5, 5) stride-2 pad-2 kernel read as the 3x3 stride-1 pad-1 kernel over the 4 input phases it is
 // equivalent to — channel phase*(Cin/4) + c, phase = py*2 + px, tap (a, b) = w[2a + py][2b + px] (zero where 2a + py or 2b + px = 5).
@@ -1547,83 +1504,60 @@ extern "C" size_t deepim_conv_wino_packed_size(int Cout, int Cin) {
   return (size_t)Cout * Cin * 16 * sizeof(float);
 }
 
-// Whether the layer should take the Winograd path. Cout % 64 == 0 (every encoder layer): the shared-transform kernel splits the input
-// channels where the grid would not fill the chip, so it pays from two tile blocks on (measured at B = 4 / 8 / 32, tools/bench_wino.py:
-// 1.45-2.1x over the direct kernels on every layer, conv5_1 / conv6_1 at B = 4 included); other channel counts fall back to the
-// one-wave kernel, which walks all of Cin per block and needs >= 128 (stride-2 form: 256) blocks of 32 channels x 128 tiles.
-// conv_max_split == 1 is the canonical-summation-order configuration (bit-exact against the oracle's default order): no Winograd there.
-#ifndef WINO_MIN_BLOCKS
-#define WINO_MIN_BLOCKS 128
-#endif
-#ifndef WINO_MIN_BLOCKS_S2D
-#define WINO_MIN_BLOCKS_S2D 256
-#endif
-#ifndef WINO_MIN_TILES
-#define WINO_MIN_TILES 64
-#endif
-// where deepim_conv_wino_preferred_s2d3_wide sends a 3x3 stride-2 layer to the nine-accumulator blocks: where they measured faster than the
-// 128 x 32 blocks (profiles/r13_s2d3_nine_tuples.md §3, nb = blocks of 256 channels x 32 tiles on 256 slots). From two whole rounds on
-// (conv4 at B = 32: nb = 600, -5 %), stream-K levels the rest; one partly filled round that covers a third of the chip or more (conv5 at
-// B = 32 / 16: nb = 160 / 80, -7 / -10 %; conv4 at B = 8: 150, -5 %) runs every block at once. Between one and two rounds the second
-// round is nearly empty (conv4 at B = 16: nb = 300, +6 %), and below 80 blocks too few CUs work (conv5 at B = 8: nb = 40, +3 %).
-#ifndef WINO_NINE_MIN_BLOCKS
-#define WINO_NINE_MIN_BLOCKS 80
-#endif
-static bool wino_nine_pays(long nb) { return nb >= 2 * 256 || (nb >= WINO_NINE_MIN_BLOCKS && nb <= 256); }
-static long wino_blocks(int B, int H, int W, int Cout) {
-  const long tiles = (long)B * ((H + 1) / 2) * ((W + 1) / 2);
-  return (long)di_div_up(tiles, 128) * (Cout / 32);
+// The context's Winograd options as the plan (csrc/wino_plan.h) reads them; no context: the defaults
+static WinoOptions wino_options(const deepim_ctx* ctx) {
+  WinoOptions o = ctx ? ctx->wino : WinoOptions();
+  o.canonical = ctx && ctx->conv_max_split == 1;
+  return o;
 }
-static int wino_pays(deepim_ctx* ctx, int B, int H, int W, int Cout, long min_blocks) {
-  if (ctx && ctx->conv_max_split == 1) return 0;
-  if ((!ctx || (ctx->wino_shared && !ctx->wino_two_wave)) && (Cout & 63) == 0)   // (no context: the defaults)
-    return (long)B * ((H + 1) / 2) * ((W + 1) / 2) >= WINO_MIN_TILES ? 1 : 0;
-  return wino_blocks(B, H, W, Cout) >= min_blocks ? 1 : 0;
-}
+
+// Whether the layer should take the Winograd path (the thresholds: wino_pays, csrc/wino_plan.h)
 extern "C" int deepim_conv_wino_preferred(deepim_ctx* ctx, int B, int Cin, int H, int W, int Cout) {
   if (B <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0 || (Cout & 31) || (Cin & 7)) return 0;
   if ((size_t)B * Cin * H * W * 4 >= (1ull << 31)) return 0;   // one buffer descriptor per launch: larger inputs stay on the direct kernels (sub-batched there)
   if ((size_t)B * Cout * H * W * 4 >= (1ull << 31)) return 0;  // ... and one for the output
-  return wino_pays(ctx, B, H, W, Cout, WINO_MIN_BLOCKS);
+  return wino_pays(wino_options(ctx), B, H, W, Cout, WINO_MIN_BLOCKS) ? 1 : 0;
 }
 // the same question for a 5x5 stride-2 pad-2 layer with input (B, Cin, H, W) run over its space-to-depth form
 extern "C" int deepim_conv_wino_preferred_s2d(deepim_ctx* ctx, int B, int Cin, int H, int W, int Cout) {
   if (B <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0 || (Cout & 31) || (Cin & 7) || ((H | W) & 1)) return 0;
   if ((size_t)B * Cin * H * W * 4 >= (1ull << 31) || (size_t)B * Cout * (H / 2) * (W / 2) * 4 >= (1ull << 31)) return 0;
-  return wino_pays(ctx, B, H / 2, W / 2, Cout, WINO_MIN_BLOCKS_S2D);
+  return wino_pays(wino_options(ctx), B, H / 2, W / 2, Cout, WINO_MIN_BLOCKS_S2D) ? 1 : 0;
 }
 // ... and for a 3x3 stride-2 pad-1 layer with input (B, Cin, H, W), run over the same space-to-depth form (deepim_conv2d_wino_forward_s2d3).
 // Shared-transform kernel only (Cout % 64 == 0, an even number of 8-channel blocks per phase), even H and W (the producing layers write
-// no zero row for an odd plane), and where it was measured faster than the direct kernel: from WINO_S2D3_MIN_WORK output tiles x
-// 8-channel input blocks (profiles/r09_stride2_wino.md: conv4 / conv5 at B = 8 = 76 800 / 40 960 units gain 8 / 14 %, at B = 4 = 38 400 /
-// 20 480 units they are within noise of the direct kernel).
-#ifndef WINO_S2D3_MIN_WORK
-#define WINO_S2D3_MIN_WORK 40000
-#endif
+// no zero row for an odd plane), and where it was measured faster than the direct kernel (wino_s2d3_pays)
 extern "C" int deepim_conv_wino_preferred_s2d3(deepim_ctx* ctx, int B, int Cin, int H, int W, int Cout) {
   if (B <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0 || (Cout & 63) || (Cin & 15) || ((H | W) & 1)) return 0;
   if ((size_t)B * Cin * H * W * 4 >= (1ull << 31) || (size_t)B * Cout * (H / 2) * (W / 2) * 4 >= (1ull << 31)) return 0;
-  if (ctx && (ctx->conv_max_split == 1 || !ctx->wino_shared || ctx->wino_two_wave)) return 0;
-  return (long)B * ((H / 2 + 1) / 2) * ((W / 2 + 1) / 2) * (Cin / 8) >= WINO_S2D3_MIN_WORK ? 1 : 0;
+  return wino_s2d3_pays(wino_options(ctx), B, Cin, H, W, Cout) ? 1 : 0;
 }
 
 // Whether a layer that deepim_conv_wino_preferred_s2d3 accepts should go through deepim_conv2d_wino_forward_s2d3_wide: where the shape
-// exists under the context's options and measured faster (wino_nine_pays above)
+// exists under the context's options, the block shape is left to the plan, and it measured faster (wino_nine_pays)
 extern "C" int deepim_conv_wino_preferred_s2d3_wide(deepim_ctx* ctx, int B, int Cin, int H, int W, int Cout) {
   if (!deepim_conv_wino_preferred_s2d3(ctx, B, Cin, H, W, Cout)) return 0;
-  if ((Cout & 255) || ((4 * Cin) % 64)) return 0;
-  if (ctx && (ctx->wino_wide != 1 || !ctx->wino_s2d_skip)) return 0;
+  const WinoOptions o = wino_options(ctx);
+  if (!wino_nine_exists(o, WINO_S2D_3X3, 4 * Cin, Cout) || o.wide != 1) return 0;
+  const WinoShapeInfo& sh = WINO_SHAPE[WINO_256X32_NINE];
   const long tiles = (long)B * ((H / 2 + 1) / 2) * ((W / 2 + 1) / 2);
-  return wino_nine_pays((long)di_div_up(tiles, 32) * (Cout / 256)) ? 1 : 0;
+  return wino_nine_pays((long)di_div_up(tiles, sh.tiles) * (Cout / sh.channels)) ? 1 : 0;
+}
+
+// U' of a (Cout, Cin) problem from `w` in one of pack_wino_kernel's readings; the stride-2 ones (mode 1, 2) pack the 4 Cin channels of
+// the space-to-depth problem
+static int wino_pack(deepim_ctx* ctx, float* packed_w, const float* w, int Cout, int Cin, int mode, const char* requirement) {
+  DI_DEVICE(ctx);
+  DI_REQUIRE(Cout > 0 && Cin > 0 && (Cout & 31) == 0 && (Cin & 7) == 0, requirement);
+  const int phases = (mode == 1 || mode == 2) ? 4 : 1;
+  const long total = (long)Cout * Cin * phases * 16;
+  pack_wino_kernel<<<di_div_up(total, 256), 256, 0, ctx->stream>>>(packed_w, w, Cout, Cin * phases, total, mode);
+  DI_LAUNCH_CHECK();
+  return 0;
 }
 
 extern "C" int deepim_conv_wino_pack_weights(deepim_ctx* ctx, float* packed_w, const float* w, int Cout, int Cin) {
-  DI_DEVICE(ctx);
-  DI_REQUIRE(Cout > 0 && Cin > 0 && (Cout & 31) == 0 && (Cin & 7) == 0, "conv_wino_pack_weights: Cout % 32 == 0 and Cin % 8 == 0 required");
-  const long total = (long)Cout * Cin * 16;
-  pack_wino_kernel<<<di_div_up(total, 256), 256, 0, ctx->stream>>>(packed_w, w, Cout, Cin, total, 0);
-  DI_LAUNCH_CHECK();
-  return 0;
+  return wino_pack(ctx, packed_w, w, Cout, Cin, 0, "conv_wino_pack_weights: Cout % 32 == 0 and Cin % 8 == 0 required");
 }
 
 // A 5x5 stride-2 pad-2 layer (conv2 / conv3) as this kernel's 3x3 stride-1 pad-1 problem over the space-to-depth input:
@@ -1631,176 +1565,101 @@ extern "C" int deepim_conv_wino_pack_weights(deepim_ctx* ctx, float* packed_w, c
 // multiplies. w is the layer's own (Cout, Cin, 5, 5) tensor; the packed size is deepim_conv_wino_packed_size(Cout, 4 * Cin) and
 // the forward call is deepim_conv2d_wino_forward(..., Cin = 4 * Cin, H / 2, W / 2, ...) on the space-to-depth NC8 tensor.
 extern "C" int deepim_conv_wino_pack_weights_s2d(deepim_ctx* ctx, float* packed_w, const float* w, int Cout, int Cin) {
-  DI_DEVICE(ctx);
-  DI_REQUIRE(Cout > 0 && Cin > 0 && (Cout & 31) == 0 && (Cin & 7) == 0, "conv_wino_pack_weights_s2d: Cout % 32 == 0 and Cin % 8 == 0 required");
-  const long total = (long)Cout * Cin * 4 * 16;
-  pack_wino_kernel<<<di_div_up(total, 256), 256, 0, ctx->stream>>>(packed_w, w, Cout, Cin * 4, total, 1);
-  DI_LAUNCH_CHECK();
-  return 0;
+  return wino_pack(ctx, packed_w, w, Cout, Cin, 1, "conv_wino_pack_weights_s2d: Cout % 32 == 0 and Cin % 8 == 0 required");
 }
 
 // A 3x3 stride-2 pad-1 layer (conv4 / conv5) over the same space-to-depth form: w is the layer's own (Cout, Cin, 3, 3) tensor, packed as
 // taps 1..3 of a 5x5 stride-2 pad-2 kernel (size deepim_conv_wino_packed_size(Cout, 4 * Cin)); 25 of the 64 (phase, position) GEMMs are
 // non-zero: 1.44x fewer multiplies than the direct sum's 36 per 2x2 tile and channel pair.
 extern "C" int deepim_conv_wino_pack_weights_s2d3(deepim_ctx* ctx, float* packed_w, const float* w, int Cout, int Cin) {
-  DI_DEVICE(ctx);
-  DI_REQUIRE(Cout > 0 && Cin > 0 && (Cout & 31) == 0 && (Cin & 7) == 0, "conv_wino_pack_weights_s2d3: Cout % 32 == 0 and Cin % 8 == 0 required");
-  const long total = (long)Cout * Cin * 4 * 16;
-  pack_wino_kernel<<<di_div_up(total, 256), 256, 0, ctx->stream>>>(packed_w, w, Cout, Cin * 4, total, 2);
-  DI_LAUNCH_CHECK();
-  return 0;
+  return wino_pack(ctx, packed_w, w, Cout, Cin, 2, "conv_wino_pack_weights_s2d3: Cout % 32 == 0 and Cin % 8 == 0 required");
 }
 
 // The data gradient of a 3x3 stride-1 pad-1 layer (Cout, Cin, 3, 3) is the same kind of convolution from its Cout to its Cin channels
 // on the transposed, flipped weights: U' of that Cin <- Cout problem straight from the layer's raw tensor `w` (no flip buffer), size
 // deepim_conv_wino_packed_size(Cin, Cout). Bit-identical to deepim_conv_wino_pack_weights on deepim_conv_flip_weights of `w`.
 extern "C" int deepim_conv_wino_pack_weights_dgrad(deepim_ctx* ctx, float* packed_w, const float* w, int Cout, int Cin) {
-  DI_DEVICE(ctx);
-  DI_REQUIRE(Cout > 0 && Cin > 0 && (Cin & 31) == 0 && (Cout & 7) == 0, "conv_wino_pack_weights_dgrad: Cin % 32 == 0 and Cout % 8 == 0 required");
-  const long total = (long)Cout * Cin * 16;
-  pack_wino_kernel<<<di_div_up(total, 256), 256, 0, ctx->stream>>>(packed_w, w, Cin, Cout, total, 3);
-  DI_LAUNCH_CHECK();
-  return 0;
+  return wino_pack(ctx, packed_w, w, Cin, Cout, 3, "conv_wino_pack_weights_dgrad: Cin % 32 == 0 and Cout % 8 == 0 required");
 }
+
+// What a caller asks of the launcher: the geometry, and whether the 3x3 stride-2 walk should take the nine-accumulator blocks where
+// they exist and the block shape is left to the plan (deepim_conv2d_wino_forward_s2d3_wide)
+struct WinoLayerKind { WinoGeom geom; bool want_nine; };
+// deepim_conv_wino_plan's `s2d` argument: 1 = the 5x5 stride-2 layers (as any other non-zero value), 2 = the 3x3 stride-2 ones, 3 = those
+// through deepim_conv2d_wino_forward_s2d3_wide
+static WinoLayerKind wino_kind_of_plan_arg(int s2d) {
+  if (s2d == 2 || s2d == 3) return {WINO_S2D_3X3, s2d == 3};
+  return {s2d ? WINO_S2D_5X5 : WINO_3X3, false};
+}
+
+// The argument checks of a layer (B, Cin, H, W) -> Cout as the kernels see it: -1 = refused (error text set), 0 = an empty batch,
+// nothing to do, 1 = go
+static int wino_check_args(const WinoOptions& o, int B, int Cin, int H, int W, int Cout, int out_nc8) {
+  DI_REQUIRE(B >= 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0, "conv2d_wino_forward: bad shape");
+  DI_REQUIRE((Cout & 31) == 0 && (Cin & 7) == 0, "conv2d_wino_forward: Cout % 32 == 0 and Cin % 8 == 0 required");
+  if (B == 0) return 0;
+  DI_REQUIRE((size_t)B * Cin * H * W * 4 < (1ull << 31) && (size_t)Cout * Cin * 64 < (1ull << 31), "conv2d_wino_forward: tensor beyond the 2 GB buffer range");
+  if (out_nc8 == 3) DI_REQUIRE(((H | W) & 1) == 0, "conv2d_wino_forward: space-to-depth output needs even H and W");
+  if (wino_shared_kernel(o, Cout))
+    DI_REQUIRE(!out_nc8 || (size_t)B * Cout * H * W * 4 < (1ull << 31), "conv2d_wino_forward: channel-blocked output beyond the 2 GB buffer range");
+  return 1;
+}
+
+// The 26 layer kernels by block shape, K walk and output layout (NCHW, channel-blocked)
+typedef void (*WinoKernel)(WinoParams);
+static const WinoKernel WINO_KERNEL[WINO_SHAPES][3][2] = {
+    {{conv_wino_kernel<0, 0>, conv_wino_kernel<1, 0>}, {conv_wino_kernel<0, 1>, conv_wino_kernel<1, 1>},
+     {conv_wino_kernel<0, 1>, conv_wino_kernel<1, 1>}},   // (its 5x5 walk serves both stride-2 geometries)
+    {{conv_wino2_kernel<0>, conv_wino2_kernel<1>}, {nullptr, nullptr}, {nullptr, nullptr}},   // (walk 0 only)
+    {{conv_wino8_kernel<0, 0, 0>, conv_wino8_kernel<1, 0, 0>}, {conv_wino8_kernel<0, 1, 0>, conv_wino8_kernel<1, 1, 0>},
+     {conv_wino8_kernel<0, 2, 0>, conv_wino8_kernel<1, 2, 0>}},
+    {{conv_wino8_kernel<0, 0, 1>, conv_wino8_kernel<1, 0, 1>}, {conv_wino8_kernel<0, 1, 1>, conv_wino8_kernel<1, 1, 1>},
+     {conv_wino8_kernel<0, 2, 1>, conv_wino8_kernel<1, 2, 1>}},
+    {{conv_wino4_kernel<0, 0>, conv_wino4_kernel<1, 0>}, {conv_wino4_kernel<0, 1>, conv_wino4_kernel<1, 1>},
+     {conv_wino4_kernel<0, 2>, conv_wino4_kernel<1, 2>}},
+    {{nullptr, nullptr}, {nullptr, nullptr}, {conv_wino9_kernel<0>, conv_wino9_kernel<1>}},   // (walk 2 only)
+};
 
 // 3x3, stride 1, pad 1 convolution + bias + LeakyReLU(slope) from channel-blocked `in` (B, Cin/8, H, W, 8) into channel-blocked
 // `out` (out_nc8 = 1; 3 = channel-blocked in space-to-depth order, what a stride-2 layer on this kernel reads) or into channels
 // [out_coff, out_coff + Cout) of an NCHW tensor of out_ctotal channels (out_nc8 = 0).
 static int wino_forward_impl(deepim_ctx* ctx, float* out, const float* in, const float* packed_w, const float* bias, int B, int Cin,
-                             int H, int W, int Cout, float slope, int out_nc8, int out_ctotal, int out_coff, int s2d,
-                             int* plan_only = nullptr, bool force_nine = false) {
-  if (!plan_only) DI_DEVICE(ctx);      // (the plan is host arithmetic)
-  DI_REQUIRE(B >= 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0, "conv2d_wino_forward: bad shape");
-  DI_REQUIRE((Cout & 31) == 0 && (Cin & 7) == 0, "conv2d_wino_forward: Cout % 32 == 0 and Cin % 8 == 0 required");
-  if (B == 0) return 0;
-  const size_t in_bytes = (size_t)B * Cin * H * W * 4, wd_bytes = (size_t)Cout * Cin * 64;
-  DI_REQUIRE(in_bytes < (1ull << 31) && wd_bytes < (1ull << 31), "conv2d_wino_forward: tensor beyond the 2 GB buffer range");
-  WinoParams p;
+                             int H, int W, int Cout, float slope, int out_nc8, int out_ctotal, int out_coff, WinoLayerKind kind) {
+  DI_DEVICE(ctx);
+  const int go = wino_check_args(ctx->wino, B, Cin, H, W, Cout, out_nc8);
+  if (go <= 0) return go;
+  const WinoPlan pl = wino_plan(ctx->wino, B, Cin, H, W, Cout, out_nc8, kind.geom, kind.want_nine);
+
+  const size_t out_elems = (size_t)B * Cout * H * W;
+  const int ctotal = out_ctotal > 0 ? out_ctotal : Cout;
+  WinoParams p = {};
   p.in = in; p.out = out; p.wd = packed_w; p.bias = bias; p.slope = slope;
   p.Cin = Cin; p.Cout = Cout; p.H = H; p.W = W;
   p.TY = (H + 1) / 2; p.TX = (W + 1) / 2;
   p.ntiles = B * p.TY * p.TX;
-  const bool two_wave = ctx->wino_two_wave != 0;   // dev option: two 8-position waves per SIMD on 64-tile blocks instead of one 16-position wave
-  const bool shared = !two_wave && ctx->wino_shared && (Cout & 63) == 0;   // default: the 8-wave shared-transform kernel
-  // block shape (ctx->wino_wide): 0 = 64 x 64; 3 = 128 channels x 32 tiles where Cout % 128 == 0; 2 = 64 x 32 on four waves, two blocks
-  // per CU; 1 (default) = by the work per CU: the wide blocks share each V among 128 channels and win the long grids (2-4 %), the
-  // four-wave blocks overlap one block's prologue / epilogue with the other's loop and win where a CU sees few blocks — measured
-  // (tools/bench_wino.py at B = 4 / 8 / 32, both forms): the crossover sits near 100 steps of 8 input channels per CU
-  bool half = shared && ctx->wino_wide == 2;
-  if (shared && ctx->wino_wide == 1) {
-    const long wide_blocks = (long)di_div_up(p.ntiles, 32) * di_div_up(Cout, 128);
-    // the 3x3 stride-2 geometry (25 MFMA blocks per 8-step body, not 49 / 64): the wide blocks win at every batch measured (B = 4 / 8 / 32,
-    // tools/bench_wino.py; profiles/r09_stride2_wino.md)
-    half = (s2d != 2 && wide_blocks * (Cin / 8) <= 100L * 256) || (Cout & 127) != 0;
-  }
-  // 4 = the nine-accumulator 256 x 32 blocks (conv_wino9_kernel) where they exist — the 3x3 stride-2 walk with its dead positions dropped
-  // and Cout % 256 == 0 —, anywhere else as 3. Under the default (1) this launcher keeps the 128 x 32 blocks for that walk; the caller
-  // that wants the new shape where it measured faster asks deepim_conv_wino_preferred_s2d3_wide and calls
-  // deepim_conv2d_wino_forward_s2d3_wide (force_nine), as the network does (profiles/r13_s2d3_nine_tuples.md)
-  const bool nine_ok = shared && s2d == 2 && (Cin % 64) == 0 && ctx->wino_s2d_skip && (Cout & 255) == 0;
-  const bool nine = nine_ok && (ctx->wino_wide == 4 || (force_nine && ctx->wino_wide == 1));
-  if (nine) half = false;
-  const bool wide = shared && !half && !nine && (Cout & 127) == 0 && ctx->wino_wide != 0;
-  p.gx = di_div_up(p.ntiles, (wide || half || nine) ? 32 : (two_wave || shared) ? 64 : 128);
-  p.gy = nine ? Cout / 256 : wide ? Cout / 128 : shared ? Cout / 64 : Cout / 32;
-  p.in_bytes = (unsigned)in_bytes; p.wd_bytes = (unsigned)wd_bytes;
-  p.out_bytes = (unsigned)std::min<size_t>((size_t)B * Cout * H * W * 4, 0x7fffffffu);
-  p.out_ctotal = out_ctotal > 0 ? out_ctotal : Cout;
-  p.out_coff = out_coff;
+  p.gx = pl.gx; p.gy = pl.gy;
+  p.in_bytes = (unsigned)((size_t)B * Cin * H * W * 4); p.wd_bytes = (unsigned)((size_t)Cout * Cin * 64);
+  p.out_bytes = (unsigned)std::min<size_t>(out_elems * 4, 0x7fffffffu);
+  p.out_ctotal = ctotal; p.out_coff = out_coff;
   p.out_s2d = out_nc8 == 3 ? 1 : 0;
-  p.grid0 = 1; p.kslice = Cin / 8; p.ksplit = 1; p.part_stride = 0; p.nvb = 1; p.part = nullptr;
-  p.sk_G = 0; p.sk_gran = 0; p.sk_F = 0; p.sk_q = 0; p.sk_rem = 0; p.sk_nlb = 0; p.sk_count = nullptr;
-  if (p.out_s2d) DI_REQUIRE(((H | W) & 1) == 0, "conv2d_wino_forward: space-to-depth output needs even H and W");
-  int grid = p.gx * p.gy;
-  if (shared) {
-    DI_REQUIRE(!out_nc8 || (size_t)B * Cout * H * W * 4 < (1ull << 31), "conv2d_wino_forward: channel-blocked output beyond the 2 GB buffer range");
-    // block -> (channel block, tile block) as conv_wino8_kernel maps it: gy < 8 dividing 8 deals 8 / gy XCDs to each channel block
-    if ((p.gy & 7) != 0 && (8 % p.gy) == 0) grid = 8 * di_div_up(p.gx, 8 / p.gy);
-    // the zero positions are dropped along an interleaved walk of the four input phases: two 8-channel blocks of each per loop body
-    // (ph8 = the geometry: 1 the 5x5, 2 the 3x3 stride-2 layers)
-    const int ph8 = (s2d && (Cin % 64) == 0 && ctx->wino_s2d_skip) ? s2d : 0;
-    // under-filled grids split the input channels (conv5_1 / conv6_1 at B = 32, every layer at the per-GPU shares of an 8-GPU node)
-    const int nK = Cin / 8;
-    const size_t out_elems = (size_t)B * Cout * H * W;
-    int ks = nK;
-    const int slots = half ? 512 : 256, gran = ph8 ? 8 : 2;
-    double cost_split = 0, cost_sk = 0;
-    int S = ctx->wino_split == 1 ? 1 : wino8_split_plan(grid, nK, gran, out_elems * 4 / 1e6, ctx->wino_split, &ks, slots, &cost_split);
-    int skF = 0, skq = 0, skrem = 0;
-    const int skG = (ctx->wino_split != 1 && ctx->wino_persistent && ctx->wino_streamk && out_nc8 && out_elems * 4 < (1ull << 31)) ? wino8_streamk_plan(grid, nK, gran, slots, &cost_sk, &skF, &skq, &skrem) : 0;
-    // measured (bench.py A/B in one box): +1 % at B = 32 (4-18 whole rounds before the cut one), -1 % at B = 4 (one): from two whole rounds on
-    // (the arrival counters are allocated with the context, deepim_create: nothing is allocated at launch time)
-    const bool streamk = skG > 0 &&
-                         (ctx->wino_streamk == 2 || (skF >= 2 && cost_sk < cost_split * 0.98));   // 2: wherever it applies (tests)
-    if (streamk) { S = 1; ks = nK; }
-    p.grid0 = grid; p.kslice = ks; p.ksplit = S; p.part_stride = 0; p.part = nullptr;
-    if ((S > 1 || streamk) && !plan_only) {
-      void* scr = nullptr;
-      const int copies = streamk ? di_div_up(skG, skq) + 1 : S;   // a tile block of G granules cut by runs of >= q: at most that many pieces
-      if (deepim_scratch(ctx, (size_t)copies * out_elems * 4, &scr) != 0) return -1;
-      p.part = (float*)scr;
-      p.part_stride = (long)out_elems;
-    }
-    if (S > 1) {
-      if (!out_nc8) { p.out_ctotal = Cout; p.out_coff = 0; }   // dense NCHW partials
-      grid *= S;
-    }
-    p.nvb = grid;
-    if (ctx->wino_persistent) grid = (int)std::min<long>(grid, slots);   // one block per resident slot, each walks its share
-    if (streamk) {
-      p.sk_G = skG; p.sk_gran = gran; p.sk_F = skF; p.sk_q = skq; p.sk_rem = skrem; p.sk_nlb = slots / 8; grid = slots;
-      if (!plan_only) p.sk_count = (int*)ctx->wino_counters;   // one word per tile block, zero between launches (the kernel leaves them so)
-    }
-    // K slices finished inside the kernel: the block whose slice of a tile block arrives last adds the S raw copies in slice order, the bias
-    // and the activation — the sums wino_reduce_kernel would form, without its launch and its pass over the whole output
-    const bool fin = S > 1 && ctx->wino_fin && p.grid0 <= DI_WINO_COUNTERS && (size_t)out_elems * 4 < (1ull << 31);
-    p.fin_nchw = 0; p.fin_ctotal = 0; p.fin_coff = 0;
-    if (fin) {
-      if (!plan_only) p.sk_count = (int*)ctx->wino_counters;
-      if (!out_nc8) { p.fin_nchw = 1; p.fin_ctotal = out_ctotal > 0 ? out_ctotal : Cout; p.fin_coff = out_coff; }
-    }
-    if (plan_only) {   // {block shape 0 / 1 wide / 2 four-wave / 3 nine-accumulator 256 x 32, grid, K slices, K steps per slice, stream-K granules per tile block (0: off), granules per run, whole tile blocks per block before the run, tile blocks of the layer (incl. the padding of the XCD deal), runs that are one granule longer}
-      plan_only[0] = half ? 2 : nine ? 3 : wide ? 1 : 0; plan_only[1] = grid; plan_only[2] = S; plan_only[3] = ks; plan_only[4] = p.sk_G; plan_only[5] = p.sk_q; plan_only[6] = p.sk_F; plan_only[7] = p.grid0; plan_only[8] = p.sk_rem;
-      return 0;
-    }
-#define W8_LAUNCH(O, S)                                                                               \
-    if (half) conv_wino4_kernel<O, S><<<grid, 256, 0, ctx->stream>>>(p);                              \
-    else if (wide) conv_wino8_kernel<O, S, 1><<<grid, 512, 0, ctx->stream>>>(p);                      \
-    else conv_wino8_kernel<O, S, 0><<<grid, 512, 0, ctx->stream>>>(p);
-    if (nine) {
-      if (out_nc8) conv_wino9_kernel<1><<<grid, 512, 0, ctx->stream>>>(p);
-      else conv_wino9_kernel<0><<<grid, 512, 0, ctx->stream>>>(p);
-    } else if (ph8 == 2) {
-      if (out_nc8) { W8_LAUNCH(1, 2) } else { W8_LAUNCH(0, 2) }
-    } else if (ph8) {
-      if (out_nc8) { W8_LAUNCH(1, 1) } else { W8_LAUNCH(0, 1) }
-    } else {
-      if (out_nc8) { W8_LAUNCH(1, 0) } else { W8_LAUNCH(0, 0) }
-    }
-#undef W8_LAUNCH
-    if (S > 1 && !fin) {
-      const long total = out_nc8 ? (long)(out_elems / 4) : (long)out_elems;
-      const int hw = p.out_s2d ? H * W / 4 : H * W;
-      wino_reduce_kernel<<<di_div_up(total, 256), 256, 0, ctx->stream>>>(out, p.part, bias, total, p.part_stride, S, slope, out_nc8 ? 1 : 0,
-                                                                           (Cout >> 3) * (p.out_s2d ? 4 : 1), hw, Cout >> 3, Cout,
-                                                                           out_ctotal > 0 ? out_ctotal : Cout, out_coff);
-    }
-    DI_LAUNCH_CHECK();
-    return 0;
+  p.grid0 = pl.grid0; p.kslice = pl.ks; p.ksplit = pl.S; p.nvb = pl.nvb;
+  if (pl.copies) {
+    void* scr = nullptr;
+    if (deepim_scratch(ctx, (size_t)pl.copies * out_elems * 4, &scr) != 0) return -1;
+    p.part = (float*)scr;
+    p.part_stride = (long)out_elems;
   }
-  if (plan_only) return 0;
-  // phase-by-phase K loop with the zero positions skipped: needs an even number of 8-channel blocks per input phase (the 5x5 walk
-  // skips a subset of the 3x3 stride-2 geometry's zero positions: it serves both)
-  const bool phases = s2d && (Cin % 64) == 0 && ctx->wino_s2d_skip;
-  if (two_wave) {
-    if (out_nc8) conv_wino2_kernel<1><<<grid, 256, 0, ctx->stream>>>(p);
-    else conv_wino2_kernel<0><<<grid, 256, 0, ctx->stream>>>(p);
-  } else if (phases) {
-    if (out_nc8) conv_wino_kernel<1, 1><<<grid, 256, 0, ctx->stream>>>(p);
-    else conv_wino_kernel<0, 1><<<grid, 256, 0, ctx->stream>>>(p);
-  } else {
-    if (out_nc8) conv_wino_kernel<1><<<grid, 256, 0, ctx->stream>>>(p);
-    else conv_wino_kernel<0><<<grid, 256, 0, ctx->stream>>>(p);
+  if (pl.S > 1 && !out_nc8) { p.out_ctotal = Cout; p.out_coff = 0; }   // dense NCHW partials
+  if (pl.sk_G) { p.sk_G = pl.sk_G; p.sk_gran = pl.gran; p.sk_F = pl.sk_F; p.sk_q = pl.sk_q; p.sk_rem = pl.sk_rem; p.sk_nlb = WINO_SHAPE[pl.shape].slots / 8; }
+  if (pl.sk_G || pl.fin) p.sk_count = (int*)ctx->wino_counters;   // one word per tile block, zero between launches (the kernel leaves them so)
+  if (pl.fin_nchw) { p.fin_nchw = 1; p.fin_ctotal = ctotal; p.fin_coff = out_coff; }
+
+  WINO_KERNEL[pl.shape][pl.walk][out_nc8 ? 1 : 0]<<<pl.grid, WINO_SHAPE[pl.shape].threads, 0, ctx->stream>>>(p);
+  if (pl.S > 1 && !pl.fin) {
+    const long total = out_nc8 ? (long)(out_elems / 4) : (long)out_elems;
+    const int hw = p.out_s2d ? H * W / 4 : H * W;
+    wino_reduce_kernel<<<di_div_up(total, 256), 256, 0, ctx->stream>>>(out, p.part, bias, total, p.part_stride, pl.S, slope, out_nc8 ? 1 : 0,
+                                                                         (Cout >> 3) * (p.out_s2d ? 4 : 1), hw, Cout >> 3, Cout, ctotal, out_coff);
   }
   DI_LAUNCH_CHECK();
   return 0;
@@ -1809,14 +1668,14 @@ static int wino_forward_impl(deepim_ctx* ctx, float* out, const float* in, const
 extern "C" int deepim_conv2d_wino_forward(deepim_ctx* ctx, float* out, const float* in, const float* packed_w, const float* bias,
                                           int B, int Cin, int H, int W, int Cout, float slope, int out_nc8, int out_ctotal,
                                           int out_coff) {
-  return wino_forward_impl(ctx, out, in, packed_w, bias, B, Cin, H, W, Cout, slope, out_nc8, out_ctotal, out_coff, 0);
+  return wino_forward_impl(ctx, out, in, packed_w, bias, B, Cin, H, W, Cout, slope, out_nc8, out_ctotal, out_coff, {WINO_3X3, false});
 }
 
 // dx (B, Cin, H, W), NCHW, of a 3x3 stride-1 pad-1 layer from its channel-blocked dz (B, Cout/8, H, W, 8) and the U' of
 // deepim_conv_wino_pack_weights_dgrad: the forward kernels on the Cin <- Cout problem, no bias, no activation (K-split second pass included).
 extern "C" int deepim_conv2d_wino_dgrad(deepim_ctx* ctx, float* dx, const float* dz_nc8, const float* packed_w, int B, int Cin, int H,
                                         int W, int Cout) {
-  return wino_forward_impl(ctx, dx, dz_nc8, packed_w, nullptr, B, Cout, H, W, Cin, 1.0f, 0, 0, 0, 0);
+  return wino_forward_impl(ctx, dx, dz_nc8, packed_w, nullptr, B, Cout, H, W, Cin, 1.0f, 0, 0, 0, {WINO_3X3, false});
 }
 
 // The 5x5 stride-2 pad-2 layer itself: `in` = the space-to-depth NC8 form (B, 4 Cin, H/2, W/2) of its (B, Cin, H, W) input, packed_w
@@ -1826,7 +1685,7 @@ extern "C" int deepim_conv2d_wino_forward_s2d(deepim_ctx* ctx, float* out, const
                                               int B, int Cin, int H, int W, int Cout, float slope, int out_nc8, int out_ctotal,
                                               int out_coff) {
   DI_REQUIRE(H > 0 && W > 0 && ((H | W) & 1) == 0, "conv2d_wino_forward_s2d: even H and W required");
-  return wino_forward_impl(ctx, out, in_s2d, packed_w, bias, B, 4 * Cin, H / 2, W / 2, Cout, slope, out_nc8, out_ctotal, out_coff, 1);
+  return wino_forward_impl(ctx, out, in_s2d, packed_w, bias, B, 4 * Cin, H / 2, W / 2, Cout, slope, out_nc8, out_ctotal, out_coff, {WINO_S2D_5X5, false});
 }
 
 // The 3x3 stride-2 pad-1 layer: `in_s2d` as above (even H and W), packed_w from deepim_conv_wino_pack_weights_s2d3, output
@@ -1835,7 +1694,7 @@ extern "C" int deepim_conv2d_wino_forward_s2d3(deepim_ctx* ctx, float* out, cons
                                                int B, int Cin, int H, int W, int Cout, float slope, int out_nc8, int out_ctotal,
                                                int out_coff) {
   DI_REQUIRE(H > 0 && W > 0 && ((H | W) & 1) == 0, "conv2d_wino_forward_s2d3: even H and W required");
-  return wino_forward_impl(ctx, out, in_s2d, packed_w, bias, B, 4 * Cin, H / 2, W / 2, Cout, slope, out_nc8, out_ctotal, out_coff, 2);
+  return wino_forward_impl(ctx, out, in_s2d, packed_w, bias, B, 4 * Cin, H / 2, W / 2, Cout, slope, out_nc8, out_ctotal, out_coff, {WINO_S2D_3X3, false});
 }
 
 // The same layer through the nine-accumulator 256-channel x 32-tile blocks (conv_wino9_kernel) where that shape exists under the
@@ -1845,19 +1704,24 @@ extern "C" int deepim_conv2d_wino_forward_s2d3_wide(deepim_ctx* ctx, float* out,
                                                     int B, int Cin, int H, int W, int Cout, float slope, int out_nc8, int out_ctotal,
                                                     int out_coff) {
   DI_REQUIRE(H > 0 && W > 0 && ((H | W) & 1) == 0, "conv2d_wino_forward_s2d3_wide: even H and W required");
-  return wino_forward_impl(ctx, out, in_s2d, packed_w, bias, B, 4 * Cin, H / 2, W / 2, Cout, slope, out_nc8, out_ctotal, out_coff, 2, nullptr, true);
+  return wino_forward_impl(ctx, out, in_s2d, packed_w, bias, B, 4 * Cin, H / 2, W / 2, Cout, slope, out_nc8, out_ctotal, out_coff, {WINO_S2D_3X3, true});
 }
 
-// The launch plan of the shared-transform kernel for a layer geometry (s2d 1: 5x5 stride 2, 2: 3x3 stride 2, 3: 3x3 stride 2 through
-// deepim_conv2d_wino_forward_s2d3_wide; the arguments are then the
-// space-to-depth problem's, as wino_forward_impl sees them) under the context's options; plan[6] as documented at the fill site. -1 where that kernel is not used.
+// The launch plan of the shared-transform kernel for a layer geometry (the arguments are the space-to-depth problem's where s2d is set, as
+// wino_forward_impl sees them) under the context's options, NULL: the defaults; plan[0..8] as include/deepim_hip.h maps them onto
+// WinoPlan. -1 where that kernel is not used. Host arithmetic: no device involved.
 extern "C" int deepim_conv_wino_plan(deepim_ctx* ctx, int B, int Cin, int H, int W, int Cout, int out_nc8, int s2d, int* plan) {
   DI_REQUIRE(plan != nullptr, "conv_wino_plan: null plan");
   for (int i = 0; i < 9; ++i) plan[i] = -1;
-  deepim_ctx defaults;                 // ctx == NULL: the plan under the default options (no device involved)
-  if (!ctx) { deepim_ctx_default_options(&defaults); ctx = &defaults; }
-  return wino_forward_impl(ctx, nullptr, nullptr, nullptr, nullptr, B, Cin, H, W, Cout, 0.f, out_nc8, 0, 0, (s2d == 2 || s2d == 3) ? 2 : s2d != 0, plan,
-                           s2d == 3);
+  const WinoOptions o = wino_options(ctx);
+  const int go = wino_check_args(o, B, Cin, H, W, Cout, out_nc8);
+  if (go <= 0) return go;
+  const WinoLayerKind kind = wino_kind_of_plan_arg(s2d);
+  const WinoPlan pl = wino_plan(o, B, Cin, H, W, Cout, out_nc8, kind.geom, kind.want_nine);
+  if (pl.shape < WINO_64X64) return 0;
+  const int ints[9] = {pl.shape - WINO_64X64, pl.grid, pl.S, pl.ks, pl.sk_G, pl.sk_q, pl.sk_F, pl.grid0, pl.sk_rem};
+  std::copy(ints, ints + 9, plan);
+  return 0;
 }
 
 #if W8_TRACE

@@ -168,6 +168,27 @@ def test_launch_plans_of_the_encoder_layers():
     assert _wino_plan(2, 256, 60, 80, 96) == [-1] * 9             # Cout % 64 != 0: the one-wave kernel, no plan of this kind
 
 
+def test_default_launch_plans_match_the_recorded_ones():
+    """Every default-option plan and deepim_conv_wino_preferred* answer recorded in tests/golden/wino_plans.json, recomputed: all nine
+    ints, the return code and the four answers, for every geometry the Winograd tests use at B = 1 ... 32. A change of a threshold or
+    of the plan arithmetic shows up here; one made on purpose regenerates the file (tests/golden/make_wino_plans.py)."""
+    import importlib.util
+    import json
+    import os
+    from mx_deepim_amd.runtime import lib
+    golden = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+    spec = importlib.util.spec_from_file_location("make_wino_plans", os.path.join(golden, "make_wino_plans.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    with open(os.path.join(golden, "wino_plans.json")) as f:
+        doc = json.load(f)
+    assert doc["columns"] == gen.COLUMNS
+    got = gen.rows(lib.load())
+    assert len(got) == len(doc["rows"]) == len(gen.geometries()) * len(gen.BATCHES) > 400
+    for want, row in zip(doc["rows"], got):
+        assert row == want, dict(zip(gen.COLUMNS, zip(want, row)))
+
+
 def _streamk_pieces(plan, slots):
     """The piece walk of conv_wino8_kernel's persistent blocks (w8_iter_next / w8_run_owner in csrc/wino.hip), restated."""
     _, _, _, ks, G, q, F, grid0, rem = plan
