@@ -421,6 +421,23 @@ int deepim_conv_f16_pack_weights(deepim_ctx* ctx, void* packed, const float* w /
 int deepim_conv2d_f16_forward(deepim_ctx* ctx, void* out_nhwc_f16, const void* in_nhwc_f16, const void* packed_w,
                               const float* bias, int B, int Cin_pad, int H, int W, int Cout, int kh, int kw,
                               int stride, int pad, float slope);
+/* fp16 Winograd F(2x2,3x3) for the fp16 path's 3x3 stride-1 pad-1 layers (csrc/wino_f16.hip; network.FP16_WINOGRAD, default off):
+ * the tensors of deepim_conv2d_f16_forward (NHWC fp16 in and out, fp32 bias, LeakyReLU), 2.25x fewer MFMAs. Its own arithmetic
+ * contract, stated operation by operation at the top of csrc/wino_f16.hip and restated in numpy by tests/fp16_wino_emulation.py:
+ * U = f16(G f16(w) G^T) from fp32 products, the input transform V = B^T d B in fp16 arithmetic (one fp16 add per entry and pass: two
+ * roundings), sixteen GEMMs on v_mfma_f32_32x32x16_f16 with fp32 accumulation, A^T M A + bias + LeakyReLU in fp32, one rounding.
+ * Not the direct fp16 kernel within one ulp: about 1.5x its per-layer error (<= 2^-9 of the layer's range from it). No K split and
+ * no atomics: bit-identical from run to run. RANGE: |V| <= 4 max|x|, so an activation above about 16 000 can become inf here where the
+ * direct kernel would not; nothing is clamped. Odd H or W are fine; the input must be smaller than 2 GiB.
+ * deepim_conv_wino_f16_supported: 1 for Cin % 32 == 0 and Cout % 64 == 0 (a pure shape predicate), else 0; pack and forward refuse the
+ * rest (-1, nothing launched), deepim_conv_wino_f16_packed_size returns 0 for them and Cout*Cin*32 bytes otherwise.
+ * Packed layout (fp16, MFMA A-operand order): the half at index ((((co / 32) * (Cin / 16) + ci / 16) * 16 + p) * 64 + lane) * 8 + ci % 8
+ * with lane = co % 32 + 32 * ((ci / 8) % 2) is U[p][co][ci], position p = 4 i + nu of U = G g G^T (i down the rows, nu along them). */
+int deepim_conv_wino_f16_supported(int Cin, int Cout);
+size_t deepim_conv_wino_f16_packed_size(int Cout, int Cin);
+int deepim_conv_wino_f16_pack_weights(deepim_ctx* ctx, void* packed, const float* w /*Cout,Cin,3,3 dev f32*/, int Cout, int Cin);
+int deepim_conv2d_wino_f16_forward(deepim_ctx* ctx, void* out_nhwc_f16, const void* in_nhwc_f16, const void* packed_w,
+                                   const float* bias, int B, int Cin, int H, int W, int Cout, float slope);
 /* Split-fp16 ("x3") convolution: the same Convolution + bias + LeakyReLU (deepIM_flownet.py:63-107) at fp32-grade accuracy on
  * the fp16 matrix cores. A value v travels as the fp16 pair hi = f16(v·s), lo = f16(v·s − hi) (22 significand bits, s a power
  * of two), a product is hi·hi + hi·lo + lo·hi (v_mfma_f32_32x32x16_f16, fp32 accumulation; the dropped lo·lo term is 2^-22

@@ -56,6 +56,10 @@ def default_config():
         # with FP16_CONV and the decoder in the test graph: decoder + flow / mask predictors in fp16 too (False: fp32 decoder). The
         # training graph ignores it: there the decoder and heads always run in fp32 on the fp16 encoder's activations
         FP16_DECODER=True,
+        # with FP16_CONV: the 3x3 stride-1 encoder layers (conv3_1 / conv4_1 / conv5_1 / conv6_1) as fp16 Winograd F(2x2,3x3)
+        # (csrc/wino_f16.hip; not a reference key). A second fp16 arithmetic with about 1.5x the direct kernel's per-layer error,
+        # 2.25x fewer MFMAs. Test graph only; the x3 and fp32 graphs and the training graph ignore it
+        FP16_WINOGRAD=False,
     )
     cfg.train_iter = AttrDict(SE3_PM_LOSS=True, SE3_PM_LOSS_TYPE="L1", LW_PM=0.1, LW_FLOW=0.25, LW_MASK=0.03,
                               NUM_3D_SAMPLE=3000, SE3_PM_SL1_SCALAR=1.0, SE3_DIST_LOSS=False,

@@ -163,6 +163,7 @@ class deepIM_flownet(object):
         if train_x3:
             self.x3_conv = True    # the forward of the x3 test graph: encoder_x3() on packed_x3 and the split16 activations
         self.fp16_decoder = False  # network.FP16_DECODER governs the test graph only: the training decoder and heads are fp32
+        self.fp16_winograd = False  # network.FP16_WINOGRAD too: the backward differentiates the direct fp16 forward
         self.is_train = True
         # TRAIN.WINOGRAD_CONV: the forward of the inference encoder (channel-blocked activations, fp32 Winograd
         # layers) with a backward that reads those activations in place. The fp16 graph ignores the key
@@ -199,6 +200,9 @@ class deepIM_flownet(object):
         # the few-filter predictors from the fp16 concats (csrc/decoder_f16.hip). network.FP16_DECODER = False: the fp32 decoder
         # fed the encoder's fp16 activations converted to fp32 (the A/B baseline)
         self.fp16_decoder = self.fp16_conv and self.with_decoder and bool(n.get("FP16_DECODER", True))
+        # fp16 conv path with the 3x3 stride-1 encoder layers as fp16 Winograd F(2x2,3x3) (csrc/wino_f16.hip): every layer the kernel
+        # supports, no per-layer choice by speed. Its own arithmetic contract (about 1.5x the direct fp16 kernel's per-layer error)
+        self.fp16_winograd = self.fp16_conv and bool(n.get("FP16_WINOGRAD", False))
         self.nc8 = bool(cfg.network.get('NC8_CONV', True)) if hasattr(cfg.network, 'get') else True
         # the 3x3 stride-1 encoder layers as fp32 Winograd F(2x2,3x3) (csrc/wino.hip) wherever the layer fills the chip: same fp32
         # arithmetic, 2.25x fewer multiplies, a different summation (<= 1e-5 of the layer's range from the direct sum). Only on
@@ -386,6 +390,16 @@ class deepIM_flownet(object):
                 pk = DeviceArray(ctx, (lib.load().deepim_conv1_f16_c10_packed_size() // 2,), dtype=np.float16)
                 lib.deepim_conv1_f16_c10_pack_weights(h, pk, self.params[ENCODER[0][0] + "_weight"])
                 self.packed_f16["conv1_patch"] = pk
+        if getattr(self, "fp16_winograd", False):   # transformed fp16 weights U = f16(G f16(w) G^T) in MFMA operand order, one-time
+            self.packed_f16_wino, self.fp16_wino_layers = {}, []
+            cin = self.cin
+            for name, cout, k, s_, p_ in ENCODER:
+                if k == 3 and s_ == 1 and p_ == 1 and lib.load().deepim_conv_wino_f16_supported(cin, cout):
+                    pk = DeviceArray(ctx, (lib.load().deepim_conv_wino_f16_packed_size(cout, cin) // 2,), dtype=np.float16)
+                    lib.deepim_conv_wino_f16_pack_weights(h, pk, self.params[name + "_weight"], cout, cin)
+                    self.packed_f16_wino[name] = pk
+                    self.fp16_wino_layers.append(name)
+                cin = cout
         if self.x3_conv:     # split-fp16 weights [hi 16 | lo 16] in MFMA octet order, scaled by a power of two into fp16's range
             self.packed_x3, self.x3_wscale = {}, {}
             if self.cin == 8 and self.W % 4 == 0:    # conv1 on the split-fp16 patch kernel (8-channel input; otherwise fp32 conv1)
@@ -572,7 +586,13 @@ class deepIM_flownet(object):
         else:
             lib.deepim_nchw_f32_to_nhwc_f16(h, A["net_input_h"], A["net_input"], B, self.cin, self.H, self.W, self.cin_pad)
             src = A["net_input_h"]
+        wino = self.packed_f16_wino if getattr(self, "fp16_winograd", False) else {}
         for name, cin, hh, ww, cout, k, s, p in geom:
+            if name in wino:     # network.FP16_WINOGRAD: same tensors, the Winograd contract of csrc/wino_f16.hip
+                lib.deepim_conv2d_wino_f16_forward(h, A[name + "_h"], src, wino[name], self.params[name + "_bias"], B, cin, hh, ww,
+                                                   cout, ctypes.c_float(SLOPE))
+                src = A[name + "_h"]
+                continue
             cpad = (cin + 7) // 8 * 8
             lib.deepim_conv2d_f16_forward(h, A[name + "_h"], src, self.packed_f16[name], self.params[name + "_bias"], B,
                                           cpad, hh, ww, cout, k, k, s, p, ctypes.c_float(SLOPE))
