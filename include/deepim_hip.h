@@ -739,7 +739,7 @@ int deepim_sgd_mom_update_multi(deepim_ctx* ctx, const unsigned long long* table
                                 float momentum, float rescale, float clip);
 
 /* ---------------------------- mixed-precision training of the encoder (network.FP16_CONV in the training graph) -- */
-/* csrc/train_f16.hip; DESIGN.md §8f-4c. q(v) = round to fp16 (RNE) and back; S = the loss scale, a power of two. Forward = the
+/* csrc/train_half.hip; DESIGN.md §8f-4c. q(v) = round to fp16 (RNE) and back; S = the loss scale, a power of two. Forward = the
  * FP16_CONV encoder; the backward of encoder layer l (conv6_1 down to flow_conv1) is
  *   e_l   = S·(fc6 data gradient + d_dec61) at conv6_1 (fp32), d_l [+ S·skip_l] below (skip: fp32 decoder gradient of conv5_1 / conv4_1)
  *   dz_l  = q(lrelu'(y_l)·e_l)                          NHWC fp16, lrelu' from the stored fp16 y_l
@@ -783,7 +783,7 @@ int deepim_sgd_mom_update_multi_amp(deepim_ctx* ctx, const unsigned long long* t
  * scale = min(2^24, 2 scale), good_steps = 0. inv_scale follows, the overflow word is cleared. */
 int deepim_amp_scale_update(deepim_ctx* ctx, unsigned* state, int window);
 
-/* Split-fp16 ("x3") training (TRAIN.X3_CONV): the encoder backward on the fp16 matrix cores at fp32 grade (csrc/train_x3.hip,
+/* Split-fp16 ("x3") training (TRAIN.X3_CONV): the encoder backward on the fp16 matrix cores at fp32 grade (csrc/train_half.hip,
  * DESIGN.md §8f-4e). split(v, s): hi = f16(clamp(v·s, ±60000)), lo = f16(clamp(v·s) − hi); a product of two pairs is hi·hi + hi·lo +
  * lo·hi with fp32 accumulation. S = the gradient scale (a power of two), the stored activations y_l are split16 at scale 16:
  *   e_l   S·(fc6 data gradient + d_dec61) at conv6_1; d_l [+ S·skip_l] below

@@ -65,7 +65,7 @@ struct ConvF16Params {
   float acc_scale, out_scale;    // X3 mode: accumulator → real units (2^-(s_act+s_w)), real units → stored activations (2^s_act)
 };
 
-// X3 ("split fp16") operands: X3Pair / x3_split / x3_report live in x3_split.h (shared with csrc/train_x3.hip)
+// X3 ("split fp16") operands: X3Pair / x3_split / x3_report live in x3_split.h (shared with csrc/train_half.hip)
 
 // validity of the (ky,kx) taps of a pixel as a 64-bit word (bit ky*8+kx), kh,kw <= 7: rows/columns hi0+k, wi0+k inside the frame
 __device__ __forceinline__ unsigned long long tap_mask64(int hi0, int wi0, int H, int W) {

@@ -1,4 +1,4 @@
-// The split-fp16 ("x3") operand rule, shared by the forward kernels (conv_f16.hip) and the training backward (train_x3.hip).
+// The split-fp16 ("x3") operand rule, shared by the forward kernels (conv_f16.hip) and the training backward (train_half.hip).
 #pragma once
 #include "common.h"
 

@@ -939,10 +939,8 @@ def _train_methods():
         self.ws["d_points"] = ctx.empty((B, 3, num_points))
         self.ws["d_rot_norm"], self.ws["d_trans_est"] = ctx.empty((B, 4)), ctx.empty((B, 3))
         self.ws["d_rot"], self.ws["d_trans"] = ctx.empty((B, 4)), ctx.empty((B, 3))
-        if self.fp16_conv:
-            self._bind_train_fp16()
-        if self.train_x3:
-            self._bind_train_x3()
+        if self.fp16_conv or self.train_x3:
+            self._bind_train_half()
         if self.se3_dist_loss:            # deepIM_flownet.py:238-262
             A["zoom_trans_gt"], A["rot_loss"] = ctx.empty((B, 3)), ctx.empty((B,))
             A["trans_loss"], A["trans_loss_sum"] = ctx.empty((B, 3, 1)), ctx.empty((1,))
@@ -950,35 +948,26 @@ def _train_methods():
         ctx.sync()
         return self
 
-    def _bind_train_fp16(self):
-        """Buffers of the fp16 encoder backward: two NHWC fp16 gradient buffers (ping-pong, sized for the largest activation), the
-        dgrad workspace (packed weights + parity-class buffer), and the loss-scale state {scale, inv_scale, overflow, good_steps}."""
-        ctx, B = self.ctx, self.B
-        big = max(B * _out_hw(hh, ww, k, s_, p_)[0] * _out_hw(hh, ww, k, s_, p_)[1] * cout
-                  for _n, _ci, hh, ww, cout, k, s_, p_ in self.enc_geom)
-        self.ws["g16a"] = ctx.empty((big,), dtype=np.float16)
-        self.ws["g16b"] = ctx.empty((big,), dtype=np.float16)
-        nb = max(lib.load().deepim_conv_dgrad_f16_workspace_size(B, cin, hh, ww, cout, k, s_, p_)
-                 for _n, cin, hh, ww, cout, k, s_, p_ in self.enc_geom[1:])
-        self.ws["dgrad16"] = ctx.empty(((nb + 1) // 2,), dtype=np.float16)
-        self.amp_state = ctx.empty((4,), dtype=np.uint32)
-        self.set_loss_scale(self.loss_scale_init)
-
-    def _bind_train_x3(self):
-        """Buffers of the split-fp16 encoder backward (bind() already made packed_x3, conv1's pack included, and the split16
-        activations): two split16 gradient buffers (ping-pong, sized for the largest activation), the dgrad workspace (packed
-        weights + parity-class buffer) and the scale state {scale, inv_scale, overflow, good_steps}."""
-        ctx, B = self.ctx, self.B
-        if ENCODER[0][0] not in self.packed_x3:
+    def _bind_train_half(self):
+        """Buffers of the half-precision encoder backward, fp16 or split-fp16 (for x3 bind() already made packed_x3, conv1's pack
+        included, and the split16 activations): two gradient buffers in the mode's layout (ping-pong, sized for the largest
+        activation), the dgrad workspace (packed weights + parity-class buffer), and the scale state {scale, inv_scale, overflow,
+        good_steps}."""
+        ctx, B, x3 = self.ctx, self.B, self.train_x3
+        if x3 and ENCODER[0][0] not in self.packed_x3:
             raise NotImplementedError("TRAIN.X3_CONV needs the 8-channel network input with W % 4 == 0 (conv1 on the split-fp16 patch "
                                       "kernel)")
+        ga, gb, gws = ("gx3a", "gx3b", "dgradx3") if x3 else ("g16a", "g16b", "dgrad16")
+        halves = 2 if x3 else 1      # fp16 words per element: a split16 tensor carries hi and lo
         big = max(B * _out_hw(hh, ww, k, s_, p_)[0] * _out_hw(hh, ww, k, s_, p_)[1] * cout
                   for _n, _ci, hh, ww, cout, k, s_, p_ in self.enc_geom)
-        self.ws["gx3a"] = ctx.empty((2 * big,), dtype=np.float16)
-        self.ws["gx3b"] = ctx.empty((2 * big,), dtype=np.float16)
-        nb = max(lib.load().deepim_conv_dgrad_x3_workspace_size(B, cin, hh, ww, cout, k, s_, p_)
-                 for _n, cin, hh, ww, cout, k, s_, p_ in self.enc_geom[1:] if cin % 128 == 0)
-        self.ws["dgradx3"] = ctx.empty(((nb + 1) // 2,), dtype=np.float16)
+        self.ws[ga] = ctx.empty((halves * big,), dtype=np.float16)
+        self.ws[gb] = ctx.empty((halves * big,), dtype=np.float16)
+        L = lib.load()
+        ws_size = L.deepim_conv_dgrad_x3_workspace_size if x3 else L.deepim_conv_dgrad_f16_workspace_size
+        nb = max(ws_size(B, cin, hh, ww, cout, k, s_, p_)      # (x3: conv2's data gradient, Cin = 64, runs on the fp32 kernels)
+                 for _n, cin, hh, ww, cout, k, s_, p_ in self.enc_geom[1:] if not x3 or cin % 128 == 0)
+        self.ws[gws] = ctx.empty(((nb + 1) // 2,), dtype=np.float16)
         self.amp_state = ctx.empty((4,), dtype=np.uint32)
         self.set_loss_scale(self.loss_scale_init)
 
@@ -996,75 +985,65 @@ def _train_methods():
         f = st[:2].view(np.float32)
         return {"scale": float(f[0]), "inv_scale": float(f[1]), "overflow": bool(st[2]), "good_steps": int(st[3])}
 
-    def _encoder_backward_f16(self, e61):
-        """Backward of the fp16 encoder, last layer first: dz = q(lrelu'(y)·e) and db in one walk, dW on the fp16
-        matrix cores, d = q(conv_transpose(dz, q(w))) into the other NHWC fp16 buffer. e61: the fp32 NCHW gradient reaching
-        conv6_1 (fc6 data gradient + d_dec61), scaled by S inside the first walk."""
+    def _encoder_backward_half(self, e61):
+        """Backward of the half-precision encoder, last layer first, one loop for both modes (csrc/train_half.hip). e61: the fp32
+        NCHW gradient reaching conv6_1 (fc6 data gradient + d_dec61), scaled by S inside the first walk.
+        fp16: dz = q(lrelu'(y)·e) and db in one walk, dW on the fp16 matrix cores, d = q(conv_transpose(dz,
+        q(w))) into the other NHWC fp16 buffer.
+        x3: dz = split(lrelu'(y)·e, 1) and db in one walk, dW as three fp16 MFMAs per fragment pair, d =
+        split(conv_transpose(dz, split(w, s_w)) / s_w, 1) into the other split16 buffer. The two shapes the x3 kernels do not take
+        run on the fp32 kernels over converted tensors: conv1's weight gradient (Cin = 8) and conv2's data gradient (64 output
+        channels); the fp32 ping-pong buffers are free for them once the first walk has read e61."""
         A, P, G, W_, h, B = self.act, self.params, self.grad, self.ws, self.ctx.handle, self.B
-        st = self.amp_state
+        c, st, x3 = ctypes.c_float, self.amp_state, self.train_x3
         skips = {"conv5_1": W_["d_skip5"], "conv4_1": W_["d_skip4"]} if self.with_decoder else {}
-        x_, y_ = W_["g16a"], W_["g16b"]
+        if x3:
+            lib.deepim_x3_status_to_state(h, st)      # a clamp in the forward: the step is skipped, as after one in the backward
+            x_, y_, sfx = W_["gx3a"], W_["gx3b"], "_x"
+            fa, fb = W_["ga"], W_["gb"]
+            lrelu_bias_backward = lib.deepim_lrelu_bias_backward_x3
+        else:
+            x_, y_, sfx = W_["g16a"], W_["g16b"], "_h"
+            lrelu_bias_backward = lib.deepim_lrelu_bias_backward_f16
         for li in range(len(self.enc_geom) - 1, -1, -1):
             name, cin_, hh_, ww_, cout_, k_, s_, p_ = self.enc_geom[li]
             ho_, wo_ = _out_hw(hh_, ww_, k_, s_, p_)
             last = li == len(self.enc_geom) - 1
-            lib.deepim_lrelu_bias_backward_f16(h, x_, G[name + "_bias"], None if last else x_, e61 if last else skips.get(name),
-                                               A[name + "_h"], st, ctypes.c_float(SLOPE), B, cout_, ho_, wo_)
-            cpad = (cin_ + 7) // 8 * 8
-            if li == 0:      # conv1's input as NHWC fp16 (the training zoom wrote NCHW fp32)
-                lib.deepim_nchw_f32_to_nhwc_f16(h, A["net_input_h"], A["net_input"], B, cin_, hh_, ww_, cpad)
-                src = A["net_input_h"]
-            else:
-                src = A[self.enc_geom[li - 1][0] + "_h"]
+            lrelu_bias_backward(h, x_, G[name + "_bias"], None if last else x_, e61 if last else skips.get(name), A[name + sfx], st,
+                                c(SLOPE), B, cout_, ho_, wo_)
             if name + "_weight" in G.tm:
                 dw, layout = G.tm[name + "_weight"][0], 1
             else:
                 dw, layout = dict.__getitem__(G, name + "_weight"), 0
-            lib.deepim_conv2d_wgrad_f16(h, dw, src, x_, st, B, cin_, cpad, hh_, ww_, cout_, k_, s_, p_, layout)
-            if li > 0:
-                lib.deepim_conv2d_dgrad_f16(h, y_, x_, P[name + "_weight"], W_["dgrad16"], B, cin_, hh_, ww_, cout_, k_, s_, p_)
-            x_, y_ = y_, x_
-        return G
-
-    def _encoder_backward_x3(self, e61):
-        """Backward of the split-fp16 encoder, last layer first: dz = split(lrelu'(y)·e, 1) and db in one walk, dW as
-        three fp16 MFMAs per fragment pair, d = split(conv_transpose(dz, split(w, s_w)) / s_w, 1) into the other split16 buffer.
-        e61: the fp32 NCHW gradient reaching conv6_1 (fc6 data gradient + d_dec61), scaled by S inside the first walk. The two
-        shapes the x3 kernels do not take run on the fp32 kernels over converted tensors: conv1's weight gradient (Cin = 8) and
-        conv2's data gradient (64 output channels); the fp32 ping-pong buffers are free for them once the first walk has read e61."""
-        A, P, G, W_, h, B = self.act, self.params, self.grad, self.ws, self.ctx.handle, self.B
-        c, st = ctypes.c_float, self.amp_state
-        lib.deepim_x3_status_to_state(h, st)      # a clamp in the forward: the step is skipped, as after one in the backward
-        skips = {"conv5_1": W_["d_skip5"], "conv4_1": W_["d_skip4"]} if self.with_decoder else {}
-        x_, y_ = W_["gx3a"], W_["gx3b"]
-        fa, fb = W_["ga"], W_["gb"]
-        for li in range(len(self.enc_geom) - 1, -1, -1):
-            name, cin_, hh_, ww_, cout_, k_, s_, p_ = self.enc_geom[li]
-            ho_, wo_ = _out_hw(hh_, ww_, k_, s_, p_)
-            last = li == len(self.enc_geom) - 1
-            lib.deepim_lrelu_bias_backward_x3(h, x_, G[name + "_bias"], None if last else x_, e61 if last else skips.get(name),
-                                              A[name + "_x"], st, c(SLOPE), B, cout_, ho_, wo_)
-            if name + "_weight" in G.tm:
-                dw, layout = G.tm[name + "_weight"][0], 1
-            else:
-                dw, layout = dict.__getitem__(G, name + "_weight"), 0
-            if li == 0:      # dz in real units as NCHW fp32, then the fp32 weight gradient from the NCHW net input
+            if x3 and li == 0:      # dz in real units as NCHW fp32, then the fp32 weight gradient from the NCHW net input
                 lib.deepim_split16_to_nchw_f32_unscaled(h, fa, x_, st, B, cout_, ho_, wo_, c(1.0))
-                if layout:
-                    lib.deepim_conv2d_wgrad_tm(h, dw, A["net_input"], fa, B, cin_, hh_, ww_, cout_, k_, k_, s_, p_)
-                else:
-                    lib.deepim_conv2d_wgrad(h, dw, A["net_input"], fa, B, cin_, hh_, ww_, cout_, k_, k_, s_, p_)
+                wgrad = lib.deepim_conv2d_wgrad_tm if layout else lib.deepim_conv2d_wgrad
+                wgrad(h, dw, A["net_input"], fa, B, cin_, hh_, ww_, cout_, k_, k_, s_, p_)
                 break
-            lib.deepim_conv2d_wgrad_x3(h, dw, A[self.enc_geom[li - 1][0] + "_x"], x_, st, B, cin_, hh_, ww_, cout_, k_, s_, p_, layout,
-                                       c(self.X3_ACT_SCALE))
-            if cin_ % 128 == 0:
-                lib.deepim_conv2d_dgrad_x3(h, y_, x_, P[name + "_weight"], W_["dgradx3"], st, B, cin_, hh_, ww_, cout_, k_, s_, p_,
-                                           c(self.x3_wscale[name]))
-            else:            # conv2: the scaled dz as NCHW fp32 → fp32 data gradient → split16 at scale 1
-                lib.deepim_split16_to_nchw_f32(h, fa, x_, B, cout_, ho_, wo_, c(1.0))
-                self._dgrad(fb, fa, P[name + "_weight"], B, cin_, hh_, ww_, cout_, k_, s_, p_, ho_, wo_)
-                lib.deepim_nchw_f32_to_split16(h, y_, fb, B, cin_, hh_, ww_, c(1.0))
-                lib.deepim_x3_status_to_state(h, st)
+            if x3:
+                lib.deepim_conv2d_wgrad_x3(h, dw, A[self.enc_geom[li - 1][0] + "_x"], x_, st, B, cin_, hh_, ww_, cout_, k_, s_, p_,
+                                           layout, c(self.X3_ACT_SCALE))
+            else:
+                cpad = (cin_ + 7) // 8 * 8
+                if li == 0:      # conv1's input as NHWC fp16 (the training zoom wrote NCHW fp32)
+                    lib.deepim_nchw_f32_to_nhwc_f16(h, A["net_input_h"], A["net_input"], B, cin_, hh_, ww_, cpad)
+                    src = A["net_input_h"]
+                else:
+                    src = A[self.enc_geom[li - 1][0] + "_h"]
+                lib.deepim_conv2d_wgrad_f16(h, dw, src, x_, st, B, cin_, cpad, hh_, ww_, cout_, k_, s_, p_, layout)
+            if li == 0:          # no data gradient below conv1 (x3 has left the loop there already)
+                break
+            if x3:
+                if cin_ % 128 == 0:
+                    lib.deepim_conv2d_dgrad_x3(h, y_, x_, P[name + "_weight"], W_["dgradx3"], st, B, cin_, hh_, ww_, cout_, k_, s_, p_,
+                                               c(self.x3_wscale[name]))
+                else:            # conv2: the scaled dz as NCHW fp32 → fp32 data gradient → split16 at scale 1
+                    lib.deepim_split16_to_nchw_f32(h, fa, x_, B, cout_, ho_, wo_, c(1.0))
+                    self._dgrad(fb, fa, P[name + "_weight"], B, cin_, hh_, ww_, cout_, k_, s_, p_, ho_, wo_)
+                    lib.deepim_nchw_f32_to_split16(h, y_, fb, B, cin_, hh_, ww_, c(1.0))
+                    lib.deepim_x3_status_to_state(h, st)
+            else:
+                lib.deepim_conv2d_dgrad_f16(h, y_, x_, P[name + "_weight"], W_["dgrad16"], B, cin_, hh_, ww_, cout_, k_, s_, p_)
             x_, y_ = y_, x_
         return G
 
@@ -1239,14 +1218,10 @@ def _train_methods():
         ga, gb = W_["ga"], W_["gb"]
         lib.deepim_fc_backward(h, ga, G["fc6_weight"], G["fc6_bias"], W_["g256b"], A["conv6_1"].reshape((B, n6)),
                                P["fc6_weight"], B, n6, 256)
-        if self.fp16_conv:
+        if self.fp16_conv or self.train_x3:
             if self.with_decoder:
                 lib.deepim_axpy(h, ga, W_["d_dec61"], c(1.0), B * n6)
-            return self._encoder_backward_f16(ga)
-        if self.train_x3:
-            if self.with_decoder:
-                lib.deepim_axpy(h, ga, W_["d_dec61"], c(1.0), B * n6)
-            return self._encoder_backward_x3(ga)
+            return self._encoder_backward_half(ga)
         skips = {"conv5_1": "d_skip5", "conv4_1": "d_skip4"} if self.with_decoder else {}
         # encoder, last layer first: dz = lrelu'(y)·(dy [+ the gradient over the layer's skip connection]) and the bias gradient in
         # one fused walk, in place over dy; dx into the other buffer. (_dgrad can apply the activation gradient of the layer below
@@ -1437,9 +1412,9 @@ def _train_methods():
                     "Convolution3": (770, 30, 40, 2, 3, 1, 1), "mask_conv3": (770, 30, 40, 1, 3, 1, 1)})
         return {n: order(h, B, cin, hh, ww, cout, k, k, s_, p_) for n, (cin, hh, ww, cout, k, s_, p_) in geo.items()}
 
-    return dict(bind_train=bind_train, _bind_train_fp16=_bind_train_fp16, set_loss_scale=set_loss_scale, loss_scale=loss_scale,
-                _encoder_backward_f16=_encoder_backward_f16, _repack_f16=_repack_f16,
-                _bind_train_x3=_bind_train_x3, _encoder_backward_x3=_encoder_backward_x3, _repack_x3=_repack_x3, forward_train=forward_train, _dgrad=_dgrad,
+    return dict(bind_train=bind_train, _bind_train_half=_bind_train_half, set_loss_scale=set_loss_scale, loss_scale=loss_scale,
+                _encoder_backward_half=_encoder_backward_half, _repack_f16=_repack_f16, _repack_x3=_repack_x3,
+                forward_train=forward_train, _dgrad=_dgrad,
                 _small_conv_backward=_small_conv_backward, _head_conv_backward=_head_conv_backward,
                 _repack_train_winograd=_repack_train_winograd,
                 _deconv_backward=_deconv_backward, _decoder_backward=_decoder_backward, backward=backward, update=update, train_step=train_step,
