@@ -738,6 +738,28 @@ int deepim_sgd_mom_update(deepim_ctx* ctx, float* w, float* mom, const float* g,
 int deepim_sgd_mom_update_multi(deepim_ctx* ctx, const unsigned long long* table, int rows, int total_blocks, float lr,
                                 float momentum, float rescale, float clip);
 
+/* MXNet 1.2 adam_update (train.py:260-294, TRAIN.optimizer = "adam"), per element in fp32:
+ *   g' = rescale*g + wd*w  [clamped to +-clip if clip > 0: the clamp acts on the sum, weight decay included]
+ *   mean = beta1*mean + (1-beta1)*g';  var = beta2*var + (1-beta2)*g'*g';  w -= lr_t * mean / (sqrt(var) + epsilon)
+ * lr_t = lr * sqrt(1-beta2^t) / (1-beta1^t), t = updates applied so far, this one included; epsilon is outside the bias correction
+ * (not torch.optim.Adam's placement). beta1 and 1-beta1 (beta2 likewise) are rounded to float separately, from the doubles given.
+ * This single-tensor entry takes lr_t from the caller. g = mean = var = 0 and wd = 0 leave w unchanged bit for bit. */
+int deepim_adam_update(deepim_ctx* ctx, float* w, float* mean, float* var, const float* g, float lr_t, float wd, double beta1,
+                       double beta2, float epsilon, float rescale, float clip, size_t n);
+
+/* the same update of every parameter in one launch, with the step count kept on the device. table (device): `rows` rows of SEVEN
+ * 64-bit words {w, mean, var, g (device addresses), n, (bits of float wd) | (first block of the row << 32), layout of g as in
+ * deepim_sgd_mom_update_multi}; blocks, alignment and row order as there.
+ * opt_state (device, 4 x 32 bit, zeroed by the owner before the first update): {uint t, float lr_t, float lr_factor, uint 0}. The
+ * call first runs a one-thread launch that sets t += 1, lr_factor = sqrt(1-beta2^t)/(1-beta1^t) and lr_t = lr*lr_factor (both
+ * evaluated in double, rounded to float once), then the update kernel, which reads lr_t from the state: the step is folded into
+ * this call, there is no separate entry for it. amp_state (NULL: none) is the loss-scale state of the fp16 / x3 training modes:
+ * while its overflow word is set nothing moves, t included; run deepim_amp_scale_update after the call. No host sync.
+ * Results are bit-identical to per-tensor deepim_adam_update calls on natural gradients with the lr_t of the state. */
+int deepim_adam_update_multi(deepim_ctx* ctx, const unsigned long long* table, int rows, int total_blocks, unsigned* opt_state,
+                             double lr, double beta1, double beta2, float epsilon, float rescale, float clip,
+                             const unsigned* amp_state);
+
 /* ---------------------------- mixed-precision training of the encoder (network.FP16_CONV in the training graph) -- */
 /* csrc/train_half.hip; DESIGN.md §8f-4c. q(v) = round to fp16 (RNE) and back; S = the loss scale, a power of two. Forward = the
  * FP16_CONV encoder; the backward of encoder layer l (conv6_1 down to flow_conv1) is

@@ -13,6 +13,7 @@
 //   LeakyReLU'                  from the saved output: dZ = dY·(y > 0 ? 1 : slope)
 //   FC     dX = dY·W, dW = dYᵀ·X, db = Σ dY
 //   SGD    mom = m·mom − lr·(rescale·g [clipped] + wd·w); w += mom     (MXNet sgd_mom_update)
+//   Adam   g' = [rescale·g + wd·w, clipped]; m = β1·m + (1−β1)·g'; v = β2·v + (1−β2)·g'²; w −= lr_t·m/(√v + ε)   (MXNet adam_update)
 #include "common.h"
 
 namespace {
@@ -931,6 +932,106 @@ __global__ __launch_bounds__(256) void sgd_mom_multi_kernel(const unsigned long 
   }
 }
 
+// one Adam element (MXNet adam_update): the gradient with weight decay is clamped as a whole, epsilon sits outside the bias
+// correction (lr_t carries it). g = m = v = 0, wd = 0 gives 0 / (0 + eps): the weight keeps its bits.
+__device__ __forceinline__ void adam_element(float& w, float& m, float& v, float g, float lr_t, float wd, float b1, float omb1, float b2,
+                                             float omb2, float eps, float rescale, float clip) {
+  float gg = g * rescale + wd * w;
+  if (clip > 0.f) gg = fminf(fmaxf(gg, -clip), clip);
+  m = b1 * m + omb1 * gg;
+  v = b2 * v + omb2 * gg * gg;
+  w = w - lr_t * m / (sqrtf(v) + eps);
+}
+
+__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ w, float* __restrict__ mean, float* __restrict__ var,
+                                                   const float* __restrict__ g, float lr_t, float wd, float b1, float omb1, float b2,
+                                                   float omb2, float eps, float rescale, float clip, size_t n) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  float wv = w[i], mv = mean[i], vv = var[i];
+  adam_element(wv, mv, vv, g[i], lr_t, wd, b1, omb1, b2, omb2, eps, rescale, clip);
+  mean[i] = mv;
+  var[i] = vv;
+  w[i] = wv;
+}
+
+// the step count of the optimizer state {uint t, float lr_t, float lr_factor, uint 0}: one thread, in a launch of its own BEFORE the
+// update kernel reads lr_t (advanced inside that kernel, late blocks would read what an early block wrote). A step whose gradients
+// overflowed (amp[2] set) is skipped by the update kernel and does not count here either.
+__global__ void adam_step_kernel(unsigned* __restrict__ opt, double lr, double beta1, double beta2, const unsigned* __restrict__ amp) {
+  if (amp && amp[2]) return;
+  const unsigned t = opt[0] + 1u;
+  const double factor = sqrt(1.0 - pow(beta2, (double)t)) / (1.0 - pow(beta1, (double)t));
+  opt[0] = t;
+  opt[1] = __float_as_uint((float)(lr * factor));
+  opt[2] = __float_as_uint((float)factor);
+}
+
+// every parameter in one launch, the design of sgd_mom_multi_kernel with one more state stream: row r of the table = {w, mean, var,
+// g, n, wd bits | first block << 32, Cin | kh*kw << 32 (0: natural g)}; lr_t from the optimizer state (adam_step_kernel, the launch
+// before); nothing moves while the overflow word of amp (NULL: no loss scaling) is set
+__global__ __launch_bounds__(256) void adam_multi_kernel(const unsigned long long* __restrict__ table, int rows,
+                                                         const unsigned* __restrict__ opt, float b1, float omb1, float b2, float omb2,
+                                                         float eps, float rescale, float clip, const unsigned* __restrict__ amp) {
+  if (amp && amp[2]) return;
+  const float lr_t = __uint_as_float(opt[1]);
+  const unsigned b = blockIdx.x;
+  const int lane = threadIdx.x & 63;
+  int r = -1;
+  for (int base = 0; base < rows; base += 64) {      // rows that start at or before this block, 64 per load + ballot
+    const int idx = base + lane;
+    const bool le = idx < rows && (unsigned)(table[idx * 7 + 5] >> 32) <= b;
+    r += __popcll(__ballot(le));
+  }
+  r = __builtin_amdgcn_readfirstlane(r);
+  const unsigned long long* e = table + r * 7;
+  float* w = reinterpret_cast<float*>(e[0]);
+  float* mean = reinterpret_cast<float*>(e[1]);
+  float* var = reinterpret_cast<float*>(e[2]);
+  const float* g = reinterpret_cast<const float*>(e[3]);
+  const size_t n = e[4];
+  const float wd = __uint_as_float((unsigned)e[5]);
+  // four consecutive parameters per thread (dwordx4 on w / mean / var and on a natural g; all 16-byte aligned)
+  const size_t i0 = ((size_t)(b - (unsigned)(e[5] >> 32)) * 256 + threadIdx.x) * 4;
+  if (i0 >= n) return;
+  const int cin = (int)(unsigned)e[6], khw = (int)(e[6] >> 32);
+  const int cnt = (int)min((size_t)4, n - i0);
+  float wv[4] = {0.f, 0.f, 0.f, 0.f}, mv[4] = {0.f, 0.f, 0.f, 0.f}, vv[4] = {0.f, 0.f, 0.f, 0.f}, gv[4] = {0.f, 0.f, 0.f, 0.f};
+  if (cnt == 4) {
+    const float4 a = *reinterpret_cast<const float4*>(w + i0), c = *reinterpret_cast<const float4*>(mean + i0),
+                 d = *reinterpret_cast<const float4*>(var + i0);
+    wv[0] = a.x; wv[1] = a.y; wv[2] = a.z; wv[3] = a.w;
+    mv[0] = c.x; mv[1] = c.y; mv[2] = c.z; mv[3] = c.w;
+    vv[0] = d.x; vv[1] = d.y; vv[2] = d.z; vv[3] = d.w;
+  } else {
+    for (int j = 0; j < cnt; ++j) { wv[j] = w[i0 + j]; mv[j] = mean[i0 + j]; vv[j] = var[i0 + j]; }
+  }
+  if (cin) {   // the gradient lies tap-major (co, tap, ci): deepim_conv2d_wgrad_tm
+    const int K = cin * khw;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (j >= cnt) break;
+      const size_t i = i0 + j, co = i / K;
+      const int rem = (int)(i - co * K), ci = rem / khw, t = rem - ci * khw;
+      gv[j] = g[co * K + (size_t)t * cin + ci];
+    }
+  } else if (cnt == 4) {
+    const float4 a = *reinterpret_cast<const float4*>(g + i0);
+    gv[0] = a.x; gv[1] = a.y; gv[2] = a.z; gv[3] = a.w;
+  } else {
+    for (int j = 0; j < cnt; ++j) gv[j] = g[i0 + j];
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) adam_element(wv[j], mv[j], vv[j], gv[j], lr_t, wd, b1, omb1, b2, omb2, eps, rescale, clip);
+  if (cnt == 4) {
+    *reinterpret_cast<float4*>(mean + i0) = make_float4(mv[0], mv[1], mv[2], mv[3]);
+    *reinterpret_cast<float4*>(var + i0) = make_float4(vv[0], vv[1], vv[2], vv[3]);
+    *reinterpret_cast<float4*>(w + i0) = make_float4(wv[0], wv[1], wv[2], wv[3]);
+  } else {
+    for (int j = 0; j < cnt; ++j) { mean[i0 + j] = mv[j]; var[i0 + j] = vv[j]; w[i0 + j] = wv[j]; }
+  }
+}
+
 void launch_wgrad_reduce(deepim_ctx* ctx, float* dw, const float* partial, long n, int S) {
   if (S >= 8 && n % 4 == 0)
     hipLaunchKernelGGL(wgrad_reduce4_kernel, dim3(di_div_up(n / 4, 64)), dim3(256), 0, ctx->stream, dw, partial, n / 4, S);
@@ -958,6 +1059,22 @@ extern "C" int deepim_sgd_mom_update_multi_amp(deepim_ctx* ctx, const unsigned l
   if (rows == 0 || total_blocks <= 0) return 0;
   hipLaunchKernelGGL(sgd_mom_multi_kernel, dim3(total_blocks), dim3(256), 0, ctx->stream, table, rows, lr, momentum, rescale, clip,
                      amp_state);
+  DI_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int deepim_adam_update_multi(deepim_ctx* ctx, const unsigned long long* table, int rows, int total_blocks,
+                                        unsigned* opt_state, double lr, double beta1, double beta2, float epsilon, float rescale,
+                                        float clip, const unsigned* amp_state) {
+  DI_DEVICE(ctx);
+  DI_REQUIRE(rows >= 0 && table != nullptr && opt_state != nullptr, "adam_update_multi: no table / no optimizer state");
+  DI_REQUIRE(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0, "adam_update_multi: beta1, beta2 must lie in [0, 1)");
+  // the step counts even with no rows: t is the number of updates applied
+  hipLaunchKernelGGL(adam_step_kernel, dim3(1), dim3(1), 0, ctx->stream, opt_state, lr, beta1, beta2, amp_state);
+  DI_LAUNCH_CHECK();
+  if (rows == 0 || total_blocks <= 0) return 0;
+  hipLaunchKernelGGL(adam_multi_kernel, dim3(total_blocks), dim3(256), 0, ctx->stream, table, rows, (const unsigned*)opt_state,
+                     (float)beta1, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), epsilon, rescale, clip, amp_state);
   DI_LAUNCH_CHECK();
   return 0;
 }
@@ -1310,6 +1427,17 @@ extern "C" int deepim_sgd_mom_update(deepim_ctx* ctx, float* w, float* mom, cons
   if (n == 0) return 0;
   hipLaunchKernelGGL(sgd_mom_kernel, dim3(di_div_up((long)n, 256)), dim3(256), 0, ctx->stream, w, mom, g, lr, wd, momentum,
                      rescale, clip, n);
+  DI_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int deepim_adam_update(deepim_ctx* ctx, float* w, float* mean, float* var, const float* g, float lr_t, float wd,
+                                  double beta1, double beta2, float epsilon, float rescale, float clip, size_t n) {
+  DI_DEVICE(ctx);
+  DI_REQUIRE(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0, "adam_update: beta1, beta2 must lie in [0, 1)");
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(adam_kernel, dim3(di_div_up((long)n, 256)), dim3(256), 0, ctx->stream, w, mean, var, g, lr_t, wd, (float)beta1,
+                     (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), epsilon, rescale, clip, n);
   DI_LAUNCH_CHECK();
   return 0;
 }

@@ -137,6 +137,11 @@ class deepIM_flownet(object):
         self.trans_loss_type = str(t.get("TRANS_LOSS_TYPE", "L2"))
         if self.se3_dist_loss and self.trans_loss_type not in ("L2", "smooth_L1", "L1"):
             raise Exception("Does not support small_cfg.TRANS_LOSS_TYPE: {}".format(self.trans_loss_type))      # :258-259
+        # TRAIN.optimizer (train.py:260-338): "sgd" = MXNet sgd_mom_update, "adam" = MXNet adam_update; update() dispatches on it
+        # (the reference compares the strings exactly and trains nothing on any other value: refuse it)
+        self.optimizer = cfg.TRAIN.get("optimizer", "sgd")
+        if self.optimizer not in ("sgd", "adam"):
+            raise ValueError("TRAIN.optimizer must be 'sgd' or 'adam', got {!r}".format(self.optimizer))
         if getattr(n, "X3_CONV", False):
             # encoder_x3 fills only the split16 activations and no backward reads them
             raise NotImplementedError("training graph runs the fp32 or the fp16 convolutions only (network.X3_CONV unset)")
@@ -869,7 +874,7 @@ def _train_methods():
         self.params["rot_weight"], self.params["trans_weight"] = w7[0:4], w7[4:7]
         self.grad = _Grads(ctx, {name: ctx.zeros(a.shape) for name, a in self.params.items()})
         self._upd_ws = None        # train_step's batch-updater workspace is sized for the bound batch
-        self._sgd_table = None     # its rows hold raw pointers of the buffers allocated here: never reuse one across binds
+        self._sgd_table = self._adam_table = None     # their rows hold raw pointers of the buffers allocated here: never reuse one across binds
         # tap-major weight gradients (deepim_conv2d_wgrad_tm) only where that entry applies: Cin % 8 == 0 and the LDS-staged
         # kernel selected on this context. Everything else (conv1 of the 6- / 10-channel inputs, wgrad_lds = 0) takes
         # deepim_conv2d_wgrad into the natural buffer and the SGD table reads that one (layout word 0).
@@ -886,7 +891,12 @@ def _train_methods():
                 self.grad.tm[gname + "_weight"] = (ctx.zeros((cin, 16, cout)), cin, cout, 16)
         self.grad["rot_weight"], self.grad["trans_weight"] = dw7[0:4], dw7[4:7]
         self.grad["rot_bias"], self.grad["trans_bias"] = db7[0:4], db7[4:7]
-        self.mom = {name: ctx.zeros(a.shape) for name, a in self.params.items()}
+        # optimizer state, zero after every bind: SGD momenta, or Adam's two moments and the device step count (deepim_adam_update_multi)
+        adam = self.optimizer == "adam"
+        self.mom = {} if adam else {name: ctx.zeros(a.shape) for name, a in self.params.items()}
+        self.adam_mean = {name: ctx.zeros(a.shape) for name, a in self.params.items()} if adam else {}
+        self.adam_var = {name: ctx.zeros(a.shape) for name, a in self.params.items()} if adam else {}
+        self.opt_state = ctx.zeros((4,), dtype=np.uint32) if adam else None      # {uint t, float lr_t, float lr_factor, 0}
         A = self.act
         A["rot"], A["rot_norm"] = ctx.empty((B, 4)), ctx.empty((B, 4))
         A["zoom_trans"], A["trans_est"] = ctx.empty((B, 3)), ctx.empty((B, 3))
@@ -1264,16 +1274,13 @@ def _train_methods():
         lib.deepim_stream_wait(h, side)          # every gradient is in place when the main stream goes on (update)
         return G
 
-    def update(self, lr, wd=0.0005, momentum=0.975, rescale_grad=1.0, clip_gradient=None):
-        """The "sgd" optimizer step of train.py:296-303 (MXNet sgd_mom_update) on every parameter, then the re-pack of the
-        conv / deconv / fc6 weights the forward kernels read. As mx.optimizer does when Module hands it the parameter
-        names: weight decay only on `*_weight` (wd_mult 0 elsewhere), and the bilinear upsampling kernels stay fixed
-        (attr lr_mult 0, deepIM_flownet.py:193,333,643,695)."""
-        h = self.ctx.handle
-        c = ctypes.c_float
-        tab = getattr(self, "_sgd_table", None)
+    def _update_table(self, key, wd, states):
+        """The device pointer table of the multi-tensor optimizer kernels, cached per bind and weight decay: rows {w, *states, g, n,
+        wd bits | first block << 32, layout of g} (deepim_sgd_mom_update_multi / deepim_adam_update_multi). As mx.optimizer does when
+        Module hands it the parameter names: weight decay only on `*_weight` (wd_mult 0 elsewhere), and the bilinear upsampling
+        kernels get no row (attr lr_mult 0, deepIM_flownet.py:193,333,643,695). -> (wd, table, rows, blocks)"""
+        tab = getattr(self, key, None)
         if tab is None or tab[0] != float(wd):
-            # one launch for all parameters: rows {w, mom, g, n, wd bits | first block << 32, layout of g} (deepim_sgd_mom_update_multi)
             rows, block = [], 0
             for name, w in self.params.items():
                 if name.endswith("upsampling_weight"):
@@ -1285,22 +1292,44 @@ def _train_methods():
                     g_ptr, layout = raw.ptr, cin_l | (khw << 32)
                 else:
                     g_ptr, layout = dict.__getitem__(self.grad, name).ptr, 0
-                rows.append([w.ptr, self.mom[name].ptr, g_ptr, w.size, wd_bits | (block << 32), layout])
+                rows.append([w.ptr] + [s[name].ptr for s in states] + [g_ptr, w.size, wd_bits | (block << 32), layout])
                 block += (w.size + 1023) // 1024
-            dev = self.ctx.empty((len(rows), 6), np.uint64)
+            dev = self.ctx.empty((len(rows), 5 + len(states)), np.uint64)
             dev.copyfrom(np.array(rows, dtype=np.uint64))
-            tab = self._sgd_table = (float(wd), dev, len(rows), block)
-        if self.fp16_conv or self.train_x3:
-            # scaled gradients: no parameter moves on a step whose gradients overflowed; then the scale step
-            lib.deepim_sgd_mom_update_multi_amp(h, tab[1], tab[2], tab[3], c(lr), c(momentum), c(rescale_grad), c(clip_gradient or 0.0),
-                                                self.amp_state)
-            lib.deepim_amp_scale_update(h, self.amp_state, self.loss_scale_window)
+            tab = (float(wd), dev, len(rows), block)
+            setattr(self, key, tab)
+        return tab
+
+    def update(self, lr, wd=None, momentum=0.975, rescale_grad=1.0, clip_gradient=None, beta1=0.9, beta2=0.999, epsilon=1e-8):
+        """The optimizer step on every parameter, then the re-pack of the conv / deconv / fc6 weights the forward kernels read.
+        TRAIN.optimizer = "sgd": train.py:296-303, MXNet sgd_mom_update; wd defaults to 0.0005; beta1 / beta2 / epsilon are ignored.
+        TRAIN.optimizer = "adam": train.py:260-294, MXNet 1.2 adam_update with the step count on the device (include/deepim_hip.h);
+        wd defaults to 0 (MXNet's default: the reference passes only the learning rate) and `momentum` is ignored. mx.optimizer
+        would fill in rescale_grad = 1 / batch_size for Adam (core/module.py:522-536): pass it, as train_step does. The reference's
+        non-xavier Adam branch (train.py:282-294) passes no optimizer_params at all and so runs at MXNet's default lr 0.01 whatever
+        TRAIN.lr says; this port follows the explicit branch (:261): `lr` is what the caller gives.
+        Weight decay only on `*_weight`, the bilinear upsampling kernels stay fixed (_update_table)."""
+        h = self.ctx.handle
+        c = ctypes.c_float
+        amp = self.amp_state if (self.fp16_conv or self.train_x3) else None
+        if self.optimizer == "adam":
+            tab = self._update_table("_adam_table", 0.0 if wd is None else wd, (self.adam_mean, self.adam_var))
+            # scaled gradients (amp): no parameter, no moment and no step count moves on a step whose gradients overflowed
+            lib.deepim_adam_update_multi(h, tab[1], tab[2], tab[3], self.opt_state, ctypes.c_double(lr), ctypes.c_double(beta1),
+                                         ctypes.c_double(beta2), c(epsilon), c(rescale_grad), c(clip_gradient or 0.0), amp)
+        else:
+            tab = self._update_table("_sgd_table", 0.0005 if wd is None else wd, (self.mom,))
+            if amp is not None:
+                lib.deepim_sgd_mom_update_multi_amp(h, tab[1], tab[2], tab[3], c(lr), c(momentum), c(rescale_grad),
+                                                    c(clip_gradient or 0.0), amp)
+            else:
+                lib.deepim_sgd_mom_update_multi(h, tab[1], tab[2], tab[3], c(lr), c(momentum), c(rescale_grad), c(clip_gradient or 0.0))
+        if amp is not None:
+            lib.deepim_amp_scale_update(h, amp, self.loss_scale_window)      # then the scale step
             if self.fp16_conv:
                 self._repack_f16()
             else:
                 self._repack_x3()
-        else:
-            lib.deepim_sgd_mom_update_multi(h, tab[1], tab[2], tab[3], c(lr), c(momentum), c(rescale_grad), c(clip_gradient or 0.0))
         orders = self._train_pack_orders()
         enc = {g[0] for g in self.enc_geom}
         for name, shape in self.arg_shape_dict().items():
@@ -1371,7 +1400,7 @@ def _train_methods():
 
     def train_step(self, data, label, updater, iters=None, lr=None, wd=None, momentum=None, on_iter=None):
         """ONE training step as the reference runs it (deepim/core/module.py:1131-1137 with network.TRAIN_ITER_SIZE = 4, yaml
-        :57-58): for every refinement iteration forward_backward → preds (rot_est, trans_est) → update (SGD + re-pack), and between
+        :57-58): for every refinement iteration forward_backward → preds (rot_est, trans_est) → update (optimizer step + re-pack), and between
         iterations `interBatchUpdater.forward(data_batch, preds)` (lib/pair_matching/batch_updater_py_multi.py:91-328): pose ←
         RT_transform(src_pose, preds), re-render at it, new rot / trans labels (calc_RT_delta), K·T + lib/flow_c flow labels and
         weights, mask_rendered = depth > 0.2 — all resident, nothing allocated inside the loop, no host round trip.
@@ -1381,8 +1410,12 @@ def _train_methods():
         t = self.cfg.TRAIN
         iters = int(iters or self.cfg.network.TRAIN_ITER_SIZE)
         lr = t.lr if lr is None else lr
-        wd = t.wd if wd is None else wd
+        adam = self.optimizer == "adam"
+        # the optimizer's defaults as the reference reaches them: SGD gets TRAIN.wd / TRAIN.momentum and rescale_grad 1 (train.py:297-303);
+        # Adam gets only the learning rate (:261), so wd = 0 and mx.optimizer's rescale_grad = 1 / batch_size (core/module.py:522-536)
+        wd = (0.0 if adam else t.wd) if wd is None else wd
         momentum = t.momentum if momentum is None else momentum
+        rescale = 1.0 / self.B if adam else 1.0
         if getattr(self, "_upd_ws", None) is None or self._upd_ws[0] is not updater:
             self._upd_ws = (updater, updater.workspace(self.ctx, self.B))
         A = self.act
@@ -1390,7 +1423,7 @@ def _train_methods():
             self.forward_train(data, label)
             self.backward()
             preds = {"rot_est": A["rot_norm"], "trans_est": A["trans_est"]}     # get_outputs() before update(), as :1133-1134
-            self.update(lr, wd, momentum)
+            self.update(lr, wd, momentum, rescale_grad=rescale)
             if on_iter is not None:
                 on_iter(it, data, label)
             if it != iters - 1:
@@ -1400,6 +1433,35 @@ def _train_methods():
                 data = {k: new[k] for k in data}
                 label = {k: new[k] for k in label}
         return data, label
+
+    def optimizer_states(self):
+        """The optimizer's state as host arrays, the resume half of module_checkpoint(..., save_optimizer_states=True) (train.py:242):
+        {"mom:<name>"} for SGD, {"mean:<name>", "var:<name>", "t"} for Adam (t: int64, shape (1,)). mx.nd.save / mx.nd.load carry the
+        dict. MXNet pickles its updater into the .states file, so no file-format parity with the reference is claimed."""
+        if self.optimizer == "adam":
+            out = {"mean:" + k: v.asnumpy() for k, v in self.adam_mean.items()}
+            out.update({"var:" + k: v.asnumpy() for k, v in self.adam_var.items()})
+            out["t"] = np.array([int(self.opt_state.asnumpy()[0])], np.int64)
+            return out
+        return {"mom:" + k: v.asnumpy() for k, v in self.mom.items()}
+
+    def load_optimizer_states(self, states):
+        """Restore what optimizer_states() returned (of the same optimizer and graph) into the bound buffers."""
+        groups = {"mean": self.adam_mean, "var": self.adam_var} if self.optimizer == "adam" else {"mom": self.mom}
+        want = {g + ":" + k for g, d_ in groups.items() for k in d_} | ({"t"} if self.optimizer == "adam" else set())
+        if set(states) != want:
+            raise ValueError("load_optimizer_states: these are not the states of this net's TRAIN.optimizer = {!r} (missing {}, unknown {})"
+                             .format(self.optimizer, sorted(want - set(states))[:3], sorted(set(states) - want)[:3]))
+        for g, d_ in groups.items():
+            for k, buf in d_.items():
+                a = np.asarray(states[g + ":" + k], np.float32)
+                if a.shape != buf.shape:
+                    raise ValueError("load_optimizer_states: {}:{} has shape {}, bound {}".format(g, k, a.shape, buf.shape))
+                buf.copyfrom(a)
+        if self.optimizer == "adam":
+            st = np.zeros(4, np.uint32)       # lr_t / lr_factor are recomputed from t by the next update
+            st[0] = int(np.asarray(states["t"]).ravel()[0])
+            self.opt_state.copyfrom(st)
 
     def _train_pack_orders(self):
         """layer → the ONE packed operand order its forward convolution reads in the training graph (NCHW activations,
@@ -1414,10 +1476,11 @@ def _train_methods():
 
     return dict(bind_train=bind_train, _bind_train_half=_bind_train_half, set_loss_scale=set_loss_scale, loss_scale=loss_scale,
                 _encoder_backward_half=_encoder_backward_half, _repack_f16=_repack_f16, _repack_x3=_repack_x3,
-                forward_train=forward_train, _dgrad=_dgrad,
+                forward_train=forward_train, _dgrad=_dgrad, _update_table=_update_table,
                 _small_conv_backward=_small_conv_backward, _head_conv_backward=_head_conv_backward,
                 _repack_train_winograd=_repack_train_winograd,
                 _deconv_backward=_deconv_backward, _decoder_backward=_decoder_backward, backward=backward, update=update, train_step=train_step,
+                optimizer_states=optimizer_states, load_optimizer_states=load_optimizer_states,
                 _train_pack_orders=_train_pack_orders)
 
 
