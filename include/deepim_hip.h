@@ -900,6 +900,35 @@ int deepim_render_lit_forward(deepim_ctx* ctx, float* image, float* depth, float
                               int tex_h, int tex_w, const float* poses, const float* K_host, const float* pixel_means_host,
                               const float* light_offset_host, const float* light_intensity /*device (B,3) or NULL*/,
                               float brightness_ratio, int V, int F, int B, int H, int W, float znear, float zfar);
+/* The three draws above for a batch whose samples belong to DIFFERENT meshes (BASELINE config 3: all 13 LINEMOD objects in one
+ * batch), in one launch group: sample b draws the mesh of class_index[b]. The class ids live on the device and the host never
+ * reads them, so a captured graph of the draw replays for any later batch's objects. The meshes are one table of plain device
+ * arrays:
+ *   vertices    (ΣV,3)  every mesh's positions, back to back
+ *   vertex_attr         every mesh's own (V,2) uv or (V,3) RGB block, back to back
+ *   normals     (ΣV,3)  or NULL. NULL = the unlit draw (light_offset_host and light_intensity must be NULL too); otherwise the
+ *                       lit draw of deepim_render_lit_forward (light_offset_host required, brightness_ratio in [0, 1])
+ *   faces       (ΣF,3)  int32, indices LOCAL to their mesh
+ *   textures            every textured mesh's (h,w,3) block, back to back; NULL when no mesh is textured
+ *   mesh_desc   (n_classes,8) int32 device, one row per class:
+ *               {v_off, V, f_off, F, attr_off (floats into vertex_attr), tex_off (floats into textures, −1 = vertex colours),
+ *                tex_h, tex_w};  v_off / f_off count vertices / faces
+ *   max_V, max_F        the largest V and F of the table (> 0): grids (ceil(max_V/256), B) and (ceil(max_F/256), B), scratch of
+ *                       B × max_V projected vertices; a row's V / F beyond them is clipped
+ * mask_rendered / mask_box may be NULL as in deepim_render_update_forward (mask_box needs mask_rendered, B <= 4096). The
+ * per-sample arithmetic is that of the single-mesh entries: a sample renders bit-identically whichever entry drew it.
+ * Since the host never sees the ids a bad one cannot be reported: a sample whose id is outside [0, n_classes) is drawn as an
+ * EMPTY FRAME (image = −means, depth = 0, mask_rendered = 0, mask_box = what an empty mask gives: zeros and status bit 2 of
+ * deepim_zoom_status) and no memory outside the table is read. The table's own contents (offsets, face indices) are the
+ * caller's to get right: Render_Py's packer checks them on the host. */
+int deepim_render_classes_forward(deepim_ctx* ctx, float* image, float* depth, float* mask_rendered /*or NULL*/,
+                                  float* mask_box /*or NULL*/, float mask_thresh, const int32_t* class_index /*device (B)*/,
+                                  const int32_t* mesh_desc /*device (n_classes,8)*/, int n_classes, int max_V, int max_F,
+                                  const float* vertices, const float* vertex_attr, const float* normals /*or NULL*/,
+                                  const int32_t* faces, const float* textures /*or NULL*/, const float* poses,
+                                  const float* K_host, const float* pixel_means_host, const float* light_offset_host /*or NULL*/,
+                                  const float* light_intensity /*device (B,3) or NULL*/, float brightness_ratio, int B, int H,
+                                  int W, float znear, float zfar);
 
 #ifdef __cplusplus
 }

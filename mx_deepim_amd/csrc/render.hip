@@ -8,7 +8,8 @@
 // OpenGL's exact rasterisation (sub-pixel snapping, 24-bit depth) cannot run here: PARITY UNPINNED, restated as
 // standard top-left-rule rasterisation; the tests check it against a CPU restatement and an analytic ray cast.
 //
-// Three kernels, all per-pair batched:
+// Three kernels, all per-pair batched, templated on where a sample's mesh comes from (OneMesh: the whole batch draws one
+// mesh; MeshTable: every sample picks its mesh by a device-resident class id). The per-sample arithmetic is one text:
 //   project:  one thread per (pair, vertex): camera transform + projection → (u, v, Z)
 //   raster:   one thread per (pair, triangle): walks the triangle's clipped bounding box, interpolates 1/Z
 //             (affine in screen space, like GL's z) and resolves visibility with ONE 64-bit atomicMin per
@@ -22,14 +23,65 @@ namespace {
 
 struct PV { float u, v, z; };
 
-__global__ __launch_bounds__(256) void project_kernel(PV* __restrict__ pv, const float* __restrict__ verts,
-                                                      const float* __restrict__ poses, Mat3 K, int V,
+// One mesh as the kernels see it. attr: per-vertex attributes — 3 floats RGB (0..255) when tex == nullptr, else 2 floats uv.
+// normals != nullptr selects the lit fragment stage.
+struct MeshRef {
+  const float* verts;    // (V,3) model-space positions
+  const float* attr;
+  const float* normals;  // (V,3) or nullptr
+  const int* faces;      // (F,3), indices local to this mesh
+  const float* tex;      // (TH,TW,3) or nullptr
+  int TH, TW, V, F;
+};
+
+// Mesh source of the single-mesh entries: every sample draws `m`; the projected-vertex scratch is B x V records.
+struct OneMesh {
+  MeshRef m;
+  __device__ __forceinline__ bool mesh(int, MeshRef& o) const { o = m; return true; }
+  __device__ __forceinline__ int pv_stride() const { return m.V; }
+};
+
+// Mesh source of deepim_render_classes_forward: sample b draws the mesh of class_index[b] out of back-to-back arrays described
+// by rows {v_off, V, f_off, F, attr_off, tex_off, tex_h, tex_w} of `desc`. The id and the row depend on blockIdx.y only, so they
+// are scalar loads. An id outside [0, n_classes) — or a textured row in a table without textures — selects no mesh: the sample
+// stays an empty frame and nothing outside the table is read. V and F are clipped to the scratch's max_V / max_F records.
+struct MeshTable {
+  const int* class_index;
+  const int* desc;
+  const float* verts;
+  const float* attr;
+  const float* normals;
+  const int* faces;
+  const float* tex;
+  int n_classes, max_V, max_F;
+  __device__ __forceinline__ bool mesh(int b, MeshRef& o) const {
+    const int cls = class_index[b];
+    if ((unsigned)cls >= (unsigned)n_classes) return false;
+    const int* d = desc + (long)cls * 8;
+    const int v_off = d[0], f_off = d[2], attr_off = d[4], tex_off = d[5];
+    if (tex_off >= 0 && tex == nullptr) return false;
+    o.V = min(d[1], max_V); o.F = min(d[3], max_F);
+    o.verts = verts + (long)v_off * 3;
+    o.normals = normals != nullptr ? normals + (long)v_off * 3 : nullptr;
+    o.faces = faces + (long)f_off * 3;
+    o.attr = attr + attr_off;
+    o.tex = tex_off >= 0 ? tex + tex_off : nullptr;
+    o.TH = d[6]; o.TW = d[7];
+    return true;
+  }
+  __device__ __forceinline__ int pv_stride() const { return max_V; }
+};
+
+template <class Src>
+__global__ __launch_bounds__(256) void project_kernel(PV* __restrict__ pv, Src src, const float* __restrict__ poses, Mat3 K,
                                                       int* __restrict__ box_words) {
   const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
   // arm this sample's bbox accumulator for the resolve pass of THIS call, in stream order (two launches earlier):
   // no state survives between calls, so changing B between calls or replaying a captured graph is safe
   if (box_words != nullptr && i < 4) box_words[b * 4 + i] = (i & 1) ? -1 : INT_MAX;
-  if (i >= V) return;
+  MeshRef m;
+  if (!src.mesh(b, m) || i >= m.V) return;
+  const float* __restrict__ verts = m.verts;
   const float* P = poses + b * 12;
   const float x = verts[i * 3], y = verts[i * 3 + 1], z = verts[i * 3 + 2];
   const float X = ((P[0] * x + P[1] * y) + P[2] * z) + P[3];
@@ -39,7 +91,7 @@ __global__ __launch_bounds__(256) void project_kernel(PV* __restrict__ pv, const
   o.u = K.v[0] * X / Z + K.v[2];
   o.v = K.v[4] * Y / Z + K.v[5];
   o.z = Z;
-  pv[(long)b * V + i] = o;
+  pv[(long)b * src.pv_stride() + i] = o;
 }
 
 // edge function of pixel (px,py) against edge a→b; > 0 on the interior side for the orientation used below
@@ -82,13 +134,14 @@ __device__ __forceinline__ float pixel_depth(const Tri& t, float w0, float w1, f
   return 1.0f / inv;
 }
 
+template <class Src>
 __global__ __launch_bounds__(256) void raster_kernel(unsigned long long* __restrict__ zbuf, const PV* __restrict__ pv_all,
-                                                     const int* __restrict__ faces, int V, int F, int H, int W,
-                                                     float znear, float zfar) {
+                                                     Src src, int H, int W, float znear, float zfar) {
   const int b = blockIdx.y, f = blockIdx.x * 256 + threadIdx.x;
-  if (f >= F) return;
+  MeshRef m;
+  if (!src.mesh(b, m) || f >= m.F) return;
   int ia, ib, ic;
-  const Tri t = load_tri(pv_all + (long)b * V, faces, f, znear, ia, ib, ic);
+  const Tri t = load_tri(pv_all + (long)b * src.pv_stride(), m.faces, f, znear, ia, ib, ic);
   if (!t.ok) return;
   const float minx = fminf(t.ax, fminf(t.bx, t.cx)), maxx = fmaxf(t.ax, fmaxf(t.bx, t.cx));
   const float miny = fminf(t.ay, fminf(t.by, t.cy)), maxy = fmaxf(t.ay, fmaxf(t.by, t.cy));
@@ -125,23 +178,20 @@ __device__ __forceinline__ float tex_bilinear(const float* __restrict__ tex, int
 //   position = u_view·u_model·v_position,  normal = (u_view·u_model)^-T·(v_normal, 1) — whose 4-vector normalisation cancels in
 //   the next line —  brightness = clamp(n·(L − position) / (|L − position|·|n|), 0, 1),
 //   colour = texture·((1 − r) + r·brightness)·intensity, read back as round(clamp(colour, 0, 1)·255) (:162-166: uint8).
-// L = light_offset + (t_x, −t_y, −t_z) of the sample's pose. verts == nullptr: the unlit stage of render_py_multi.py.
+// L = light_offset + (t_x, −t_y, −t_z) of the sample's pose. v_position / v_normal are the mesh's verts / normals; a mesh without
+// normals takes the unlit stage of render_py_multi.py.
 struct LitParams {
-  const float* verts;      // (V,3) model-space positions (v_position)
-  const float* normals;    // (V,3) per-vertex normals (v_normal)
   const float* poses;      // (B,3,4)
   const float* intensity;  // (B,3) device, or nullptr = (1,1,1)
   Vec3 light_offset;       // 0.5·(0,1,1) in the reference's loops
   float ratio;             // brightness_ratio (0.7)
 };
 
-// attr: per-vertex attributes — 3 floats RGB (0..255) when tex == nullptr, else 2 floats uv
+template <class Src>
 __global__ __launch_bounds__(256) void resolve_kernel(float* __restrict__ image, float* __restrict__ depth,
                                                       unsigned long long* __restrict__ zbuf,
-                                                      const PV* __restrict__ pv_all, const int* __restrict__ faces,
-                                                      const float* __restrict__ attr, const float* __restrict__ tex,
-                                                      int TH, int TW, Vec3 means, int V, int H, int W, float znear,
-                                                      float* __restrict__ mask, float mask_thresh,
+                                                      const PV* __restrict__ pv_all, Src src, Vec3 means, int H, int W,
+                                                      float znear, float* __restrict__ mask, float mask_thresh,
                                                       int* __restrict__ box_words, LitParams lit) {
   const int b = blockIdx.y;
   const long p = (long)blockIdx.x * 256 + threadIdx.x;
@@ -151,11 +201,14 @@ __global__ __launch_bounds__(256) void resolve_kernel(float* __restrict__ image,
   if (inside && key != ~0ull) zbuf[(long)b * plane + p] = ~0ull;      // the z-buffer leaves the call as it entered it: all-ones
   float rgb[3] = {0.f, 0.f, 0.f};
   float z = 0.f;
-  if (key != ~0ull) {
+  MeshRef m;
+  if (key != ~0ull && src.mesh(b, m)) {      // only a sample with a mesh ever rasterised a key
+    const float* __restrict__ attr = m.attr;
+    const float* __restrict__ tex = m.tex;
     const int f = (int)(unsigned)(key & 0xffffffffu);
     z = __uint_as_float((unsigned)(key >> 32));
     int ia, ib, ic;
-    const Tri t = load_tri(pv_all + (long)b * V, faces, f, znear, ia, ib, ic);
+    const Tri t = load_tri(pv_all + (long)b * src.pv_stride(), m.faces, f, znear, ia, ib, ic);
     const int y = (int)(p / W), x = (int)(p - (long)y * W);
     float w0, w1, w2;
     cover(t, (float)x, (float)y, w0, w1, w2);
@@ -170,15 +223,15 @@ __global__ __launch_bounds__(256) void resolve_kernel(float* __restrict__ image,
       const float u = ((q0 * attr[ia * 2] + q1 * attr[ib * 2]) + q2 * attr[ic * 2]) / qs;
       const float v = ((q0 * attr[ia * 2 + 1] + q1 * attr[ib * 2 + 1]) + q2 * attr[ic * 2 + 1]) / qs;
 #pragma unroll
-      for (int c = 0; c < 3; ++c) rgb[c] = tex_bilinear(tex, TH, TW, c, u, v);
+      for (int c = 0; c < 3; ++c) rgb[c] = tex_bilinear(tex, m.TH, m.TW, c, u, v);
     }
-    if (lit.verts != nullptr) {
+    if (m.normals != nullptr) {
       const float* P = lit.poses + b * 12;
       float mp[3], mn[3];      // perspective-correct model-space position and normal of the fragment (GL varyings)
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
-        mp[c] = ((q0 * lit.verts[ia * 3 + c] + q1 * lit.verts[ib * 3 + c]) + q2 * lit.verts[ic * 3 + c]) / qs;
-        mn[c] = ((q0 * lit.normals[ia * 3 + c] + q1 * lit.normals[ib * 3 + c]) + q2 * lit.normals[ic * 3 + c]) / qs;
+        mp[c] = ((q0 * m.verts[ia * 3 + c] + q1 * m.verts[ib * 3 + c]) + q2 * m.verts[ic * 3 + c]) / qs;
+        mn[c] = ((q0 * m.normals[ia * 3 + c] + q1 * m.normals[ib * 3 + c]) + q2 * m.normals[ic * 3 + c]) / qs;
       }
       float pos[3], nrm[3], s2l[3];
 #pragma unroll
@@ -231,17 +284,17 @@ __global__ __launch_bounds__(256) void resolve_kernel(float* __restrict__ image,
 
 }  // namespace
 
-static int render_impl(deepim_ctx* ctx, float* image, float* depth, float* mask, float* mask_box, float mask_thresh,
-                       const float* vertices, const float* vertex_attr, const int32_t* faces, const float* texture,
-                       int tex_h, int tex_w, const float* poses, const float* K_host, const float* pixel_means_host,
-                       int V, int F, int B, int H, int W, float znear, float zfar, const float* normals = nullptr,
-                       const float* light_offset_host = nullptr, const float* light_intensity = nullptr, float ratio = 0.f) {
-  if (B == 0) return 0;
-  DI_REQUIRE(V > 0 && F > 0 && H > 0 && W > 0, "render: empty mesh or image");
+// The launch group of every entry: project (grid (ceil(max_V/256), B)), raster (grid (ceil(max_F/256), B)), resolve, box fill.
+// max_V / max_F: the largest mesh `src` can select; the projected-vertex scratch is B x max_V records.
+template <class Src>
+static int render_launch(deepim_ctx* ctx, float* image, float* depth, float* mask, float* mask_box, float mask_thresh,
+                         const Src& src, int max_V, int max_F, const float* poses, const float* K_host,
+                         const float* pixel_means_host, int B, int H, int W, float znear, float zfar,
+                         const float* light_offset_host, const float* light_intensity, float ratio) {
   DI_REQUIRE(znear > 0.f && zfar > znear, "render: need 0 < zNear < zFar");
   DI_REQUIRE(mask_box == nullptr || (mask != nullptr && B <= DI_MAX_BOX_SAMPLES), "render: mask_box needs mask, B <= 4096");
   const size_t zbytes = (size_t)B * H * W * sizeof(unsigned long long);
-  const size_t pbytes = (size_t)B * V * sizeof(PV);
+  const size_t pbytes = (size_t)B * max_V * sizeof(PV);
   void* scratch;
   int rc = deepim_scratch(ctx, pbytes + 64, &scratch);
   if (rc) return rc;
@@ -268,24 +321,31 @@ static int render_impl(deepim_ctx* ctx, float* image, float* depth, float* mask,
   Vec3 means = {{0, 0, 0}};
   if (pixel_means_host) for (int i = 0; i < 3; ++i) means.v[i] = pixel_means_host[i];
   int* words = mask_box ? ctx->box_words : nullptr;
-  LitParams lit = {nullptr, nullptr, poses, light_intensity, {{0, 0, 0}}, ratio};
-  if (normals != nullptr) {
-    lit.verts = vertices; lit.normals = normals;
-    if (light_offset_host) for (int i = 0; i < 3; ++i) lit.light_offset.v[i] = light_offset_host[i];
-  }
-  hipLaunchKernelGGL(project_kernel, dim3(di_div_up(V, 256), B), dim3(256), 0, ctx->stream, pv, vertices, poses, K, V,
-                     words);
+  LitParams lit = {poses, light_intensity, {{0, 0, 0}}, ratio};
+  if (light_offset_host) for (int i = 0; i < 3; ++i) lit.light_offset.v[i] = light_offset_host[i];
+  hipLaunchKernelGGL(project_kernel<Src>, dim3(di_div_up(max_V, 256), B), dim3(256), 0, ctx->stream, pv, src, poses, K, words);
   DI_LAUNCH_CHECK();
   ctx->zbuf_dirty = 1;
-  hipLaunchKernelGGL(raster_kernel, dim3(di_div_up(F, 256), B), dim3(256), 0, ctx->stream, zbuf, pv, (const int*)faces, V,
-                     F, H, W, znear, zfar);
-  hipLaunchKernelGGL(resolve_kernel, dim3(di_div_up((long)H * W, 256), B), dim3(256), 0, ctx->stream, image, depth, zbuf,
-                     pv, (const int*)faces, vertex_attr, texture, tex_h, tex_w, means, V, H, W, znear, mask, mask_thresh,
-                     words, lit);
+  hipLaunchKernelGGL(raster_kernel<Src>, dim3(di_div_up(max_F, 256), B), dim3(256), 0, ctx->stream, zbuf, pv, src, H, W, znear,
+                     zfar);
+  hipLaunchKernelGGL(resolve_kernel<Src>, dim3(di_div_up((long)H * W, 256), B), dim3(256), 0, ctx->stream, image, depth, zbuf,
+                     pv, src, means, H, W, znear, mask, mask_thresh, words, lit);
   DI_LAUNCH_CHECK();
   ctx->zbuf_dirty = 0;        // the resolve pass is queued behind the raster pass: the buffer will be all-ones again
   if (mask_box) return deepim_mask_box_fill(ctx, mask_box, words, B, H, W);
   return 0;
+}
+
+static int render_impl(deepim_ctx* ctx, float* image, float* depth, float* mask, float* mask_box, float mask_thresh,
+                       const float* vertices, const float* vertex_attr, const int32_t* faces, const float* texture,
+                       int tex_h, int tex_w, const float* poses, const float* K_host, const float* pixel_means_host,
+                       int V, int F, int B, int H, int W, float znear, float zfar, const float* normals = nullptr,
+                       const float* light_offset_host = nullptr, const float* light_intensity = nullptr, float ratio = 0.f) {
+  if (B == 0) return 0;
+  DI_REQUIRE(V > 0 && F > 0 && H > 0 && W > 0, "render: empty mesh or image");
+  const OneMesh src = {{vertices, vertex_attr, normals, (const int*)faces, texture, tex_h, tex_w, V, F}};
+  return render_launch(ctx, image, depth, mask, mask_box, mask_thresh, src, V, F, poses, K_host, pixel_means_host, B, H, W, znear,
+                       zfar, normals != nullptr ? light_offset_host : nullptr, light_intensity, ratio);
 }
 
 extern "C" int deepim_render_forward(deepim_ctx* ctx, float* image, float* depth, const float* vertices,
@@ -325,4 +385,31 @@ extern "C" int deepim_render_lit_forward(deepim_ctx* ctx, float* image, float* d
   return render_impl(ctx, image, depth, mask_rendered, mask_box, mask_thresh, vertices, vertex_attr, faces, texture, tex_h, tex_w,
                      poses, K_host, pixel_means_host, V, F, B, H, W, znear, zfar, normals, light_offset_host, light_intensity,
                      brightness_ratio);
+}
+
+// One launch group for a batch whose samples belong to different meshes: sample b draws class class_index[b] of the mesh table
+// (layout: include/deepim_hip.h). normals == NULL: the unlit draw; else the lit one. The host never sees the ids.
+extern "C" int deepim_render_classes_forward(deepim_ctx* ctx, float* image, float* depth, float* mask_rendered, float* mask_box,
+                                             float mask_thresh, const int32_t* class_index, const int32_t* mesh_desc,
+                                             int n_classes, int max_V, int max_F, const float* vertices,
+                                             const float* vertex_attr, const float* normals, const int32_t* faces,
+                                             const float* textures, const float* poses, const float* K_host,
+                                             const float* pixel_means_host, const float* light_offset_host,
+                                             const float* light_intensity, float brightness_ratio, int B, int H, int W,
+                                             float znear, float zfar) {
+  DI_DEVICE(ctx);
+  if (B == 0) return 0;
+  DI_REQUIRE(n_classes > 0 && max_V > 0 && max_F > 0 && H > 0 && W > 0, "render_classes: empty mesh table or image");
+  DI_REQUIRE(class_index != nullptr && mesh_desc != nullptr, "render_classes: class_index and mesh_desc are required");
+  DI_REQUIRE(mask_box == nullptr || mask_rendered != nullptr, "render_classes: mask_box needs mask_rendered");
+  if (normals != nullptr) {
+    DI_REQUIRE(light_offset_host != nullptr, "render_classes: the lit draw needs the light offset");
+    DI_REQUIRE(brightness_ratio >= 0.f && brightness_ratio <= 1.f, "render_classes: brightness_ratio in [0, 1]");
+  } else {
+    DI_REQUIRE(light_offset_host == nullptr && light_intensity == nullptr, "render_classes: the lit draw needs normals");
+  }
+  const MeshTable src = {(const int*)class_index, (const int*)mesh_desc, vertices, vertex_attr, normals, (const int*)faces,
+                         textures, n_classes, max_V, max_F};
+  return render_launch(ctx, image, depth, mask_rendered, mask_box, mask_thresh, src, max_V, max_F, poses, K_host,
+                       pixel_means_host, B, H, W, znear, zfar, light_offset_host, light_intensity, brightness_ratio);
 }

@@ -16,6 +16,7 @@ import numpy as np
 
 from ...config import ROT_COORD_CODE
 from ...runtime import lib
+from ..render_glumpy.render_py_multi import is_device_ids
 
 
 class batchUpdaterPyMulti(object):
@@ -48,6 +49,8 @@ class batchUpdaterPyMulti(object):
     def forward(self, data_batch, preds, big_cfg=None, out=None):
         """data_batch: dict name -> DeviceArray with src_pose, tgt_pose (B,3,4) [, depth_gt_observed (B,1,H,W),
         class_index]; preds: dict with rot_est (B,4), trans_est (B,3) (or se3 (B,7)). Returns the updated batch.
+        class_index goes to the render machine as it is: host ids are drawn per run of equal ids, a device int32 array of B ids
+        in one launch group for the whole batch without a read-back (Render_Py.render_batch).
         `out`: a `workspace()` whose buffers receive the results instead of fresh allocations."""
         cfg = big_cfg or self.big_cfg
         src_pose, tgt_pose = data_batch["src_pose"], data_batch["tgt_pose"]
@@ -118,7 +121,9 @@ def update_test_batch(cfg, data, render_machine, refined_pose, class_index=None,
     depth > 0.2, and (TEST.UPDATE_MASK == "box_rendered") mask_observed = rectangle of the new rendered mask. All on the
     device; `out` may carry preallocated image_rendered / depth_rendered / mask_rendered / mask_observed arrays.
     With the lit ModelNet render machine (tester.py:114-172) `light_intensity` = device (B,3) per-sample light colour (the
-    reference draws U(0.9, 1.1) per render; None = 1.0)."""
+    reference draws U(0.9, 1.1) per render; None = 1.0).
+    `class_index`: None, a scalar or a host sequence of B ids (one launch group per run of equal ids), or a device int32 array
+    of B ids (one launch group for the whole batch, no read-back)."""
     ctx = refined_pose.context
     B, H, W = refined_pose.shape[0], render_machine.height, render_machine.width
     out = out or {}
@@ -135,7 +140,13 @@ def update_test_batch(cfg, data, render_machine, refined_pose, class_index=None,
                 box = out.get("mask_observed") or ctx.empty((B, 1, H, W))
             elif cfg.TEST.UPDATE_MASK != "init":
                 raise Exception("Unknown UPDATE_MASK type: {}".format(cfg.TEST.UPDATE_MASK))
-    # one fused pass per run of equal class ids: draw, mask_rendered = depth > 0.2, rectangle
+    if is_device_ids(class_index) and class_index.size == B:
+        # class ids resident on the device: ONE fused pass (draw, mask_rendered = depth > 0.2, rectangle) over the whole mixed
+        # batch; the host never reads the ids, so a captured graph of the iteration replays for any batch's objects
+        render_machine.render_classes_into(image, depth, class_index, refined_pose, mask_rendered=mask, mask_box=box,
+                                           mask_thresh=0.2, light_intensity=light_intensity)
+        return _updated(cfg, new, image, depth, mask, box, refined_pose)
+    # host ids: one fused pass per run of equal class ids
     ids = np.zeros(B, np.int64) if class_index is None else np.broadcast_to(
         np.asarray(class_index).astype(np.int64).reshape(-1), (B,)) if np.size(class_index) == 1 else \
         np.asarray(class_index).astype(np.int64).reshape(B)
@@ -149,6 +160,10 @@ def update_test_batch(cfg, data, render_machine, refined_pose, class_index=None,
                                    mask_box=None if box is None else box[b0:b1], mask_thresh=0.2,
                                    light_intensity=None if light_intensity is None else light_intensity[b0:b1])
         b0 = b1
+    return _updated(cfg, new, image, depth, mask, box, refined_pose)
+
+
+def _updated(cfg, new, image, depth, mask, box, refined_pose):
     new["image_rendered"], new["src_pose"] = image, refined_pose
     if cfg.network.INPUT_DEPTH:
         new["depth_rendered"] = depth

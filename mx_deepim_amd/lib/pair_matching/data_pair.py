@@ -80,7 +80,8 @@ def get_data_pair_train_batch(batch, config):
         image_observed, image_rendered (B,3,H,W); depth_gt_observed, depth_rendered (B,1,H,W) in metres;
         pose_rendered, pose_observed (B,3,4); mask_gt_observed (B,1,H,W) [INPUT_MASK / PRED_MASK];
         depth_observed (B,1,H,W) [INPUT_DEPTH]; point_cloud_model, point_cloud_weights (B,3,N) [SE3_PM_LOSS];
-        class_index (host).
+        class_index: handed over as given — host ids, or a device int32 array (B) that the render machine draws in one launch
+        group without reading it back.
     Returns {"data": {...}, "label": {...}} with the reference's keys."""
     n, c = config.network, config
     data = {"image_observed": batch["image_observed"], "image_rendered": batch["image_rendered"],

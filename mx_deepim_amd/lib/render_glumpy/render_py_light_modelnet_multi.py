@@ -69,6 +69,7 @@ class Render_Py_Light_ModelNet_Multi(Render_Py):
         self.ctx = ctx or Context.default()
         self.pixel_means = None if pixel_means is None else np.ascontiguousarray(pixel_means, np.float32).reshape(3)
         self.mesh_list, self.normal_list = [], []
+        self._table = None
         texture = None if meshes is not None else load_texture(texture_path)
         for i, path in enumerate(self.model_path_list):
             if meshes is not None:
@@ -82,6 +83,9 @@ class Render_Py_Light_ModelNet_Multi(Render_Py):
             if len(normals) != self.mesh_list[-1].V:
                 raise ValueError("one normal per vertex")
             self.normal_list.append(self.ctx.array(normals))
+            self.mesh_list[-1].host["normals"] = normals
+
+    _lit = True          # the mesh table of render_classes_into carries the normals (mesh.host["normals"])
 
     # -- device API ----------------------------------------------------------------------------------------------
     def render_into(self, image, depth, cls_idx, poses, K=None, pixel_means="default", mask_rendered=None, mask_box=None,
@@ -96,6 +100,14 @@ class Render_Py_Light_ModelNet_Multi(Render_Py):
                                       m.attr, nrm, m.faces, m.texture, m.tex_h, m.tex_w, poses, K, means, off, light_intensity,
                                       ctypes.c_float(self.brightness_ratios[brightness_k]), m.V, m.F, poses.shape[0], self.height,
                                       self.width, ctypes.c_float(self.zNear), ctypes.c_float(self.zFar))
+
+    def render_classes_into(self, image, depth, class_index, poses, K=None, pixel_means="default", mask_rendered=None,
+                            mask_box=None, mask_thresh=0.2, light_offset=None, light_intensity=None, brightness_k=0):
+        """As `render_into`, lit, for a batch of mixed models: `class_index` (n) is a DEVICE int32 array, sample b draws model
+        class_index[b]; one launch group, the ids never read on the host (Render_Py.render_classes_into)."""
+        off = np.ascontiguousarray(LIGHT_OFFSET if light_offset is None else light_offset, np.float32).reshape(3)
+        self._draw_classes(image, depth, class_index, poses, K, pixel_means, mask_rendered, mask_box, mask_thresh,
+                           light_offset=off, light_intensity=light_intensity, ratio=self.brightness_ratios[brightness_k])
 
     # -- reference API -------------------------------------------------------------------------------------------
     def render(self, model_idx, r, t, light_position, light_intensity, brightness_k=0, r_type="quat"):

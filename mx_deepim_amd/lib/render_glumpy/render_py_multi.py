@@ -4,6 +4,7 @@ drawn by the HIP rasteriser (csrc/render.hip, `deepim_render_forward`) instead o
     render_machine = Render_Py(model_dir, classes, K, width, height, zNear, zFar)
     bgr, depth = render_machine.render(cls_idx, quat_or_mat, t)          # reference call (:101), host arrays
     image, depth = render_machine.render_batch(class_index, poses)       # device tensors for the batch updater
+    render_machine.render_classes_into(image, depth, class_index_dev, poses)   # mixed-class batch, ids on the device
 
 `render` returns what the reference returns (:121-129): (H,W,3) float32 BGR on the 0..255 scale and (H,W)
 metric depth with 0 background. `render_batch` skips that host round trip: it writes the network-input tensors
@@ -12,6 +13,9 @@ metric depth with 0 background. `render_batch` skips that host round trip: it wr
 Meshes come from `<model_dir>/<class>/textured.obj` + `texture_map.png` like the reference (:68-77), or from
 memory through `meshes={class: dict(vertices, faces, uv, texture | colors)}` (what the tests and bench use:
 there are no model files offline).
+
+A batch whose samples belong to different classes is one launch group when its class ids are a device int32 array
+(`deepim_render_classes_forward` over the mesh table `pack_mesh_table` builds): the host never reads the ids.
 """
 import ctypes
 import os
@@ -71,6 +75,78 @@ def load_texture(path):
     return np.ascontiguousarray(img[::-1])
 
 
+DESC_FIELDS = ("v_off", "V", "f_off", "F", "attr_off", "tex_off", "tex_h", "tex_w")
+
+
+def pack_mesh_table(meshes, with_normals=False):
+    """Host packer of the mesh table of `deepim_render_classes_forward` (layout: include/deepim_hip.h). `meshes`: one
+    dict(vertices, faces, uv + texture | colors [, normals]) per class, in class-id order. Returns a dict of numpy arrays:
+    vertices (ΣV,3), vertex_attr (flat: each mesh's own (V,2) uv or (V,3) colour block back to back), normals (ΣV,3) or None,
+    faces (ΣF,3) int32 with indices local to their mesh, textures (flat: each textured mesh's (h,w,3) block) or None,
+    mesh_desc (n,8) int32 rows of DESC_FIELDS (offsets of attr / tex in floats, tex_off −1 = vertex colours), max_V, max_F.
+    The device trusts this table, so everything it indexes with is checked here."""
+    if len(meshes) == 0:
+        raise ValueError("mesh table needs at least one mesh")
+    verts, attrs, nrms, faces, texs, desc = [], [], [], [], [], []
+    v_off = f_off = attr_off = tex_off = 0
+    for m in meshes:
+        v = np.ascontiguousarray(m["vertices"], dtype=np.float32).reshape(-1, 3)
+        f = np.ascontiguousarray(m["faces"], dtype=np.int32).reshape(-1, 3)
+        V, F = len(v), len(f)
+        if V == 0 or F == 0:
+            raise ValueError("empty mesh")
+        if f.min() < 0 or f.max() >= V:
+            raise ValueError("face index out of range")
+        texture = m.get("texture")
+        if texture is not None:
+            texture = np.ascontiguousarray(texture, dtype=np.float32)
+            if m.get("uv") is None or texture.ndim != 3 or texture.shape[2] != 3 or texture.size == 0:
+                raise ValueError("textured mesh needs uv (V,2) and texture (h,w,3)")
+            a = np.ascontiguousarray(m["uv"], dtype=np.float32).reshape(V, 2)
+            row_tex = (tex_off, texture.shape[0], texture.shape[1])
+            texs.append(texture.reshape(-1))
+            tex_off += texture.size
+        else:
+            if m.get("colors") is None:
+                raise ValueError("mesh needs a texture or per-vertex colors")
+            a = np.ascontiguousarray(m["colors"], dtype=np.float32).reshape(V, 3)
+            row_tex = (-1, 0, 0)
+        if with_normals:
+            n = np.ascontiguousarray(m["normals"], dtype=np.float32).reshape(-1, 3)
+            if len(n) != V:
+                raise ValueError("one normal per vertex")
+            nrms.append(n)
+        desc.append((v_off, V, f_off, F, attr_off) + row_tex)
+        verts.append(v)
+        faces.append(f)
+        attrs.append(a.reshape(-1))
+        v_off, f_off, attr_off = v_off + V, f_off + F, attr_off + a.size
+    if max(3 * v_off, 3 * f_off, attr_off, tex_off) >= 2 ** 31:
+        raise ValueError("mesh table too large for int32 offsets")
+    desc = np.asarray(desc, dtype=np.int32).reshape(-1, 8)
+    return {"vertices": np.concatenate(verts), "vertex_attr": np.concatenate(attrs),
+            "normals": np.concatenate(nrms) if with_normals else None, "faces": np.concatenate(faces),
+            "textures": np.concatenate(texs) if texs else None, "mesh_desc": desc,
+            "max_V": int(desc[:, 1].max()), "max_F": int(desc[:, 3].max())}
+
+
+class _MeshTable(object):
+    """The packed table on the device, uploaded once."""
+
+    def __init__(self, ctx, host):
+        self.n_classes, self.max_V, self.max_F = len(host["mesh_desc"]), host["max_V"], host["max_F"]
+        self.vertices, self.vertex_attr = ctx.array(host["vertices"]), ctx.array(host["vertex_attr"])
+        self.normals = None if host["normals"] is None else ctx.array(host["normals"])
+        self.faces = ctx.array(host["faces"], dtype=np.int32)
+        self.textures = None if host["textures"] is None else ctx.array(host["textures"])
+        self.mesh_desc = ctx.array(host["mesh_desc"], dtype=np.int32)
+
+
+def is_device_ids(class_index):
+    """True for what takes the one-launch-group path: a device array of dtype int32."""
+    return hasattr(class_index, "asnumpy") and hasattr(class_index, "ptr") and class_index.dtype == np.int32
+
+
 class _Mesh(object):
     def __init__(self, ctx, vertices, faces, uv=None, texture=None, colors=None):
         vertices = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
@@ -78,6 +154,7 @@ class _Mesh(object):
         if faces.size and (faces.min() < 0 or faces.max() >= len(vertices)):
             raise ValueError("face index out of range")
         self.V, self.F = len(vertices), len(faces)
+        self.host = dict(vertices=vertices, faces=faces, uv=uv, texture=texture, colors=colors)    # what pack_mesh_table reads
         self.vertices = ctx.array(vertices)
         self.faces = ctx.array(faces, dtype=np.int32)
         if texture is not None:
@@ -103,6 +180,7 @@ class Render_Py(object):
         # tensor-channel order (RGB): the updater subtracts PIXEL_MEANS[[2,1,0]] (batch_updater_py_multi.py:124-127)
         self.pixel_means = None if pixel_means is None else np.ascontiguousarray(pixel_means, np.float32).reshape(3)
         self.mesh_list = []
+        self._table = None
         for cls in self.classes:
             if meshes is not None and cls in meshes:
                 self.mesh_list.append(_Mesh(self.ctx, **meshes[cls]))
@@ -132,13 +210,49 @@ class Render_Py(object):
             lib.deepim_render_update_forward(self.ctx.handle, image, depth, mask_rendered, mask_box,
                                              ctypes.c_float(mask_thresh), *tail)
 
+    _lit = False         # the lit machine's mesh table carries the normals
+
+    def mesh_table(self):
+        """The device mesh table of `render_classes_into`: packed and uploaded once per render machine, on first use."""
+        if self._table is None:
+            self._table = _MeshTable(self.ctx, pack_mesh_table([m.host for m in self.mesh_list], with_normals=self._lit))
+        return self._table
+
+    def _draw_classes(self, image, depth, class_index, poses, K, pixel_means, mask_rendered, mask_box, mask_thresh,
+                      light_offset=None, light_intensity=None, ratio=0.0):
+        if not is_device_ids(class_index):
+            raise TypeError("render_classes_into needs class_index as a device int32 array")
+        if mask_rendered is None and mask_box is not None:
+            raise ValueError("mask_box needs mask_rendered")
+        t = self.mesh_table()
+        K = self.K if K is None else np.ascontiguousarray(K, dtype=np.float32).reshape(3, 3)
+        means = self.pixel_means if isinstance(pixel_means, str) else pixel_means
+        lib.deepim_render_classes_forward(self.ctx.handle, image, depth, mask_rendered, mask_box, ctypes.c_float(mask_thresh),
+                                          class_index, t.mesh_desc, t.n_classes, t.max_V, t.max_F, t.vertices, t.vertex_attr,
+                                          t.normals, t.faces, t.textures, poses, K, means, light_offset, light_intensity,
+                                          ctypes.c_float(ratio), poses.shape[0], self.height, self.width,
+                                          ctypes.c_float(self.zNear), ctypes.c_float(self.zFar))
+
+    def render_classes_into(self, image, depth, class_index, poses, K=None, pixel_means="default", mask_rendered=None,
+                            mask_box=None, mask_thresh=0.2, light_intensity=None):
+        """As `render_into` for a batch of mixed classes: `class_index` (n) is a DEVICE int32 array and sample b draws mesh
+        class_index[b], all in one launch group. The ids are never read on the host; a sample whose id is outside
+        [0, len(classes)) comes out as an empty frame (see include/deepim_hip.h). (`light_intensity`: ignored, as in `render_into`.)"""
+        self._draw_classes(image, depth, class_index, poses, K, pixel_means, mask_rendered, mask_box, mask_thresh)
+
     def render_batch(self, class_index, poses, K=None, out=None, mask_rendered=None, mask_thresh=0.2, light_intensity=None):
-        """poses (B,3,4) device; class_index: scalar, host sequence of B class ids, or None (= class 0).
-        Samples of the same class in consecutive runs are drawn by one launch group. `out` = (image, depth) preallocated device
-        tensors; `mask_rendered` (B,1,H,W): also written, = depth > mask_thresh, by the same pass."""
+        """poses (B,3,4) device; class_index: scalar, host sequence of B class ids, None (= class 0), or a device array.
+        Host ids: samples of the same class in consecutive runs are drawn by one launch group each. A DEVICE int32 array of B ids:
+        the whole batch is one launch group (`render_classes_into`) and the ids are never read back. (A device array of another
+        dtype is read back and split into runs like host ids.) `out` = (image, depth) preallocated device tensors;
+        `mask_rendered` (B,1,H,W): also written, = depth > mask_thresh, by the same pass."""
         B = poses.shape[0]
         image, depth = out if out is not None else (self.ctx.empty((B, 3, self.height, self.width)),
                                                     self.ctx.empty((B, 1, self.height, self.width)))
+        if is_device_ids(class_index) and class_index.size == B:
+            self.render_classes_into(image, depth, class_index, poses, K=K, mask_rendered=mask_rendered, mask_thresh=mask_thresh,
+                                     light_intensity=light_intensity)
+            return image, depth
         if class_index is None:
             ids = np.zeros(B, np.int64)
         else:
