@@ -930,6 +930,39 @@ int deepim_render_classes_forward(deepim_ctx* ctx, float* image, float* depth, f
                                   const float* light_intensity /*device (B,3) or NULL*/, float brightness_ratio, int B, int H,
                                   int W, float znear, float zfar);
 
+/* ------------------------------------------- I-group: ingest of decoded frames -- */
+/* csrc/ingest.hip. What lib/utils/image.py does on the host between cv2.imread and the tensors of a batch, on frames that
+ * are already on the device as the camera / decoder left them (uint8 / uint16): 1 or 2 bytes per value cross PCIe, not 4.
+ * All four run on the context's stream, are asynchronous, allocate nothing and are legal inside deepim_graph_begin/end.
+ * Per-sample ids and draws are device int32 arrays the host never reads, so a captured graph follows what they hold at replay.
+ *
+ * `transform` (image.py:583-594) for a batch: frames (B,H,W,3) uint8 in BGR order (cv2.imread), out (B,3,H,W) fp32,
+ *   out[b,i,y,x] = float(frames[b,y,x,2-i]) - means_rgb[i]      (one fp32 subtraction)
+ * means_rgb: 3 HOST floats in tensor-channel order (Render_Py's pixel_means), NULL = zeros. bg_frames (B,H,W,3) and
+ * fg_labels (B,H,W) uint8, both or neither: the data_syn / REPLACE_OBSERVED_BG_RATIO composite of image.py:147-155 — where
+ * fg_labels == 0 the pixel comes from bg_frames (the reference tests != 0, not == mask_idx), for the samples with
+ * use_bg[b] != 0; use_bg NULL = every sample. The background is already cropped and resized to H x W. */
+int deepim_ingest_bgr8(deepim_ctx* ctx, float* out /*B,3,H,W*/, const uint8_t* frames /*B,H,W,3*/,
+                       const uint8_t* bg_frames /*B,H,W,3 or NULL*/, const uint8_t* fg_labels /*B,H,W or NULL*/,
+                       const int32_t* use_bg /*device (B) or NULL*/, const float* means_rgb /*host 3 or NULL*/, int B, int H,
+                       int W);
+/* image.py:178-181, :203-219: out[b,0,y,x] = float(depth[b,y,x]) / depth_factor, a correctly rounded fp32 division as numpy's.
+ * labels (B,H,W) uint8 and mask_idx (B), both or neither: the value is 0 where labels != mask_idx[b] (image.py:211,
+ * tester.py:556). */
+int deepim_ingest_depth16(deepim_ctx* ctx, float* out /*B,1,H,W*/, const uint16_t* depth /*B,H,W*/,
+                          const uint8_t* labels /*B,H,W or NULL*/, const int32_t* mask_idx /*device (B) or NULL*/,
+                          float depth_factor, int B, int H, int W);
+/* image.py:255-260, :308-312: out[b,0,y,x] = labels[b,y,x] == mask_idx[b] ? 1 : 0 */
+int deepim_ingest_label_mask(deepim_ctx* ctx, float* out /*B,1,H,W*/, const uint8_t* labels /*B,H,W*/,
+                             const int32_t* mask_idx /*device (B)*/, int B, int H, int W);
+/* lib/utils/mask_dilate.py:19-47 with the random draws handed in: thickness (B,4) int32, columns in the order of the file's
+ * four blocks — the origin mask shifted down (:24), up (:30), right (:36), left (:42) by that many pixels; 0 = that side is
+ * not dilated. Where mask != 0 the output is mask, clamped to 1 where it exceeds 1; elsewhere 1 if an enabled side has a
+ * non-zero origin pixel exactly its thickness away, else 0. A thickness >= H (or W) contributes nothing (empty slices).
+ * out == mask is refused: the gather cannot run in place. */
+int deepim_mask_dilate(deepim_ctx* ctx, float* out /*B,1,H,W*/, const float* mask /*B,1,H,W*/,
+                       const int32_t* thickness /*device (B,4)*/, int B, int H, int W);
+
 #ifdef __cplusplus
 }
 #endif

@@ -39,6 +39,7 @@ def default_config():
         NORMALIZE_3D_POINT=0.1,
         trans_means=np.array([0.0, 0.0, 0.0]),
         trans_stds=np.array([1.0, 1.0, 1.0]),
+        DEPTH_FACTOR=1000,   # config.py:55 — raw uint16 depth per metre (lib/utils/image.py)
     )
     cfg.network = AttrDict(
         PIXEL_MEANS=np.array([123.68, 116.779, 103.939], dtype=np.float32),
@@ -65,7 +66,8 @@ def default_config():
                               NUM_3D_SAMPLE=3000, SE3_PM_SL1_SCALAR=1.0, SE3_DIST_LOSS=False,
                               LW_ROT=0.0, LW_TRANS=0.0, TRANS_LOSS_TYPE="L2", TRANS_SMOOTH_L1_SCALAR=3.0)   # config.py:104-108
     # experiments/deepim/cfgs/deepim_flownet_LM_SIXD_v1_ape_RFMx4_8epoch.yaml:76-92 (keys the label generation reads)
-    # (the yaml also sets MASK_DILATE: True — a random cv2 dilation, i.e. loader-side augmentation, not built here)
+    # (the yaml also sets MASK_DILATE: True — lib/utils/mask_dilate.py: the loader draws the thicknesses with mask_dilate_draws
+    # and hands them over in the batch as "mask_dilate_thickness"; the shifted ORs run on the device, deepim_mask_dilate)
     cfg.TRAIN = AttrDict(INIT_MASK="box_gt", FLOW_WEIGHT_TYPE="viz", MASK_DILATE=False,
                          optimizer="sgd", lr=0.0001, momentum=0.975, wd=0.0005,   # config.py:68-77
                          # mixed-precision training (network.FP16_CONV in the training graph; not reference keys): the initial loss
@@ -82,7 +84,8 @@ def default_config():
                          # X3_GRAD_SCALE, which halves on an overflow and doubles after X3_SCALE_WINDOW clean steps. Ignored with
                          # network.FP16_CONV; excludes WINOGRAD_CONV. network.X3_CONV stays a test-graph key
                          X3_CONV=False, X3_GRAD_SCALE=X3_GRAD_SCALE_DEFAULT, X3_SCALE_WINDOW=X3_SCALE_WINDOW_DEFAULT)
-    cfg.TEST = AttrDict(test_iter=4, FAST_TEST=True, UPDATE_MASK="box_rendered", INIT_MASK="box_rendered")
+    cfg.TEST = AttrDict(test_iter=4, FAST_TEST=True, UPDATE_MASK="box_rendered", INIT_MASK="box_rendered",
+                        MASK_DILATE=False)   # yaml :104; image.py:380-381
     cfg.SCALES = [(480, 640)]
     return cfg
 

@@ -1,0 +1,314 @@
+// I-group: decoded camera frames -> the fp32 NCHW tensors the graph reads (lib/utils/image.py `transform` :583-594, the
+// depth / DEPTH_FACTOR of :178-181 / :203-219, `label == mask_idx` of :255-260 / :308-312) and the loader's mask dilation
+// (lib/utils/mask_dilate.py:19-47). Four HBM streams: no LDS, no reductions, nothing allocated, per-sample ids and draws read
+// from device arrays — legal inside a graph capture, and a replay follows whatever the buffers hold then.
+//
+// The first three are per-pixel maps, so they walk the batch as ONE flat run of B·H·W pixels, four pixels per lane: a lane
+// reads 12 contiguous bytes of an interleaved BGR frame (8 of a uint16 depth map, 4 of a label map) and writes one float4 per
+// plane. Four pixels of a frame start at byte 12·g of the batch, so the loads are dword-aligned whatever W is; the float4
+// stores need H·W % 4 == 0 (else the planes of one sample start at odd offsets) and fall back to scalar stores. The last
+// B·H·W % 4 pixels are a scalar tail.
+#include "common.h"
+
+namespace {
+
+struct alignas(4) Bytes12 { uint32_t w[3]; };
+
+__device__ __forceinline__ uint32_t byte_of(const Bytes12& v, int i) { return (v.w[i >> 2] >> ((i & 3) * 8)) & 0xffu; }
+
+// sample b and in-sample pixel q of flat pixel p: ONE division per lane (32-bit where the batch allows), the lane's next pixels
+// follow by next_pixel
+__device__ __forceinline__ void locate_pixel(long p, long hw, long n, long& b, long& q) {
+  b = n <= 0x7fffffffL ? (long)((uint32_t)p / (uint32_t)hw) : p / hw;
+  q = p - b * hw;
+}
+__device__ __forceinline__ void next_pixel(long hw, long& b, long& q) {
+  if (++q == hw) { q = 0; ++b; }
+}
+
+// VEC_IN: every input pointer is dword-aligned (12-byte loads); VEC_OUT: hw % 4 == 0 and `out` 16-byte aligned (float4 stores)
+template <bool VEC_IN, bool VEC_OUT>
+__global__ __launch_bounds__(256) void ingest_bgr8_kernel(float* __restrict__ out, const uint8_t* __restrict__ frames,
+                                                          const uint8_t* __restrict__ bg, const uint8_t* __restrict__ fg,
+                                                          const int32_t* __restrict__ use_bg, Vec3 means, long hw, long n) {
+  const long p0 = ((long)blockIdx.x * 256 + threadIdx.x) * 4;
+  if (p0 >= n) return;
+  const int cnt = (int)min(4L, n - p0);
+  float px[3][4];   // [tensor channel][pixel]
+  long bs[4], qs[4];
+  locate_pixel(p0, hw, n, bs[0], qs[0]);
+#pragma unroll
+  for (int j = 1; j < 4; ++j) { bs[j] = bs[j - 1]; qs[j] = qs[j - 1]; next_pixel(hw, bs[j], qs[j]); }
+  if (VEC_IN && cnt == 4) {
+    Bytes12 v = *reinterpret_cast<const Bytes12*>(frames + p0 * 3);
+    if (bg) {
+      const Bytes12 g = *reinterpret_cast<const Bytes12*>(bg + p0 * 3);
+      const uint32_t l = *reinterpret_cast<const uint32_t*>(fg + p0);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const bool take_bg = ((l >> (8 * j)) & 0xffu) == 0 && (!use_bg || use_bg[bs[j]] != 0);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) px[c][j] = (float)(take_bg ? byte_of(g, j * 3 + 2 - c) : byte_of(v, j * 3 + 2 - c));
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) px[c][j] = (float)byte_of(v, j * 3 + 2 - c);
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (j < cnt) {
+        const long p = p0 + j;
+        const bool take_bg = bg && fg[p] == 0 && (!use_bg || use_bg[bs[j]] != 0);
+        const uint8_t* s = (take_bg ? bg : frames) + p * 3;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) px[c][j] = (float)s[2 - c];
+      } else {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) px[c][j] = 0.f;
+      }
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) px[c][j] -= means.v[c];
+  if (VEC_OUT) {   // hw % 4 == 0: the four pixels share a sample and cnt == 4
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+      *reinterpret_cast<float4*>(out + (bs[0] * 3 + c) * hw + qs[0]) = make_float4(px[c][0], px[c][1], px[c][2], px[c][3]);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (j < cnt) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) out[(bs[j] * 3 + c) * hw + qs[j]] = px[c][j];
+      }
+  }
+}
+
+// out (B,1,H,W) is as flat as the inputs: pixel p of the batch goes to out[p]
+template <bool VEC>
+__global__ __launch_bounds__(256) void ingest_depth16_kernel(float* __restrict__ out, const uint16_t* __restrict__ depth,
+                                                             const uint8_t* __restrict__ labels,
+                                                             const int32_t* __restrict__ mask_idx, float depth_factor,
+                                                             long hw, long n) {
+  const long p0 = ((long)blockIdx.x * 256 + threadIdx.x) * 4;
+  if (p0 >= n) return;
+  const int cnt = (int)min(4L, n - p0);
+  long b, q;
+  locate_pixel(p0, hw, n, b, q);
+  if (VEC && cnt == 4) {
+    const uint2 d = *reinterpret_cast<const uint2*>(depth + p0);
+    float r[4] = {(float)(d.x & 0xffffu), (float)(d.x >> 16), (float)(d.y & 0xffffu), (float)(d.y >> 16)};
+    // a correctly rounded fp32 division, as numpy's: a reciprocal multiply gives other bits
+#pragma unroll
+    for (int j = 0; j < 4; ++j) r[j] = __fdiv_rn(r[j], depth_factor);
+    if (labels) {
+      const uint32_t l = *reinterpret_cast<const uint32_t*>(labels + p0);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        if ((int)((l >> (8 * j)) & 0xffu) != mask_idx[b]) r[j] = 0.f;
+        next_pixel(hw, b, q);
+      }
+    }
+    *reinterpret_cast<float4*>(out + p0) = make_float4(r[0], r[1], r[2], r[3]);
+  } else {
+    for (int j = 0; j < cnt; ++j) {
+      const long p = p0 + j;
+      float r = __fdiv_rn((float)depth[p], depth_factor);
+      if (labels && (int)labels[p] != mask_idx[b]) r = 0.f;
+      out[p] = r;
+      next_pixel(hw, b, q);
+    }
+  }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void ingest_label_mask_kernel(float* __restrict__ out, const uint8_t* __restrict__ labels,
+                                                                const int32_t* __restrict__ mask_idx, long hw, long n) {
+  const long p0 = ((long)blockIdx.x * 256 + threadIdx.x) * 4;
+  if (p0 >= n) return;
+  const int cnt = (int)min(4L, n - p0);
+  long b, q;
+  locate_pixel(p0, hw, n, b, q);
+  if (VEC && cnt == 4) {
+    const uint32_t l = *reinterpret_cast<const uint32_t*>(labels + p0);
+    float r[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      r[j] = (int)((l >> (8 * j)) & 0xffu) == mask_idx[b] ? 1.f : 0.f;
+      next_pixel(hw, b, q);
+    }
+    *reinterpret_cast<float4*>(out + p0) = make_float4(r[0], r[1], r[2], r[3]);
+  } else {
+    for (int j = 0; j < cnt; ++j) {
+      out[p0 + j] = (int)labels[p0 + j] == mask_idx[b] ? 1.f : 0.f;
+      next_pixel(hw, b, q);
+    }
+  }
+}
+
+// mask_dilate.py:19-47 as a gather. Block k of the file ORs the origin mask, shifted by its thickness t_k, into the pixels the
+// origin leaves empty: :24 reads origin[y - t], :30 origin[y + t], :36 origin[:, x - t], :42 origin[:, x + t]. A source row
+// or column outside the frame is outside the reference's slices too, which also covers t >= H (or W): empty slices. Where the
+// origin is non-zero the sum keeps it, and :46 clamps what exceeds 1.
+__device__ __forceinline__ float dilate_pixel(const float* __restrict__ m, float c, int y, int x, int H, int W, int td, int tu,
+                                              int tr, int tl) {
+  if (c != 0.f) return c > 1.f ? 1.f : c;
+  bool hit = false;
+  if (td > 0 && y >= td) hit = m[(long)(y - td) * W + x] != 0.f;
+  if (!hit && tu > 0 && y + (long)tu < H) hit = m[(long)(y + tu) * W + x] != 0.f;
+  if (!hit && tr > 0 && x >= tr) hit = m[(long)y * W + (x - tr)] != 0.f;
+  if (!hit && tl > 0 && x + (long)tl < W) hit = m[(long)y * W + (x + tl)] != 0.f;
+  return hit ? 1.f : 0.f;
+}
+
+struct alignas(4) Floats4 { float v[4]; };   // four floats at a dword-aligned address: one 16-byte load
+
+// grid (pixel blocks, B). VEC: W % 4 == 0 and both pointers 16-byte aligned — a lane owns four pixels of one row and gathers each
+// enabled side with ONE 16-byte load (rows above / below are float4-aligned, the shifted run of its own row is dword-aligned);
+// only the lanes whose run crosses the row's end fall back to per-pixel loads. Lanes without an empty pixel load nothing more.
+template <bool VEC>
+__global__ __launch_bounds__(256) void mask_dilate_kernel(float* __restrict__ out, const float* __restrict__ mask,
+                                                          const int32_t* __restrict__ thickness, int H, int W) {
+  const int b = blockIdx.y;
+  const long hw = (long)H * W;
+  const float* m = mask + b * hw;
+  float* o = out + b * hw;
+  const int td = thickness[b * 4 + 0], tu = thickness[b * 4 + 1], tr = thickness[b * 4 + 2], tl = thickness[b * 4 + 3];
+  if (VEC) {
+    const long p0 = ((long)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (p0 >= hw) return;
+    const int y = (int)((uint32_t)p0 / (uint32_t)W), x = (int)(p0 - (long)y * W);   // hw < 2^31 (checked by the launcher)
+    const float4 c4 = *reinterpret_cast<const float4*>(m + p0);
+    const float c[4] = {c4.x, c4.y, c4.z, c4.w};
+    bool hit[4] = {false, false, false, false};
+    if (c[0] == 0.f || c[1] == 0.f || c[2] == 0.f || c[3] == 0.f) {
+      if (td > 0 && y >= td) {                                                    // :24 origin[y - t]
+        const float4 v = *reinterpret_cast<const float4*>(m + p0 - (long)td * W);
+        hit[0] |= v.x != 0.f; hit[1] |= v.y != 0.f; hit[2] |= v.z != 0.f; hit[3] |= v.w != 0.f;
+      }
+      if (tu > 0 && y + (long)tu < H) {                                           // :30 origin[y + t]
+        const float4 v = *reinterpret_cast<const float4*>(m + p0 + (long)tu * W);
+        hit[0] |= v.x != 0.f; hit[1] |= v.y != 0.f; hit[2] |= v.z != 0.f; hit[3] |= v.w != 0.f;
+      }
+      if (tr > 0) {                                                               // :36 origin[:, x - t]
+        if (x >= tr) {
+          const Floats4 v = *reinterpret_cast<const Floats4*>(m + p0 - tr);
+#pragma unroll
+          for (int i = 0; i < 4; ++i) hit[i] |= v.v[i] != 0.f;
+        } else {
+#pragma unroll
+          for (int i = 0; i < 4; ++i)
+            if (x + i >= tr) hit[i] |= m[p0 + i - tr] != 0.f;
+        }
+      }
+      if (tl > 0) {                                                               // :42 origin[:, x + t]
+        if (x + 3 + (long)tl < W) {
+          const Floats4 v = *reinterpret_cast<const Floats4*>(m + p0 + tl);
+#pragma unroll
+          for (int i = 0; i < 4; ++i) hit[i] |= v.v[i] != 0.f;
+        } else {
+#pragma unroll
+          for (int i = 0; i < 4; ++i)
+            if (x + i + (long)tl < W) hit[i] |= m[p0 + i + tl] != 0.f;
+        }
+      }
+    }
+    float r[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) r[i] = c[i] != 0.f ? (c[i] > 1.f ? 1.f : c[i]) : (hit[i] ? 1.f : 0.f);
+    *reinterpret_cast<float4*>(o + p0) = make_float4(r[0], r[1], r[2], r[3]);
+  } else {
+    const long p = (long)blockIdx.x * 256 + threadIdx.x;
+    if (p >= hw) return;
+    const int y = (int)((uint32_t)p / (uint32_t)W), x = (int)(p - (long)y * W);
+    o[p] = dilate_pixel(m, m[p], y, x, H, W, td, tu, tr, tl);
+  }
+}
+
+inline bool aligned_to(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
+
+}  // namespace
+
+extern "C" int deepim_ingest_bgr8(deepim_ctx* ctx, float* out, const uint8_t* frames, const uint8_t* bg_frames,
+                                  const uint8_t* fg_labels, const int32_t* use_bg, const float* means_rgb, int B, int H,
+                                  int W) {
+  DI_DEVICE(ctx);
+  DI_REQUIRE(B >= 0 && H >= 0 && W >= 0, "ingest_bgr8: negative size");
+  DI_REQUIRE((bg_frames == NULL) == (fg_labels == NULL), "ingest_bgr8: bg_frames and fg_labels come together or not at all");
+  DI_REQUIRE(bg_frames != NULL || use_bg == NULL, "ingest_bgr8: use_bg without bg_frames");
+  const long hw = (long)H * W, n = (long)B * hw;
+  if (n == 0) return 0;
+  Vec3 means = {{0.f, 0.f, 0.f}};
+  if (means_rgb) for (int i = 0; i < 3; ++i) means.v[i] = means_rgb[i];
+  const bool vin = aligned_to(frames, 4) && (!bg_frames || (aligned_to(bg_frames, 4) && aligned_to(fg_labels, 4)));
+  const bool vout = hw % 4 == 0 && aligned_to(out, 16);
+  const dim3 grid(di_div_up(di_div_up(n, 4), 256)), block(256);
+#define DI_INGEST_BGR(VI, VO)                                                                                            \
+  hipLaunchKernelGGL((ingest_bgr8_kernel<VI, VO>), grid, block, 0, ctx->stream, out, frames, bg_frames, fg_labels, use_bg, \
+                     means, hw, n)
+  if (vin && vout) DI_INGEST_BGR(true, true);
+  else if (vin) DI_INGEST_BGR(true, false);
+  else if (vout) DI_INGEST_BGR(false, true);
+  else DI_INGEST_BGR(false, false);
+#undef DI_INGEST_BGR
+  DI_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int deepim_ingest_depth16(deepim_ctx* ctx, float* out, const uint16_t* depth, const uint8_t* labels,
+                                     const int32_t* mask_idx, float depth_factor, int B, int H, int W) {
+  DI_DEVICE(ctx);
+  DI_REQUIRE(B >= 0 && H >= 0 && W >= 0, "ingest_depth16: negative size");
+  DI_REQUIRE((labels == NULL) == (mask_idx == NULL), "ingest_depth16: labels and mask_idx come together or not at all");
+  const long hw = (long)H * W, n = (long)B * hw;
+  if (n == 0) return 0;
+  const bool vec = aligned_to(out, 16) && aligned_to(depth, 8) && (!labels || aligned_to(labels, 4));
+  const dim3 grid(di_div_up(di_div_up(n, 4), 256)), block(256);
+  if (vec)
+    hipLaunchKernelGGL(ingest_depth16_kernel<true>, grid, block, 0, ctx->stream, out, depth, labels, mask_idx, depth_factor,
+                       hw, n);
+  else
+    hipLaunchKernelGGL(ingest_depth16_kernel<false>, grid, block, 0, ctx->stream, out, depth, labels, mask_idx, depth_factor,
+                       hw, n);
+  DI_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int deepim_ingest_label_mask(deepim_ctx* ctx, float* out, const uint8_t* labels, const int32_t* mask_idx, int B,
+                                        int H, int W) {
+  DI_DEVICE(ctx);
+  DI_REQUIRE(B >= 0 && H >= 0 && W >= 0, "ingest_label_mask: negative size");
+  const long hw = (long)H * W, n = (long)B * hw;
+  if (n == 0) return 0;
+  const bool vec = aligned_to(out, 16) && aligned_to(labels, 4);
+  const dim3 grid(di_div_up(di_div_up(n, 4), 256)), block(256);
+  if (vec) hipLaunchKernelGGL(ingest_label_mask_kernel<true>, grid, block, 0, ctx->stream, out, labels, mask_idx, hw, n);
+  else hipLaunchKernelGGL(ingest_label_mask_kernel<false>, grid, block, 0, ctx->stream, out, labels, mask_idx, hw, n);
+  DI_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int deepim_mask_dilate(deepim_ctx* ctx, float* out, const float* mask, const int32_t* thickness, int B, int H,
+                                  int W) {
+  DI_DEVICE(ctx);
+  DI_REQUIRE(B >= 0 && H >= 0 && W >= 0, "mask_dilate: negative size");
+  DI_REQUIRE(out != mask, "mask_dilate: out == mask (the dilation gathers from its input and cannot run in place)");
+  DI_REQUIRE(B <= 65535, "mask_dilate: batch too large");
+  const long hw = (long)H * W;
+  DI_REQUIRE(hw <= 0x7fffffffL, "mask_dilate: frame too large");
+  if (B == 0 || hw == 0) return 0;
+  const bool vec = W % 4 == 0 && aligned_to(out, 16) && aligned_to(mask, 16);
+  if (vec)
+    hipLaunchKernelGGL(mask_dilate_kernel<true>, dim3(di_div_up(hw / 4, 256), B), dim3(256), 0, ctx->stream, out, mask,
+                       thickness, H, W);
+  else
+    hipLaunchKernelGGL(mask_dilate_kernel<false>, dim3(di_div_up(hw, 256), B), dim3(256), 0, ctx->stream, out, mask,
+                       thickness, H, W);
+  DI_LAUNCH_CHECK();
+  return 0;
+}

@@ -9,13 +9,18 @@ round trip:
     flow, flow_weights      calc_flow → (B,2,H,W), weights by TRAIN.FLOW_WEIGHT_TYPE             deepim_pair_flow_labels
     mask_rendered           depth_rendered with values > 0.2 set to 1                            deepim_depth_clip_mask
     mask_observed           TRAIN.INIT_MASK: mask_gt | box_gt | box_rendered                     deepim_mask_box_forward
+                            then TRAIN.MASK_DILATE with the loader's draws (image.py:289-290)    deepim_mask_dilate
     point_cloud_observed    R·X + T of the sampled model points                                  deepim_points_transform
+
+`get_data_pair_test_batch` mirrors data_pair.py:22-63 from decoded uint8 / uint16 frames (lib/utils/image.py).
 """
 import ctypes
 
 import numpy as np
 
-from ...runtime import lib
+from ...runtime import DeviceArray, lib
+from ..utils import image as _image
+from ..utils.mask_dilate import mask_dilate_batch
 from .RT_transform import calc_RT_delta_batch
 
 FLOW_WEIGHT_TYPE_CODE = {"all": 0, "viz": 1, "valid": 2}
@@ -47,7 +52,9 @@ def get_pair_flow(batch, config):
 
 
 def get_pair_mask(batch, config):
-    """image.py:229-390, train phase, on resident tensors → (mask_observed, mask_gt_observed, mask_rendered)."""
+    """image.py:229-390, train phase, on resident tensors → (mask_observed, mask_gt_observed, mask_rendered).
+    With TRAIN.MASK_DILATE the batch carries "mask_dilate_thickness": a device int32 (B,4) array of the loader's draws
+    (lib/utils/mask_dilate.mask_dilate_draws) — the random numbers are the loader's, the device path has no generator."""
     dr, gt = batch["depth_rendered"], batch["mask_gt_observed"]
     ctx = dr.context
     B, _, H, W = dr.shape
@@ -70,9 +77,35 @@ def get_pair_mask(batch, config):
     else:
         raise Exception("Unknown mask type: {}".format(init))
     if config.TRAIN.get("MASK_DILATE", False):
-        raise NotImplementedError("TRAIN.MASK_DILATE: the random cv2 dilation (image.py:287-288) is loader-side "
-                                  "augmentation and is not part of the device path")
+        thickness = batch.get("mask_dilate_thickness")
+        if thickness is None:
+            raise NotImplementedError("TRAIN.MASK_DILATE: the batch carries no 'mask_dilate_thickness' — the random draws of "
+                                      "image.py:289-290 are the loader's (lib/utils/mask_dilate.mask_dilate_draws); the "
+                                      "device path has no generator of its own")
+        mask_observed = mask_dilate_batch(mask_observed, thickness)
     return mask_observed, gt, mask_rendered
+
+
+def get_data_pair_test_batch(frames, config):
+    """data_pair.py:22-63 from decoded frames (see lib/utils/image.py for the dict): the reference's `data` keys (:43-60) as
+    device tensors for the whole batch — image_observed, image_rendered (B,3,H,W), src_pose (B,3,4) from frames["pose_rendered"],
+    class_index handed over as given [, depth_observed, depth_rendered with INPUT_DEPTH][, mask_observed, mask_rendered with
+    INPUT_MASK]."""
+    data = {}
+    data["image_observed"], data["image_rendered"] = _image.get_pair_image(frames, config, "test")
+    ctx = data["image_observed"].context
+    B = data["image_observed"].shape[0]
+    pose = frames["pose_rendered"]
+    if not isinstance(pose, DeviceArray):
+        pose = ctx.array(np.asarray(pose, dtype=np.float32).reshape(B, 3, 4))
+    data["src_pose"] = pose
+    data["class_index"] = frames.get("class_index")
+    if config.network.INPUT_DEPTH:
+        data["depth_observed"], data["depth_rendered"] = _image.get_pair_depth(frames, config, "test")
+    if config.network.INPUT_MASK:
+        data["mask_observed"], _, data["mask_rendered"] = _image.get_pair_mask(frames, config, "test",
+                                                                               depth_rendered=data.get("depth_rendered"))
+    return data
 
 
 def get_data_pair_train_batch(batch, config):
@@ -80,6 +113,7 @@ def get_data_pair_train_batch(batch, config):
         image_observed, image_rendered (B,3,H,W); depth_gt_observed, depth_rendered (B,1,H,W) in metres;
         pose_rendered, pose_observed (B,3,4); mask_gt_observed (B,1,H,W) [INPUT_MASK / PRED_MASK];
         depth_observed (B,1,H,W) [INPUT_DEPTH]; point_cloud_model, point_cloud_weights (B,3,N) [SE3_PM_LOSS];
+        mask_dilate_thickness: device int32 (B,4) [TRAIN.MASK_DILATE], see get_pair_mask;
         class_index: handed over as given — host ids, or a device int32 array (B) that the render machine draws in one launch
         group without reading it back.
     Returns {"data": {...}, "label": {...}} with the reference's keys."""

@@ -1,0 +1,213 @@
+"""Mirror of the tensor-making half of lib/utils/image.py on the device: `transform` (:583-594), `get_pair_image` (:58-163),
+`get_gt_observed_depth` (:166-187), `get_pair_depth` (:190-227) and `get_pair_mask` (:230-399), computed by the ingest kernels
+(csrc/ingest.hip) from frames as the decoder left them — uint8 BGR images, uint16 depth maps, uint8 label maps — so 1 or 2
+bytes per value cross PCIe and no host arithmetic stands between a camera and the graph.
+
+Where the reference takes a `pairdb` of file paths, these take `frames`: a dict of DECODED arrays, each a device array or a
+numpy array (uploaded as it is, never converted on the host), for a batch of B pairs:
+
+    image_observed, image_rendered        (B,H,W,3) uint8, BGR (cv2.imread)
+    bg_image                              (B,H,W,3) uint8, optional: the background already cropped and resized to the frame
+                                          (image.py:108-145 is cv2 work); composited under mask_gt_observed != 0 (:147-155),
+                                          for the samples with use_bg != 0 (int32 (B), optional: every sample)
+    depth_observed, depth_rendered, depth_gt_observed     (B,H,W) uint16
+    mask_gt_observed, mask_observed, mask_observed_est    (B,H,W) uint8 label maps
+    mask_idx                              (B) int32: the pair's label value (pair_rec["mask_idx"])
+    mask_dilate_thickness                 (B,4) int32 from lib/utils/mask_dilate.mask_dilate_draws, for MASK_DILATE
+
+File decoding, the cv2 resize (:552-580) and the choice of a background are the caller's: a frame whose size is not
+config.SCALES[0] is refused. The test phase's `np.sum(depth_rendered) == 0` guard (:301-303) is a host decision per pair and is
+the caller's too; an empty rectangle source gives zeros and sets bit 2 of the status word (deepim_zoom_status).
+
+The kernels are asynchronous on the context's stream. These wrappers stay asynchronous when frames, ids and draws are device
+arrays; a numpy input is uploaded with a synchronous copy into a temporary whose release synchronises the stream again.
+"""
+import ctypes
+
+import numpy as np
+
+from ...runtime import Context, DeviceArray, lib
+from .mask_dilate import mask_dilate_batch
+
+
+def _context(frames):
+    for v in frames.values():
+        if isinstance(v, DeviceArray):
+            return v.context
+    return Context.default()
+
+
+def _frame(ctx, frames, key, dtype, inner=()):
+    """frames[key] as a device array of `dtype`, shape (B,H,W)+inner; numpy input is uploaded in its own dtype."""
+    if key not in frames or frames[key] is None:
+        raise KeyError("frames carry no '%s'" % key)
+    v = frames[key]
+    if not isinstance(v, DeviceArray):
+        v = np.asarray(v)
+        if v.dtype != np.dtype(dtype):
+            raise TypeError("frames['%s'] is %s; the decoded %s frame is expected" % (key, v.dtype, np.dtype(dtype)))
+        v = ctx.array(v, dtype=dtype)
+    if v.dtype != np.dtype(dtype):
+        raise TypeError("frames['%s'] is %s; the decoded %s frame is expected" % (key, v.dtype, np.dtype(dtype)))
+    if v.ndim != 3 + len(inner) or v.shape[3:] != tuple(inner):
+        raise ValueError("frames['%s'] has shape %s; (B,H,W%s) expected" % (key, v.shape, "".join(",%d" % i for i in inner)))
+    return v
+
+
+def _ids(ctx, frames, key, B, cols=None):
+    """frames[key] as a device int32 array of B rows (never read back)."""
+    if key not in frames or frames[key] is None:
+        raise KeyError("frames carry no '%s'" % key)
+    v = frames[key]
+    if not isinstance(v, DeviceArray):
+        v = ctx.array(np.asarray(v).reshape((B,) if cols is None else (B, cols)), dtype=np.int32)
+    if v.dtype != np.int32 or v.size != B * (cols or 1):
+        raise TypeError("frames['%s'] must be int32 with %d values" % (key, B * (cols or 1)))
+    return v
+
+
+def _check_size(config, H, W):
+    if (H, W) != tuple(int(s) for s in config.SCALES[0]):
+        raise ValueError("frame size %dx%d is not config.SCALES[0] = %s: the resize of image.py:552-580 is not part of the "
+                         "device path — resize before handing the frames over" % (H, W, tuple(config.SCALES[0])))
+
+
+def _depth_factor(config):
+    return ctypes.c_float(float(config.dataset.get("DEPTH_FACTOR", 1000)))
+
+
+def transform_batch(ctx, frames_bgr, means_rgb=None, bg=None, fg=None, use_bg=None):
+    """(B,H,W,3) uint8 BGR device frames → (B,3,H,W) fp32, channel i = image channel 2-i minus means_rgb[i]."""
+    B, H, W, _ = frames_bgr.shape
+    out = ctx.empty((B, 3, H, W))
+    means = None if means_rgb is None else np.ascontiguousarray(means_rgb, dtype=np.float32).reshape(3)
+    lib.deepim_ingest_bgr8(ctx.handle, out, frames_bgr, bg, fg, use_bg, means, B, H, W)
+    return out
+
+
+def transform(im, pixel_means):
+    """image.py:583-594: im [height, width, channel] uint8 in BGR, pixel_means in the image's BGR order → numpy
+    [1, channel, height, width] in RGB order, computed on the default device in fp32 (the reference computes in float64)."""
+    ctx = Context.default()
+    im = np.ascontiguousarray(im)
+    if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
+        raise TypeError("transform: a (height, width, 3) uint8 image is expected")
+    means = np.asarray(pixel_means, dtype=np.float64).reshape(-1)[[2, 1, 0]]     # batch_updater_py_multi.py:24
+    return transform_batch(ctx, ctx.array(im[np.newaxis], dtype=np.uint8), means).asnumpy()
+
+
+def _means_rgb(config):
+    return np.asarray(config.network.PIXEL_MEANS, dtype=np.float64).reshape(-1)[[2, 1, 0]]
+
+
+def get_pair_image(frames, config, phase="train"):
+    """image.py:58-163 → (image_observed, image_rendered), device (B,3,H,W). In the train phase, frames with a "bg_image" get the
+    observed background replaced where mask_gt_observed == 0 (:147-155)."""
+    ctx = _context(frames)
+    obs = _frame(ctx, frames, "image_observed", np.uint8, (3,))
+    ren = _frame(ctx, frames, "image_rendered", np.uint8, (3,))
+    B, H, W, _ = obs.shape
+    _check_size(config, H, W)
+    if ren.shape != obs.shape:
+        raise ValueError("image_rendered %s and image_observed %s differ in shape" % (ren.shape, obs.shape))
+    means = _means_rgb(config)
+    bg = fg = use_bg = None
+    if phase == "train" and frames.get("bg_image") is not None:
+        bg = _frame(ctx, frames, "bg_image", np.uint8, (3,))
+        fg = _frame(ctx, frames, "mask_gt_observed", np.uint8)
+        if bg.shape != obs.shape or fg.shape != obs.shape[:3]:
+            raise ValueError("bg_image / mask_gt_observed do not match image_observed's shape")
+        if frames.get("use_bg") is not None:
+            use_bg = _ids(ctx, frames, "use_bg", B)
+    return transform_batch(ctx, obs, means, bg, fg, use_bg), transform_batch(ctx, ren, means)
+
+
+def _depth(ctx, frames, key, config, label_key=None):
+    d = _frame(ctx, frames, key, np.uint16)
+    B, H, W = d.shape
+    _check_size(config, H, W)
+    labels = idx = None
+    if label_key is not None:
+        labels = _frame(ctx, frames, label_key, np.uint8)
+        if labels.shape != d.shape:
+            raise ValueError("frames['%s'] and frames['%s'] differ in shape" % (label_key, key))
+        idx = _ids(ctx, frames, "mask_idx", B)
+    out = ctx.empty((B, 1, H, W))
+    lib.deepim_ingest_depth16(ctx.handle, out, d, labels, idx, _depth_factor(config), B, H, W)
+    return out
+
+
+def get_gt_observed_depth(frames, config, phase="train"):
+    """image.py:166-187 → depth_gt_observed, device (B,1,H,W) in metres."""
+    return _depth(_context(frames), frames, "depth_gt_observed", config)
+
+
+def get_pair_depth(frames, config, phase="train"):
+    """image.py:190-227 → (depth_observed, depth_rendered). With network.MASK_INPUTS the observed depth is zeroed outside the
+    pair's label (:204-211): mask_gt_observed in the train phase or with dataset.MASK_GT, else mask_observed_est."""
+    ctx = _context(frames)
+    label_key = None
+    if config.network.get("MASK_INPUTS", False):
+        if config.TRAIN.get("MASK_SYN", False) and phase == "train":
+            raise NotImplementedError("TRAIN.MASK_SYN (image.py:205-206) is not part of the device path")
+        label_key = "mask_gt_observed" if (config.dataset.get("MASK_GT", False) or phase == "train") else "mask_observed_est"
+    return _depth(ctx, frames, "depth_observed", config, label_key), _depth(ctx, frames, "depth_rendered", config)
+
+
+def label_mask(ctx, frames, key):
+    """`label == mask_idx` (image.py:255-260, :308-312) → device (B,1,H,W) of 0 / 1."""
+    labels = _frame(ctx, frames, key, np.uint8)
+    B, H, W = labels.shape
+    out = ctx.empty((B, 1, H, W))
+    lib.deepim_ingest_label_mask(ctx.handle, out, labels, _ids(ctx, frames, "mask_idx", B), B, H, W)
+    return out
+
+
+def _box(ctx, mask):
+    B, _, H, W = mask.shape
+    out = ctx.empty(mask.shape)
+    lib.deepim_mask_box_forward(ctx.handle, out, mask, B, H, W)
+    return out
+
+
+def get_pair_mask(frames, config, phase="train", depth_rendered=None):
+    """image.py:230-399 → (mask_observed, mask_gt_observed, mask_rendered), device (B,1,H,W).
+    train: TRAIN.INIT_MASK mask_gt | box_gt | box_rendered, then TRAIN.MASK_DILATE (:289-290); "mask_gt" hands over the 0 / 1
+    mask of the pair's label, as lib/pair_matching/data_pair.get_pair_mask does (the reference copies the raw label map there).
+    test: TEST.INIT_MASK mask_gt_observed | mask_observed | box_gt_observed | box_ | box_rendered (:305-378), then
+    TEST.MASK_DILATE (:380-381); mask_gt_observed is mask_observed, as at :387.
+    depth_rendered: the (B,1,H,W) tensor get_pair_depth already made of frames["depth_rendered"], to skip a second ingest."""
+    ctx = _context(frames)
+    dr = depth_rendered if depth_rendered is not None else _depth(ctx, frames, "depth_rendered", config)
+    B, _, H, W = dr.shape
+    if phase == "train":
+        from ..pair_matching import data_pair
+        batch = {"depth_rendered": dr, "mask_gt_observed": label_mask(ctx, frames, "mask_gt_observed")}
+        if frames.get("mask_dilate_thickness") is not None:
+            batch["mask_dilate_thickness"] = _ids(ctx, frames, "mask_dilate_thickness", B, 4)
+        return data_pair.get_pair_mask(batch, config)
+    n = B * H * W
+    mask_rendered = ctx.empty((B, 1, H, W))
+    lib.deepim_depth_clip_mask(ctx.handle, mask_rendered, dr, ctypes.c_float(0.2), n)
+    init = config.TEST.INIT_MASK
+    if init == "mask_gt_observed":
+        mask_observed = label_mask(ctx, frames, "mask_gt_observed")
+    elif init == "mask_observed":
+        mask_observed = label_mask(ctx, frames, "mask_observed")
+    elif init == "box_gt_observed":
+        # [y_start:y_end, x_start:x_end] with end = the LAST index holding a non-zero (:327-336): deepim_mask_box_forward's rectangle
+        mask_observed = _box(ctx, label_mask(ctx, frames, "mask_gt_observed"))
+    elif init == "box_":
+        mask_observed = _box(ctx, label_mask(ctx, frames, "mask_observed"))
+    elif init == "box_rendered":
+        fg = ctx.empty((B, 1, H, W))
+        lib.deepim_depth_to_mask(ctx.handle, fg, dr, ctypes.c_float(0.2), n)
+        mask_observed = _box(ctx, fg)
+    else:
+        raise Exception("Unknown init mask type: {}".format(init))
+    if config.TEST.get("MASK_DILATE", False):
+        if frames.get("mask_dilate_thickness") is None:
+            raise NotImplementedError("TEST.MASK_DILATE: the frames carry no 'mask_dilate_thickness' — the random draws are the "
+                                      "loader's (lib/utils/mask_dilate.mask_dilate_draws); the device path has no generator")
+        mask_observed = mask_dilate_batch(mask_observed, _ids(ctx, frames, "mask_dilate_thickness", B, 4))
+    return mask_observed, mask_observed, mask_rendered
