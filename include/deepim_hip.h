@@ -164,6 +164,21 @@ int deepim_pair_flow_labels(deepim_ctx* ctx, float* flow /*B,2,H,W*/, float* flo
                             const float* depth_rendered, const float* depth_observed, const float* pose_rendered,
                             const float* pose_observed, const float* K_host, float thresh, int standard_rep,
                             int weight_type, int B, int H, int W);
+/* Flow EPE of the test loop, fused (deepim/core/tester.py:366-378: par_generate_gt :530-569 + calc_EPE_one_pair :572-589):
+ * per pixel of pair b the float64 ground truth of calc_flow(depth_rendered, pose_rendered, pose_observed, K, depth_observed,
+ * thresh, standard_rep) — un-rounded pw − w, ph − h, zero where not visible — against flow_est rounded to fp16 (nearest even,
+ * |x| > 65504 → ±inf, as tester.py:350-352's astype) and widened to double; point_diff = sqrt(dx² + dy²); channel 0 of the
+ * prediction meets channel 0 of the ground truth under both standard_rep settings. No flow tensor is written.
+ * out[b] = { epe_all, num_all, epe_viz, num_viz, epe_vizbg, num_vizbg } (:581-588), vizbg = visible or (not visible and
+ * depth_rendered == 0); the counts are integer counts stored as doubles. totals (6 doubles, caller-owned, or NULL) receives
+ * totals[k] += out[b][k] for b = 0 … B-1 in that order, so a loop reads it once at its end. skip: device int32 (B) the host
+ * never reads, or NULL: a pair with skip[b] != 0 contributes nothing and its row is zeros. Partials are combined in a fixed
+ * order without atomics: the same inputs give the same bytes. Asynchronous on the context's stream; scratch grows on a first
+ * call only, outside a capture; legal inside deepim_graph_begin/end (K_host, thresh and standard_rep are baked in). */
+int deepim_flow_epe(deepim_ctx* ctx, double* out /*B,6*/, double* totals /*6, accumulated; or NULL*/,
+                    const float* flow_est /*B,2,H,W*/, const float* depth_rendered, const float* depth_observed,
+                    const float* pose_rendered, const float* pose_observed /*B,3,4*/, const float* K_host,
+                    const int32_t* skip /*device (B) or NULL*/, float thresh, int standard_rep, int B, int H, int W);
 /* image.py:381-387: mask_rendered = depth_rendered with values > thresh set to 1 (others kept) */
 int deepim_depth_clip_mask(deepim_ctx* ctx, float* mask, const float* depth, float thresh, size_t n);
 /* deepim/operator_py/flow_updater.py:42-102 `FlowUpdater` forward: integer flow

@@ -85,7 +85,9 @@ def default_config():
                          # network.FP16_CONV; excludes WINOGRAD_CONV. network.X3_CONV stays a test-graph key
                          X3_CONV=False, X3_GRAD_SCALE=X3_GRAD_SCALE_DEFAULT, X3_SCALE_WINDOW=X3_SCALE_WINDOW_DEFAULT)
     cfg.TEST = AttrDict(test_iter=4, FAST_TEST=True, UPDATE_MASK="box_rendered", INIT_MASK="box_rendered",
-                        MASK_DILATE=False)   # yaml :104; image.py:380-381
+                        MASK_DILATE=False,   # yaml :104; image.py:380-381
+                        # the other keys the test loop reads (core/tester.py; config.py:93-99): the three below are refused when set
+                        VISUALIZE=False, PRECOMPUTED_ICP=False, BEFORE_ICP=False)
     cfg.SCALES = [(480, 640)]
     return cfg
 

@@ -3,8 +3,10 @@
 //   F2  lib/pair_matching/flow.py:12-63        (calc_flow, float64 numpy variant)
 //   F3  deepim/operator_py/flow_updater.py:42-102 (FlowUpdater, integer flow)
 //   F4  lib/pair_matching/batch_updater_py_multi.py:255-265 (KT, mask from depth)
+//   F5  deepim/core/tester.py:530-589          (par_generate_gt + calc_EPE_one_pair: flow EPE of the test loop, a fused
+//       reduction over F2's per-pixel body — flow_epe_partial_kernel / flow_epe_finish_kernel below)
 //
-// All three are one-thread-per-pixel HBM-bound kernels: 4 B read (depth_src) + one
+// F1-F3 are one-thread-per-pixel HBM-bound kernels: 4 B read (depth_src) + one
 // 4 B gather (depth_tgt) + 12 B written per pixel = 20 B/px algorithmic.
 // Layout: each thread owns 4 consecutive pixels of a row → dwordx4 loads/stores; the
 // per-sample 3x4 transform is read through the scalar cache (wave-uniform).
@@ -96,16 +98,15 @@ __global__ __launch_bounds__(256) void flow_kernel_scalar(float* __restrict__ fl
 
 // F2: flow.py:12-63. float64 arithmetic like numpy: X = d·(Kinv·[w,h,1]) with Kinv f32→f64,
 // Xp = KT(f32→f64)·[X;1]; np.round = half-to-even (rint); flow from UN-rounded projections.
-struct CalcFlowOut { float f0, f1, vis; };
-__device__ __forceinline__ CalcFlowOut calc_flow_pixel(int b, int p, const float* __restrict__ depth_src,
-                                                       const float* __restrict__ depth_tgt,
-                                                       const float* __restrict__ KT_all, const Mat3& Kinv, float thresh,
-                                                       int standard_rep, int height, int width, float* dsf_out) {
-  const int plane = height * width;
-  const int h = p / width, w = p - h * width;
-  const float* KT = KT_all + b * 12;
-  const float dsf = depth_src[(size_t)b * plane + p];
-  *dsf_out = dsf;
+// calc_flow_core is the one body: visibility and the un-rounded float64 differences pw − w, ph − h (zero where the pixel is
+// not visible, as flow.py:60 leaves them). The label kernels round them to the fp32 tensors they write (calc_flow_pixel); the
+// EPE reduction keeps them in double, as the reference's float64 ground truth is (flow_epe_partial_kernel).
+struct CalcFlowCore { double dw, dh; bool vis; };
+__device__ __forceinline__ CalcFlowCore calc_flow_core(int h, int w, float dsf, const float* __restrict__ KT,
+                                                       const float* __restrict__ depth_tgt_b, const Mat3& Kinv,
+                                                       float thresh, int height, int width) {
+  CalcFlowCore o = {0.0, 0.0, false};
+  if (dsf == 0.f) return o;                 // flow.py:36: only depth_src != 0 can be visible
   const double d = (double)dsf;
   const double rx = (double)Kinv.v[0] * w + (double)Kinv.v[1] * h + (double)Kinv.v[2];
   const double ry = (double)Kinv.v[3] * w + (double)Kinv.v[4] * h + (double)Kinv.v[5];
@@ -116,18 +117,32 @@ __device__ __forceinline__ CalcFlowOut calc_flow_pixel(int b, int p, const float
   const double zp = (double)KT[8] * X + (double)KT[9] * Y + (double)KT[10] * Z + (double)KT[11];
   const double pz = zp + 1e-15;
   const double pw = xp / pz, ph = yp / pz;
-  float vis = 0.f;
-  if (dsf != 0.f) {
-    const long pwr = (long)rint(pw), phr = (long)rint(ph);
-    const bool within = pwr >= 0 && pwr < width && phr >= 0 && phr < height;
-    const long pwc = pwr < 0 ? 0 : (pwr > width - 1 ? width - 1 : pwr);
-    const long phc = phr < 0 ? 0 : (phr > height - 1 ? height - 1 : phr);
-    const double dt = (double)depth_tgt[(size_t)b * plane + phc * width + pwc];
-    if (within && fabs(dt - pz) < (double)thresh && fabs(dt) > 1e-10) vis = 1.f;
+  const long pwr = (long)rint(pw), phr = (long)rint(ph);
+  const bool within = pwr >= 0 && pwr < width && phr >= 0 && phr < height;
+  const long pwc = pwr < 0 ? 0 : (pwr > width - 1 ? width - 1 : pwr);
+  const long phc = phr < 0 ? 0 : (phr > height - 1 ? height - 1 : phr);
+  const double dt = (double)depth_tgt_b[phc * width + pwc];
+  if (within && fabs(dt - pz) < (double)thresh && fabs(dt) > 1e-10) {
+    o.vis = true;
+    o.dw = pw - (double)w;
+    o.dh = ph - (double)h;
   }
-  CalcFlowOut o = {0.f, 0.f, vis};
-  if (vis == 1.f) {
-    const float fw = (float)(pw - (double)w), fh = (float)(ph - (double)h);
+  return o;
+}
+
+struct CalcFlowOut { float f0, f1, vis; };
+__device__ __forceinline__ CalcFlowOut calc_flow_pixel(int b, int p, const float* __restrict__ depth_src,
+                                                       const float* __restrict__ depth_tgt,
+                                                       const float* __restrict__ KT_all, const Mat3& Kinv, float thresh,
+                                                       int standard_rep, int height, int width, float* dsf_out) {
+  const int plane = height * width;
+  const int h = p / width, w = p - h * width;
+  const float dsf = depth_src[(size_t)b * plane + p];
+  *dsf_out = dsf;
+  const CalcFlowCore c = calc_flow_core(h, w, dsf, KT_all + b * 12, depth_tgt + (size_t)b * plane, Kinv, thresh, height, width);
+  CalcFlowOut o = {0.f, 0.f, c.vis ? 1.f : 0.f};
+  if (c.vis) {
+    const float fw = (float)c.dw, fh = (float)c.dh;
     if (standard_rep) { o.f0 = fw; o.f1 = fh; } else { o.f0 = fh; o.f1 = fw; }
   }
   return o;
@@ -167,6 +182,144 @@ __global__ __launch_bounds__(256) void pair_flow_labels_kernel(float* __restrict
   const size_t o0 = ((size_t)b * 2 + 0) * plane + p, o1 = o0 + plane;
   flow[o0] = o.f0; flow[o1] = o.f1;
   weights[o0] = wgt; weights[o1] = wgt;
+}
+
+// Flow EPE of the test loop (deepim/core/tester.py:366-378: par_generate_gt :530-569 + calc_EPE_one_pair :572-589), fused:
+// ground truth from calc_flow_core in double, the prediction rounded to fp16 as tester.py:350-352 casts it (round to nearest
+// even, overflow to ±inf) and widened to double, point_diff = sqrt(dx² + dy²), and the three sums with their pixel counts — no
+// flow tensor is written. Streaming: 4 B (rendered depth) + 8 B (prediction) read per pixel and one 4 B gather of the observed
+// depth where the rendered depth is non-zero. A lane owns four consecutive pixels of one pair: 16-byte loads at dword-aligned
+// addresses (planes of an odd H·W start anywhere), the last H·W % 4 pixels of a pair are a scalar tail; a lane takes 1 … 8 such
+// quads, 256 quads apart. Reduction: lane (pixels in order) → wave (xor shuffles) → block (waves in order, LDS) → one partial per block; flow_epe_finish_kernel adds the
+// partials in a fixed order. No atomics: the same inputs give the same bytes.
+struct alignas(4) Floats4u { float v[4]; };      // four floats at a dword-aligned address: one 16-byte load
+struct EpePartial { double e[3]; long long n[2]; };   // epe_all, epe_viz, epe_vizbg; num_viz, num_vizbg
+
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+__device__ __forceinline__ long long wave_sum(long long v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+__device__ __forceinline__ int wave_sum(int v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+constexpr int EPE_MAX_ITERS = 8;   // quads per lane: the launcher picks 1 … 8 so that a 480x640 pair takes 60 blocks
+
+// grid (ceil(quads / (256·iters)), B), 256 threads. Block x owns the quads [x·256·iters, (x + 1)·256·iters) of its pair and walks
+// them in `iters` coalesced steps of 256 quads, so that the reduction below is paid once per 4·iters pixels of a lane.
+__global__ __launch_bounds__(256) void flow_epe_partial_kernel(EpePartial* __restrict__ partials,
+                                                               const float* __restrict__ flow_est,
+                                                               const float* __restrict__ depth_src,
+                                                               const float* __restrict__ depth_tgt,
+                                                               const float* __restrict__ KT_all, Mat3 Kinv,
+                                                               const int32_t* __restrict__ skip, float thresh,
+                                                               int standard_rep, int height, int width, int iters) {
+  const int b = blockIdx.y;
+  if (skip && skip[b] != 0) return;          // block-uniform: the finish pass writes the zero row
+  const int plane = height * width;
+  const float* KT = KT_all + b * 12;
+  const float* tgt = depth_tgt + (size_t)b * plane;
+  double e_all = 0.0, e_viz = 0.0, e_vizbg = 0.0;
+  int n_viz = 0, n_vizbg = 0;                // at most 4 · EPE_MAX_ITERS per lane
+  for (int it = 0; it < iters; ++it) {
+    const int p0 = ((blockIdx.x * iters + it) * 256 + threadIdx.x) * 4;
+    if (p0 >= plane) break;
+    const int cnt = min(4, plane - p0);
+    const float* ds_p = depth_src + (size_t)b * plane + p0;
+    const float* e0_p = flow_est + (size_t)b * 2 * plane + p0;
+    const float* e1_p = e0_p + plane;
+    float ds[4] = {0.f, 0.f, 0.f, 0.f}, e0[4] = {0.f, 0.f, 0.f, 0.f}, e1[4] = {0.f, 0.f, 0.f, 0.f};
+    if (cnt == 4) {
+      const Floats4u a = *reinterpret_cast<const Floats4u*>(ds_p);
+      const Floats4u x = *reinterpret_cast<const Floats4u*>(e0_p);
+      const Floats4u y = *reinterpret_cast<const Floats4u*>(e1_p);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) { ds[j] = a.v[j]; e0[j] = x.v[j]; e1[j] = y.v[j]; }
+    } else {
+      for (int j = 0; j < cnt; ++j) { ds[j] = ds_p[j]; e0[j] = e0_p[j]; e1[j] = e1_p[j]; }
+    }
+    int h = p0 / width, w = p0 - h * width;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (j < cnt) {
+        const CalcFlowCore c = calc_flow_core(h, w, ds[j], KT, tgt, Kinv, thresh, height, width);
+        // channel 0 of the prediction against channel 0 of the ground truth: [pw − w, ph − h] with standard_rep, else [ph − h, pw − w]
+        const double g0 = standard_rep ? c.dw : c.dh, g1 = standard_rep ? c.dh : c.dw;
+        const double dx = g0 - (double)(float)(_Float16)e0[j];
+        const double dy = g1 - (double)(float)(_Float16)e1[j];
+        const double diff = sqrt(dx * dx + dy * dy);
+        e_all += diff;
+        if (c.vis) { e_viz += diff; ++n_viz; }
+        if (c.vis || ds[j] == 0.f) { e_vizbg += diff; ++n_vizbg; }   // visible or bg = (visible == 0 && depth_rendered == 0)
+        if (++w == width) { w = 0; ++h; }
+      }
+    }
+  }
+  e_all = wave_sum(e_all); e_viz = wave_sum(e_viz); e_vizbg = wave_sum(e_vizbg);
+  n_viz = wave_sum(n_viz); n_vizbg = wave_sum(n_vizbg);
+  __shared__ EpePartial sh[4];
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) {
+    sh[wave].e[0] = e_all; sh[wave].e[1] = e_viz; sh[wave].e[2] = e_vizbg;
+    sh[wave].n[0] = n_viz; sh[wave].n[1] = n_vizbg;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    EpePartial r = sh[0];
+    for (int i = 1; i < 4; ++i) {
+      for (int k = 0; k < 3; ++k) r.e[k] += sh[i].e[k];
+      for (int k = 0; k < 2; ++k) r.n[k] += sh[i].n[k];
+    }
+    partials[(size_t)b * gridDim.x + blockIdx.x] = r;
+  }
+}
+
+// one block of four waves. Wave v takes the pairs v, v + 4, …: lane l adds the partials l, l + 64, … in order, then the xor
+// tree; row = {epe_all, num_all, epe_viz, num_viz, epe_vizbg, num_vizbg} (zeros for a skipped pair). After every round of four
+// pairs thread 0 adds their rows, in pair order, to the running totals.
+__global__ __launch_bounds__(256) void flow_epe_finish_kernel(double* __restrict__ out, double* __restrict__ totals,
+                                                              const EpePartial* __restrict__ partials,
+                                                              const int32_t* __restrict__ skip, int nblk, int B, int plane) {
+  __shared__ double rows[4][6];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  double t[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  if (totals && threadIdx.x == 0)
+    for (int k = 0; k < 6; ++k) t[k] = totals[k];
+  for (int b0 = 0; b0 < B; b0 += 4) {
+    const int b = b0 + wave;
+    if (b < B) {
+      const bool skipped = skip && skip[b] != 0;
+      double e[3] = {0.0, 0.0, 0.0};
+      long long n[2] = {0, 0};
+      if (!skipped)
+        for (int i = lane; i < nblk; i += 64) {
+          const EpePartial q = partials[(size_t)b * nblk + i];
+          for (int k = 0; k < 3; ++k) e[k] += q.e[k];
+          for (int k = 0; k < 2; ++k) n[k] += q.n[k];
+        }
+      for (int k = 0; k < 3; ++k) e[k] = wave_sum(e[k]);
+      for (int k = 0; k < 2; ++k) n[k] = wave_sum(n[k]);
+      if (lane == 0) {
+        const double r[6] = {e[0], skipped ? 0.0 : (double)plane, e[1], (double)n[0], e[2], (double)n[1]};
+        for (int k = 0; k < 6; ++k) { rows[wave][k] = r[k]; out[(size_t)b * 6 + k] = r[k]; }
+      }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0)
+      for (int i = 0; i < 4 && b0 + i < B; ++i)
+        for (int k = 0; k < 6; ++k) t[k] += rows[i][k];
+    __syncthreads();
+  }
+  if (totals && threadIdx.x == 0)
+    for (int k = 0; k < 6; ++k) totals[k] = t[k];
 }
 
 // image.py:381-387: mask_rendered = depth_rendered with every value > thresh set to 1 (smaller values are KEPT, not zeroed;
@@ -423,6 +576,38 @@ extern "C" int deepim_pair_flow_labels(deepim_ctx* ctx, float* flow, float* flow
   dim3 grid(di_div_up((long)W * H, 256), B);
   hipLaunchKernelGGL(pair_flow_labels_kernel, grid, dim3(256), 0, ctx->stream, flow, flow_weights, depth_rendered,
                      depth_observed, KT, Kinv, thresh, standard_rep, weight_type, H, W);
+  DI_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int deepim_flow_epe(deepim_ctx* ctx, double* out, double* totals, const float* flow_est,
+                               const float* depth_rendered, const float* depth_observed, const float* pose_rendered,
+                               const float* pose_observed, const float* K_host, const int32_t* skip, float thresh,
+                               int standard_rep, int B, int H, int W) {
+  DI_DEVICE(ctx);
+  DI_REQUIRE(B >= 0 && H > 0 && W > 0, "flow_epe: bad shape");
+  DI_REQUIRE(B <= 65535, "flow_epe: batch too large");
+  DI_REQUIRE((long)H * W <= (1L << 30), "flow_epe: frame too large");
+  if (B == 0) return 0;
+  const int plane = H * W;
+  const int quads = di_div_up(plane, 4);
+  const int iters = std::min(EPE_MAX_ITERS, std::max(1, di_div_up(quads, 64 * 256)));   // 480x640: 5, so 60 blocks per pair
+  const int nblk = di_div_up(quads, 256 * iters);
+  // scratch: K·T of the batch, then one partial per block (grows only outside a capture, deepim_scratch)
+  void* scratch;
+  int rc = deepim_scratch(ctx, (size_t)B * 48 + (size_t)B * nblk * sizeof(EpePartial), &scratch);
+  if (rc) return rc;
+  float* KT = (float*)scratch;
+  EpePartial* partials = (EpePartial*)((char*)scratch + (size_t)B * 48);
+  rc = deepim_calc_KT(ctx, KT, pose_rendered, pose_observed, K_host, B);   // np.matmul(K, se3_mul(tgt, se3_inverse(src))), f32
+  if (rc) return rc;
+  double kinv[9];
+  inv3d(K_host, kinv);                    // np.linalg.inv(np.matrix(K)): float32 result for a float32 K
+  Mat3 Kinv;
+  for (int i = 0; i < 9; ++i) Kinv.v[i] = (float)kinv[i];
+  hipLaunchKernelGGL(flow_epe_partial_kernel, dim3(nblk, B), dim3(256), 0, ctx->stream, partials, flow_est, depth_rendered,
+                     depth_observed, KT, Kinv, skip, thresh, standard_rep, H, W, iters);
+  hipLaunchKernelGGL(flow_epe_finish_kernel, dim3(1), dim3(256), 0, ctx->stream, out, totals, partials, skip, nblk, B, plane);
   DI_LAUNCH_CHECK();
   return 0;
 }

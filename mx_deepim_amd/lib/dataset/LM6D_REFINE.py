@@ -40,9 +40,13 @@ def _turn_z(poses):
 
 
 class LM6D_REFINE(object):
-    def __init__(self, classes, points, diameters, ctx=None, logger=None):
+    def __init__(self, classes, points, diameters, ctx=None, logger=None, name=None, result_path=None):
         """classes: list of names; points: name → (N,3) model points; diameters: name → metres.
-        ctx: runtime.Context for the device metrics (default: device 0, created on first use)."""
+        ctx: runtime.Context for the device metrics (default: device 0, created on first use).
+        name, result_path: the imdb's name and result directory, as the test loop reads them for its result cache
+        `<result_path>/<name>_pose_iter<N>.pkl` and the plot directories (deepim/core/tester.py:62-79)."""
+        self.name = name
+        self.result_path = result_path
         self.classes = list(classes)
         self.num_classes = len(self.classes)
         self._points = points
