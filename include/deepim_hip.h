@@ -978,6 +978,26 @@ int deepim_ingest_label_mask(deepim_ctx* ctx, float* out /*B,1,H,W*/, const uint
 int deepim_mask_dilate(deepim_ctx* ctx, float* out /*B,1,H,W*/, const float* mask /*B,1,H,W*/,
                        const int32_t* thickness /*device (B,4)*/, int B, int H, int W);
 
+/* ------------------------------------------------ training metrics (csrc/metric.hip) -- */
+/* The sums the reference's metrics take on the host once per batch (deepim/core/metric.py:51-137), as one fused reduction.
+ * Slot order: 0 flow_loss, 1 rot_loss, 2 trans_loss, 3 point_matching_loss, 4 mask. Slots 0-3 are the plain sum of the tensor's
+ * n floats; slot 4 is the sum over n_mask pixels of -(g*log(p + 1e-19) + (1 - g)*log(1 - p + 1e-19)) (:135) with p = mask_prob,
+ * g = mask_gt, every operation of the element in float32 as numpy evaluates it on float32 inputs (p == 1 gives log(1e-19f)),
+ * logf on the device. Every accumulation is in double. step (5 doubles or NULL) is overwritten with the sums of this call;
+ * totals (5 doubles or NULL) receives totals[s] += step[s]. A NULL tensor leaves its slot of totals untouched and writes 0 into
+ * step; mask_prob and mask_gt are both NULL or both set; n == 0 is legal. The tensors need only be 4-byte aligned. Partials are
+ * combined in a fixed order without atomics: the same inputs give the same bytes. Asynchronous on the context's stream, never
+ * synchronises the host, two launches whatever the sizes; scratch grows on a first call only, outside a capture; legal inside
+ * deepim_graph_begin/end after one eager call. */
+int deepim_train_metrics(deepim_ctx* ctx, double* totals /*5, accumulated; or NULL*/, double* step /*5, overwritten; or NULL*/,
+                         const float* flow_loss, long n_flow, const float* rot_loss, long n_rot,
+                         const float* trans_loss, long n_trans, const float* pm_loss, long n_pm,
+                         const float* mask_prob, const float* mask_gt, long n_mask);
+/* out[r] = the 2-norm of row r of `table`, a DEVICE array of rows x {pointer to floats (4-byte aligned), count}: the weight-norm
+ * line of deepim/core/module.py:1113-1122 without a read-back per parameter. Squares and sums in double, sqrtf of the sum rounded
+ * to float; fixed order, no atomics. Asynchronous; scratch (rows x 2 KB) grows outside a capture only. rows <= 65535. */
+int deepim_l2_norms_multi(deepim_ctx* ctx, float* out /*rows*/, const uint64_t* table /*rows x {ptr, count}*/, int rows);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,6 +33,7 @@ X3_SCALE_WINDOW_DEFAULT = 1000
 
 def default_config():
     cfg = AttrDict()
+    cfg.default = AttrDict(frequent=1000)   # config.py:21 — Speedometer's interval (train.py:241 passes args.frequent)
     cfg.dataset = AttrDict(
         INTRINSIC_MATRIX=np.array([[572.4114, 0, 325.2611], [0, 573.57043, 242.04899], [0, 0, 1]], dtype=np.float32),
         NORMALIZE_FLOW=20.0,
@@ -70,6 +71,10 @@ def default_config():
     # and hands them over in the batch as "mask_dilate_thickness"; the shifted ORs run on the device, deepim_mask_dilate)
     cfg.TRAIN = AttrDict(INIT_MASK="box_gt", FLOW_WEIGHT_TYPE="viz", MASK_DILATE=False,
                          optimizer="sgd", lr=0.0001, momentum=0.975, wd=0.0005,   # config.py:68-77
+                         # the keys the training loop reads (core/module.py fit; config.py:69-84): the schedule, the epochs and resume;
+                         # VISUALIZE and TENSORBOARD_LOG are refused when set
+                         warmup=False, warmup_lr=0, warmup_step=0, begin_epoch=0, end_epoch=0, lr_step="4, 6", RESUME=False,
+                         VISUALIZE=False, TENSORBOARD_LOG=False,
                          # mixed-precision training (network.FP16_CONV in the training graph; not reference keys): the initial loss
                          # scale (a power of two) and the number of overflow-free steps after which it doubles
                          FP16_LOSS_SCALE=FP16_LOSS_SCALE_DEFAULT, FP16_SCALE_WINDOW=FP16_SCALE_WINDOW_DEFAULT,

@@ -1406,7 +1406,8 @@ def _train_methods():
         weights, mask_rendered = depth > 0.2 — all resident, nothing allocated inside the loop, no host round trip.
         data must also carry tgt_pose [, depth_gt_observed with PRED_FLOW, class_index]; `updater` = batchUpdaterPyMulti with a
         device render machine. `on_iter(it, data, label)` is called after each iteration's update (tests, timers).
-        Returns (data, label) of the last iteration."""
+        `lr` is a float, or a callable lr(it) giving the learning rate of iteration `it`'s update (core/module.py fit hands the
+        scheduler's value per update, as mx.optimizer asks its lr_scheduler). Returns (data, label) of the last iteration."""
         t = self.cfg.TRAIN
         iters = int(iters or self.cfg.network.TRAIN_ITER_SIZE)
         lr = t.lr if lr is None else lr
@@ -1423,7 +1424,7 @@ def _train_methods():
             self.forward_train(data, label)
             self.backward()
             preds = {"rot_est": A["rot_norm"], "trans_est": A["trans_est"]}     # get_outputs() before update(), as :1133-1134
-            self.update(lr, wd, momentum, rescale_grad=rescale)
+            self.update(lr(it) if callable(lr) else lr, wd, momentum, rescale_grad=rescale)
             if on_iter is not None:
                 on_iter(it, data, label)
             if it != iters - 1:
@@ -1433,6 +1434,20 @@ def _train_methods():
                 data = {k: new[k] for k in data}
                 label = {k: new[k] for k in label}
         return data, label
+
+    def train_outputs(self):
+        """The outputs of the last forward_train that the training metrics read (core/metric.py), under the reference's output
+        names (deepim/core/metric.py:13-48): views of self.act, nothing is copied."""
+        A, out = self.act, {}
+        if self.with_flow_head:
+            out["flow_loss"] = A["flow_loss"]
+        if self.se3_dist_loss:
+            out["rot_loss"], out["trans_loss"] = A["rot_loss"], A["trans_loss"]
+        if self.se3_pm_loss:
+            out["point_matching_loss"] = A["pm_loss"]
+        if self.with_mask_head:
+            out["mask_prob"], out["mask_gt"] = A["mask_prob"], A["zoom_mask_gt_observed"]
+        return out
 
     def optimizer_states(self):
         """The optimizer's state as host arrays, the resume half of module_checkpoint(..., save_optimizer_states=True) (train.py:242):
@@ -1480,7 +1495,7 @@ def _train_methods():
                 _small_conv_backward=_small_conv_backward, _head_conv_backward=_head_conv_backward,
                 _repack_train_winograd=_repack_train_winograd,
                 _deconv_backward=_deconv_backward, _decoder_backward=_decoder_backward, backward=backward, update=update, train_step=train_step,
-                optimizer_states=optimizer_states, load_optimizer_states=load_optimizer_states,
+                train_outputs=train_outputs, optimizer_states=optimizer_states, load_optimizer_states=load_optimizer_states,
                 _train_pack_orders=_train_pack_orders)
 
 
