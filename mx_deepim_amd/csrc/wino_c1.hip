@@ -38,6 +38,24 @@
 //     spans 10 input rows, a tile row 4) are read into its L2 once.
 #include "common.h"
 
+// dev switches for measuring the parts alone (SRC=wino_c1 tools/build_variants_f16.sh); the shipped build has one path
+#ifndef C1_UDEEP
+#define C1_UDEEP 2   // U operands a step requests ahead, see c1_udepth: 0 = C1_D in every step; 1 = all nine only in the step behind the
+#endif               // wave's own input loads; 2 = all nine in every nine-pair step
+#ifndef C1_PIN
+#define C1_PIN 1     // 0: the compiler may move instructions across the two barriers of a tile block
+#endif
+// dev builds (-DC1_TRACE=1, tools/c1_trace.py): the eight waves of one block in the middle of the grid sum the s_memtime ticks of
+// their step segments (C1Tr below). A stamp is subtracted one segment after it was requested, so the scalar wait is free. Stamps
+// cost issue slots and make the next LDS wait a full one: for attribution only, timings come from unstamped builds.
+#ifndef C1_TRACE
+#define C1_TRACE 0
+#endif
+
+#if C1_TRACE
+__device__ unsigned* g_c1_trace = nullptr;   // [wave][16]: the 13 segment sums, tile blocks walked, total ticks
+#endif
+
 namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -101,6 +119,28 @@ struct C1Params {
   int out_s2d;          // 1: NC8 in space-to-depth order; 0: plain NC8
   float slope;
   unsigned in_bytes;
+};
+
+// segment K ends at stamp K; the stamps of a tile block, in order:
+//   step 0:  0 finish | 1 the first C1_D pairs | 2 pair C1_D (the first whose U the loop requested, where there is one) | 3 the other
+//            pairs | 4 transform of row phase 1, U prefetch, input loads | 5 barrier
+//   step 1:  6 transform of row phase 0 | 7, 8, 9 as 1, 2, 3 | 10 nu-pass and exchange | 11 U prefetch, input loads | 12 barrier
+struct C1Tr {
+#if C1_TRACE
+  unsigned seg[13], a, b;
+  template <int K>
+  __device__ __forceinline__ void stamp() {
+    __builtin_amdgcn_sched_barrier(0);
+    const unsigned t = (unsigned)__builtin_amdgcn_s_memtime();
+    __builtin_amdgcn_sched_barrier(0);
+    seg[(K + 12) % 13] += b - a;   // the segment that ended one stamp ago
+    a = b;
+    b = t;
+  }
+#else
+  template <int K>
+  __device__ __forceinline__ void stamp() {}
+#endif
 };
 
 // one row of B^T applied to a 5-vector; OUT = which output (compile-time)
@@ -179,24 +219,34 @@ __device__ __forceinline__ void c1_transform(const float (&raw)[5][10], char* sm
   }
 }
 
-// U of role R's first C1_D pairs in row phase PY: issued at the end of the step before, ahead of the transform's input loads (vmcnt
-// is in order: a U load issued behind them would wait for HBM)
+// U operands requested ahead of their use. vmcnt is in order, so a U load issued behind a transform job's input loads (HBM misses)
+// waits for them, and the CU's vector memory path serves its waves in order too: behind ANOTHER wave's input loads a U load waits
+// as long (R2 / R3 measured 1 800 cycles on the first U their row phase 0 loop requested, right after R0 / R1's input loads). So a
+// step of nine pairs — row phase 0 in every role, row phase 1 in R2 / R3, all on five accumulator tuples — requests all nine
+// operands (36 registers) at the end of the step before, ahead of the wave's input loads and, for R2 / R3, of the barrier the others
+// reach thousands of cycles later. R0 / R1's row phase 1 (14 / 13 pairs on 8 / 7 tuples) requests C1_D there and the rest inside its
+// MFMA loop: its own input loads come after that loop and R2 / R3's were issued a whole transform earlier.
 constexpr int C1_D = 3;
+constexpr int C1_UMAX = C1_UDEEP ? 9 : C1_D;
+__host__ __device__ constexpr int c1_udepth(int R, int PY) {
+  return C1_UDEEP == 2 ? (c1_entries(R, PY).n <= C1_UMAX ? C1_UMAX : C1_D) : C1_UDEEP && PY == (R >= 2) ? C1_UMAX : C1_D;
+}
 template <int R, int PY>
-__device__ __forceinline__ void c1_upre(f32x4 (&ua)[C1_D], const __amdgpu_buffer_rsrc_t rsrw, int lane) {
+__device__ __forceinline__ void c1_upre(f32x4 (&ua)[C1_UMAX], const __amdgpu_buffer_rsrc_t rsrw, int lane) {
   constexpr C1Entries E = c1_entries(R, PY);
+  static_assert(c1_udepth(R, PY) == C1_D || E.n <= C1_UMAX, "a deep step requests every U operand ahead");
 #pragma unroll
-  for (int e = 0; e < C1_D; ++e)
+  for (int e = 0; e < c1_udepth(R, PY); ++e)
     if (e < E.n) ua[e] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrw, lane * 16, E.pair[e] * 1024, 0));
 }
 
-// the MFMAs of role R in row phase PY: per pair one 16-byte U load (rsrw: this channel half's U) and one ds_read_b128 of V, both
-// issued C1_D pairs ahead of their use (ua: the first C1_D pairs' U, from c1_upre)
+// the MFMAs of role R in row phase PY: per pair one 16-byte U load (rsrw: this channel half's U) and one ds_read_b128 of V, issued
+// c1_udepth and C1_D pairs ahead of their use (ua: the first c1_udepth pairs' U, from c1_upre)
 template <int R, int PY>
 __device__ __forceinline__ void c1_mfma(f32x16 (&acc)[8], const char* smem, const __amdgpu_buffer_rsrc_t rsrw, int lane,
-                                        f32x4 (&ua)[C1_D]) {
+                                        f32x4 (&ua)[C1_UMAX], C1Tr& tr) {
   constexpr C1Entries E = c1_entries(R, PY);
-  constexpr int D = C1_D;
+  constexpr int D = C1_D, DU = c1_udepth(R, PY);
   const char* const vr = smem + (PY ? C1_V1 : 0) + lane * 16;
   f32x4 va[D];
   const f32x16 zero = {};
@@ -205,17 +255,18 @@ __device__ __forceinline__ void c1_mfma(f32x16 (&acc)[8], const char* smem, cons
     if (e < E.n) va[e] = *reinterpret_cast<const f32x4*>(vr + (E.pair[e] - (PY ? C1_PY1 : 0)) * 1024);
 #pragma unroll
   for (int e = 0; e < E.n; ++e) {
-    const int s = e % D;
+    const int s = e % D, su = e % DU;
     f32x16 c = E.first[e] ? zero : acc[E.q[e]];
-    c = __builtin_amdgcn_mfma_f32_32x32x2f32(ua[s].x, va[s].x, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x2f32(ua[s].y, va[s].y, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x2f32(ua[s].z, va[s].z, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x2f32(ua[s].w, va[s].w, c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_32x32x2f32(ua[su].x, va[s].x, c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_32x32x2f32(ua[su].y, va[s].y, c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_32x32x2f32(ua[su].z, va[s].z, c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_32x32x2f32(ua[su].w, va[s].w, c, 0, 0, 0);
     acc[E.q[e]] = c;
-    if (e + D < E.n) {
-      ua[s] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrw, lane * 16, E.pair[e + D] * 1024, 0));
-      va[s] = *reinterpret_cast<const f32x4*>(vr + (E.pair[e + D] - (PY ? C1_PY1 : 0)) * 1024);
-    }
+    if (e + DU < E.n)
+      ua[su] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrw, lane * 16, E.pair[e + DU] * 1024, 0));
+    if (e + D < E.n) va[s] = *reinterpret_cast<const f32x4*>(vr + (E.pair[e + D] - (PY ? C1_PY1 : 0)) * 1024);
+    if (e == D - 1) tr.template stamp<PY ? 7 : 1>();
+    if (e == D) tr.template stamp<PY ? 8 : 2>();
   }
 }
 
@@ -287,7 +338,7 @@ __device__ __forceinline__ void c1_finish(const f32x16 (&keep)[2], const char* x
 
 // one role's whole walk over the block's tile blocks. Step 0 of a tile block: MFMAs of row phase 0 (R0 / R1 first finish the previous
 // tile block's output; R2 / R3 then transform this tile block's row phase 1). Step 1: R0 / R1 transform the next tile block's row
-// phase 0; MFMAs of row phase 1; nu-pass and exchange. At the end of a step a wave requests the next step's first U operands and
+// phase 0; MFMAs of row phase 1; nu-pass and exchange. At the end of a step a wave requests the next step's U operands (c1_udepth of them) and
 // then its next transform job's input (one and a half steps ahead), and every wave passes one barrier. No load is conditional: past
 // the last tile block the input loads are out of range (zeros, no traffic), so the compiler's vmcnt waits stay counted.
 template <int VEC, int R>
@@ -320,7 +371,7 @@ __device__ __forceinline__ void c1_body(const C1Params& p, char* smem, const int
   if (threadIdx.x < 64) reinterpret_cast<float*>(smem + C1_BIAS)[threadIdx.x] = p.bias ? p.bias[threadIdx.x] : 0.f;
   float raw[5][10];
   f32x16 acc[8], keep[2];
-  f32x4 ua[C1_D];
+  f32x4 ua[C1_UMAX];
   load(raw, item);
   if constexpr (TPY == 0) {
     c1_transform<0>(raw, smem, vbase);
@@ -330,26 +381,57 @@ __device__ __forceinline__ void c1_body(const C1Params& p, char* smem, const int
     c1_upre<R, 0>(ua, rsrw, lane);
   }
   __syncthreads();
+  C1Tr tr;
+#if C1_TRACE
+  for (int k = 0; k < 13; ++k) tr.seg[k] = 0;
+  const unsigned tr_t0 = tr.a = tr.b = (unsigned)__builtin_amdgcn_s_memtime();
+  unsigned tr_n = 0;
+#endif
   int prev = -1;
   for (;;) {
     const int next = item + nslot;
     if constexpr (R < 2)
       if (prev >= 0) c1_finish<R>(keep, xr, bl, p, prev, half, lane);
-    c1_mfma<R, 0>(acc, smem, rsrw, lane, ua);
+    tr.template stamp<0>();
+    c1_mfma<R, 0>(acc, smem, rsrw, lane, ua, tr);
+    tr.template stamp<3>();
     if constexpr (TPY == 1) c1_transform<1>(raw, smem, vbase);
     c1_upre<R, 1>(ua, rsrw, lane);
     if constexpr (TPY == 1) load(raw, next);
+    tr.template stamp<4>();
     __syncthreads();
+    // nothing moves up across a barrier: the compiler otherwise starts R0 / R1's transform among the MFMAs of the step before, whose
+    // second MFMA then waits for the input loads issued a moment earlier. (VEC = 0 keeps the compiler's order: with its 50 scalar
+    // input loads in flight the pinned stream does not fit 256 registers.)
+    if (C1_PIN && VEC) __builtin_amdgcn_sched_barrier(0);
+    tr.template stamp<5>();
     if constexpr (TPY == 0) c1_transform<0>(raw, smem, vbase);   // past the last tile block: zeros nobody reads
-    c1_mfma<R, 1>(acc, smem, rsrw, lane, ua);
+    tr.template stamp<6>();
+    c1_mfma<R, 1>(acc, smem, rsrw, lane, ua, tr);
+    tr.template stamp<9>();
     c1_send<R>(acc, keep, xw);
+    tr.template stamp<10>();
     c1_upre<R, 0>(ua, rsrw, lane);
     if constexpr (TPY == 0) load(raw, next + nslot);
+    tr.template stamp<11>();
     __syncthreads();
+    if (C1_PIN && VEC) __builtin_amdgcn_sched_barrier(0);
+    tr.template stamp<12>();
+#if C1_TRACE
+    ++tr_n;
+#endif
     prev = item;
     if (next >= end) break;
     item = next;
   }
+#if C1_TRACE
+  if (g_c1_trace && blockIdx.x == gridDim.x / 2 && lane == 0) {
+    tr.seg[12] += tr.b - tr.a;
+    unsigned* const o = g_c1_trace + wave * 16;
+    for (int k = 0; k < 13; ++k) o[k] = tr.seg[k];
+    o[13] = tr_n; o[14] = tr.b - tr_t0;
+  }
+#endif
   if constexpr (R < 2) c1_finish<R>(keep, xr, bl, p, prev, half, lane);
 }
 
@@ -395,6 +477,13 @@ __global__ void pack_conv1_wino_kernel(float* __restrict__ packed, const float* 
 }
 
 }  // namespace
+
+#if C1_TRACE
+extern "C" int deepim_dev_c1_trace(void* buf) {
+  unsigned* b = (unsigned*)buf;
+  return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_c1_trace), &b, sizeof(b));
+}
+#endif
 
 extern "C" size_t deepim_conv1_wino_packed_size(void) { return (size_t)C1_PACKED_FLOATS * sizeof(float); }
 

@@ -154,3 +154,43 @@ for name, cin, H, W, cout in [("conv4", 256, 60, 80, 512), ("conv5", 512, 30, 40
     fle = 2.0 * cout * cin * 25 * B * ((Ho + 1) // 2) * ((Wo + 1) // 2)
     print("%-8s B %2d: direct %.3f ms %5.1f TF | winograd over space-to-depth %.3f ms  %5.1f TF algorithmic, %5.1f TF executed | x%.2f | max diff %.1e of range | other block shape %.3f ms"
           % (name, B, d, fl / d / 1e9, wv, fl / wv / 1e9, fle / wv / 1e9, d / wv, err, wo))
+# conv1 (7x7 stride 2, 8 -> 64) on its Winograd kernel over the four input phases (csrc/wino_c1.hip), B = 4, 8, 32 at 480 x 640 into the
+# space-to-depth NC8 layout conv2 reads. WINO_LIB2=<path of a second libdeepim_hip.so> times that build's kernel in the same process,
+# interleaved with this one's, and compares the two outputs bit for bit.
+if not ONLY or "conv1" in ONLY:
+    lib2 = None
+    if os.environ.get("WINO_LIB2"):
+        lib2 = ctypes.CDLL(os.environ["WINO_LIB2"], mode=os.RTLD_LOCAL | os.RTLD_DEEPBIND)
+        lib2.deepim_conv1_wino_forward.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_int] * 3 + [cf, ctypes.c_int]
+    H, W = 480, 640
+    w = (rng.standard_normal((64, 8, 7, 7)) / np.sqrt(8 * 49)).astype(np.float32)
+    pw = DeviceArray(ctx, (lib.load().deepim_conv1_wino_packed_size() // 4,))
+    lib.deepim_conv1_wino_pack_weights(ctx.handle, pw, ctx.array(w))
+    bias = ctx.array(rng.standard_normal(64).astype(np.float32))
+    for b in (4, 8, 32):
+        n = b * 8 * H * W
+        x = ctx.array(np.resize(rng.standard_normal(min(n, 1 << 24)).astype(np.float32), n).reshape(b, 8, H, W))
+        o1, o2 = ctx.empty((b, 64, H // 2, W // 2)), ctx.empty((b, 64, H // 2, W // 2))
+        this = lambda: lib.deepim_conv1_wino_forward(ctx.handle, o1, x, pw, bias, b, H, W, cf(0.1), 3)
+        def other():
+            rc = lib2.deepim_conv1_wino_forward(ctx.handle, ctypes.c_void_p(o2.ptr), ctypes.c_void_p(x.ptr), ctypes.c_void_p(pw.ptr),
+                                                ctypes.c_void_p(bias.ptr), b, H, W, cf(0.1), 3)
+            assert rc == 0, rc
+        fns = [("this", this)] + ([("other", other)] if lib2 else [])
+        ts = {}
+        for r in range(ROUNDS):
+            for key, fn in fns:
+                fn()
+                t = ctx.timer(); t.start()
+                for _ in range(REPS):
+                    fn()
+                t.stop()
+                ts.setdefault(key, []).append(t.elapsed_ms() / REPS)
+        wv = float(np.median(ts["this"]))
+        fl = 2.0 * 64 * 8 * 49 * (H // 2) * (W // 2) * b
+        fle = 2.0 * 64 * 8 * 81 * b * (H // 4) * (W // 4)
+        line = "conv1    B %2d: winograd over four phases %.3f ms  %5.1f TF algorithmic, %5.1f TF executed" % (b, wv, fl / wv / 1e9, fle / wv / 1e9)
+        if lib2:
+            wo = float(np.median(ts["other"]))
+            line += " | second library %.3f ms (x%.3f) | outputs %s" % (wo, wo / wv, "bit-identical" if np.array_equal(o1.asnumpy(), o2.asnumpy()) else "DIFFER")
+        print(line)
