@@ -222,13 +222,14 @@ __device__ void sym4_max_eigvec(double A[4][4], double* vec) {
 
 // mat2quat (RT_transform.py:432-509) of a float32 3x3: float64 quaternion, w >= 0
 __device__ void mat2quat_f64(const float* Rd, double* q) {
-  // K from the 3x3 (Q_ab = contribution of input a to output b = M[b][a])
-  const double Qxx = Rd[0], Qyx = Rd[1], Qzx = Rd[2], Qxy = Rd[3], Qyy = Rd[4], Qzy = Rd[5], Qxz = Rd[6], Qyz = Rd[7],
-               Qzz = Rd[8];
-  double K[4][4] = {{Qxx - Qyy - Qzz, Qyx + Qxy, Qzx + Qxz, Qyz - Qzy},
-                    {Qyx + Qxy, Qyy - Qxx - Qzz, Qzy + Qyz, Qzx - Qxz},
-                    {Qzx + Qxz, Qzy + Qyz, Qzz - Qxx - Qyy, Qxy - Qyx},
-                    {Qyz - Qzy, Qzx - Qxz, Qxy - Qyx, Qxx + Qyy + Qzz}};
+  // K from the 3x3 (Q_ab = contribution of input a to output b = M[b][a]). The entries are sums of float32 scalars (M.flat
+  // of a float32 matrix, :488-500) and so float32 themselves; float64 starts at the `/ 3.0` of the assembled array
+  const float Qxx = Rd[0], Qyx = Rd[1], Qzx = Rd[2], Qxy = Rd[3], Qyy = Rd[4], Qzy = Rd[5], Qxz = Rd[6], Qyz = Rd[7],
+              Qzz = Rd[8];
+  double K[4][4] = {{(Qxx - Qyy) - Qzz, Qyx + Qxy, Qzx + Qxz, Qyz - Qzy},
+                    {Qyx + Qxy, (Qyy - Qxx) - Qzz, Qzy + Qyz, Qzx - Qxz},
+                    {Qzx + Qxz, Qzy + Qyz, (Qzz - Qxx) - Qyy, Qxy - Qyx},
+                    {Qyz - Qzy, Qzx - Qxz, Qxy - Qyx, (Qxx + Qyy) + Qzz}};
   for (int i = 0; i < 4; ++i)
     for (int j = 0; j < 4; ++j) K[i][j] /= 3.0;
   double v[4];
@@ -579,14 +580,17 @@ __global__ __launch_bounds__(256) void pose_error_kernel(float* __restrict__ out
   if (tid == 0) {
     double tot[3];
     for (int i = 0; i < 3; ++i) tot[i] = ((red[0][i] + red[1][i]) + (red[2][i] + red[3][i])) / N;
-    // re: angle of R_est^T R_gt; te: ||t_gt - t_est||
-    double tr = 0.0;
+    // re: angle of M = R_est^T R_gt (the reference takes ||logm(M)||_F / sqrt 2); te: ||t_gt - t_est||.
+    // atan2(sin, cos) from the antisymmetric part and the trace: float32 rotations are orthonormal only to ~1e-7, which
+    // acos of the trace alone turns into percents of a 1e-3 rad angle and into 0.01 degrees next to 0 and 180 degrees
+    double M[3][3];
     for (int i = 0; i < 3; ++i)
-      for (int j = 0; j < 3; ++j) tr += Ed[j * 4 + i] * Gd[j * 4 + i];
-    const double c = fmin(1.0, fmax(-1.0, (tr - 1.0) * 0.5));
+      for (int j = 0; j < 3; ++j) M[i][j] = (Ed[i] * Gd[j] + Ed[4 + i] * Gd[4 + j]) + Ed[8 + i] * Gd[8 + j];
+    const double c = ((M[0][0] + M[1][1] + M[2][2]) - 1.0) * 0.5;
+    const double sx = (M[2][1] - M[1][2]) * 0.5, sy = (M[0][2] - M[2][0]) * 0.5, sz = (M[1][0] - M[0][1]) * 0.5;
     const double dtx = Gd[3] - Ed[3], dty = Gd[7] - Ed[7], dtz = Gd[11] - Ed[11];
     float* o = out + b * 5;
-    o[0] = (float)(acos(c) * 180.0 / 3.141592653589793);
+    o[0] = (float)(atan2(sqrt((sx * sx + sy * sy) + sz * sz), c) * 180.0 / 3.141592653589793);
     o[1] = (float)sqrt(dtx * dtx + dty * dty + dtz * dtz);
     o[2] = (float)tot[0];
     o[3] = (float)tot[1];

@@ -11,6 +11,7 @@ import numpy as np
 f32 = np.float32
 f64 = np.float64
 _FLOAT_EPS = np.finfo(np.float64).eps
+_EPS4 = np.finfo(np.float64).eps * 4.0
 
 
 def se3_inverse(RT):
@@ -57,8 +58,10 @@ def quat2mat(q):
 
 
 def mat2quat(M):
-    """RT_transform.py:432-509 (Bar-Itzhack, eigh of the 4x4 K matrix, w >= 0)."""
-    Qxx, Qyx, Qzx, Qxy, Qyy, Qzy, Qxz, Qyz, Qzz = np.asarray(M, dtype=f64).flat
+    """RT_transform.py:432-509 (Bar-Itzhack, eigh of the 4x4 K matrix, w >= 0).  The entries of K are sums of M.flat's
+    scalars and keep M's dtype (float32 sums for the float32 delta calc_RT_delta passes in); the array assembled from them
+    and the Python zeros is float64."""
+    Qxx, Qyx, Qzx, Qxy, Qyy, Qzy, Qxz, Qyz, Qzz = np.asarray(M).flat
     K = np.array(
         [
             [Qxx - Qyy - Qzz, 0, 0, 0],
@@ -66,12 +69,31 @@ def mat2quat(M):
             [Qzx + Qxz, Qzy + Qyz, Qzz - Qxx - Qyy, 0],
             [Qyz - Qzy, Qzx - Qxz, Qxy - Qyx, Qxx + Qyy + Qzz],
         ]
-    ) / 3.0
+    , dtype=f64) / 3.0
     vals, vecs = np.linalg.eigh(K)
     q = vecs[[3, 0, 1, 2], np.argmax(vals)]
     if q[0] < 0:
         q *= -1
     return q
+
+
+def euler2mat(ai, aj, ak):
+    """RT_transform.py:240-307 for the default axes 'sxyz' (what RT_transform calls it with, :132): math.sin / math.cos
+    take Python floats, so float64 throughout."""
+    ai, aj, ak = float(ai), float(aj), float(ak)
+    si, sj, sk = math.sin(ai), math.sin(aj), math.sin(ak)
+    ci, cj, ck = math.cos(ai), math.cos(aj), math.cos(ak)
+    cc, cs, sc, ss = ci * ck, ci * sk, si * ck, si * sk
+    return np.array([[cj * ck, sj * sc - cs, sj * cc + ss], [cj * sk, sj * ss + cc, sj * cs - sc], [-sj, cj * si, cj * ci]])
+
+
+def mat2euler(mat):
+    """RT_transform.py:310-373 for 'sxyz': float64; the gimbal branch (cy <= 4 eps) puts the whole in-plane turn into ax."""
+    M = np.asarray(mat, dtype=f64)[:3, :3]
+    cy = math.sqrt(M[0, 0] * M[0, 0] + M[1, 0] * M[1, 0])
+    if cy > _EPS4:
+        return math.atan2(M[2, 1], M[2, 2]), math.atan2(-M[2, 0], cy), math.atan2(M[1, 0], M[0, 0])
+    return math.atan2(-M[1, 2], M[1, 1]), math.atan2(-M[2, 0], cy), 0.0
 
 
 def R_transform(R_src, R_delta, rot_coord="MODEL"):
@@ -132,16 +154,19 @@ def T_inv_transform(T_src, T_tgt, T_means, T_stds, rot_coord):
 
 
 def RT_transform(pose_src, r, t, T_means, T_stds, rot_coord="MODEL"):
-    """RT_transform.py:127-151 (quaternion input). -> (3,4) float64."""
+    """RT_transform.py:127-151 (r: quaternion, or three Euler angles). -> (3,4) float64."""
     pose_src = np.asarray(pose_src)
     r = np.squeeze(np.asarray(r))
-    assert r.shape[0] == 4
-    if r.dtype == f32:
-        nrm = f32(np.sqrt(f32(f32(f32(r[0] * r[0] + r[1] * r[1]) + r[2] * r[2]) + r[3] * r[3])))
+    assert r.shape[0] in (3, 4)
+    if r.shape[0] == 3:
+        Rm_delta = euler2mat(r[0], r[1], r[2])
     else:
-        nrm = np.linalg.norm(r)
-    quat = r / nrm
-    Rm_delta = quat2mat(quat)
+        if r.dtype == f32:
+            nrm = f32(np.sqrt(f32(f32(f32(r[0] * r[0] + r[1] * r[1]) + r[2] * r[2]) + r[3] * r[3])))
+        else:
+            nrm = np.linalg.norm(r)
+        quat = r / nrm
+        Rm_delta = quat2mat(quat)
     t_delta = np.squeeze(np.asarray(t))
     if rot_coord.lower() == "naive":
         se3_mx = np.zeros((3, 4))
@@ -164,6 +189,8 @@ def calc_RT_delta(pose_src, pose_tgt, T_means, T_stds, rot_coord="MODEL", rot_ty
         T_delta = T_inv_transform(pose_src[:, 3], pose_tgt[:, 3], T_means, T_stds, rot_coord)
     if rot_type.lower() == "quat":
         r = mat2quat(Rm_delta)
+    elif rot_type.lower() == "euler":
+        r = np.array(mat2euler(Rm_delta))
     elif rot_type.lower() == "matrix":
         r = Rm_delta
     else:
@@ -172,10 +199,13 @@ def calc_RT_delta(pose_src, pose_tgt, T_means, T_stds, rot_coord="MODEL", rot_ty
 
 
 def calc_rt_dist_m(pose_src, pose_tgt):
-    """RT_transform.py:162-173 (rotation geodesic via the trace instead of scipy logm; same value)."""
+    """RT_transform.py:162-173.  The rotation geodesic ||logm(R)||_F / sqrt 2 as atan2(sin, cos) from the antisymmetric
+    part and the trace of R: the same value for a rotation, and, unlike acos of the trace alone, not at the mercy of
+    float32 poses being orthonormal only to ~1e-7 (which acos turns into percents of a 1e-3 rad angle and into 0.01
+    degrees next to 0 and 180 degrees; pinned at those angles by tests/golden/pose_edges_golden.npz)."""
     R = np.dot(np.transpose(pose_src[:, :3]).astype(f64), np.asarray(pose_tgt[:, :3], f64))
-    c = np.clip((np.trace(R) - 1.0) / 2.0, -1.0, 1.0)
-    rd_deg = math.acos(c) / math.pi * 180
+    s = 0.5 * np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+    rd_deg = math.atan2(math.sqrt(float(np.dot(s, s))), (np.trace(R) - 1.0) / 2.0) / math.pi * 180
     td = np.linalg.norm(np.asarray(pose_tgt[:, 3], f64) - np.asarray(pose_src[:, 3], f64))
     return rd_deg, td
 
