@@ -268,6 +268,44 @@ int deepim_zoom_concat_forward_h16(deepim_ctx* ctx, const float* image_observed,
                                    const float* depth_rendered, const float* src_pose, const float* K_host,
                                    const float* pixel_means_host, void* main8, void* extra2, float* zoom_factor, int B,
                                    int H, int W);
+/* deepim_zoom_concat_forward for a batch whose pairs look at SHARED camera frames (several objects in one frame): the observed
+ * channels are gathered from N decoded frames that stay as the decoder left them, so no fp32 copy of an observed image or
+ * depth map exists. frame_index: device int32 (B), the frame pair b looks at; the host never reads it, so a captured graph
+ * follows what it holds at replay.
+ *   frames_bgr8     (N,H,W,3) uint8, BGR interleaved, any byte alignment. Tensor channel c of pair b is byte 2-c of frame
+ *                   frame_index[b]; a tap is float(byte) - pixel_means_host[c], the fp32 subtraction of deepim_ingest_bgr8
+ *   depth_frames16  (N,H,W) uint16, 2-byte aligned, or NULL. A tap is float(d) / depth_factor, correctly rounded as in
+ *                   deepim_ingest_depth16. depth_frames16 and depth_rendered are both NULL (C = 8) or both set (C = 10)
+ *   depth_labels    (N,H,W) uint8 and mask_idx device int32 (B), both or neither, only with depth_frames16: the depth tap is 0
+ *                   where depth_labels[frame][pixel] != mask_idx[b] (network.MASK_INPUTS)
+ * image_rendered, mask_observed, mask_rendered and depth_rendered are per pair, (B,·,H,W) fp32, as in deepim_zoom_concat_forward.
+ * net_input and zoom_factor come out with the bits deepim_zoom_concat_forward gives when it is fed deepim_ingest_bgr8 /
+ * deepim_ingest_depth16 of frames[frame_index]. Needs W % 4 == 0, a 16-byte aligned net_input and N >= 1. Both masks are
+ * required: the mask-less ZoomImage box search reads fp32 images and is refused.
+ * Since the host never sees the ids a bad one cannot be reported: a pair whose frame_index is outside [0, N) reads no memory
+ * outside the frames, its observed image and depth come out as if every tap fell outside the frame (image = (0 - mean) / 255,
+ * depth = 0), and bit 4 (16) of the status word (deepim_zoom_status) is set. The other pairs are unaffected. */
+int deepim_zoom_concat_frames_forward(deepim_ctx* ctx, const uint8_t* frames_bgr8 /*N,H,W,3*/,
+                                      const int32_t* frame_index /*device (B)*/, int N, const float* image_rendered,
+                                      const float* mask_observed, const float* mask_rendered,
+                                      const uint16_t* depth_frames16 /*N,H,W or NULL*/,
+                                      const uint8_t* depth_labels /*N,H,W or NULL*/,
+                                      const int32_t* mask_idx /*device (B) or NULL*/, float depth_factor,
+                                      const float* depth_rendered /*or NULL*/, const float* src_pose, const float* K_host,
+                                      const float* pixel_means_host, float* net_input, float* zoom_factor, int B, int H,
+                                      int W);
+/* the shared-frame front end of the fp16 conv path: the observed channels as in deepim_zoom_concat_frames_forward, the outputs
+ * as in deepim_zoom_concat_forward_h16 (main8, extra2: 16-byte aligned; extra2 is set exactly when depth_frames16 is). Same
+ * bad-index rule and status bit. */
+int deepim_zoom_concat_frames_forward_h16(deepim_ctx* ctx, const uint8_t* frames_bgr8 /*N,H,W,3*/,
+                                          const int32_t* frame_index /*device (B)*/, int N, const float* image_rendered,
+                                          const float* mask_observed, const float* mask_rendered,
+                                          const uint16_t* depth_frames16 /*N,H,W or NULL*/,
+                                          const uint8_t* depth_labels /*N,H,W or NULL*/,
+                                          const int32_t* mask_idx /*device (B) or NULL*/, float depth_factor,
+                                          const float* depth_rendered /*or NULL*/, const float* src_pose,
+                                          const float* K_host, const float* pixel_means_host, void* main8, void* extra2,
+                                          float* zoom_factor, int B, int H, int W);
 /* the same front end in the TRAINING graph (deepIM_flownet.py:392-412): the zoom region comes from mask_gt_observed
  * (B,1,H,W; NULL = mask_observed, i.e. the test graph) */
 int deepim_zoom_concat_train_forward(deepim_ctx* ctx, const float* image_observed, const float* image_rendered,
@@ -292,7 +330,9 @@ int deepim_zoom_inverse_factor(deepim_ctx* ctx, const float* zoom_factor, float*
  * bit1 (2) = GroupPicker index out of range
  * bit2 (4) = deepim_mask_box_forward / deepim_render_update_forward saw an empty mask (data_pair.py:98 raises)
  * bit3 (8) = split-fp16 conv path: a value left fp16's range after scaling (|v·scale| > 60000 or NaN) and was clamped — the
- *            results of that call are not fp32-grade; lower the activation scale or use the fp32 path */
+ *            results of that call are not fp32-grade; lower the activation scale or use the fp32 path
+ * bit4 (16) = a shared-frame entry (deepim_zoom_concat_frames_forward[_h16], deepim_ingest_*_frames) met a frame_index outside
+ *            [0, N): that pair's observed channels / output plane are those of an empty frame */
 int deepim_zoom_status(deepim_ctx* ctx, int* status);
 
 /* ------------------------------------------ N-group: matching network ops -- */
@@ -970,6 +1010,18 @@ int deepim_ingest_depth16(deepim_ctx* ctx, float* out /*B,1,H,W*/, const uint16_
 /* image.py:255-260, :308-312: out[b,0,y,x] = labels[b,y,x] == mask_idx[b] ? 1 : 0 */
 int deepim_ingest_label_mask(deepim_ctx* ctx, float* out /*B,1,H,W*/, const uint8_t* labels /*B,H,W*/,
                              const int32_t* mask_idx /*device (B)*/, int B, int H, int W);
+/* The two maps above for a batch whose pairs look at SHARED frames: depth / labels are (N,H,W) and pair b reads frame
+ * frame_index[b] (device int32 (B), never read by the host) instead of sample b; out is still (B,1,H,W) fp32 with the bits the
+ * per-sample entries give on depth[frame_index] / labels[frame_index]. mask_idx stays per pair. N >= 1. A pair whose
+ * frame_index is outside [0, N) reads nothing outside the frames, gets an all-zero plane and sets bit 4 (16) of the status
+ * word (deepim_zoom_status); the other pairs are unaffected. */
+int deepim_ingest_depth16_frames(deepim_ctx* ctx, float* out /*B,1,H,W*/, const uint16_t* depth /*N,H,W*/,
+                                 const uint8_t* labels /*N,H,W or NULL*/, const int32_t* frame_index /*device (B)*/,
+                                 const int32_t* mask_idx /*device (B) or NULL*/, float depth_factor, int N, int B, int H,
+                                 int W);
+int deepim_ingest_label_mask_frames(deepim_ctx* ctx, float* out /*B,1,H,W*/, const uint8_t* labels /*N,H,W*/,
+                                    const int32_t* frame_index /*device (B)*/, const int32_t* mask_idx /*device (B)*/, int N,
+                                    int B, int H, int W);
 /* lib/utils/mask_dilate.py:19-47 with the random draws handed in: thickness (B,4) int32, columns in the order of the file's
  * four blocks — the origin mask shifted down (:24), up (:30), right (:36), left (:42) by that many pixels; 0 = that side is
  * not dilated. Where mask != 0 the output is mask, clamped to 1 where it exceeds 1; elsewhere 1 if an enabled side has a

@@ -89,63 +89,97 @@ __global__ __launch_bounds__(256) void ingest_bgr8_kernel(float* __restrict__ ou
   }
 }
 
-// out (B,1,H,W) is as flat as the inputs: pixel p of the batch goes to out[p]
-template <bool VEC>
+// Shared frames (the *_frames entries): the input of pair b is frame frame_index[b] of N, not sample b. The ids live on the
+// device: one outside [0, N) reads nothing (the pair's output is zeros) and is reported through DI_STATUS_FRAME_RANGE by the
+// lane that owns the pair's first pixel. Unused (and never read) by the per-sample entries.
+struct FrameSel {
+  const int32_t* frame_index;   // (B)
+  int* status;
+  int N;
+};
+// input offset of in-sample pixel q of pair b, or -1 for a pair without a frame
+template <bool FRAMES>
+__device__ __forceinline__ long source_pixel(const FrameSel& fs, long p, long b, long q, long hw) {
+  if (!FRAMES) return p;
+  const int id = fs.frame_index[b];
+  if (id < 0 || id >= fs.N) {
+    if (q == 0) atomicOr(fs.status, DI_STATUS_FRAME_RANGE);
+    return -1;
+  }
+  return (long)id * hw + q;
+}
+
+// out (B,1,H,W) is as flat as the inputs: pixel p of the batch goes to out[p]. VEC with FRAMES: hw % 4 == 0 as well, so that
+// a lane's four pixels share a pair and a frame
+template <bool VEC, bool FRAMES>
 __global__ __launch_bounds__(256) void ingest_depth16_kernel(float* __restrict__ out, const uint16_t* __restrict__ depth,
                                                              const uint8_t* __restrict__ labels,
                                                              const int32_t* __restrict__ mask_idx, float depth_factor,
-                                                             long hw, long n) {
+                                                             long hw, long n, FrameSel fs) {
   const long p0 = ((long)blockIdx.x * 256 + threadIdx.x) * 4;
   if (p0 >= n) return;
   const int cnt = (int)min(4L, n - p0);
   long b, q;
   locate_pixel(p0, hw, n, b, q);
   if (VEC && cnt == 4) {
-    const uint2 d = *reinterpret_cast<const uint2*>(depth + p0);
-    float r[4] = {(float)(d.x & 0xffffu), (float)(d.x >> 16), (float)(d.y & 0xffffu), (float)(d.y >> 16)};
-    // a correctly rounded fp32 division, as numpy's: a reciprocal multiply gives other bits
+    const long s0 = source_pixel<FRAMES>(fs, p0, b, q, hw);
+    float r[4] = {0.f, 0.f, 0.f, 0.f};
+    if (s0 >= 0) {
+      const uint2 d = *reinterpret_cast<const uint2*>(depth + s0);
+      r[0] = (float)(d.x & 0xffffu); r[1] = (float)(d.x >> 16); r[2] = (float)(d.y & 0xffffu); r[3] = (float)(d.y >> 16);
+      // a correctly rounded fp32 division, as numpy's: a reciprocal multiply gives other bits
 #pragma unroll
-    for (int j = 0; j < 4; ++j) r[j] = __fdiv_rn(r[j], depth_factor);
-    if (labels) {
-      const uint32_t l = *reinterpret_cast<const uint32_t*>(labels + p0);
+      for (int j = 0; j < 4; ++j) r[j] = __fdiv_rn(r[j], depth_factor);
+      if (labels) {
+        const uint32_t l = *reinterpret_cast<const uint32_t*>(labels + s0);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        if ((int)((l >> (8 * j)) & 0xffu) != mask_idx[b]) r[j] = 0.f;
-        next_pixel(hw, b, q);
+        for (int j = 0; j < 4; ++j) {
+          if ((int)((l >> (8 * j)) & 0xffu) != mask_idx[b]) r[j] = 0.f;
+          next_pixel(hw, b, q);
+        }
       }
     }
     *reinterpret_cast<float4*>(out + p0) = make_float4(r[0], r[1], r[2], r[3]);
   } else {
     for (int j = 0; j < cnt; ++j) {
       const long p = p0 + j;
-      float r = __fdiv_rn((float)depth[p], depth_factor);
-      if (labels && (int)labels[p] != mask_idx[b]) r = 0.f;
+      const long s = source_pixel<FRAMES>(fs, p, b, q, hw);
+      float r = 0.f;
+      if (s >= 0) {
+        r = __fdiv_rn((float)depth[s], depth_factor);
+        if (labels && (int)labels[s] != mask_idx[b]) r = 0.f;
+      }
       out[p] = r;
       next_pixel(hw, b, q);
     }
   }
 }
 
-template <bool VEC>
+template <bool VEC, bool FRAMES>
 __global__ __launch_bounds__(256) void ingest_label_mask_kernel(float* __restrict__ out, const uint8_t* __restrict__ labels,
-                                                                const int32_t* __restrict__ mask_idx, long hw, long n) {
+                                                                const int32_t* __restrict__ mask_idx, long hw, long n,
+                                                                FrameSel fs) {
   const long p0 = ((long)blockIdx.x * 256 + threadIdx.x) * 4;
   if (p0 >= n) return;
   const int cnt = (int)min(4L, n - p0);
   long b, q;
   locate_pixel(p0, hw, n, b, q);
   if (VEC && cnt == 4) {
-    const uint32_t l = *reinterpret_cast<const uint32_t*>(labels + p0);
-    float r[4];
+    const long s0 = source_pixel<FRAMES>(fs, p0, b, q, hw);
+    float r[4] = {0.f, 0.f, 0.f, 0.f};
+    if (s0 >= 0) {
+      const uint32_t l = *reinterpret_cast<const uint32_t*>(labels + s0);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      r[j] = (int)((l >> (8 * j)) & 0xffu) == mask_idx[b] ? 1.f : 0.f;
-      next_pixel(hw, b, q);
+      for (int j = 0; j < 4; ++j) {
+        r[j] = (int)((l >> (8 * j)) & 0xffu) == mask_idx[b] ? 1.f : 0.f;
+        next_pixel(hw, b, q);
+      }
     }
     *reinterpret_cast<float4*>(out + p0) = make_float4(r[0], r[1], r[2], r[3]);
   } else {
     for (int j = 0; j < cnt; ++j) {
-      out[p0 + j] = (int)labels[p0 + j] == mask_idx[b] ? 1.f : 0.f;
+      const long s = source_pixel<FRAMES>(fs, p0 + j, b, q, hw);
+      out[p0 + j] = s >= 0 && (int)labels[s] == mask_idx[b] ? 1.f : 0.f;
       next_pixel(hw, b, q);
     }
   }
@@ -269,12 +303,36 @@ extern "C" int deepim_ingest_depth16(deepim_ctx* ctx, float* out, const uint16_t
   if (n == 0) return 0;
   const bool vec = aligned_to(out, 16) && aligned_to(depth, 8) && (!labels || aligned_to(labels, 4));
   const dim3 grid(di_div_up(di_div_up(n, 4), 256)), block(256);
+  const FrameSel none = {NULL, NULL, 0};
   if (vec)
-    hipLaunchKernelGGL(ingest_depth16_kernel<true>, grid, block, 0, ctx->stream, out, depth, labels, mask_idx, depth_factor,
-                       hw, n);
+    hipLaunchKernelGGL((ingest_depth16_kernel<true, false>), grid, block, 0, ctx->stream, out, depth, labels, mask_idx,
+                       depth_factor, hw, n, none);
   else
-    hipLaunchKernelGGL(ingest_depth16_kernel<false>, grid, block, 0, ctx->stream, out, depth, labels, mask_idx, depth_factor,
-                       hw, n);
+    hipLaunchKernelGGL((ingest_depth16_kernel<false, false>), grid, block, 0, ctx->stream, out, depth, labels, mask_idx,
+                       depth_factor, hw, n, none);
+  DI_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int deepim_ingest_depth16_frames(deepim_ctx* ctx, float* out, const uint16_t* depth, const uint8_t* labels,
+                                            const int32_t* frame_index, const int32_t* mask_idx, float depth_factor, int N,
+                                            int B, int H, int W) {
+  DI_DEVICE(ctx);
+  DI_REQUIRE(B >= 0 && H >= 0 && W >= 0, "ingest_depth16_frames: negative size");
+  DI_REQUIRE((labels == NULL) == (mask_idx == NULL), "ingest_depth16_frames: labels and mask_idx come together or not at all");
+  const long hw = (long)H * W, n = (long)B * hw;
+  if (n == 0) return 0;
+  DI_REQUIRE(N >= 1 && depth && frame_index, "ingest_depth16_frames: depth, frame_index and N >= 1 are required");
+  DI_REQUIRE(aligned_to(depth, 2), "ingest_depth16_frames: depth must be 2-byte aligned");
+  const bool vec = hw % 4 == 0 && aligned_to(out, 16) && aligned_to(depth, 8) && (!labels || aligned_to(labels, 4));
+  const dim3 grid(di_div_up(di_div_up(n, 4), 256)), block(256);
+  const FrameSel fs = {frame_index, ctx->status, N};
+  if (vec)
+    hipLaunchKernelGGL((ingest_depth16_kernel<true, true>), grid, block, 0, ctx->stream, out, depth, labels, mask_idx,
+                       depth_factor, hw, n, fs);
+  else
+    hipLaunchKernelGGL((ingest_depth16_kernel<false, true>), grid, block, 0, ctx->stream, out, depth, labels, mask_idx,
+                       depth_factor, hw, n, fs);
   DI_LAUNCH_CHECK();
   return 0;
 }
@@ -287,8 +345,25 @@ extern "C" int deepim_ingest_label_mask(deepim_ctx* ctx, float* out, const uint8
   if (n == 0) return 0;
   const bool vec = aligned_to(out, 16) && aligned_to(labels, 4);
   const dim3 grid(di_div_up(di_div_up(n, 4), 256)), block(256);
-  if (vec) hipLaunchKernelGGL(ingest_label_mask_kernel<true>, grid, block, 0, ctx->stream, out, labels, mask_idx, hw, n);
-  else hipLaunchKernelGGL(ingest_label_mask_kernel<false>, grid, block, 0, ctx->stream, out, labels, mask_idx, hw, n);
+  const FrameSel none = {NULL, NULL, 0};
+  if (vec) hipLaunchKernelGGL((ingest_label_mask_kernel<true, false>), grid, block, 0, ctx->stream, out, labels, mask_idx, hw, n, none);
+  else hipLaunchKernelGGL((ingest_label_mask_kernel<false, false>), grid, block, 0, ctx->stream, out, labels, mask_idx, hw, n, none);
+  DI_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int deepim_ingest_label_mask_frames(deepim_ctx* ctx, float* out, const uint8_t* labels, const int32_t* frame_index,
+                                               const int32_t* mask_idx, int N, int B, int H, int W) {
+  DI_DEVICE(ctx);
+  DI_REQUIRE(B >= 0 && H >= 0 && W >= 0, "ingest_label_mask_frames: negative size");
+  const long hw = (long)H * W, n = (long)B * hw;
+  if (n == 0) return 0;
+  DI_REQUIRE(N >= 1 && labels && frame_index && mask_idx, "ingest_label_mask_frames: labels, frame_index, mask_idx and N >= 1 are required");
+  const bool vec = hw % 4 == 0 && aligned_to(out, 16) && aligned_to(labels, 4);
+  const dim3 grid(di_div_up(di_div_up(n, 4), 256)), block(256);
+  const FrameSel fs = {frame_index, ctx->status, N};
+  if (vec) hipLaunchKernelGGL((ingest_label_mask_kernel<true, true>), grid, block, 0, ctx->stream, out, labels, mask_idx, hw, n, fs);
+  else hipLaunchKernelGGL((ingest_label_mask_kernel<false, true>), grid, block, 0, ctx->stream, out, labels, mask_idx, hw, n, fs);
   DI_LAUNCH_CHECK();
   return 0;
 }

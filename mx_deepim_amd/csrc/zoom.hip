@@ -300,27 +300,58 @@ __device__ __forceinline__ Quad make_quad(const Affine& a, int h, int w0, int H,
   return q;
 }
 
+// Where the taps of a channel come from: s(o) is the value of in-plane pixel o as the resampler's pre-op expects it, `live`
+// false turns every tap into an outside-the-frame one. PlaneTap: an fp32 plane (every per-pair tensor). Bgr8Tap / Depth16Tap: a
+// decoded frame that several pairs share, converted tap by tap with the operations of csrc/ingest.hip — float(byte) - mean
+// (ingest_bgr8_kernel; the pre-op adds the mean back, as it does to the ingested tensor) and the correctly rounded
+// float(d) / depth_factor, zeroed outside the pair's label (ingest_depth16_kernel) — so the blend sees the bits it sees behind
+// the ingest kernels.
+struct PlaneTap {
+  const float* __restrict__ s;
+  static constexpr bool live = true;
+  __device__ __forceinline__ float operator()(long o) const { return s[o]; }
+};
+struct Bgr8Tap {
+  const uint8_t* __restrict__ s;   // byte 2-c of pixel 0 of the frame: tensor channel c of an interleaved BGR image
+  float mean;
+  bool live;
+  __device__ __forceinline__ float operator()(long o) const { return (float)s[o * 3] - mean; }
+};
+template <bool LABELS>
+struct Depth16Tap {
+  const uint16_t* __restrict__ d;
+  const uint8_t* __restrict__ labels;
+  int idx;
+  float factor;
+  bool live;
+  __device__ __forceinline__ float operator()(long o) const {
+    float r = __fdiv_rn((float)d[o], factor);
+    if (LABELS && (int)labels[o] != idx) r = 0.f;
+    return r;
+  }
+};
+
 // One channel of a quad. FLS >= 0: the channel's flags are a compile-time constant (the fused front end: every flag test
 // folds away); FLS < 0: flags come from the plan at run time (the generic Z ops).
-template <int FLS>
-__device__ __forceinline__ void resample_channel4_vals(const float* __restrict__ s, float (&o)[4], float mean, int fl_dyn,
-                                                       const Quad& q, const Affine& a, int H, int W) {
+template <int FLS, class TAP>
+__device__ __forceinline__ void resample_channel4_vals(const TAP& s, float (&o)[4], float mean, int fl_dyn, const Quad& q,
+                                                       const Affine& a, int H, int W) {
   const int fl = FLS >= 0 ? FLS : fl_dyn;
   float tl[4], tr[4], bl[4], br[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    tl[i] = s[q.row0 + q.xc0[i]];
-    tr[i] = s[q.row0 + q.xc1[i]];
-    bl[i] = s[q.row1 + q.xc0[i]];
-    br[i] = s[q.row1 + q.xc1[i]];
+    tl[i] = s(q.row0 + q.xc0[i]);
+    tr[i] = s(q.row0 + q.xc1[i]);
+    bl[i] = s(q.row1 + q.xc0[i]);
+    br[i] = s(q.row1 + q.xc1[i]);
   }
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const Taps& t = q.t[i];
-    const float ptl = t.in00 ? pre_op(tl[i], mean, fl) : 0.f;
-    const float ptr_ = t.in01 ? pre_op(tr[i], mean, fl) : 0.f;
-    const float pbl = t.in10 ? pre_op(bl[i], mean, fl) : 0.f;
-    const float pbr = t.in11 ? pre_op(br[i], mean, fl) : 0.f;
+    const float ptl = (s.live && t.in00) ? pre_op(tl[i], mean, fl) : 0.f;
+    const float ptr_ = (s.live && t.in01) ? pre_op(tr[i], mean, fl) : 0.f;
+    const float pbl = (s.live && t.in10) ? pre_op(bl[i], mean, fl) : 0.f;
+    const float pbr = (s.live && t.in11) ? pre_op(br[i], mean, fl) : 0.f;
     float v = blend(ptl, ptr_, pbl, pbr, t.wy0, t.wx0);
     if (fl & CF_HIGHLIGHT) {
       const int sy0 = (int)floorf((float)H / 2 - 5), sy1 = (int)ceilf((float)H / 2 + 5);
@@ -338,9 +369,9 @@ __device__ __forceinline__ void resample_channel4_vals(const float* __restrict__
   }
 }
 
-template <int FLS>
-__device__ __forceinline__ void resample_channel4(const float* __restrict__ s, float* __restrict__ d, float mean, int fl_dyn,
-                                                  const Quad& q, const Affine& a, int H, int W) {
+template <int FLS, class TAP>
+__device__ __forceinline__ void resample_channel4(const TAP& s, float* __restrict__ d, float mean, int fl_dyn, const Quad& q,
+                                                  const Affine& a, int H, int W) {
   float o[4];
   resample_channel4_vals<FLS>(s, o, mean, fl_dyn, q, a, H, W);
   *reinterpret_cast<float4*>(d + q.opix) = make_float4(o[0], o[1], o[2], o[3]);
@@ -358,7 +389,7 @@ __global__ __launch_bounds__(256) void resample4_kernel(Plan plan, const float* 
 #pragma unroll 2
   for (int c = 0; c < plan.n; ++c) {
     const Chan& ch = plan.ch[c];
-    resample_channel4<-1>(ch.src + (long)b * ch.src_bstride, ch.dst + (long)b * ch.dst_bstride, ch.mean, ch.flags, q, a, H, W);
+    resample_channel4<-1>(PlaneTap{ch.src + (long)b * ch.src_bstride}, ch.dst + (long)b * ch.dst_bstride, ch.mean, ch.flags, q, a, H, W);
   }
 }
 
@@ -373,9 +404,52 @@ struct ConcatArgs {
   Vec3 means;
   int C;
 };
-template <bool DEPTH, bool MASK>
-__global__ __launch_bounds__(256) void zoom_concat4_kernel(ConcatArgs g, const float* __restrict__ zoom_factor, int H, int W,
-                                                           float gx_step, float gy_step) {
+
+// The observed image and depth of pair b as tap sources. ObsPlanes: the per-pair fp32 tensors of ConcatArgs. ObsFrames: N decoded
+// frames shared by the batch (deepim_zoom_concat_frames_forward), pair b looking at frame frame_index[b]. The ids live on the
+// device: one outside [0, N) is clamped to frame 0 for the addresses, marked not live (every tap an outside one) and reported
+// through DI_STATUS_FRAME_RANGE by the pair's first lane.
+struct FrameArgs {
+  const uint8_t* bgr8;          // (N,H,W,3), any alignment
+  const uint16_t* depth16;      // (N,H,W) or unused
+  const uint8_t* labels;        // (N,H,W) or unused: the depth is zeroed where labels != mask_idx[b]
+  const int32_t* frame_index;   // (B)
+  const int32_t* mask_idx;      // (B) or unused
+  int* status;
+  float depth_factor;
+  int N;
+};
+struct ObsPlanes {
+  const float* image; const float* depth;
+  int b;
+  __device__ __forceinline__ ObsPlanes(const ConcatArgs& g, int b_) : image(g.image_observed), depth(g.depth_observed), b(b_) {}
+  __device__ __forceinline__ PlaneTap image_tap(int c, long p, float) const { return PlaneTap{image + ((long)b * 3 + c) * p}; }
+  __device__ __forceinline__ PlaneTap depth_tap(long p) const { return PlaneTap{depth + (long)b * p}; }
+};
+template <bool LABELS>
+struct ObsFrames {
+  const FrameArgs& f;
+  long frame;
+  int idx;
+  bool live;
+  __device__ __forceinline__ ObsFrames(const FrameArgs& f_, int b, bool first_lane) : f(f_) {
+    const int id = f.frame_index[b];
+    live = id >= 0 && id < f.N;
+    frame = live ? id : 0;
+    idx = LABELS ? f.mask_idx[b] : 0;
+    if (!live && first_lane) atomicOr(f.status, DI_STATUS_FRAME_RANGE);
+  }
+  __device__ __forceinline__ Bgr8Tap image_tap(int c, long p, float mean) const {
+    return Bgr8Tap{f.bgr8 + frame * p * 3 + (2 - c), mean, live};
+  }
+  __device__ __forceinline__ Depth16Tap<LABELS> depth_tap(long p) const {
+    return Depth16Tap<LABELS>{f.depth16 + frame * p, LABELS ? f.labels + frame * p : nullptr, idx, f.depth_factor, live};
+  }
+};
+
+template <bool DEPTH, bool MASK, class OBS>
+__device__ __forceinline__ void zoom_concat4_body(const ConcatArgs& g, const OBS& obs, const float* __restrict__ zoom_factor,
+                                                  int H, int W, float gx_step, float gy_step) {
   const int qpr = W >> 2;
   const int qid = blockIdx.x * 256 + threadIdx.x;
   const int b = blockIdx.y;
@@ -387,20 +461,32 @@ __global__ __launch_bounds__(256) void zoom_concat4_kernel(ConcatArgs g, const f
   float* out = g.net_input + (long)b * g.C * p;
 #pragma unroll
   for (int c = 0; c < 3; ++c)
-    resample_channel4<CF_POST_DIV255>(g.image_observed + ((long)b * 3 + c) * p, out + c * p, g.means.v[c], 0, q, a, H, W);
+    resample_channel4<CF_POST_DIV255>(obs.image_tap(c, p, g.means.v[c]), out + c * p, g.means.v[c], 0, q, a, H, W);
 #pragma unroll
   for (int c = 0; c < 3; ++c)
-    resample_channel4<CF_POST_DIV255>(g.image_rendered + ((long)b * 3 + c) * p, out + (3 + c) * p, g.means.v[c], 0, q, a, H, W);
+    resample_channel4<CF_POST_DIV255>(PlaneTap{g.image_rendered + ((long)b * 3 + c) * p}, out + (3 + c) * p, g.means.v[c], 0, q, a, H, W);
   int n = 6;
   if (DEPTH) {
-    resample_channel4<CF_POST_DIV255>(g.depth_observed + (long)b * p, out + (long)n * p, 0.f, 0, q, a, H, W);
-    resample_channel4<CF_POST_DIV255>(g.depth_rendered + (long)b * p, out + (long)(n + 1) * p, 0.f, 0, q, a, H, W);
+    resample_channel4<CF_POST_DIV255>(obs.depth_tap(p), out + (long)n * p, 0.f, 0, q, a, H, W);
+    resample_channel4<CF_POST_DIV255>(PlaneTap{g.depth_rendered + (long)b * p}, out + (long)(n + 1) * p, 0.f, 0, q, a, H, W);
     n += 2;
   }
   if (MASK) {
-    resample_channel4<CF_POST_ROUND>(g.mask_observed + (long)b * p, out + (long)n * p, 0.f, 0, q, a, H, W);
-    resample_channel4<CF_PRE_BIN02 | CF_POST_ROUND>(g.mask_rendered + (long)b * p, out + (long)(n + 1) * p, 0.f, 0, q, a, H, W);
+    resample_channel4<CF_POST_ROUND>(PlaneTap{g.mask_observed + (long)b * p}, out + (long)n * p, 0.f, 0, q, a, H, W);
+    resample_channel4<CF_PRE_BIN02 | CF_POST_ROUND>(PlaneTap{g.mask_rendered + (long)b * p}, out + (long)(n + 1) * p, 0.f, 0, q, a, H, W);
   }
+}
+template <bool DEPTH, bool MASK>
+__global__ __launch_bounds__(256) void zoom_concat4_kernel(ConcatArgs g, const float* __restrict__ zoom_factor, int H, int W,
+                                                           float gx_step, float gy_step) {
+  zoom_concat4_body<DEPTH, MASK>(g, ObsPlanes(g, blockIdx.y), zoom_factor, H, W, gx_step, gy_step);
+}
+// the masked front end over shared frames; LABELS: the observed depth is zeroed outside the pair's label
+template <bool DEPTH, bool LABELS>
+__global__ __launch_bounds__(256) void zoom_concat4_frames_kernel(ConcatArgs g, FrameArgs f, const float* __restrict__ zoom_factor,
+                                                                  int H, int W, float gx_step, float gy_step) {
+  zoom_concat4_body<DEPTH, true>(g, ObsFrames<LABELS>(f, blockIdx.y, blockIdx.x == 0 && threadIdx.x == 0), zoom_factor, H, W,
+                                 gx_step, gy_step);
 }
 
 // The same front end for the shipped 8-channel input (RGB pair + masks) writing CHANNEL-BLOCKED records — [n][h][w][8], the
@@ -420,12 +506,12 @@ __global__ __launch_bounds__(256) void zoom_concat4_nc8_kernel(ConcatArgs g, con
   float o[8][4];
 #pragma unroll
   for (int c = 0; c < 3; ++c)
-    resample_channel4_vals<CF_POST_DIV255>(g.image_observed + ((long)b * 3 + c) * p, o[c], g.means.v[c], 0, q, a, H, W);
+    resample_channel4_vals<CF_POST_DIV255>(PlaneTap{g.image_observed + ((long)b * 3 + c) * p}, o[c], g.means.v[c], 0, q, a, H, W);
 #pragma unroll
   for (int c = 0; c < 3; ++c)
-    resample_channel4_vals<CF_POST_DIV255>(g.image_rendered + ((long)b * 3 + c) * p, o[3 + c], g.means.v[c], 0, q, a, H, W);
-  resample_channel4_vals<CF_POST_ROUND>(g.mask_observed + (long)b * p, o[6], 0.f, 0, q, a, H, W);
-  resample_channel4_vals<CF_PRE_BIN02 | CF_POST_ROUND>(g.mask_rendered + (long)b * p, o[7], 0.f, 0, q, a, H, W);
+    resample_channel4_vals<CF_POST_DIV255>(PlaneTap{g.image_rendered + ((long)b * 3 + c) * p}, o[3 + c], g.means.v[c], 0, q, a, H, W);
+  resample_channel4_vals<CF_POST_ROUND>(PlaneTap{g.mask_observed + (long)b * p}, o[6], 0.f, 0, q, a, H, W);
+  resample_channel4_vals<CF_PRE_BIN02 | CF_POST_ROUND>(PlaneTap{g.mask_rendered + (long)b * p}, o[7], 0.f, 0, q, a, H, W);
   float4* rec = reinterpret_cast<float4*>(g.net_input + ((long)b * p + q.opix) * 8);
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -438,11 +524,10 @@ __global__ __launch_bounds__(256) void zoom_concat4_nc8_kernel(ConcatArgs g, con
 // NCHW fp32 → NHWC fp16 pass did) and written as the pixel records conv1's patch kernel reads — main (B,H,W,8 halves) = the
 // first eight net-input channels, and with DEPTH the two remaining ones (the masks) as (B,H,W,2 halves). Half the bytes of
 // the fp32 net input on the way out, a quarter on conv1's way in.
-template <bool DEPTH>
-__global__ __launch_bounds__(256) void zoom_concat4_h16_kernel(ConcatArgs g, _Float16* __restrict__ main8,
-                                                               _Float16* __restrict__ extra2,
-                                                               const float* __restrict__ zoom_factor, int H, int W,
-                                                               float gx_step, float gy_step) {
+template <bool DEPTH, class OBS>
+__device__ __forceinline__ void zoom_concat4_h16_body(const ConcatArgs& g, const OBS& obs, _Float16* __restrict__ main8,
+                                                      _Float16* __restrict__ extra2, const float* __restrict__ zoom_factor,
+                                                      int H, int W, float gx_step, float gy_step) {
   constexpr int C = DEPTH ? 10 : 8;
   const int qpr = W >> 2;
   const int qid = blockIdx.x * 256 + threadIdx.x;
@@ -455,16 +540,16 @@ __global__ __launch_bounds__(256) void zoom_concat4_h16_kernel(ConcatArgs g, _Fl
   float o[C][4];
 #pragma unroll
   for (int c = 0; c < 3; ++c)
-    resample_channel4_vals<CF_POST_DIV255>(g.image_observed + ((long)b * 3 + c) * p, o[c], g.means.v[c], 0, q, a, H, W);
+    resample_channel4_vals<CF_POST_DIV255>(obs.image_tap(c, p, g.means.v[c]), o[c], g.means.v[c], 0, q, a, H, W);
 #pragma unroll
   for (int c = 0; c < 3; ++c)
-    resample_channel4_vals<CF_POST_DIV255>(g.image_rendered + ((long)b * 3 + c) * p, o[3 + c], g.means.v[c], 0, q, a, H, W);
+    resample_channel4_vals<CF_POST_DIV255>(PlaneTap{g.image_rendered + ((long)b * 3 + c) * p}, o[3 + c], g.means.v[c], 0, q, a, H, W);
   if (DEPTH) {
-    resample_channel4_vals<CF_POST_DIV255>(g.depth_observed + (long)b * p, o[6], 0.f, 0, q, a, H, W);
-    resample_channel4_vals<CF_POST_DIV255>(g.depth_rendered + (long)b * p, o[7], 0.f, 0, q, a, H, W);
+    resample_channel4_vals<CF_POST_DIV255>(obs.depth_tap(p), o[6], 0.f, 0, q, a, H, W);
+    resample_channel4_vals<CF_POST_DIV255>(PlaneTap{g.depth_rendered + (long)b * p}, o[7], 0.f, 0, q, a, H, W);
   }
-  resample_channel4_vals<CF_POST_ROUND>(g.mask_observed + (long)b * p, o[C - 2], 0.f, 0, q, a, H, W);
-  resample_channel4_vals<CF_PRE_BIN02 | CF_POST_ROUND>(g.mask_rendered + (long)b * p, o[C - 1], 0.f, 0, q, a, H, W);
+  resample_channel4_vals<CF_POST_ROUND>(PlaneTap{g.mask_observed + (long)b * p}, o[C - 2], 0.f, 0, q, a, H, W);
+  resample_channel4_vals<CF_PRE_BIN02 | CF_POST_ROUND>(PlaneTap{g.mask_rendered + (long)b * p}, o[C - 1], 0.f, 0, q, a, H, W);
   typedef _Float16 h8v __attribute__((ext_vector_type(8)));
   h8v* rec = reinterpret_cast<h8v*>(main8 + ((long)b * p + q.opix) * 8);
 #pragma unroll
@@ -480,6 +565,21 @@ __global__ __launch_bounds__(256) void zoom_concat4_h16_kernel(ConcatArgs g, _Fl
     for (int i = 0; i < 4; ++i) { r[2 * i] = (_Float16)o[8][i]; r[2 * i + 1] = (_Float16)o[9][i]; }
     *reinterpret_cast<h8v*>(extra2 + ((long)b * p + q.opix) * 2) = r;
   }
+}
+template <bool DEPTH>
+__global__ __launch_bounds__(256) void zoom_concat4_h16_kernel(ConcatArgs g, _Float16* __restrict__ main8,
+                                                               _Float16* __restrict__ extra2,
+                                                               const float* __restrict__ zoom_factor, int H, int W,
+                                                               float gx_step, float gy_step) {
+  zoom_concat4_h16_body<DEPTH>(g, ObsPlanes(g, blockIdx.y), main8, extra2, zoom_factor, H, W, gx_step, gy_step);
+}
+template <bool DEPTH, bool LABELS>
+__global__ __launch_bounds__(256) void zoom_concat4_h16_frames_kernel(ConcatArgs g, FrameArgs f, _Float16* __restrict__ main8,
+                                                                      _Float16* __restrict__ extra2,
+                                                                      const float* __restrict__ zoom_factor, int H, int W,
+                                                                      float gx_step, float gy_step) {
+  zoom_concat4_h16_body<DEPTH>(g, ObsFrames<LABELS>(f, blockIdx.y, blockIdx.x == 0 && threadIdx.x == 0), main8, extra2,
+                               zoom_factor, H, W, gx_step, gy_step);
 }
 
 // every float bit pattern through div255 against the IEEE division (parity hook)
@@ -768,6 +868,92 @@ extern "C" int deepim_zoom_concat_forward_h16(deepim_ctx* ctx, const float* imag
   dim3 grid(di_div_up((long)(W / 4) * H, 256), B);
   if (dep) hipLaunchKernelGGL(zoom_concat4_h16_kernel<true>, grid, dim3(256), 0, ctx->stream, g, (_Float16*)main8, (_Float16*)extra2, zoom_factor, H, W, gx, gy);
   else hipLaunchKernelGGL(zoom_concat4_h16_kernel<false>, grid, dim3(256), 0, ctx->stream, g, (_Float16*)main8, (_Float16*)nullptr, zoom_factor, H, W, gx, gy);
+  DI_LAUNCH_CHECK();
+  return 0;
+}
+
+// Shared frames (several objects in one camera frame): the two front ends above with the observed channels gathered from N
+// decoded frames through frame_index. Checks and argument blocks common to both entries; 0 or the error code.
+static int frames_front_end_args(deepim_ctx* ctx, ConcatArgs& g, FrameArgs& f, const uint8_t* frames_bgr8,
+                                 const int32_t* frame_index, int N, const float* image_rendered, const float* mask_observed,
+                                 const float* mask_rendered, const uint16_t* depth_frames16, const uint8_t* depth_labels,
+                                 const int32_t* mask_idx, float depth_factor, const float* depth_rendered,
+                                 const float* pixel_means_host, int W) {
+  DI_REQUIRE(mask_observed && mask_rendered, "zoom_concat_frames: needs both masks — the mask-less ZoomImage box search reads fp32 "
+                                             "images, which a shared-frame batch does not have");
+  DI_REQUIRE(frames_bgr8 && frame_index && N >= 1, "zoom_concat_frames: frames_bgr8, frame_index and N >= 1 are required");
+  DI_REQUIRE((W & 3) == 0, "zoom_concat_frames: W % 4 == 0 and 16-byte aligned outputs");
+  DI_REQUIRE((depth_frames16 != nullptr) == (depth_rendered != nullptr), "zoom_concat_frames: depth_frames16 and depth_rendered go together");
+  DI_REQUIRE(((size_t)depth_frames16 & 1) == 0, "zoom_concat_frames: depth_frames16 must be 2-byte aligned");
+  DI_REQUIRE((depth_labels != nullptr) == (mask_idx != nullptr) && (!depth_labels || depth_frames16),
+             "zoom_concat_frames: depth_labels and mask_idx come together, and only with depth_frames16");
+  g.image_observed = nullptr; g.image_rendered = image_rendered;
+  g.depth_observed = nullptr; g.depth_rendered = depth_rendered;
+  g.mask_observed = mask_observed; g.mask_rendered = mask_rendered;
+  g.net_input = nullptr; g.C = depth_frames16 ? 10 : 8;
+  for (int i = 0; i < 3; ++i) g.means.v[i] = pixel_means_host ? pixel_means_host[i] : 0.f;
+  f.bgr8 = frames_bgr8; f.depth16 = depth_frames16; f.labels = depth_labels;
+  f.frame_index = frame_index; f.mask_idx = mask_idx; f.status = ctx->status;
+  f.depth_factor = depth_factor; f.N = N;
+  return 0;
+}
+
+extern "C" int deepim_zoom_concat_frames_forward(deepim_ctx* ctx, const uint8_t* frames_bgr8, const int32_t* frame_index, int N,
+                                                 const float* image_rendered, const float* mask_observed,
+                                                 const float* mask_rendered, const uint16_t* depth_frames16,
+                                                 const uint8_t* depth_labels, const int32_t* mask_idx, float depth_factor,
+                                                 const float* depth_rendered, const float* src_pose, const float* K_host,
+                                                 const float* pixel_means_host, float* net_input, float* zoom_factor, int B,
+                                                 int H, int W) {
+  DI_DEVICE(ctx);
+  if (B == 0) return 0;
+  ConcatArgs g;
+  FrameArgs f;
+  int rc = frames_front_end_args(ctx, g, f, frames_bgr8, frame_index, N, image_rendered, mask_observed, mask_rendered,
+                                 depth_frames16, depth_labels, mask_idx, depth_factor, depth_rendered, pixel_means_host, W);
+  if (rc) return rc;
+  DI_REQUIRE(((size_t)net_input & 15) == 0, "zoom_concat_frames: W % 4 == 0 and 16-byte aligned outputs");
+  g.net_input = net_input;
+  rc = compute_zoom_factor(ctx, zoom_factor, mask_observed, mask_rendered, BB_MASK_GT, BB_MASK_RENDERED, nullptr, src_pose,
+                           K_host, B, H, W);
+  if (rc) return rc;
+  const float gx = (float)(2.0 / (W - 1)), gy = (float)(2.0 / (H - 1));
+  dim3 grid(di_div_up((long)(W / 4) * H, 256), B);
+#define DI_FRAMES(D, L) hipLaunchKernelGGL((zoom_concat4_frames_kernel<D, L>), grid, dim3(256), 0, ctx->stream, g, f, zoom_factor, H, W, gx, gy)
+  if (!depth_frames16) DI_FRAMES(false, false);
+  else if (!depth_labels) DI_FRAMES(true, false);
+  else DI_FRAMES(true, true);
+#undef DI_FRAMES
+  DI_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int deepim_zoom_concat_frames_forward_h16(deepim_ctx* ctx, const uint8_t* frames_bgr8, const int32_t* frame_index,
+                                                     int N, const float* image_rendered, const float* mask_observed,
+                                                     const float* mask_rendered, const uint16_t* depth_frames16,
+                                                     const uint8_t* depth_labels, const int32_t* mask_idx, float depth_factor,
+                                                     const float* depth_rendered, const float* src_pose, const float* K_host,
+                                                     const float* pixel_means_host, void* main8, void* extra2,
+                                                     float* zoom_factor, int B, int H, int W) {
+  DI_DEVICE(ctx);
+  if (B == 0) return 0;
+  ConcatArgs g;
+  FrameArgs f;
+  int rc = frames_front_end_args(ctx, g, f, frames_bgr8, frame_index, N, image_rendered, mask_observed, mask_rendered,
+                                 depth_frames16, depth_labels, mask_idx, depth_factor, depth_rendered, pixel_means_host, W);
+  if (rc) return rc;
+  DI_REQUIRE((depth_frames16 != nullptr) == (extra2 != nullptr), "zoom_concat_frames_h16: depth pair and extra2 go together");
+  DI_REQUIRE(main8 && ((size_t)main8 & 15) == 0 && ((size_t)extra2 & 15) == 0, "zoom_concat_frames_h16: W % 4 == 0 and 16-byte aligned outputs");
+  rc = compute_zoom_factor(ctx, zoom_factor, mask_observed, mask_rendered, BB_MASK_GT, BB_MASK_RENDERED, nullptr, src_pose,
+                           K_host, B, H, W);
+  if (rc) return rc;
+  const float gx = (float)(2.0 / (W - 1)), gy = (float)(2.0 / (H - 1));
+  dim3 grid(di_div_up((long)(W / 4) * H, 256), B);
+#define DI_FRAMES(D, L) hipLaunchKernelGGL((zoom_concat4_h16_frames_kernel<D, L>), grid, dim3(256), 0, ctx->stream, g, f, (_Float16*)main8, (_Float16*)extra2, zoom_factor, H, W, gx, gy)
+  if (!depth_frames16) DI_FRAMES(false, false);
+  else if (!depth_labels) DI_FRAMES(true, false);
+  else DI_FRAMES(true, true);
+#undef DI_FRAMES
   DI_LAUNCH_CHECK();
   return 0;
 }

@@ -90,17 +90,34 @@ def get_data_pair_test_batch(frames, config):
     """data_pair.py:22-63 from decoded frames (see lib/utils/image.py for the dict): the reference's `data` keys (:43-60) as
     device tensors for the whole batch — image_observed, image_rendered (B,3,H,W), src_pose (B,3,4) from frames["pose_rendered"],
     class_index handed over as given [, depth_observed, depth_rendered with INPUT_DEPTH][, mask_observed, mask_rendered with
-    INPUT_MASK]."""
+    INPUT_MASK].
+    A shared-frame batch (frames["frame_index"], lib/utils/image.py: N frames for B pairs) gives the same keys except that
+    image_observed [and depth_observed] are replaced by ONE entry, data["observed_frames"] (lib/utils/image.ObservedFrames): the
+    uint8 / uint16 frames on the device with the device frame_index [, the label maps, mask_idx and DEPTH_FACTOR of the observed
+    depth], which the network's zoom front end reads in place. A numpy frame_index outside [0, N) raises ValueError before
+    anything is uploaded or launched."""
     data = {}
-    data["image_observed"], data["image_rendered"] = _image.get_pair_image(frames, config, "test")
-    ctx = data["image_observed"].context
-    B = data["image_observed"].shape[0]
+    shared = _image.is_shared(frames)
+    if shared:
+        _image.check_frame_index(frames)
+        frames = dict(frames)
+        data["observed_frames"] = _image.observed_frames(frames, config, "test")
+        frames["frame_index"] = data["observed_frames"].frame_index     # uploaded once for the calls below
+        data["image_rendered"] = _image.get_rendered_image(frames, config)
+    else:
+        data["image_observed"], data["image_rendered"] = _image.get_pair_image(frames, config, "test")
+    ctx = data["image_rendered"].context
+    B = data["image_rendered"].shape[0]
+    if shared and data["observed_frames"].n_pairs != B:
+        raise ValueError("frame_index names %d pairs, image_rendered holds %d" % (data["observed_frames"].n_pairs, B))
     pose = frames["pose_rendered"]
     if not isinstance(pose, DeviceArray):
         pose = ctx.array(np.asarray(pose, dtype=np.float32).reshape(B, 3, 4))
     data["src_pose"] = pose
     data["class_index"] = frames.get("class_index")
-    if config.network.INPUT_DEPTH:
+    if config.network.INPUT_DEPTH and shared:
+        data["depth_rendered"] = _image._depth(ctx, frames, "depth_rendered", config)
+    elif config.network.INPUT_DEPTH:
         data["depth_observed"], data["depth_rendered"] = _image.get_pair_depth(frames, config, "test")
     if config.network.INPUT_MASK:
         data["mask_observed"], _, data["mask_rendered"] = _image.get_pair_mask(frames, config, "test",

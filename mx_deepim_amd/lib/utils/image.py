@@ -15,6 +15,23 @@ numpy array (uploaded as it is, never converted on the host), for a batch of B p
     mask_idx                              (B) int32: the pair's label value (pair_rec["mask_idx"])
     mask_dilate_thickness                 (B,4) int32 from lib/utils/mask_dilate.mask_dilate_draws, for MASK_DILATE
 
+A dict that carries `frame_index` is a SHARED-FRAME batch: several objects in one camera frame (Occluded LINEMOD, YCB-style
+scenes, a detector front end). The observed side then holds N <= B frames once, as the decoder left them, and pair b looks at
+frame frame_index[b]:
+
+    frame_index                           (B) int32, numpy or device
+    image_observed                        (N,H,W,3) uint8, BGR
+    depth_observed, depth_gt_observed     (N,H,W) uint16
+    mask_gt_observed, mask_observed, mask_observed_est    (N,H,W) uint8 label maps
+    image_rendered, depth_rendered, pose_rendered, mask_idx, mask_dilate_thickness     per pair, (B,...) as above
+
+No fp32 copy of an observed image or depth map is made for the network: `observed_frames` hands the frames themselves to the
+zoom front end (deepim_zoom_concat_frames_forward), which gathers its taps from them in every iteration. The per-pair masks and
+the flow ground truth's depth are still (B,1,H,W) tensors (deepim_ingest_label_mask_frames / deepim_ingest_depth16_frames). A
+numpy frame_index is range-checked on the host before anything is launched (ValueError naming the pair); a device one cannot
+be: a pair whose id is outside [0, N) sees an empty frame and sets bit 4 of the status word. Shared frames are test-phase only:
+`get_pair_image` (which would have to make the fp32 copies), bg_image and the training loader refuse them.
+
 File decoding, the cv2 resize (:552-580) and the choice of a background are the caller's: a frame whose size is not
 config.SCALES[0] is refused. The test phase's `np.sum(depth_rendered) == 0` guard (:301-303) is a host decision per pair and is
 the caller's too; an empty rectangle source gives zeros and sets bit 2 of the status word (deepim_zoom_status).
@@ -66,6 +83,95 @@ def _ids(ctx, frames, key, B, cols=None):
     return v
 
 
+SHARED_KEYS = ("image_observed", "depth_observed", "depth_gt_observed", "mask_gt_observed", "mask_observed", "mask_observed_est")
+
+
+def is_shared(frames):
+    """Whether `frames` is a shared-frame batch (module docstring): it carries a frame_index."""
+    return frames.get("frame_index") is not None
+
+
+def check_frame_index(frames):
+    """The host half of a shared-frame batch, no device needed → (B, N). The shared arrays must agree on N; a numpy frame_index
+    must lie in [0, N) — ValueError naming the first offending pair. A device frame_index is never read: the kernels guard it."""
+    counts = {k: int(frames[k].shape[0] if isinstance(frames[k], DeviceArray) else np.shape(frames[k])[0])
+              for k in SHARED_KEYS if frames.get(k) is not None}
+    if not counts:
+        raise KeyError("a shared-frame batch carries at least one of %s" % ", ".join(SHARED_KEYS))
+    N = max(counts.values())
+    if min(counts.values()) != N or N < 1:
+        raise ValueError("the shared arrays of the batch disagree on the number of frames (or have none): %s" % counts)
+    fi = frames["frame_index"]
+    if isinstance(fi, DeviceArray):
+        if fi.dtype != np.int32:
+            raise TypeError("frames['frame_index'] on the device must be int32")
+        return int(fi.size), N
+    fi = np.asarray(fi)
+    if fi.dtype.kind not in "iu":
+        raise TypeError("frames['frame_index'] is %s; integer frame numbers are expected" % fi.dtype)
+    fi = fi.reshape(-1)
+    bad = np.nonzero((fi < 0) | (fi >= N))[0]
+    if bad.size:
+        raise ValueError("frame_index[%d] = %d: pair %d looks at a frame outside the batch's %d shared frame%s"
+                         % (bad[0], fi[bad[0]], bad[0], N, "" if N == 1 else "s"))
+    return int(fi.size), N
+
+
+def _frame_index(ctx, frames):
+    """→ (device int32 (B) frame_index, B, N) of a shared-frame batch, after the host checks."""
+    B, N = check_frame_index(frames)
+    fi = frames["frame_index"]
+    if not isinstance(fi, DeviceArray):
+        fi = ctx.array(np.asarray(fi).reshape(B), dtype=np.int32)
+    return fi, B, N
+
+
+class ObservedFrames(object):
+    """The observed side of a shared-frame batch as the zoom front end reads it (data["observed_frames"]), all on the device:
+    image (N,H,W,3) uint8 BGR and frame_index (B) int32; with network.INPUT_DEPTH depth (N,H,W) uint16 and depth_factor, and
+    with network.MASK_INPUTS labels (N,H,W) uint8 + mask_idx (B) int32, outside of which the depth is zero."""
+
+    def __init__(self, image, frame_index, depth=None, labels=None, mask_idx=None, depth_factor=1000.0):
+        self.image, self.frame_index, self.depth, self.labels, self.mask_idx = image, frame_index, depth, labels, mask_idx
+        self.depth_factor = float(depth_factor)
+        self.context = image.context
+
+    @property
+    def n_frames(self):
+        return self.image.shape[0]
+
+    @property
+    def n_pairs(self):
+        return self.frame_index.size
+
+    def nbytes(self):
+        """device bytes the observed side of the batch occupies"""
+        return sum(a.nbytes for a in (self.image, self.frame_index, self.depth, self.labels, self.mask_idx) if a is not None)
+
+
+def observed_frames(frames, config, phase="test"):
+    """The observed half of `get_pair_image` / `get_pair_depth` for a shared-frame batch → ObservedFrames: the uint8 / uint16
+    frames go to the device as they are (or stay there) and nothing is converted."""
+    if phase != "test":
+        raise NotImplementedError("shared frames (frames['frame_index']) are a test-phase input: the training loader is per pair")
+    ctx = _context(frames)
+    fi, B, N = _frame_index(ctx, frames)
+    obs = _frame(ctx, frames, "image_observed", np.uint8, (3,))
+    _check_size(config, obs.shape[1], obs.shape[2])
+    depth = labels = idx = None
+    if config.network.INPUT_DEPTH:
+        depth = _frame(ctx, frames, "depth_observed", np.uint16)
+        if depth.shape != obs.shape[:3]:
+            raise ValueError("depth_observed %s and image_observed %s differ in shape" % (depth.shape, obs.shape))
+        if config.network.get("MASK_INPUTS", False):
+            key = "mask_gt_observed" if config.dataset.get("MASK_GT", False) else "mask_observed_est"      # get_pair_depth
+            labels = _frame(ctx, frames, key, np.uint8)
+            if labels.shape != depth.shape:
+                raise ValueError("frames['%s'] and frames['depth_observed'] differ in shape" % key)
+            idx = _ids(ctx, frames, "mask_idx", B)
+    return ObservedFrames(obs, fi, depth, labels, idx, _depth_factor(config).value)
+
+
 def _check_size(config, H, W):
     if (H, W) != tuple(int(s) for s in config.SCALES[0]):
         raise ValueError("frame size %dx%d is not config.SCALES[0] = %s: the resize of image.py:552-580 is not part of the "
@@ -103,6 +209,9 @@ def _means_rgb(config):
 def get_pair_image(frames, config, phase="train"):
     """image.py:58-163 → (image_observed, image_rendered), device (B,3,H,W). In the train phase, frames with a "bg_image" get the
     observed background replaced where mask_gt_observed == 0 (:147-155)."""
+    if is_shared(frames):
+        raise NotImplementedError("get_pair_image would make B fp32 copies of the shared frames (frames['frame_index']): use "
+                                  "observed_frames for the observed side and get_rendered_image for image_rendered")
     ctx = _context(frames)
     obs = _frame(ctx, frames, "image_observed", np.uint8, (3,))
     ren = _frame(ctx, frames, "image_rendered", np.uint8, (3,))
@@ -122,10 +231,23 @@ def get_pair_image(frames, config, phase="train"):
     return transform_batch(ctx, obs, means, bg, fg, use_bg), transform_batch(ctx, ren, means)
 
 
+def get_rendered_image(frames, config):
+    """The rendered half of `get_pair_image` → image_rendered, device (B,3,H,W): per pair in every kind of batch."""
+    ctx = _context(frames)
+    ren = _frame(ctx, frames, "image_rendered", np.uint8, (3,))
+    _check_size(config, ren.shape[1], ren.shape[2])
+    return transform_batch(ctx, ren, _means_rgb(config))
+
+
 def _depth(ctx, frames, key, config, label_key=None):
+    """frames[key] / DEPTH_FACTOR → device (B,1,H,W), zeroed outside the pair's label of frames[label_key]. In a shared-frame
+    batch the observed maps are (N,H,W) and pair b reads frame frame_index[b] (deepim_ingest_depth16_frames)."""
     d = _frame(ctx, frames, key, np.uint16)
     B, H, W = d.shape
     _check_size(config, H, W)
+    shared = is_shared(frames) and key in SHARED_KEYS
+    if shared:
+        fi, B, N = _frame_index(ctx, frames)
     labels = idx = None
     if label_key is not None:
         labels = _frame(ctx, frames, label_key, np.uint8)
@@ -133,7 +255,10 @@ def _depth(ctx, frames, key, config, label_key=None):
             raise ValueError("frames['%s'] and frames['%s'] differ in shape" % (label_key, key))
         idx = _ids(ctx, frames, "mask_idx", B)
     out = ctx.empty((B, 1, H, W))
-    lib.deepim_ingest_depth16(ctx.handle, out, d, labels, idx, _depth_factor(config), B, H, W)
+    if shared:
+        lib.deepim_ingest_depth16_frames(ctx.handle, out, d, labels, fi, idx, _depth_factor(config), N, B, H, W)
+    else:
+        lib.deepim_ingest_depth16(ctx.handle, out, d, labels, idx, _depth_factor(config), B, H, W)
     return out
 
 
@@ -155,9 +280,15 @@ def get_pair_depth(frames, config, phase="train"):
 
 
 def label_mask(ctx, frames, key):
-    """`label == mask_idx` (image.py:255-260, :308-312) → device (B,1,H,W) of 0 / 1."""
+    """`label == mask_idx` (image.py:255-260, :308-312) → device (B,1,H,W) of 0 / 1. In a shared-frame batch the label maps
+    are (N,H,W) and pair b reads frame frame_index[b] (deepim_ingest_label_mask_frames)."""
     labels = _frame(ctx, frames, key, np.uint8)
     B, H, W = labels.shape
+    if is_shared(frames):
+        fi, B, N = _frame_index(ctx, frames)
+        out = ctx.empty((B, 1, H, W))
+        lib.deepim_ingest_label_mask_frames(ctx.handle, out, labels, fi, _ids(ctx, frames, "mask_idx", B), N, B, H, W)
+        return out
     out = ctx.empty((B, 1, H, W))
     lib.deepim_ingest_label_mask(ctx.handle, out, labels, _ids(ctx, frames, "mask_idx", B), B, H, W)
     return out
@@ -181,6 +312,8 @@ def get_pair_mask(frames, config, phase="train", depth_rendered=None):
     dr = depth_rendered if depth_rendered is not None else _depth(ctx, frames, "depth_rendered", config)
     B, _, H, W = dr.shape
     if phase == "train":
+        if is_shared(frames):
+            raise NotImplementedError("shared frames (frames['frame_index']) are a test-phase input: the training loader is per pair")
         from ..pair_matching import data_pair
         batch = {"depth_rendered": dr, "mask_gt_observed": label_mask(ctx, frames, "mask_gt_observed")}
         if frames.get("mask_dilate_thickness") is not None:

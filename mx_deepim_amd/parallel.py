@@ -42,6 +42,9 @@ def shard_counts(n_pairs, world_size):
 def shard_pairs(batch, world_size, rank, n_pairs=None, replicated=("K",)):
     """Slice every per-pair array of a batch dict (leading axis = pairs; frame-major arrays have the pair
     axis second) to this rank's block. Keys in `replicated` (the intrinsics) are handed to every rank whole."""
+    if batch.get("frame_index") is not None or batch.get("observed_frames") is not None:
+        raise NotImplementedError("shard_pairs: a shared-frame batch (frame_index) holds N frames for its pairs and cannot be "
+                                  "cut along the pair axis; shard the pairs first and build each rank's batch from its own frames")
     n_pairs = n_pairs if n_pairs is not None else batch["image_observed"].shape[0]
     lo, hi = shard_bounds(n_pairs, world_size, rank)
     out = {}

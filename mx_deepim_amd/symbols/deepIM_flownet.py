@@ -543,8 +543,36 @@ class deepIM_flownet(object):
         return (getattr(self, "conv1_nc8", False) and self.nc8 and self.cin == 8 and self.input_mask and not self.input_depth
                 and not self.fp16_conv and not self.x3_conv and not getattr(self, "is_train", False) and self.W % 4 == 0)
 
+    def _zoom_frames(self, data, of):
+        """zoom() of a shared-frame batch (data["observed_frames"], lib/utils/image.ObservedFrames): the observed image [and
+        depth] are gathered from the N uint8 / uint16 frames through the device frame_index — the fp16 records on the fused fp16
+        path, else the NCHW net input (which the fp32, x3 and two-step fp16 encoders read; the opt-in NC8 front end has no
+        shared-frame variant). Both masks are required: the library refuses the mask-less ZoomImage configuration."""
+        A, h = self.act, self.ctx.handle
+        if of.n_pairs != self.B:
+            raise ValueError("observed_frames index %d pairs; the network is bound for %d" % (of.n_pairs, self.B))
+        if self.input_depth and of.depth is None:
+            raise ValueError("network.INPUT_DEPTH: the observed_frames of this batch carry no depth frames")
+        depth = of.depth if self.input_depth else None
+        labels, idx = (of.labels, of.mask_idx) if depth is not None else (None, None)
+        args = (of.image, of.frame_index, of.n_frames, data["image_rendered"],
+                data["mask_observed"] if self.input_mask else None, data["mask_rendered"] if self.input_mask else None,
+                depth, labels, idx, ctypes.c_float(of.depth_factor), data.get("depth_rendered") if self.input_depth else None,
+                data["src_pose"], self.K, self.pixel_means)
+        self._input_live_nc8 = False
+        if self.fp16_conv and getattr(self, "fp16_fused_input", False) and "net_input_h8" in A:
+            x2 = dict.__getitem__(A, "net_input_x2") if self.cin == 10 else None
+            lib.deepim_zoom_concat_frames_forward_h16(h, *(args + (dict.__getitem__(A, "net_input_h8"), x2, A["zoom_factor"],
+                                                                   self.B, self.H, self.W)))
+            self._input_live_h16 = True
+            return
+        self._input_live_h16 = False
+        lib.deepim_zoom_concat_frames_forward(h, *(args + (A["net_input"], A["zoom_factor"], self.B, self.H, self.W)))
+
     def zoom(self, data):
         A, h = self.act, self.ctx.handle
+        if data.get("observed_frames") is not None:
+            return self._zoom_frames(data, data["observed_frames"])
         if self.fp16_conv and getattr(self, "fp16_fused_input", False) and "net_input_h8" in A:
             x2 = dict.__getitem__(A, "net_input_x2") if self.cin == 10 else None
             lib.deepim_zoom_concat_forward_h16(h, data["image_observed"], data["image_rendered"], data["mask_observed"],
@@ -1062,6 +1090,9 @@ def _train_methods():
         mask_gt_observed, point_cloud_model, point_cloud_weights, point_cloud_observed [, flow, flow_weights] (device arrays).
         Returns the point-matching loss sum (device scalar) after filling every activation the backward needs; the flow loss
         and the mask probability land in self.act["flow_loss"] / ["mask_prob"]."""
+        if data.get("observed_frames") is not None:
+            raise NotImplementedError("forward_train: a shared-frame batch (data['observed_frames']) is a test-phase input; the "
+                                      "training graph reads per-pair image_observed tensors")
         A, P, h, B, H, W = self.act, self.params, self.ctx.handle, self.B, self.H, self.W
         c = ctypes.c_float
         t = self.cfg.train_iter
