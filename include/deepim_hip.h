@@ -240,7 +240,16 @@ int deepim_zoom_trans_forward(deepim_ctx* ctx, const float* zoom_factor, const f
                               float* zoom_trans_delta, int b_inv_zoom, int B);
 int deepim_zoom_trans_backward(deepim_ctx* ctx, const float* zoom_factor, const float* out_grad,
                                float* in_grad, int b_inv_zoom, int b_zoom_grad, int B);
-/* Fused front end of the test graph (deepIM_flownet.py:33-62 + :563-622): ZoomMask +
+/* The fused zoom front end: six entries over ONE channel list (csrc/zoom.hip zoom_concat4_body) and ONE launcher
+ * (launch_front_end), which differ along two independent axes only:
+ *   observed source  per-pair fp32 tensors (image_observed, depth_observed)   | N shared decoded frames + frame_index (_frames_)
+ *   output form      (B,C,H,W) fp32 planes | (B,H,W,8) fp32 NC8 records (_nc8, per-pair tensors only) | fp16 records (_h16)
+ * Channels, in order, each with the same operations in every entry: observed and rendered image (un-mean, /255), observed
+ * and rendered depth (/255, when given), observed mask (round) and rendered mask (>0.2, round) (when given). Every form
+ * carries the bits of the planes form; W % 4 != 0 or a misaligned output is served by the planes form from per-pair tensors
+ * only (generic resampler), the other entries refuse it.
+ *
+ * Fused front end of the test graph (deepIM_flownet.py:33-62 + :563-622): ZoomMask +
  * ZoomImageWithFactor [+ ZoomDepth] + `/255` + Concat written straight into the
  * conv1 input (B,C,H,W), C = 8 (+2 with depth). Also returns zoom_factor. depth_* may be NULL.
  * With both masks NULL (INPUT_MASK=False, deepIM_flownet.py:594-605) the factor comes from ZoomImage's

@@ -396,11 +396,13 @@ __global__ __launch_bounds__(256) void resample4_kernel(Plan plan, const float* 
 // The fused front end of the test graph (deepIM_flownet.py:563-622 + :33-62: ZoomMask / ZoomImageWithFactor / ZoomDepth +
 // /255 + Concat) with every channel's pre/post op known at compile time: the generic plan kernel spends more instructions
 // on run-time flag tests and IEEE divisions than on the blend itself (85 VALU ops per output there).
+// Two independent axes: where the observed image and depth come from (ObsPlanes / ObsFrames) and what form the network
+// input leaves in (PlanesSink / Nc8Sink / H16Sink). zoom_concat4_body walks the channel list once for all of them.
 struct ConcatArgs {
   const float* image_observed; const float* image_rendered;   // (B,3,H,W)
   const float* depth_observed; const float* depth_rendered;   // (B,1,H,W) or unused
   const float* mask_observed;  const float* mask_rendered;    // (B,1,H,W) or unused
-  float* net_input;                                           // (B,C,H,W)
+  float* net_input;                                           // planes (B,C,H,W) or NC8 records (B,H,W,8); fp16 records: unused
   Vec3 means;
   int C;
 };
@@ -447,9 +449,80 @@ struct ObsFrames {
   }
 };
 
-template <bool DEPTH, bool MASK, class OBS>
-__device__ __forceinline__ void zoom_concat4_body(const ConcatArgs& g, const OBS& obs, const float* __restrict__ zoom_factor,
-                                                  int H, int W, float gx_step, float gy_step) {
+// Where the channels of a pixel quad go. begin(b, p): before the first channel, for pair b with planes of p pixels;
+// channel<FLS>(slot, tap, mean, ...): resample net-input channel `slot` (a constant once the body is unrolled) from `tap` with
+// the compile-time flags FLS; flush(b, p, opix): after the last channel, opix the quad's first pixel.
+// PlanesSink: (B,C,H,W) fp32, one dwordx4 store per channel as soon as it is done (resample_channel4).
+struct PlanesSink {
+  float* out;
+  int C;
+  long p;
+  __device__ __forceinline__ PlanesSink(const ConcatArgs& g) : out(g.net_input), C(g.C) {}
+  __device__ __forceinline__ void begin(int b, long p_) { out += (long)b * C * p_; p = p_; }
+  template <int FLS, class TAP>
+  __device__ __forceinline__ void channel(int slot, const TAP& s, float mean, const Quad& q, const Affine& a, int H, int W) {
+    resample_channel4<FLS>(s, out + slot * p, mean, 0, q, a, H, W);
+  }
+  __device__ __forceinline__ void flush(int, long, long) {}
+};
+template <int C>
+struct RecordSink {   // keeps the quad's C channels in registers for the sink's flush()
+  float o[C][4];
+  __device__ __forceinline__ void begin(int, long) {}
+  template <int FLS, class TAP>
+  __device__ __forceinline__ void channel(int slot, const TAP& s, float mean, const Quad& q, const Affine& a, int H, int W) {
+    resample_channel4_vals<FLS>(s, o[slot], mean, 0, q, a, H, W);
+  }
+};
+// Nc8Sink: the shipped 8-channel input (RGB pair + masks) as CHANNEL-BLOCKED records — [n][h][w][8], the "NC8" layout with
+// C = 8 — so that conv1 runs on the 16-byte-load kernel of the other encoder layers instead of gathering dwords from eight
+// NCHW planes. A thread owns 4 consecutive pixels of all 8 channels: 128 contiguous bytes, eight dwordx4 stores.
+struct Nc8Sink : RecordSink<8> {
+  float* out;
+  __device__ __forceinline__ Nc8Sink(const ConcatArgs& g) : out(g.net_input) {}
+  __device__ __forceinline__ void flush(int b, long p, long opix) {
+    float4* rec = reinterpret_cast<float4*>(out + ((long)b * p + opix) * 8);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      rec[2 * i] = make_float4(o[0][i], o[1][i], o[2][i], o[3][i]);
+      rec[2 * i + 1] = make_float4(o[4][i], o[5][i], o[6][i], o[7][i]);
+    }
+  }
+};
+// H16Sink, the fp16 conv path (BASELINE config 5): the same values rounded once to fp16 (RNE, what the separate NCHW fp32 →
+// NHWC fp16 pass did) and written as the pixel records conv1's patch kernel reads — main (B,H,W,8 halves) = the first eight
+// net-input channels, and with DEPTH the two remaining ones (the masks) as (B,H,W,2 halves). Half the bytes of the fp32 net
+// input on the way out, a quarter on conv1's way in.
+template <bool DEPTH>
+struct H16Sink : RecordSink<DEPTH ? 10 : 8> {
+  _Float16* __restrict__ main8;
+  _Float16* __restrict__ extra2;
+  __device__ __forceinline__ H16Sink(_Float16* __restrict__ m, _Float16* __restrict__ x) : main8(m), extra2(x) {}
+  __device__ __forceinline__ void flush(int b, long p, long opix) {
+    typedef _Float16 h8v __attribute__((ext_vector_type(8)));
+    h8v* rec = reinterpret_cast<h8v*>(main8 + ((long)b * p + opix) * 8);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      h8v r;
+#pragma unroll
+      for (int c = 0; c < 8; ++c) r[c] = (_Float16)this->o[c][i];
+      rec[i] = r;
+    }
+    if (DEPTH) {
+      h8v r;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) { r[2 * i] = (_Float16)this->o[8][i]; r[2 * i + 1] = (_Float16)this->o[9][i]; }
+      *reinterpret_cast<h8v*>(extra2 + ((long)b * p + opix) * 2) = r;
+    }
+  }
+};
+
+// The channel list, the parity contract with the reference graph: image pair (un-mean, /255), [depth pair (/255)], [mask
+// pair (round; the rendered one binarised at 0.2 first)] — the masks are the last two channels.
+template <bool DEPTH, bool MASK, class OBS, class SINK>
+__device__ __forceinline__ void zoom_concat4_body(const ConcatArgs& g, const OBS& obs, SINK sink,
+                                                  const float* __restrict__ zoom_factor, int H, int W, float gx_step,
+                                                  float gy_step) {
   const int qpr = W >> 2;
   const int qid = blockIdx.x * 256 + threadIdx.x;
   const int b = blockIdx.y;
@@ -458,128 +531,56 @@ __device__ __forceinline__ void zoom_concat4_body(const ConcatArgs& g, const OBS
   const Affine a = load_affine(zoom_factor, b, 0, H, W);
   const Quad q = make_quad(a, h, w0, H, W, gx_step, gy_step);
   const long p = (long)H * W;
-  float* out = g.net_input + (long)b * g.C * p;
+  sink.begin(b, p);
 #pragma unroll
   for (int c = 0; c < 3; ++c)
-    resample_channel4<CF_POST_DIV255>(obs.image_tap(c, p, g.means.v[c]), out + c * p, g.means.v[c], 0, q, a, H, W);
+    sink.template channel<CF_POST_DIV255>(c, obs.image_tap(c, p, g.means.v[c]), g.means.v[c], q, a, H, W);
 #pragma unroll
   for (int c = 0; c < 3; ++c)
-    resample_channel4<CF_POST_DIV255>(PlaneTap{g.image_rendered + ((long)b * 3 + c) * p}, out + (3 + c) * p, g.means.v[c], 0, q, a, H, W);
-  int n = 6;
+    sink.template channel<CF_POST_DIV255>(3 + c, PlaneTap{g.image_rendered + ((long)b * 3 + c) * p}, g.means.v[c], q, a, H, W);
   if (DEPTH) {
-    resample_channel4<CF_POST_DIV255>(obs.depth_tap(p), out + (long)n * p, 0.f, 0, q, a, H, W);
-    resample_channel4<CF_POST_DIV255>(PlaneTap{g.depth_rendered + (long)b * p}, out + (long)(n + 1) * p, 0.f, 0, q, a, H, W);
-    n += 2;
+    sink.template channel<CF_POST_DIV255>(6, obs.depth_tap(p), 0.f, q, a, H, W);
+    sink.template channel<CF_POST_DIV255>(7, PlaneTap{g.depth_rendered + (long)b * p}, 0.f, q, a, H, W);
   }
   if (MASK) {
-    resample_channel4<CF_POST_ROUND>(PlaneTap{g.mask_observed + (long)b * p}, out + (long)n * p, 0.f, 0, q, a, H, W);
-    resample_channel4<CF_PRE_BIN02 | CF_POST_ROUND>(PlaneTap{g.mask_rendered + (long)b * p}, out + (long)(n + 1) * p, 0.f, 0, q, a, H, W);
+    constexpr int n = DEPTH ? 8 : 6;
+    sink.template channel<CF_POST_ROUND>(n, PlaneTap{g.mask_observed + (long)b * p}, 0.f, q, a, H, W);
+    sink.template channel<CF_PRE_BIN02 | CF_POST_ROUND>(n + 1, PlaneTap{g.mask_rendered + (long)b * p}, 0.f, q, a, H, W);
   }
+  sink.flush(b, p, q.opix);
 }
+
+// The entry points: a name per (observed source, output form), each only choosing the body's source and sink. With frames the
+// masks are always there; LABELS: the observed depth is zeroed outside the pair's label.
 template <bool DEPTH, bool MASK>
 __global__ __launch_bounds__(256) void zoom_concat4_kernel(ConcatArgs g, const float* __restrict__ zoom_factor, int H, int W,
                                                            float gx_step, float gy_step) {
-  zoom_concat4_body<DEPTH, MASK>(g, ObsPlanes(g, blockIdx.y), zoom_factor, H, W, gx_step, gy_step);
+  zoom_concat4_body<DEPTH, MASK>(g, ObsPlanes(g, blockIdx.y), PlanesSink(g), zoom_factor, H, W, gx_step, gy_step);
 }
-// the masked front end over shared frames; LABELS: the observed depth is zeroed outside the pair's label
 template <bool DEPTH, bool LABELS>
 __global__ __launch_bounds__(256) void zoom_concat4_frames_kernel(ConcatArgs g, FrameArgs f, const float* __restrict__ zoom_factor,
                                                                   int H, int W, float gx_step, float gy_step) {
-  zoom_concat4_body<DEPTH, true>(g, ObsFrames<LABELS>(f, blockIdx.y, blockIdx.x == 0 && threadIdx.x == 0), zoom_factor, H, W,
-                                 gx_step, gy_step);
+  zoom_concat4_body<DEPTH, true>(g, ObsFrames<LABELS>(f, blockIdx.y, blockIdx.x == 0 && threadIdx.x == 0), PlanesSink(g),
+                                 zoom_factor, H, W, gx_step, gy_step);
 }
-
-// The same front end for the shipped 8-channel input (RGB pair + masks) writing CHANNEL-BLOCKED records — [n][h][w][8], the
-// "NC8" layout with C = 8 — so that conv1 runs on the 16-byte-load kernel of the other encoder layers instead of gathering
-// dwords from eight NCHW planes. A thread owns 4 consecutive pixels of all 8 channels: 128 contiguous bytes, eight dwordx4
-// stores; values identical to the NCHW kernel's (same resample_channel4_vals calls).
 __global__ __launch_bounds__(256) void zoom_concat4_nc8_kernel(ConcatArgs g, const float* __restrict__ zoom_factor, int H, int W,
                                                                float gx_step, float gy_step) {
-  const int qpr = W >> 2;
-  const int qid = blockIdx.x * 256 + threadIdx.x;
-  const int b = blockIdx.y;
-  if (qid >= qpr * H) return;
-  const int h = qid / qpr, w0 = (qid - h * qpr) << 2;
-  const Affine a = load_affine(zoom_factor, b, 0, H, W);
-  const Quad q = make_quad(a, h, w0, H, W, gx_step, gy_step);
-  const long p = (long)H * W;
-  float o[8][4];
-#pragma unroll
-  for (int c = 0; c < 3; ++c)
-    resample_channel4_vals<CF_POST_DIV255>(PlaneTap{g.image_observed + ((long)b * 3 + c) * p}, o[c], g.means.v[c], 0, q, a, H, W);
-#pragma unroll
-  for (int c = 0; c < 3; ++c)
-    resample_channel4_vals<CF_POST_DIV255>(PlaneTap{g.image_rendered + ((long)b * 3 + c) * p}, o[3 + c], g.means.v[c], 0, q, a, H, W);
-  resample_channel4_vals<CF_POST_ROUND>(PlaneTap{g.mask_observed + (long)b * p}, o[6], 0.f, 0, q, a, H, W);
-  resample_channel4_vals<CF_PRE_BIN02 | CF_POST_ROUND>(PlaneTap{g.mask_rendered + (long)b * p}, o[7], 0.f, 0, q, a, H, W);
-  float4* rec = reinterpret_cast<float4*>(g.net_input + ((long)b * p + q.opix) * 8);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    rec[2 * i] = make_float4(o[0][i], o[1][i], o[2][i], o[3][i]);
-    rec[2 * i + 1] = make_float4(o[4][i], o[5][i], o[6][i], o[7][i]);
-  }
-}
-
-// The front end of the fp16 conv path (BASELINE config 5): the same values rounded once to fp16 (RNE, what the separate
-// NCHW fp32 → NHWC fp16 pass did) and written as the pixel records conv1's patch kernel reads — main (B,H,W,8 halves) = the
-// first eight net-input channels, and with DEPTH the two remaining ones (the masks) as (B,H,W,2 halves). Half the bytes of
-// the fp32 net input on the way out, a quarter on conv1's way in.
-template <bool DEPTH, class OBS>
-__device__ __forceinline__ void zoom_concat4_h16_body(const ConcatArgs& g, const OBS& obs, _Float16* __restrict__ main8,
-                                                      _Float16* __restrict__ extra2, const float* __restrict__ zoom_factor,
-                                                      int H, int W, float gx_step, float gy_step) {
-  constexpr int C = DEPTH ? 10 : 8;
-  const int qpr = W >> 2;
-  const int qid = blockIdx.x * 256 + threadIdx.x;
-  const int b = blockIdx.y;
-  if (qid >= qpr * H) return;
-  const int h = qid / qpr, w0 = (qid - h * qpr) << 2;
-  const Affine a = load_affine(zoom_factor, b, 0, H, W);
-  const Quad q = make_quad(a, h, w0, H, W, gx_step, gy_step);
-  const long p = (long)H * W;
-  float o[C][4];
-#pragma unroll
-  for (int c = 0; c < 3; ++c)
-    resample_channel4_vals<CF_POST_DIV255>(obs.image_tap(c, p, g.means.v[c]), o[c], g.means.v[c], 0, q, a, H, W);
-#pragma unroll
-  for (int c = 0; c < 3; ++c)
-    resample_channel4_vals<CF_POST_DIV255>(PlaneTap{g.image_rendered + ((long)b * 3 + c) * p}, o[3 + c], g.means.v[c], 0, q, a, H, W);
-  if (DEPTH) {
-    resample_channel4_vals<CF_POST_DIV255>(obs.depth_tap(p), o[6], 0.f, 0, q, a, H, W);
-    resample_channel4_vals<CF_POST_DIV255>(PlaneTap{g.depth_rendered + (long)b * p}, o[7], 0.f, 0, q, a, H, W);
-  }
-  resample_channel4_vals<CF_POST_ROUND>(PlaneTap{g.mask_observed + (long)b * p}, o[C - 2], 0.f, 0, q, a, H, W);
-  resample_channel4_vals<CF_PRE_BIN02 | CF_POST_ROUND>(PlaneTap{g.mask_rendered + (long)b * p}, o[C - 1], 0.f, 0, q, a, H, W);
-  typedef _Float16 h8v __attribute__((ext_vector_type(8)));
-  h8v* rec = reinterpret_cast<h8v*>(main8 + ((long)b * p + q.opix) * 8);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    h8v r;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) r[c] = (_Float16)o[c][i];
-    rec[i] = r;
-  }
-  if (DEPTH) {
-    h8v r;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { r[2 * i] = (_Float16)o[8][i]; r[2 * i + 1] = (_Float16)o[9][i]; }
-    *reinterpret_cast<h8v*>(extra2 + ((long)b * p + q.opix) * 2) = r;
-  }
+  zoom_concat4_body<false, true>(g, ObsPlanes(g, blockIdx.y), Nc8Sink(g), zoom_factor, H, W, gx_step, gy_step);
 }
 template <bool DEPTH>
 __global__ __launch_bounds__(256) void zoom_concat4_h16_kernel(ConcatArgs g, _Float16* __restrict__ main8,
                                                                _Float16* __restrict__ extra2,
                                                                const float* __restrict__ zoom_factor, int H, int W,
                                                                float gx_step, float gy_step) {
-  zoom_concat4_h16_body<DEPTH>(g, ObsPlanes(g, blockIdx.y), main8, extra2, zoom_factor, H, W, gx_step, gy_step);
+  zoom_concat4_body<DEPTH, true>(g, ObsPlanes(g, blockIdx.y), H16Sink<DEPTH>(main8, extra2), zoom_factor, H, W, gx_step, gy_step);
 }
 template <bool DEPTH, bool LABELS>
 __global__ __launch_bounds__(256) void zoom_concat4_h16_frames_kernel(ConcatArgs g, FrameArgs f, _Float16* __restrict__ main8,
                                                                       _Float16* __restrict__ extra2,
                                                                       const float* __restrict__ zoom_factor, int H, int W,
                                                                       float gx_step, float gy_step) {
-  zoom_concat4_h16_body<DEPTH>(g, ObsFrames<LABELS>(f, blockIdx.y, blockIdx.x == 0 && threadIdx.x == 0), main8, extra2,
-                               zoom_factor, H, W, gx_step, gy_step);
+  zoom_concat4_body<DEPTH, true>(g, ObsFrames<LABELS>(f, blockIdx.y, blockIdx.x == 0 && threadIdx.x == 0), H16Sink<DEPTH>(main8, extra2),
+                                 zoom_factor, H, W, gx_step, gy_step);
 }
 
 // every float bit pattern through div255 against the IEEE division (parity hook)
@@ -808,6 +809,115 @@ extern "C" int deepim_zoom_trans_backward(deepim_ctx* ctx, const float* zoom_fac
   return 0;
 }
 
+// ------------------------------------------------------- fused front end ----
+// What one deepim_zoom_concat_* entry asks for: the tensors, where the observed image and depth come from, which map gives
+// the observed box, and the form of the network input. launch_front_end() does the rest for all of them.
+enum FrontForm { FORM_PLANES = 0, FORM_NC8 = 1, FORM_H16 = 2 };
+struct FrontEnd {
+  ConcatArgs g;               // tensors and the fp32 output (means and C are filled in by the launcher)
+  _Float16* main8;            // FORM_H16: the fp16 records (B,H,W,8) and, with depth, (B,H,W,2)
+  _Float16* extra2;
+  FrameArgs f;                // observed source when `frames` (bgr8, depth16, labels, frame_index, mask_idx, depth_factor, N)
+  bool frames;                // false: g.image_observed / g.depth_observed
+  const float* box_observed;  // ZoomMask's observed map; NULL: g.mask_observed, and the two images when there are no masks
+  FrontForm form;
+  const char* need_masks;     // the entry's wording of its three refusals (need_together: NULL = nothing to check)
+  const char* need_together;
+  const char* need_aligned;
+};
+static FrontEnd front_end(const float* image_observed, const float* image_rendered, const float* mask_observed,
+                          const float* mask_rendered, const float* depth_observed, const float* depth_rendered) {
+  FrontEnd e = {};
+  e.g.image_observed = image_observed; e.g.image_rendered = image_rendered;
+  e.g.depth_observed = depth_observed; e.g.depth_rendered = depth_rendered;
+  e.g.mask_observed = mask_observed; e.g.mask_rendered = mask_rendered;
+  return e;
+}
+
+// [form][frames][depth][mask (per-pair tensors) | labels (frames, always with masks)]; NULL: no such front end
+template <class... A>
+static const void* fk(void (*kernel)(A...)) { return reinterpret_cast<const void*>(kernel); }
+static const void* const FRONT_KERNEL[3][2][2][2] = {
+    {{{fk(zoom_concat4_kernel<false, false>), fk(zoom_concat4_kernel<false, true>)},
+      {fk(zoom_concat4_kernel<true, false>), fk(zoom_concat4_kernel<true, true>)}},
+     {{fk(zoom_concat4_frames_kernel<false, false>), nullptr},
+      {fk(zoom_concat4_frames_kernel<true, false>), fk(zoom_concat4_frames_kernel<true, true>)}}},
+    {{{nullptr, fk(zoom_concat4_nc8_kernel)}, {nullptr, nullptr}},   // (8 channels, per-pair tensors only)
+     {{nullptr, nullptr}, {nullptr, nullptr}}},
+    {{{nullptr, fk(zoom_concat4_h16_kernel<false>)}, {nullptr, fk(zoom_concat4_h16_kernel<true>)}},
+     {{fk(zoom_concat4_h16_frames_kernel<false, false>), nullptr},
+      {fk(zoom_concat4_h16_frames_kernel<true, false>), fk(zoom_concat4_h16_frames_kernel<true, true>)}}},
+};
+
+static int launch_front_end(deepim_ctx* ctx, FrontEnd e, const float* src_pose, const float* K_host,
+                            const float* pixel_means_host, float* zoom_factor, int B, int H, int W) {
+  DI_DEVICE(ctx);
+  if (B == 0) return 0;
+  ConcatArgs& g = e.g;
+  const FrameArgs& f = e.f;
+  const bool with_mask = g.mask_observed != nullptr;
+  const bool dep = e.frames ? f.depth16 != nullptr : g.depth_observed != nullptr;
+  // only the planes form from per-pair tensors also comes without masks (ZoomImage boxes) and with any W or alignment
+  const bool plain = e.form == FORM_PLANES && !e.frames;
+  DI_REQUIRE(with_mask == (g.mask_rendered != nullptr) && (with_mask || plain), e.need_masks);
+  if (e.frames) {
+    DI_REQUIRE(f.bgr8 && f.frame_index && f.N >= 1, "zoom_concat_frames: frames_bgr8, frame_index and N >= 1 are required");
+    DI_REQUIRE((W & 3) == 0, "zoom_concat_frames: W % 4 == 0 and 16-byte aligned outputs");
+    DI_REQUIRE(dep == (g.depth_rendered != nullptr), "zoom_concat_frames: depth_frames16 and depth_rendered go together");
+    DI_REQUIRE(((size_t)f.depth16 & 1) == 0, "zoom_concat_frames: depth_frames16 must be 2-byte aligned");
+    DI_REQUIRE((f.labels != nullptr) == (f.mask_idx != nullptr) && (!f.labels || f.depth16),
+               "zoom_concat_frames: depth_labels and mask_idx come together, and only with depth_frames16");
+  }
+  if (e.need_together)   // fp16 records: the depth pair and the masks' extra2 records
+    DI_REQUIRE(dep == (g.depth_rendered != nullptr) && dep == (e.extra2 != nullptr), e.need_together);
+  const void* out = e.form == FORM_H16 ? (const void*)e.main8 : (const void*)g.net_input;
+  const bool aligned = (W & 3) == 0 && ((size_t)out & 15) == 0 && ((size_t)e.extra2 & 15) == 0;
+  if (!plain) DI_REQUIRE(aligned && (e.form != FORM_H16 || e.main8), e.need_aligned);
+
+  int rc;
+  if (with_mask)  // ZoomMask; test graph: mask_gt_observed ≡ mask_observed (deepIM_flownet.py:564)
+    rc = compute_zoom_factor(ctx, zoom_factor, e.box_observed ? e.box_observed : g.mask_observed, g.mask_rendered, BB_MASK_GT,
+                             BB_MASK_RENDERED, nullptr, src_pose, K_host, B, H, W);
+  else            // ZoomImage: boxes of the non-black pixels (deepIM_flownet.py:594-605, zoom_image.py:31-37)
+    rc = compute_zoom_factor(ctx, zoom_factor, g.image_observed, g.image_rendered, BB_IMAGE, BB_IMAGE, pixel_means_host,
+                             src_pose, K_host, B, H, W);
+  if (rc) return rc;
+  g.C = 6 + (dep ? 2 : 0) + (with_mask ? 2 : 0);
+  for (int i = 0; i < 3; ++i) g.means.v[i] = pixel_means_host ? pixel_means_host[i] : 0.f;
+
+  if (plain && !aligned) {   // W % 4 != 0 or a misaligned net_input: the same channel list on the generic plan kernels
+    const long p = (long)H * W, db = (long)g.C * p;
+    float* out_p = g.net_input;
+    Plan plan; plan.inverse = 0;
+    image_plan(plan, 0, g.image_observed, out_p, 3 * p, db, p, pixel_means_host, CF_POST_DIV255, 0);
+    image_plan(plan, 3, g.image_rendered, out_p + 3 * p, 3 * p, db, p, pixel_means_host, CF_POST_DIV255, 0);
+    int n = 6;
+    if (dep) {
+      plan.ch[n] = make_chan(g.depth_observed, out_p + n * p, p, db, 0.f, CF_POST_DIV255); ++n;
+      plan.ch[n] = make_chan(g.depth_rendered, out_p + n * p, p, db, 0.f, CF_POST_DIV255); ++n;
+    }
+    if (with_mask) {
+      plan.ch[n] = make_chan(g.mask_observed, out_p + n * p, p, db, 0.f, CF_POST_ROUND); ++n;
+      plan.ch[n] = make_chan(g.mask_rendered, out_p + n * p, p, db, 0.f, CF_PRE_BIN02 | CF_POST_ROUND); ++n;
+    }
+    plan.n = n;
+    return launch_resample(ctx, plan, zoom_factor, B, H, W);
+  }
+  const void* kernel = FRONT_KERNEL[e.form][e.frames][dep][e.frames ? f.labels != nullptr : with_mask];
+  DI_REQUIRE(kernel, "zoom front end: no kernel for this source, form and channel set");
+  float gx = (float)(2.0 / (W - 1)), gy = (float)(2.0 / (H - 1));
+  // the kernels' parameter lists: (g, [f with frames], [main8, extra2 for fp16 records], zoom_factor, H, W, gx, gy)
+  void* args[10];
+  int n = 0;
+  args[n++] = &g;
+  if (e.frames) args[n++] = &e.f;
+  if (e.form == FORM_H16) { args[n++] = &e.main8; args[n++] = &e.extra2; }
+  args[n++] = &zoom_factor; args[n++] = &H; args[n++] = &W; args[n++] = &gx; args[n++] = &gy;
+  (void)hipLaunchKernel(kernel, dim3(di_div_up((long)(W / 4) * H, 256), B), dim3(256), args, 0, ctx->stream);
+  DI_LAUNCH_CHECK();
+  return 0;
+}
+
 extern "C" int deepim_zoom_concat_forward(deepim_ctx* ctx, const float* image_observed, const float* image_rendered,
                                           const float* mask_observed, const float* mask_rendered,
                                           const float* depth_observed, const float* depth_rendered,
@@ -823,24 +933,11 @@ extern "C" int deepim_zoom_concat_forward_nc8(deepim_ctx* ctx, const float* imag
                                               const float* mask_observed, const float* mask_rendered, const float* src_pose,
                                               const float* K_host, const float* pixel_means_host, float* net_input_nc8,
                                               float* zoom_factor, int B, int H, int W) {
-  DI_DEVICE(ctx);
-  if (B == 0) return 0;
-  DI_REQUIRE(mask_observed && mask_rendered, "zoom_concat_nc8: the 8-channel input needs both masks");
-  DI_REQUIRE((W & 3) == 0 && ((size_t)net_input_nc8 & 15) == 0, "zoom_concat_nc8: W % 4 == 0 and a 16-byte aligned output");
-  int rc = compute_zoom_factor(ctx, zoom_factor, mask_observed, mask_rendered, BB_MASK_GT, BB_MASK_RENDERED, nullptr, src_pose,
-                               K_host, B, H, W);
-  if (rc) return rc;
-  ConcatArgs g;
-  g.image_observed = image_observed; g.image_rendered = image_rendered;
-  g.depth_observed = g.depth_rendered = nullptr;
-  g.mask_observed = mask_observed; g.mask_rendered = mask_rendered;
-  g.net_input = net_input_nc8; g.C = 8;
-  for (int i = 0; i < 3; ++i) g.means.v[i] = pixel_means_host ? pixel_means_host[i] : 0.f;
-  const float gx = (float)(2.0 / (W - 1)), gy = (float)(2.0 / (H - 1));
-  dim3 grid(di_div_up((long)(W / 4) * H, 256), B);
-  hipLaunchKernelGGL(zoom_concat4_nc8_kernel, grid, dim3(256), 0, ctx->stream, g, zoom_factor, H, W, gx, gy);
-  DI_LAUNCH_CHECK();
-  return 0;
+  FrontEnd e = front_end(image_observed, image_rendered, mask_observed, mask_rendered, nullptr, nullptr);
+  e.form = FORM_NC8; e.g.net_input = net_input_nc8;
+  e.need_masks = "zoom_concat_nc8: the 8-channel input needs both masks";
+  e.need_aligned = "zoom_concat_nc8: W % 4 == 0 and a 16-byte aligned output";
+  return launch_front_end(ctx, e, src_pose, K_host, pixel_means_host, zoom_factor, B, H, W);
 }
 
 // front end of the fp16 conv path: fp16 pixel records for deepim_conv1_f16_h16_forward (depth_* and extra2 both NULL or both set)
@@ -849,53 +946,28 @@ extern "C" int deepim_zoom_concat_forward_h16(deepim_ctx* ctx, const float* imag
                                               const float* depth_observed, const float* depth_rendered, const float* src_pose,
                                               const float* K_host, const float* pixel_means_host, void* main8, void* extra2,
                                               float* zoom_factor, int B, int H, int W) {
-  DI_DEVICE(ctx);
-  if (B == 0) return 0;
-  DI_REQUIRE(mask_observed && mask_rendered, "zoom_concat_h16: needs both masks (8- or 10-channel input)");
-  const bool dep = depth_observed != nullptr;
-  DI_REQUIRE(dep == (depth_rendered != nullptr) && dep == (extra2 != nullptr), "zoom_concat_h16: depth pair and extra2 go together");
-  DI_REQUIRE((W & 3) == 0 && ((size_t)main8 & 15) == 0 && ((size_t)extra2 & 15) == 0, "zoom_concat_h16: W % 4 == 0, 16-byte aligned outputs");
-  int rc = compute_zoom_factor(ctx, zoom_factor, mask_observed, mask_rendered, BB_MASK_GT, BB_MASK_RENDERED, nullptr, src_pose,
-                               K_host, B, H, W);
-  if (rc) return rc;
-  ConcatArgs g;
-  g.image_observed = image_observed; g.image_rendered = image_rendered;
-  g.depth_observed = depth_observed; g.depth_rendered = depth_rendered;
-  g.mask_observed = mask_observed; g.mask_rendered = mask_rendered;
-  g.net_input = nullptr; g.C = dep ? 10 : 8;
-  for (int i = 0; i < 3; ++i) g.means.v[i] = pixel_means_host ? pixel_means_host[i] : 0.f;
-  const float gx = (float)(2.0 / (W - 1)), gy = (float)(2.0 / (H - 1));
-  dim3 grid(di_div_up((long)(W / 4) * H, 256), B);
-  if (dep) hipLaunchKernelGGL(zoom_concat4_h16_kernel<true>, grid, dim3(256), 0, ctx->stream, g, (_Float16*)main8, (_Float16*)extra2, zoom_factor, H, W, gx, gy);
-  else hipLaunchKernelGGL(zoom_concat4_h16_kernel<false>, grid, dim3(256), 0, ctx->stream, g, (_Float16*)main8, (_Float16*)nullptr, zoom_factor, H, W, gx, gy);
-  DI_LAUNCH_CHECK();
-  return 0;
+  FrontEnd e = front_end(image_observed, image_rendered, mask_observed, mask_rendered, depth_observed, depth_rendered);
+  e.form = FORM_H16; e.main8 = (_Float16*)main8; e.extra2 = (_Float16*)extra2;
+  e.need_masks = "zoom_concat_h16: needs both masks (8- or 10-channel input)";
+  e.need_together = "zoom_concat_h16: depth pair and extra2 go together";
+  e.need_aligned = "zoom_concat_h16: W % 4 == 0, 16-byte aligned outputs";
+  return launch_front_end(ctx, e, src_pose, K_host, pixel_means_host, zoom_factor, B, H, W);
 }
 
-// Shared frames (several objects in one camera frame): the two front ends above with the observed channels gathered from N
-// decoded frames through frame_index. Checks and argument blocks common to both entries; 0 or the error code.
-static int frames_front_end_args(deepim_ctx* ctx, ConcatArgs& g, FrameArgs& f, const uint8_t* frames_bgr8,
-                                 const int32_t* frame_index, int N, const float* image_rendered, const float* mask_observed,
-                                 const float* mask_rendered, const uint16_t* depth_frames16, const uint8_t* depth_labels,
-                                 const int32_t* mask_idx, float depth_factor, const float* depth_rendered,
-                                 const float* pixel_means_host, int W) {
-  DI_REQUIRE(mask_observed && mask_rendered, "zoom_concat_frames: needs both masks — the mask-less ZoomImage box search reads fp32 "
-                                             "images, which a shared-frame batch does not have");
-  DI_REQUIRE(frames_bgr8 && frame_index && N >= 1, "zoom_concat_frames: frames_bgr8, frame_index and N >= 1 are required");
-  DI_REQUIRE((W & 3) == 0, "zoom_concat_frames: W % 4 == 0 and 16-byte aligned outputs");
-  DI_REQUIRE((depth_frames16 != nullptr) == (depth_rendered != nullptr), "zoom_concat_frames: depth_frames16 and depth_rendered go together");
-  DI_REQUIRE(((size_t)depth_frames16 & 1) == 0, "zoom_concat_frames: depth_frames16 must be 2-byte aligned");
-  DI_REQUIRE((depth_labels != nullptr) == (mask_idx != nullptr) && (!depth_labels || depth_frames16),
-             "zoom_concat_frames: depth_labels and mask_idx come together, and only with depth_frames16");
-  g.image_observed = nullptr; g.image_rendered = image_rendered;
-  g.depth_observed = nullptr; g.depth_rendered = depth_rendered;
-  g.mask_observed = mask_observed; g.mask_rendered = mask_rendered;
-  g.net_input = nullptr; g.C = depth_frames16 ? 10 : 8;
-  for (int i = 0; i < 3; ++i) g.means.v[i] = pixel_means_host ? pixel_means_host[i] : 0.f;
-  f.bgr8 = frames_bgr8; f.depth16 = depth_frames16; f.labels = depth_labels;
-  f.frame_index = frame_index; f.mask_idx = mask_idx; f.status = ctx->status;
-  f.depth_factor = depth_factor; f.N = N;
-  return 0;
+// Shared frames (several objects in one camera frame): the planes and fp16-record front ends with the observed channels
+// gathered from N decoded frames through frame_index.
+static FrontEnd frames_front_end(deepim_ctx* ctx, const uint8_t* frames_bgr8, const int32_t* frame_index, int N,
+                                 const float* image_rendered, const float* mask_observed, const float* mask_rendered,
+                                 const uint16_t* depth_frames16, const uint8_t* depth_labels, const int32_t* mask_idx,
+                                 float depth_factor, const float* depth_rendered) {
+  FrontEnd e = front_end(nullptr, image_rendered, mask_observed, mask_rendered, nullptr, depth_rendered);
+  e.frames = true;
+  e.f.bgr8 = frames_bgr8; e.f.depth16 = depth_frames16; e.f.labels = depth_labels;
+  e.f.frame_index = frame_index; e.f.mask_idx = mask_idx; e.f.status = ctx->status;
+  e.f.depth_factor = depth_factor; e.f.N = N;
+  e.need_masks = "zoom_concat_frames: needs both masks — the mask-less ZoomImage box search reads fp32 "
+                 "images, which a shared-frame batch does not have";
+  return e;
 }
 
 extern "C" int deepim_zoom_concat_frames_forward(deepim_ctx* ctx, const uint8_t* frames_bgr8, const int32_t* frame_index, int N,
@@ -905,27 +977,11 @@ extern "C" int deepim_zoom_concat_frames_forward(deepim_ctx* ctx, const uint8_t*
                                                  const float* depth_rendered, const float* src_pose, const float* K_host,
                                                  const float* pixel_means_host, float* net_input, float* zoom_factor, int B,
                                                  int H, int W) {
-  DI_DEVICE(ctx);
-  if (B == 0) return 0;
-  ConcatArgs g;
-  FrameArgs f;
-  int rc = frames_front_end_args(ctx, g, f, frames_bgr8, frame_index, N, image_rendered, mask_observed, mask_rendered,
-                                 depth_frames16, depth_labels, mask_idx, depth_factor, depth_rendered, pixel_means_host, W);
-  if (rc) return rc;
-  DI_REQUIRE(((size_t)net_input & 15) == 0, "zoom_concat_frames: W % 4 == 0 and 16-byte aligned outputs");
-  g.net_input = net_input;
-  rc = compute_zoom_factor(ctx, zoom_factor, mask_observed, mask_rendered, BB_MASK_GT, BB_MASK_RENDERED, nullptr, src_pose,
-                           K_host, B, H, W);
-  if (rc) return rc;
-  const float gx = (float)(2.0 / (W - 1)), gy = (float)(2.0 / (H - 1));
-  dim3 grid(di_div_up((long)(W / 4) * H, 256), B);
-#define DI_FRAMES(D, L) hipLaunchKernelGGL((zoom_concat4_frames_kernel<D, L>), grid, dim3(256), 0, ctx->stream, g, f, zoom_factor, H, W, gx, gy)
-  if (!depth_frames16) DI_FRAMES(false, false);
-  else if (!depth_labels) DI_FRAMES(true, false);
-  else DI_FRAMES(true, true);
-#undef DI_FRAMES
-  DI_LAUNCH_CHECK();
-  return 0;
+  FrontEnd e = frames_front_end(ctx, frames_bgr8, frame_index, N, image_rendered, mask_observed, mask_rendered, depth_frames16,
+                                depth_labels, mask_idx, depth_factor, depth_rendered);
+  e.form = FORM_PLANES; e.g.net_input = net_input;
+  e.need_aligned = "zoom_concat_frames: W % 4 == 0 and 16-byte aligned outputs";
+  return launch_front_end(ctx, e, src_pose, K_host, pixel_means_host, zoom_factor, B, H, W);
 }
 
 extern "C" int deepim_zoom_concat_frames_forward_h16(deepim_ctx* ctx, const uint8_t* frames_bgr8, const int32_t* frame_index,
@@ -935,27 +991,12 @@ extern "C" int deepim_zoom_concat_frames_forward_h16(deepim_ctx* ctx, const uint
                                                      const float* depth_rendered, const float* src_pose, const float* K_host,
                                                      const float* pixel_means_host, void* main8, void* extra2,
                                                      float* zoom_factor, int B, int H, int W) {
-  DI_DEVICE(ctx);
-  if (B == 0) return 0;
-  ConcatArgs g;
-  FrameArgs f;
-  int rc = frames_front_end_args(ctx, g, f, frames_bgr8, frame_index, N, image_rendered, mask_observed, mask_rendered,
-                                 depth_frames16, depth_labels, mask_idx, depth_factor, depth_rendered, pixel_means_host, W);
-  if (rc) return rc;
-  DI_REQUIRE((depth_frames16 != nullptr) == (extra2 != nullptr), "zoom_concat_frames_h16: depth pair and extra2 go together");
-  DI_REQUIRE(main8 && ((size_t)main8 & 15) == 0 && ((size_t)extra2 & 15) == 0, "zoom_concat_frames_h16: W % 4 == 0 and 16-byte aligned outputs");
-  rc = compute_zoom_factor(ctx, zoom_factor, mask_observed, mask_rendered, BB_MASK_GT, BB_MASK_RENDERED, nullptr, src_pose,
-                           K_host, B, H, W);
-  if (rc) return rc;
-  const float gx = (float)(2.0 / (W - 1)), gy = (float)(2.0 / (H - 1));
-  dim3 grid(di_div_up((long)(W / 4) * H, 256), B);
-#define DI_FRAMES(D, L) hipLaunchKernelGGL((zoom_concat4_h16_frames_kernel<D, L>), grid, dim3(256), 0, ctx->stream, g, f, (_Float16*)main8, (_Float16*)extra2, zoom_factor, H, W, gx, gy)
-  if (!depth_frames16) DI_FRAMES(false, false);
-  else if (!depth_labels) DI_FRAMES(true, false);
-  else DI_FRAMES(true, true);
-#undef DI_FRAMES
-  DI_LAUNCH_CHECK();
-  return 0;
+  FrontEnd e = frames_front_end(ctx, frames_bgr8, frame_index, N, image_rendered, mask_observed, mask_rendered, depth_frames16,
+                                depth_labels, mask_idx, depth_factor, depth_rendered);
+  e.form = FORM_H16; e.main8 = (_Float16*)main8; e.extra2 = (_Float16*)extra2;
+  e.need_together = "zoom_concat_frames_h16: depth pair and extra2 go together";
+  e.need_aligned = "zoom_concat_frames_h16: W % 4 == 0 and 16-byte aligned outputs";
+  return launch_front_end(ctx, e, src_pose, K_host, pixel_means_host, zoom_factor, B, H, W);
 }
 
 // training graph (deepIM_flownet.py:392-412): ZoomMask takes the zoom region from mask_GT_observed (NULL = the test graph,
@@ -966,55 +1007,11 @@ extern "C" int deepim_zoom_concat_train_forward(deepim_ctx* ctx, const float* im
                                                 const float* depth_rendered, const float* src_pose, const float* K_host,
                                                 const float* pixel_means_host, float* net_input, float* zoom_factor, int B,
                                                 int H, int W) {
-  DI_DEVICE(ctx);
-  if (B == 0) return 0;
-  DI_REQUIRE((mask_observed == nullptr) == (mask_rendered == nullptr), "zoom_concat: pass both masks or neither");
-  const bool with_mask = mask_observed != nullptr;
-  const long p = (long)H * W;
-  const int C = 6 + (with_mask ? 2 : 0) + (depth_observed ? 2 : 0);
-  int rc;
-  if (with_mask)  // ZoomMask; test graph: mask_gt_observed ≡ mask_observed (deepIM_flownet.py:564)
-    rc = compute_zoom_factor(ctx, zoom_factor, mask_gt_observed ? mask_gt_observed : mask_observed, mask_rendered, BB_MASK_GT,
-                             BB_MASK_RENDERED, nullptr, src_pose, K_host, B, H, W);
-  else            // ZoomImage: boxes of the non-black pixels (deepIM_flownet.py:594-605, zoom_image.py:31-37)
-    rc = compute_zoom_factor(ctx, zoom_factor, image_observed, image_rendered, BB_IMAGE, BB_IMAGE, pixel_means_host,
-                             src_pose, K_host, B, H, W);
-  if (rc) return rc;
-  const long db = (long)C * p;
-  if ((W & 3) == 0 && ((size_t)net_input & 15) == 0) {   // the fused, compile-time-specialised front end
-    ConcatArgs g;
-    g.image_observed = image_observed; g.image_rendered = image_rendered;
-    g.depth_observed = depth_observed; g.depth_rendered = depth_rendered;
-    g.mask_observed = mask_observed; g.mask_rendered = mask_rendered;
-    g.net_input = net_input; g.C = C;
-    for (int i = 0; i < 3; ++i) g.means.v[i] = pixel_means_host ? pixel_means_host[i] : 0.f;
-    const float gx = (float)(2.0 / (W - 1)), gy = (float)(2.0 / (H - 1));
-    dim3 grid(di_div_up((long)(W / 4) * H, 256), B);
-    const bool dep = depth_observed != nullptr;
-#define DI_CONCAT(D, M) hipLaunchKernelGGL((zoom_concat4_kernel<D, M>), grid, dim3(256), 0, ctx->stream, g, zoom_factor, H, W, gx, gy)
-    if (dep && with_mask) DI_CONCAT(true, true);
-    else if (dep) DI_CONCAT(true, false);
-    else if (with_mask) DI_CONCAT(false, true);
-    else DI_CONCAT(false, false);
-#undef DI_CONCAT
-    DI_LAUNCH_CHECK();
-    return 0;
-  }
-  Plan plan; plan.inverse = 0;
-  int n = 0;
-  image_plan(plan, 0, image_observed, net_input, 3 * p, db, p, pixel_means_host, CF_POST_DIV255, 0);
-  image_plan(plan, 3, image_rendered, net_input + 3 * p, 3 * p, db, p, pixel_means_host, CF_POST_DIV255, 0);
-  n = 6;
-  if (depth_observed) {
-    plan.ch[n] = make_chan(depth_observed, net_input + n * p, p, db, 0.f, CF_POST_DIV255); ++n;
-    plan.ch[n] = make_chan(depth_rendered, net_input + n * p, p, db, 0.f, CF_POST_DIV255); ++n;
-  }
-  if (with_mask) {
-    plan.ch[n] = make_chan(mask_observed, net_input + n * p, p, db, 0.f, CF_POST_ROUND); ++n;
-    plan.ch[n] = make_chan(mask_rendered, net_input + n * p, p, db, 0.f, CF_PRE_BIN02 | CF_POST_ROUND); ++n;
-  }
-  plan.n = n;
-  return launch_resample(ctx, plan, zoom_factor, B, H, W);
+  FrontEnd e = front_end(image_observed, image_rendered, mask_observed, mask_rendered, depth_observed, depth_rendered);
+  e.box_observed = mask_gt_observed;
+  e.form = FORM_PLANES; e.g.net_input = net_input;
+  e.need_masks = "zoom_concat: pass both masks or neither";
+  return launch_front_end(ctx, e, src_pose, K_host, pixel_means_host, zoom_factor, B, H, W);
 }
 
 extern "C" int deepim_selfcheck_div255(deepim_ctx* ctx, unsigned long long* mismatches_host) {

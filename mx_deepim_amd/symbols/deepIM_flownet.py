@@ -427,7 +427,6 @@ class deepIM_flownet(object):
         # activations
         A = self.act
         A["net_input"] = ctx.empty((B, self.cin, H, W))
-        self._input_live_nc8 = False
         A["zoom_factor"] = ctx.empty((B, 4))
         hh, ww, cin = H, W, self.cin
         self.enc_geom = []
@@ -450,7 +449,7 @@ class deepIM_flownet(object):
                 if self.cin == 10:
                     A["net_input_x2"] = ctx.empty((B, H, W, 2), dtype=np.float16)
                 self.fp16_fused_input = True
-        self._input_live_h16 = False
+        self._input_live_h16 = self._input_live_nc8 = False   # set by zoom(): which form of the net input is the live one
         A["fc6"], A["fc7"], A["se3"] = ctx.empty((B, 256)), ctx.empty((B, 256)), ctx.empty((B, getattr(self, "rot_param", 4) + 3))
         if getattr(self, "rot_type", "QUAT") == "EULER":
             A["rot_e"], A["zoom_trans_e"], A["trans_e"] = ctx.empty((B, 3)), ctx.empty((B, 3)), ctx.empty((B, 3))
@@ -543,61 +542,42 @@ class deepIM_flownet(object):
         return (getattr(self, "conv1_nc8", False) and self.nc8 and self.cin == 8 and self.input_mask and not self.input_depth
                 and not self.fp16_conv and not self.x3_conv and not getattr(self, "is_train", False) and self.W % 4 == 0)
 
-    def _zoom_frames(self, data, of):
-        """zoom() of a shared-frame batch (data["observed_frames"], lib/utils/image.ObservedFrames): the observed image [and
-        depth] are gathered from the N uint8 / uint16 frames through the device frame_index — the fp16 records on the fused fp16
-        path, else the NCHW net input (which the fp32, x3 and two-step fp16 encoders read; the opt-in NC8 front end has no
-        shared-frame variant). Both masks are required: the library refuses the mask-less ZoomImage configuration."""
-        A, h = self.act, self.ctx.handle
-        if of.n_pairs != self.B:
-            raise ValueError("observed_frames index %d pairs; the network is bound for %d" % (of.n_pairs, self.B))
-        if self.input_depth and of.depth is None:
-            raise ValueError("network.INPUT_DEPTH: the observed_frames of this batch carry no depth frames")
-        depth = of.depth if self.input_depth else None
-        labels, idx = (of.labels, of.mask_idx) if depth is not None else (None, None)
-        args = (of.image, of.frame_index, of.n_frames, data["image_rendered"],
-                data["mask_observed"] if self.input_mask else None, data["mask_rendered"] if self.input_mask else None,
-                depth, labels, idx, ctypes.c_float(of.depth_factor), data.get("depth_rendered") if self.input_depth else None,
-                data["src_pose"], self.K, self.pixel_means)
-        self._input_live_nc8 = False
-        if self.fp16_conv and getattr(self, "fp16_fused_input", False) and "net_input_h8" in A:
-            x2 = dict.__getitem__(A, "net_input_x2") if self.cin == 10 else None
-            lib.deepim_zoom_concat_frames_forward_h16(h, *(args + (dict.__getitem__(A, "net_input_h8"), x2, A["zoom_factor"],
-                                                                   self.B, self.H, self.W)))
-            self._input_live_h16 = True
-            return
-        self._input_live_h16 = False
-        lib.deepim_zoom_concat_frames_forward(h, *(args + (A["net_input"], A["zoom_factor"], self.B, self.H, self.W)))
-
     def zoom(self, data):
-        A, h = self.act, self.ctx.handle
-        if data.get("observed_frames") is not None:
-            return self._zoom_frames(data, data["observed_frames"])
+        """The fused zoom front end: this iteration's network input and zoom factor. Two independent choices.
+        Observed source: the per-pair fp32 tensors, or a shared-frame batch (data["observed_frames"], lib/utils/image.ObservedFrames)
+        whose observed image [and depth] are gathered from the N uint8 / uint16 frames through the device frame_index; the library
+        refuses the mask-less ZoomImage configuration there.
+        Output form: conv1's fp16 pixel records on the fused fp16 path, the opt-in NC8 records (_conv1_from_nc8; per-pair tensors
+        only, there is no shared-frame variant), else the NCHW net input that the fp32, x3 and two-step fp16 encoders read."""
+        A, h, raw = self.act, self.ctx.handle, dict.__getitem__
+        of = data.get("observed_frames")
+        if of is not None and of.n_pairs != self.B:
+            raise ValueError("observed_frames index %d pairs; the network is bound for %d" % (of.n_pairs, self.B))
+        if of is not None and self.input_depth and of.depth is None:
+            raise ValueError("network.INPUT_DEPTH: the observed_frames of this batch carry no depth frames")
         if self.fp16_conv and getattr(self, "fp16_fused_input", False) and "net_input_h8" in A:
-            x2 = dict.__getitem__(A, "net_input_x2") if self.cin == 10 else None
-            lib.deepim_zoom_concat_forward_h16(h, data["image_observed"], data["image_rendered"], data["mask_observed"],
-                                               data["mask_rendered"], data.get("depth_observed") if self.input_depth else None,
-                                               data.get("depth_rendered") if self.input_depth else None, data["src_pose"],
-                                               self.K, self.pixel_means, dict.__getitem__(A, "net_input_h8"), x2,
-                                               A["zoom_factor"], self.B, self.H, self.W)
-            self._input_live_h16, self._input_live_nc8 = True, False
-            return
-        self._input_live_h16 = False
-        if self._conv1_from_nc8():
+            form, out = "h16", (raw(A, "net_input_h8"), raw(A, "net_input_x2") if self.cin == 10 else None)
+        elif of is None and self._conv1_from_nc8():
             if "net_input_nc8" not in A:       # opt-in path: allocated on first use (run once eagerly before a graph capture)
                 A["net_input_nc8"] = self.ctx.empty((self.B, self.H, self.W, 8))
-            lib.deepim_zoom_concat_forward_nc8(h, data["image_observed"], data["image_rendered"], data["mask_observed"],
-                                               data["mask_rendered"], data["src_pose"], self.K, self.pixel_means,
-                                               dict.__getitem__(A, "net_input_nc8"), A["zoom_factor"], self.B, self.H, self.W)
-            self._input_live_nc8 = True
-            return
-        self._input_live_nc8 = False
-        lib.deepim_zoom_concat_forward(
-            h, data["image_observed"], data["image_rendered"],
-            data["mask_observed"] if self.input_mask else None, data["mask_rendered"] if self.input_mask else None,
-            data.get("depth_observed") if self.input_depth else None,
-            data.get("depth_rendered") if self.input_depth else None,
-            data["src_pose"], self.K, self.pixel_means, A["net_input"], A["zoom_factor"], self.B, self.H, self.W)
+            form, out = "nc8", (raw(A, "net_input_nc8"),)
+        else:
+            form, out = "nchw", (raw(A, "net_input"),)
+        self._input_live_h16, self._input_live_nc8 = form == "h16", form == "nc8"
+        masks = (data["mask_observed"], data["mask_rendered"]) if self.input_mask else (None, None)
+        depth_rendered = data.get("depth_rendered") if self.input_depth else None
+        if of is not None:
+            depth = of.depth if self.input_depth else None
+            labels, idx = (of.labels, of.mask_idx) if depth is not None else (None, None)
+            entry = lib.deepim_zoom_concat_frames_forward_h16 if form == "h16" else lib.deepim_zoom_concat_frames_forward
+            src = (of.image, of.frame_index, of.n_frames, data["image_rendered"]) + masks + \
+                  (depth, labels, idx, ctypes.c_float(of.depth_factor), depth_rendered)
+        else:
+            entry = {"h16": lib.deepim_zoom_concat_forward_h16, "nc8": lib.deepim_zoom_concat_forward_nc8,
+                     "nchw": lib.deepim_zoom_concat_forward}[form]
+            depths = () if form == "nc8" else (data.get("depth_observed") if self.input_depth else None, depth_rendered)
+            src = (data["image_observed"], data["image_rendered"]) + masks + depths
+        entry(h, *(src + (data["src_pose"], self.K, self.pixel_means) + out + (A["zoom_factor"], self.B, self.H, self.W)))
 
     def encoder_fp16(self):
         """Same 10 layers on the fp16 matrix cores: NCHW fp32 net input → NHWC fp16 → convs → conv6_1 back to

@@ -148,6 +148,55 @@ def test_fused_front_end_without_masks(ctx, small_batch):
     np.testing.assert_array_equal(x.asnumpy(), ref)
 
 
+def test_fused_front_end_depth_without_masks(ctx):
+    """INPUT_DEPTH without INPUT_MASK (C = 8: image pair + depth pair), the one channel set of the fused front end that no
+    network configuration of the suite binds: bit for bit the separate ops — ZoomImage for the factor, ZoomImageWithFactor and
+    ZoomDepth for the tensors, then the /255 — and the oracle. Pair 0's crop lies inside the frame, pair 1's object sits in the
+    top-right corner so that its crop hangs over two edges (zero-padding taps)."""
+    rng = np.random.default_rng(24)
+    B, H, W = 2, 24, 32
+    K = np.array([[W, 0, W / 2.0], [0, W, H / 2.0], [0, 0, 1]], np.float32)
+    boxes = {"image_observed": [(8, 16, 10, 20), (0, 7, 22, 32)], "image_rendered": [(9, 15, 12, 22), (0, 6, 24, 32)]}
+    d = {}
+    for key, bb in boxes.items():       # black (raw 0 = -mean) outside the object: what ZoomImage takes its boxes from
+        raw = np.zeros((B, 3, H, W), np.float32)
+        for b, (y0, y1, x0, x1) in enumerate(bb):
+            raw[b, :, y0:y1, x0:x1] = rng.uniform(20, 255, (3, y1 - y0, x1 - x0))
+        d[key] = raw - MEANS_REV[None, :, None, None]
+    d["depth_observed"], d["depth_rendered"] = (rng.uniform(0, 2, (B, 1, H, W)).astype(np.float32) for _ in range(2))
+    pose = np.zeros((B, 3, 4), np.float32)
+    for b, (u, v, z) in enumerate([(15.0, 12.0, 0.8), (27.0, 3.0, 0.9)]):
+        pose[b, :, :3] = np.eye(3)
+        pose[b, :, 3] = ((u - K[0, 2]) / K[0, 0] * z, (v - K[1, 2]) / K[1, 1] * z, z)
+    g = {k: ctx.array(v) for k, v in d.items()}
+    sp = ctx.array(pose)
+    # the separate ops
+    zi = [ctx.empty((B, 3, H, W)) for _ in range(2)]
+    zd = [ctx.empty((B, 1, H, W)) for _ in range(2)]
+    zf = ctx.empty((B, 4))
+    lib.deepim_zoom_image_forward(ctx.handle, g["image_observed"], g["image_rendered"], sp, K, MEANS_REV, zi[0], zi[1], zf, B, H, W)
+    lib.deepim_zoom_image_with_factor_forward(ctx.handle, zf, g["image_observed"], g["image_rendered"], MEANS_REV, 0, zi[0], zi[1],
+                                              B, H, W)
+    lib.deepim_zoom_depth_forward(ctx.handle, zf, g["depth_observed"], g["depth_rendered"], zd[0], zd[1], B, H, W)
+    want = np.concatenate([a.asnumpy() for a in zi + zd], axis=1) / np.float32(255.0)
+    assert want.dtype == np.float32
+    # the fused front end
+    x, zf_fused = ctx.empty((B, 8, H, W)), ctx.empty((B, 4))
+    lib.deepim_zoom_concat_forward(ctx.handle, g["image_observed"], g["image_rendered"], None, None, g["depth_observed"],
+                                   g["depth_rendered"], sp, K, MEANS_REV, x, zf_fused, B, H, W)
+    f = zf.asnumpy()
+    np.testing.assert_array_equal(zf_fused.asnumpy().view(np.uint32), f.view(np.uint32))
+    np.testing.assert_array_equal(x.asnumpy().view(np.uint32), want.view(np.uint32))
+    ref, rzf = oz.net_input(d["image_observed"], d["image_rendered"], None, None, pose, K, MEANS_REV, d["depth_observed"],
+                            d["depth_rendered"])
+    np.testing.assert_array_equal(f, rzf)
+    np.testing.assert_array_equal(x.asnumpy(), ref)
+    # the scene is what the docstring says, and the depth channels are not trivially zero
+    assert f[0, 0] + abs(f[0, 2]) < 1 and f[0, 1] + abs(f[0, 3]) < 1
+    assert f[1, 0] + abs(f[1, 2]) > 1 and f[1, 1] + abs(f[1, 3]) > 1
+    assert np.count_nonzero(want[:, 6:8]) > 0 and np.count_nonzero(want[1] == 0) > 0
+
+
 def test_resample_scalar_path_unaligned_width(ctx):
     """W % 4 != 0 takes the one-pixel-per-thread kernel; same results as the oracle."""
     rng = np.random.default_rng(8)
