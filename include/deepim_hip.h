@@ -1059,6 +1059,50 @@ int deepim_train_metrics(deepim_ctx* ctx, double* totals /*5, accumulated; or NU
  * to float; fixed order, no atomics. Asynchronous; scratch (rows x 2 KB) grows outside a capture only. rows <= 65535. */
 int deepim_l2_norms_multi(deepim_ctx* ctx, float* out /*rows*/, const uint64_t* table /*rows x {ptr, count}*/, int rows);
 
+/* ------------------------------------------ R-group: the loader's random draws (csrc/sample.hip) -- */
+/* A counter-based generator, Philox4x32-10, and on top of it the rendered-pose rule of toolkit/LM6d_1_gen_rendered_pose.py:80-107
+ * and the draws of lib/utils/mask_dilate.py. Every draw is a pure function of (seed, draw id, attempt, stream):
+ *   key     = (seed low word, seed high word)
+ *   counter = (draw id low, draw id high, attempt, stream)      streams 0, 1: the two blocks of a pose draw; 2: mask dilate
+ * so a pair's draw does not depend on the batch size, its position in the batch or the order of launches. The draw id of pair b
+ * is draw_ids[b] where draw_ids (device, B) is given, else draw_base + b (draw_base is not added to given ids).
+ * A 32-bit word x becomes the uniform u = (x + 0.5) 2^-32 in double, strictly inside (0,1); six normals come pairwise from the
+ * first six of a candidate's eight words by Box-Muller in double, r = sqrt(-2 ln u0), z0 = r cos 2 pi u1, z1 = r sin 2 pi u1
+ * (block 0: z0..z3, block 1: z4, z5). A word maps to [0, n) as (uint64(x) n) >> 32: the bias is at most n 2^-32.
+ * All five entries are asynchronous on the context's stream, allocate nothing and read nothing back. B >= 0.
+ *
+ * deepim_selfcheck_philox: out[i] = Philox4x32-10(ctr[i], key[i]), the generator alone (known-answer tests). */
+int deepim_selfcheck_philox(deepim_ctx* ctx, unsigned int* out /*n,4 dev*/, const unsigned int* ctr /*n,4 dev*/,
+                            const unsigned int* key /*n,2 dev*/, int n);
+/* One candidate of the rule from GIVEN normals, in double:
+ *   tgt_euler = mat2euler(R_src) + z[0:3] angle_std pi/180      tgt_trans = T_src + z[3:6] (x_std, y_std, z_std)
+ *   R_tgt = euler2mat(tgt_euler)      r_dist = the angle of R_src^T R_tgt in degrees (atan2 of half the norm of the antisymmetric
+ *   part and (trace - 1)/2)           (cx, cy) = the projection of tgt_trans through K
+ *   accept iff r_dist <= angle_max and border < cx < width - border and border < cy < height - border and tgt_trans.z > 0
+ * (z > 0 is not the toolkit's, which divides by z unguarded). pose_out is the candidate rounded to float, accepted or not;
+ * stat_out may be NULL. K: 9 HOST floats; noise: 5 HOST floats, stds >= 0. pose_out must not overlap pose_src. */
+int deepim_pose_perturb(deepim_ctx* ctx, float* pose_out /*B,3,4*/, double* stat_out /*B,4: r_dist deg, cx, cy, accept*/,
+                        const float* pose_src, const double* normals /*B,6 dev*/, const float* K /*host 3x3*/,
+                        const float* noise /*host 5: angle_std deg, angle_max deg, x,y,z std*/, int width, int height,
+                        float border, int B);
+/* The toolkit's loop with a bound: candidates of attempt 0 .. max_attempts-1 (>= 1) are drawn and tried until one is accepted.
+ * Accepted: pose_out = that candidate, attempts[b] = the number of candidates drawn (1 .. max_attempts), normals_out[b] = its
+ * normals. None accepted: pose_out = pose_src unchanged, attempts[b] = 0, normals_out[b] = zeros (the toolkit loops for ever). */
+int deepim_sample_rendered_poses(deepim_ctx* ctx, float* pose_out /*B,3,4*/, int32_t* attempts /*B dev*/,
+                                 double* normals_out /*B,6 or NULL: the accepted draw's*/, const float* pose_src,
+                                 const float* K, const float* noise, int width, int height, float border, int max_attempts,
+                                 unsigned long long seed, unsigned long long draw_base,
+                                 const unsigned long long* draw_ids /*B dev or NULL: draw_base + b*/, int B);
+/* lib/utils/mask_dilate.py:19-47's draws for B pairs, as deepim_mask_dilate takes them: word 0 of the stream-2 call with
+ * attempt 0 is the direction in [0,10); words 1..3 of that call and word 0 of the call with attempt 1 are the four sides'
+ * randint(max_thickness) + 1 (max_thickness >= 1) in the order of the file's four blocks; a side is 0 where the file skips it
+ * for the direction. thickness must be 16-byte aligned. */
+int deepim_sample_mask_dilate(deepim_ctx* ctx, int32_t* thickness /*B,4 dev*/, int max_thickness, unsigned long long seed,
+                              unsigned long long draw_base, const unsigned long long* draw_ids, int B);
+/* The loader's running counts, kept on the device: totals[0] += B, totals[1] += the sum of attempts, totals[2] += the pairs with
+ * attempts == 0 (exhausted). */
+int deepim_sample_stats_accumulate(deepim_ctx* ctx, unsigned long long* totals /*3 dev*/, const int32_t* attempts /*B dev*/, int B);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,314 @@
+// R-group: the random draws of the training loader, on the device.
+//   Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11) as a counter-based generator
+//   the rendered-pose rule of toolkit/LM6d_1_gen_rendered_pose.py:80-107 on top of it
+//   the draws of lib/utils/mask_dilate.py:19-47
+//
+// Every draw is a pure function of (seed, draw id, attempt, stream): key = (seed lo, seed hi), counter = (id lo, id hi, attempt,
+// stream). Streams 0 and 1 are the two blocks of a pose draw, stream 2 is the mask-dilate draw. Nothing depends on the batch
+// size, on a pair's position in the batch or on the order of launches.
+//
+// The kernels run one thread per pair; every array below is indexed by constants after unrolling, so nothing lives in
+// private memory. Arithmetic is float64 throughout (full rate on CDNA4, a few hundred flops per candidate).
+#include "common.h"
+#include "euler_f64.h"
+
+namespace {
+
+struct Philox4 { unsigned int w[4]; };
+
+__device__ __forceinline__ Philox4 philox4x32_10(unsigned int c0, unsigned int c1, unsigned int c2, unsigned int c3,
+                                                 unsigned int k0, unsigned int k1) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0;
+    const unsigned long long p1 = (unsigned long long)0xCD9E8D57u * c2;
+    const unsigned int n0 = (unsigned int)(p1 >> 32) ^ c1 ^ k0;
+    const unsigned int n2 = (unsigned int)(p0 >> 32) ^ c3 ^ k1;
+    c1 = (unsigned int)p1;
+    c3 = (unsigned int)p0;
+    c0 = n0;
+    c2 = n2;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  Philox4 o;
+  o.w[0] = c0; o.w[1] = c1; o.w[2] = c2; o.w[3] = c3;
+  return o;
+}
+
+__device__ __forceinline__ Philox4 philox_draw(unsigned long long seed, unsigned long long id, unsigned int attempt,
+                                               unsigned int stream) {
+  return philox4x32_10((unsigned int)id, (unsigned int)(id >> 32), attempt, stream, (unsigned int)seed,
+                       (unsigned int)(seed >> 32));
+}
+
+// a 32-bit word as a uniform strictly inside (0,1): (x + 0.5) 2^-32, exact in double
+__device__ __forceinline__ double word_uniform(unsigned int x) { return ((double)x + 0.5) * 2.3283064365386963e-10; }
+
+// Box-Muller in double: two words -> two independent standard normals
+__device__ __forceinline__ void box_muller(unsigned int a, unsigned int b, double& z0, double& z1) {
+  const double r = sqrt(-2.0 * log(word_uniform(a)));
+  const double t = 6.283185307179586 * word_uniform(b);
+  z0 = r * cos(t);
+  z1 = r * sin(t);
+}
+
+// the six normals of one candidate: block 0 (stream 0) gives z0..z3, block 1 (stream 1) z4, z5 from its first two words
+__device__ __forceinline__ void pose_normals(unsigned long long seed, unsigned long long id, unsigned int attempt, double* z) {
+  const Philox4 a = philox_draw(seed, id, attempt, 0u);
+  const Philox4 b = philox_draw(seed, id, attempt, 1u);
+  box_muller(a.w[0], a.w[1], z[0], z[1]);
+  box_muller(a.w[2], a.w[3], z[2], z[3]);
+  box_muller(b.w[0], b.w[1], z[4], z[5]);
+}
+
+// a word mapped to [0, n): (x n) >> 32. The bias of any value's probability is at most n 2^-32.
+__device__ __forceinline__ int word_below(unsigned int x, int n) {
+  return (int)(((unsigned long long)x * (unsigned long long)(unsigned int)n) >> 32);
+}
+
+struct PoseNoise {
+  Mat3 K;
+  float angle_std, angle_max, x_std, y_std, z_std;   // degrees, degrees, metres
+  float border;
+  int width, height;
+};
+
+// One candidate of LM6d_1_gen_rendered_pose.py:86-97 from given normals, in float64:
+//   tgt_euler = mat2euler(R_src) + z[0:3] angle_std pi/180, tgt_trans = T_src + z[3:6] (x_std, y_std, z_std), R_tgt = euler2mat
+//   r_dist = angle of R_src^T R_tgt in degrees, as atan2(|antisymmetric part| / 2, (trace - 1) / 2): calc_rt_dist_m takes
+//   ||logm||_F / sqrt 2, the same value for a rotation; this form keeps its digits at small angles
+//   (cx, cy) = projection of tgt_trans through K
+//   accept iff r_dist <= angle_max and border < cx < W - border and border < cy < H - border and tgt_trans.z > 0
+// The z > 0 clause is not the reference's, which divides by z unguarded.
+// pose: the candidate [R | t] in double (12); stat: r_dist, cx, cy. Returns the accept flag.
+__device__ __forceinline__ bool pose_perturb_one(const float* src, const double* z, const PoseNoise& p, double* pose, double* stat) {
+  double Rs[9];
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) Rs[i * 3 + j] = (double)src[i * 4 + j];
+  double e[3];
+  mat2euler_sxyz_f64(Rs, e);
+  const double scale = (double)p.angle_std / 180.0 * 3.141592653589793;
+  double Rt[9];
+  euler2mat_sxyz_f64(e[0] + z[0] * scale, e[1] + z[1] * scale, e[2] + z[2] * scale, Rt);
+  const double tx = (double)src[3] + z[3] * (double)p.x_std;
+  const double ty = (double)src[7] + z[4] * (double)p.y_std;
+  const double tz = (double)src[11] + z[5] * (double)p.z_std;
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) pose[i * 4 + j] = Rt[i * 3 + j];
+  pose[3] = tx; pose[7] = ty; pose[11] = tz;
+  // M = R_src^T R_tgt
+  double M[9];
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) M[i * 3 + j] = (Rs[i] * Rt[j] + Rs[3 + i] * Rt[3 + j]) + Rs[6 + i] * Rt[6 + j];
+  const double c = ((M[0] + M[4] + M[8]) - 1.0) * 0.5;
+  const double sx = (M[7] - M[5]) * 0.5, sy = (M[2] - M[6]) * 0.5, sz = (M[3] - M[1]) * 0.5;
+  const double r_dist = atan2(sqrt((sx * sx + sy * sy) + sz * sz), c) / 3.141592653589793 * 180.0;
+  const double px = ((double)p.K.v[0] * tx + (double)p.K.v[1] * ty) + (double)p.K.v[2] * tz;
+  const double py = ((double)p.K.v[3] * tx + (double)p.K.v[4] * ty) + (double)p.K.v[5] * tz;
+  const double pz = ((double)p.K.v[6] * tx + (double)p.K.v[7] * ty) + (double)p.K.v[8] * tz;
+  const double cx = px / pz, cy = py / pz;
+  stat[0] = r_dist; stat[1] = cx; stat[2] = cy;
+  const double lo = (double)p.border;
+  return r_dist <= (double)p.angle_max && lo < cx && cx < (double)p.width - lo && lo < cy && cy < (double)p.height - lo &&
+         tz > 0.0;
+}
+
+__global__ __launch_bounds__(256) void philox_selfcheck_kernel(unsigned int* __restrict__ out, const unsigned int* __restrict__ ctr,
+                                                               const unsigned int* __restrict__ key, int n) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const Philox4 o = philox4x32_10(ctr[i * 4], ctr[i * 4 + 1], ctr[i * 4 + 2], ctr[i * 4 + 3], key[i * 2], key[i * 2 + 1]);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) out[i * 4 + k] = o.w[k];
+}
+
+__global__ __launch_bounds__(256) void pose_perturb_kernel(float* __restrict__ pose_out, double* __restrict__ stat_out,
+                                                           const float* __restrict__ pose_src, const double* __restrict__ normals,
+                                                           PoseNoise p, int B) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= B) return;
+  float P[12];
+  double z[6], pose[12], stat[3];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) P[i] = pose_src[(long)b * 12 + i];
+#pragma unroll
+  for (int i = 0; i < 6; ++i) z[i] = normals[(long)b * 6 + i];
+  const bool ok = pose_perturb_one(P, z, p, pose, stat);
+#pragma unroll
+  for (int i = 0; i < 12; ++i) pose_out[(long)b * 12 + i] = (float)pose[i];
+  if (stat_out) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) stat_out[(long)b * 4 + i] = stat[i];
+    stat_out[(long)b * 4 + 3] = ok ? 1.0 : 0.0;
+  }
+}
+
+// The attempt loop of LM6d_1_gen_rendered_pose.py:86-110 with a bound: the first accepted candidate of attempts
+// 0 .. max_attempts-1, attempts[b] = candidates drawn (1 .. max_attempts); none accepted: pose_src unchanged, attempts[b] = 0
+// and zeros in normals_out (the reference loops for ever there).
+__global__ __launch_bounds__(256) void sample_rendered_poses_kernel(float* __restrict__ pose_out, int* __restrict__ attempts,
+                                                                    double* __restrict__ normals_out,
+                                                                    const float* __restrict__ pose_src, PoseNoise p, int max_attempts,
+                                                                    unsigned long long seed, unsigned long long draw_base,
+                                                                    const unsigned long long* __restrict__ draw_ids, int B) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= B) return;
+  const unsigned long long id = draw_ids ? draw_ids[b] : draw_base + (unsigned long long)b;
+  float P[12], out[12];
+  double zk[6];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) { P[i] = pose_src[(long)b * 12 + i]; out[i] = P[i]; }
+#pragma unroll
+  for (int i = 0; i < 6; ++i) zk[i] = 0.0;
+  int used = 0;
+  for (int a = 0; a < max_attempts; ++a) {
+    double z[6], pose[12], stat[3];
+    pose_normals(seed, id, (unsigned int)a, z);
+    if (pose_perturb_one(P, z, p, pose, stat)) {
+#pragma unroll
+      for (int i = 0; i < 12; ++i) out[i] = (float)pose[i];
+#pragma unroll
+      for (int i = 0; i < 6; ++i) zk[i] = z[i];
+      used = a + 1;
+      break;
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 12; ++i) pose_out[(long)b * 12 + i] = out[i];
+  attempts[b] = used;
+  if (normals_out) {
+#pragma unroll
+    for (int i = 0; i < 6; ++i) normals_out[(long)b * 6 + i] = zk[i];
+  }
+}
+
+// mask_dilate.py:19-47's draws from stream 2: word 0 of the call with attempt 0 is the direction in [0,10); words 1..3 of that
+// call and word 0 of the call with attempt 1 are the four sides' randint(max_thickness) + 1, in the order of the file's four
+// blocks; a side is 0 where the file skips it for the direction (:22 0,1,4; :28 1,2,5; :34 2,3,6; :40 0,3,7).
+__global__ __launch_bounds__(256) void sample_mask_dilate_kernel(int* __restrict__ thickness, int max_thickness,
+                                                                 unsigned long long seed, unsigned long long draw_base,
+                                                                 const unsigned long long* __restrict__ draw_ids, int B) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= B) return;
+  const unsigned long long id = draw_ids ? draw_ids[b] : draw_base + (unsigned long long)b;
+  const Philox4 c0 = philox_draw(seed, id, 0u, 2u);
+  const Philox4 c1 = philox_draw(seed, id, 1u, 2u);
+  const int direction = word_below(c0.w[0], 10);
+  const unsigned int bit = 1u << direction;
+  int4 t;
+  t.x = (bit & 0x013u) ? 0 : word_below(c0.w[1], max_thickness) + 1;
+  t.y = (bit & 0x026u) ? 0 : word_below(c0.w[2], max_thickness) + 1;
+  t.z = (bit & 0x04Cu) ? 0 : word_below(c0.w[3], max_thickness) + 1;
+  t.w = (bit & 0x089u) ? 0 : word_below(c1.w[0], max_thickness) + 1;
+  reinterpret_cast<int4*>(thickness)[b] = t;
+}
+
+// totals[0] += B, totals[1] += sum of attempts, totals[2] += pairs with attempts == 0. One block: integer sums, any order.
+__global__ __launch_bounds__(256) void sample_stats_kernel(unsigned long long* __restrict__ totals, const int* __restrict__ attempts,
+                                                           int B) {
+  __shared__ unsigned long long red[4][2];
+  unsigned long long sum = 0, zero = 0;
+  for (int b = threadIdx.x; b < B; b += 256) {
+    const int a = attempts[b];
+    sum += (unsigned long long)a;
+    zero += a == 0 ? 1ull : 0ull;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    sum += __shfl_xor(sum, off, 64);
+    zero += __shfl_xor(zero, off, 64);
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) { red[wave][0] = sum; red[wave][1] = zero; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    totals[0] += (unsigned long long)B;
+    totals[1] += (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]);
+    totals[2] += (red[0][1] + red[1][1]) + (red[2][1] + red[3][1]);
+  }
+}
+
+int pose_noise_from(PoseNoise* p, const float* K_host, const float* noise_host, int width, int height, float border) {
+  DI_REQUIRE(K_host && noise_host, "pose sampler: K and noise are host arrays, not NULL");
+  for (int i = 0; i < 9; ++i) p->K.v[i] = K_host[i];
+  p->angle_std = noise_host[0]; p->angle_max = noise_host[1];
+  p->x_std = noise_host[2]; p->y_std = noise_host[3]; p->z_std = noise_host[4];
+  DI_REQUIRE(p->angle_std >= 0.f && p->x_std >= 0.f && p->y_std >= 0.f && p->z_std >= 0.f,
+             "pose sampler: the standard deviations must be >= 0");
+  DI_REQUIRE(width > 0 && height > 0, "pose sampler: width and height must be positive");
+  p->border = border; p->width = width; p->height = height;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int deepim_selfcheck_philox(deepim_ctx* ctx, unsigned int* out, const unsigned int* ctr, const unsigned int* key, int n) {
+  DI_DEVICE(ctx);
+  DI_REQUIRE(n >= 0, "selfcheck_philox: n must be >= 0");
+  if (n == 0) return 0;
+  DI_REQUIRE(out && ctr && key, "selfcheck_philox: NULL argument");
+  hipLaunchKernelGGL(philox_selfcheck_kernel, dim3(di_div_up(n, 256)), dim3(256), 0, ctx->stream, out, ctr, key, n);
+  DI_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int deepim_pose_perturb(deepim_ctx* ctx, float* pose_out, double* stat_out, const float* pose_src, const double* normals,
+                                   const float* K, const float* noise, int width, int height, float border, int B) {
+  DI_DEVICE(ctx);
+  DI_REQUIRE(B >= 0, "pose_perturb: B must be >= 0");
+  PoseNoise p;
+  if (pose_noise_from(&p, K, noise, width, height, border)) return -1;
+  if (B == 0) return 0;
+  DI_REQUIRE(pose_out && pose_src && normals, "pose_perturb: NULL argument");
+  hipLaunchKernelGGL(pose_perturb_kernel, dim3(di_div_up(B, 256)), dim3(256), 0, ctx->stream, pose_out, stat_out, pose_src, normals,
+                     p, B);
+  DI_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int deepim_sample_rendered_poses(deepim_ctx* ctx, float* pose_out, int32_t* attempts, double* normals_out, const float* pose_src,
+                                            const float* K, const float* noise, int width, int height, float border,
+                                            int max_attempts, unsigned long long seed, unsigned long long draw_base,
+                                            const unsigned long long* draw_ids, int B) {
+  DI_DEVICE(ctx);
+  DI_REQUIRE(B >= 0, "sample_rendered_poses: B must be >= 0");
+  DI_REQUIRE(max_attempts >= 1, "sample_rendered_poses: max_attempts must be >= 1");
+  PoseNoise p;
+  if (pose_noise_from(&p, K, noise, width, height, border)) return -1;
+  if (B == 0) return 0;
+  DI_REQUIRE(pose_out && attempts && pose_src, "sample_rendered_poses: NULL argument");
+  hipLaunchKernelGGL(sample_rendered_poses_kernel, dim3(di_div_up(B, 256)), dim3(256), 0, ctx->stream, pose_out, attempts,
+                     normals_out, pose_src, p, max_attempts, seed, draw_base, draw_ids, B);
+  DI_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int deepim_sample_mask_dilate(deepim_ctx* ctx, int32_t* thickness, int max_thickness, unsigned long long seed,
+                                         unsigned long long draw_base, const unsigned long long* draw_ids, int B) {
+  DI_DEVICE(ctx);
+  DI_REQUIRE(B >= 0, "sample_mask_dilate: B must be >= 0");
+  DI_REQUIRE(max_thickness >= 1, "sample_mask_dilate: max_thickness must be >= 1");
+  if (B == 0) return 0;
+  DI_REQUIRE(thickness, "sample_mask_dilate: NULL argument");
+  hipLaunchKernelGGL(sample_mask_dilate_kernel, dim3(di_div_up(B, 256)), dim3(256), 0, ctx->stream, thickness, max_thickness, seed,
+                     draw_base, draw_ids, B);
+  DI_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int deepim_sample_stats_accumulate(deepim_ctx* ctx, unsigned long long* totals, const int32_t* attempts, int B) {
+  DI_DEVICE(ctx);
+  DI_REQUIRE(B >= 0, "sample_stats_accumulate: B must be >= 0");
+  if (B == 0) return 0;
+  DI_REQUIRE(totals && attempts, "sample_stats_accumulate: NULL argument");
+  hipLaunchKernelGGL(sample_stats_kernel, dim3(1), dim3(256), 0, ctx->stream, totals, attempts, B);
+  DI_LAUNCH_CHECK();
+  return 0;
+}

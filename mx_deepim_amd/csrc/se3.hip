@@ -10,6 +10,7 @@
 // N model points use wavefront shuffles + one LDS hop.
 #include "common.h"
 #include "pose_head.h"
+#include "euler_f64.h"
 
 namespace {
 
@@ -45,31 +46,7 @@ __device__ void t_transform_f64(const float* Tsrc, const float* Td, const Vec3d&
   }
 }
 
-// euler2mat(ai, aj, ak, 'sxyz') (RT_transform.py:240-307, the default axes RT_transform calls it with at :131):
-// math.sin/cos take Python floats, so everything is float64
-__device__ void euler2mat_sxyz_f64(double ai, double aj, double ak, double* M) {
-  const double si = sin(ai), sj = sin(aj), sk = sin(ak);
-  const double ci = cos(ai), cj = cos(aj), ck = cos(ak);
-  const double cc = ci * ck, cs = ci * sk, sc = si * ck, ss = si * sk;
-  M[0] = cj * ck; M[1] = sj * sc - cs; M[2] = sj * cc + ss;
-  M[3] = cj * sk; M[4] = sj * ss + cc; M[5] = sj * cs - sc;
-  M[6] = -sj;     M[7] = cj * si;      M[8] = cj * ci;
-}
-
-// mat2euler(M, 'sxyz') (RT_transform.py:310-373), float64
-__device__ void mat2euler_sxyz_f64(const double* M, double* e) {
-  const double eps4 = 2.220446049250313e-16 * 4.0;
-  const double cy = sqrt(M[0] * M[0] + M[3] * M[3]);
-  if (cy > eps4) {
-    e[0] = atan2(M[7], M[8]);
-    e[1] = atan2(-M[6], cy);
-    e[2] = atan2(M[3], M[0]);
-  } else {
-    e[0] = atan2(-M[5], M[4]);
-    e[1] = atan2(-M[6], cy);
-    e[2] = 0.0;
-  }
-}
+// euler2mat_sxyz_f64 / mat2euler_sxyz_f64 (RT_transform.py:240-373): csrc/euler_f64.h, shared with csrc/sample.hip
 
 // quat2mat (RT_transform.py:383-429) on float32 scalars: eye(3) when Nq < _FLOAT_EPS (:236,412)
 __device__ void quat2mat_checked_f64(float w, float x, float y, float z, double* Rd) {

@@ -3,7 +3,12 @@ generator), the shifted ORs run as one kernel over the batch (csrc/ingest.hip, d
 
     draws = mask_dilate_draws(B)                     # host int32 (B,4): what B reference calls would have drawn
     out = mask_dilate_batch(mask, ctx.array(draws, dtype=np.int32))
+
+The training loader (core/loader.py) takes its draws from the device's counter-based generator instead, without a host random
+number or a read-back: mask_dilate_draws_device (csrc/sample.hip, deepim_sample_mask_dilate).
 """
+import ctypes
+
 import numpy as np
 
 from ...runtime import Context, DeviceArray, lib
@@ -23,6 +28,23 @@ def mask_dilate_draws(n, max_thickness=10, rng=np.random):
         for k, skipped in enumerate(_SKIPPED):
             if direction not in skipped:
                 out[i, k] = rng.randint(max_thickness) + 1
+    return out
+
+
+def mask_dilate_draws_device(ctx, B, seed, draw_base=0, draw_ids=None, max_thickness=10):
+    """The draws of mask_dilate_draws from the device's counter-based generator (csrc/sample.hip, stream 2) → device int32 (B,4),
+    never read back. Pair b has draw id draw_ids[b] (device uint64 (B) or host integers), or draw_base + b: its draw does not
+    depend on where it lands in a batch. The numbers are the device generator's, not numpy's: the distribution of
+    mask_dilate_draws (direction uniform in [0,10), thickness uniform in [1, max_thickness]), not its sequence."""
+    B = int(B)
+    if draw_ids is not None and not isinstance(draw_ids, DeviceArray):
+        draw_ids = ctx.array(np.asarray(draw_ids).reshape(B), dtype=np.uint64)
+    if draw_ids is not None and (draw_ids.dtype != np.uint64 or draw_ids.size != B):
+        raise TypeError("mask_dilate_draws_device: draw_ids must be uint64 with %d values" % B)
+    out = ctx.empty((B, 4), np.int32)
+    u64 = (1 << 64) - 1
+    lib.deepim_sample_mask_dilate(ctx.handle, out, int(max_thickness), ctypes.c_ulonglong(int(seed) & u64),
+                                  ctypes.c_ulonglong(int(draw_base) & u64), draw_ids, B)
     return out
 
 
