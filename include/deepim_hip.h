@@ -341,7 +341,9 @@ int deepim_zoom_inverse_factor(deepim_ctx* ctx, const float* zoom_factor, float*
  * bit3 (8) = split-fp16 conv path: a value left fp16's range after scaling (|v·scale| > 60000 or NaN) and was clamped — the
  *            results of that call are not fp32-grade; lower the activation scale or use the fp32 path
  * bit4 (16) = a shared-frame entry (deepim_zoom_concat_frames_forward[_h16], deepim_ingest_*_frames) met a frame_index outside
- *            [0, N): that pair's observed channels / output plane are those of an empty frame */
+ *            [0, N): that pair's observed channels / output plane are those of an empty frame
+ * bit5 (32) = deepim_ingest_bgr8_pool met a bg_index outside [0, P) in a pair that composites a background: that pair's
+ *            background is black */
 int deepim_zoom_status(deepim_ctx* ctx, int* status);
 
 /* ------------------------------------------ N-group: matching network ops -- */
@@ -1010,6 +1012,32 @@ int deepim_ingest_bgr8(deepim_ctx* ctx, float* out /*B,3,H,W*/, const uint8_t* f
                        const uint8_t* bg_frames /*B,H,W,3 or NULL*/, const uint8_t* fg_labels /*B,H,W or NULL*/,
                        const int32_t* use_bg /*device (B) or NULL*/, const float* means_rgb /*host 3 or NULL*/, int B, int H,
                        int W);
+/* deepim_ingest_bgr8 with the background of image.py:108-145 made on the fly from a POOL of decoded images that is uploaded
+ * once (lib/utils/background.BackgroundPool): the top-left crop to the frame's aspect ratio (:119-141), cv2.resize's 8-bit
+ * INTER_LINEAR resample (:143) and the paste at the top-left corner of a black frame (:118,145) happen inside the composite, and
+ * no resized background exists in memory. Everything that depends only on an image's size and the frame's is a table:
+ *   pool_pixels  the images' (bh,bw,3) uint8 BGR pixels back to back, 4-byte aligned, every image's start too, with 12 readable
+ *                bytes behind the last image (the taps are read as aligned 12-byte windows)
+ *   pool_desc    (P,4) int64: the image's byte offset in pool_pixels, its row stride in bytes, oh, ow = the size of its
+ *                resized crop (oh <= H, ow <= W)
+ *   xtab, ytab   (P,W) / (P,H) int32: per output column x0, x1, a0, a1, per output row y0, y1, b0, b1 — the two source indices
+ *                inside the crop and their 11-bit weights — packed as i0 << 13 | (i1 != i0) << 12 | w1: i1 is i0 or i0 + 1 and
+ *                w0 = 2048 - w1 (an image side < 2^19); zeros from ow / oh on
+ * A pixel of pair b with fg_labels != 0, or of a pair with use_bg[b] == 0 (NULL: every pair composites), is the frame's. The
+ * others are, per channel, with P the image bg_index[b], for y < oh and x < ow
+ *   r0 = P[y0][x0] a0 + P[y0][x1] a1        r1 = P[y1][x0] a0 + P[y1][x1] a1
+ *   v  = clamp((((b0 (r0 >> 4)) >> 16) + ((b1 (r1 >> 4)) >> 16) + 2) >> 2, 0, 255)
+ * and 0 outside. Then the channel swap and the fp32 subtraction of deepim_ingest_bgr8: the output has the bits
+ * deepim_ingest_bgr8 gives from the same frames with a bg_frames holding the resampled, padded images. Lanes without a
+ * label-0 pixel read nothing of the pool; no LDS, nothing allocated, legal inside a graph capture. H*W < 2^31.
+ * Since the host never sees the draws a bad one cannot be reported: a compositing pair whose bg_index is outside [0, P) reads
+ * nothing outside the pool, gets a black background and sets bit 5 (32) of the status word (deepim_zoom_status); the other
+ * pairs are unaffected. The tables' own contents are the caller's to get right: BackgroundPool builds and checks them on the host. */
+int deepim_ingest_bgr8_pool(deepim_ctx* ctx, float* out /*B,3,H,W*/, const uint8_t* frames /*B,H,W,3*/,
+                            const uint8_t* fg_labels /*B,H,W*/, const int32_t* use_bg /*device (B) or NULL*/,
+                            const int32_t* bg_index /*device (B)*/, const uint8_t* pool_pixels, const int64_t* pool_desc,
+                            const int32_t* xtab /*P,W*/, const int32_t* ytab /*P,H*/, int P,
+                            const float* means_rgb /*host 3 or NULL*/, int B, int H, int W);
 /* image.py:178-181, :203-219: out[b,0,y,x] = float(depth[b,y,x]) / depth_factor, a correctly rounded fp32 division as numpy's.
  * labels (B,H,W) uint8 and mask_idx (B), both or neither: the value is 0 where labels != mask_idx[b] (image.py:211,
  * tester.py:556). */
@@ -1061,15 +1089,17 @@ int deepim_l2_norms_multi(deepim_ctx* ctx, float* out /*rows*/, const uint64_t* 
 
 /* ------------------------------------------ R-group: the loader's random draws (csrc/sample.hip) -- */
 /* A counter-based generator, Philox4x32-10, and on top of it the rendered-pose rule of toolkit/LM6d_1_gen_rendered_pose.py:80-107
- * and the draws of lib/utils/mask_dilate.py. Every draw is a pure function of (seed, draw id, attempt, stream):
+ * and the draws of lib/utils/mask_dilate.py and of the background replacement (lib/utils/image.py:97-116). Every draw is a pure
+ * function of (seed, draw id, attempt, stream):
  *   key     = (seed low word, seed high word)
- *   counter = (draw id low, draw id high, attempt, stream)      streams 0, 1: the two blocks of a pose draw; 2: mask dilate
+ *   counter = (draw id low, draw id high, attempt, stream)      streams 0, 1: the two blocks of a pose draw; 2: mask dilate;
+ *                                                               3: background
  * so a pair's draw does not depend on the batch size, its position in the batch or the order of launches. The draw id of pair b
  * is draw_ids[b] where draw_ids (device, B) is given, else draw_base + b (draw_base is not added to given ids).
  * A 32-bit word x becomes the uniform u = (x + 0.5) 2^-32 in double, strictly inside (0,1); six normals come pairwise from the
  * first six of a candidate's eight words by Box-Muller in double, r = sqrt(-2 ln u0), z0 = r cos 2 pi u1, z1 = r sin 2 pi u1
  * (block 0: z0..z3, block 1: z4, z5). A word maps to [0, n) as (uint64(x) n) >> 32: the bias is at most n 2^-32.
- * All five entries are asynchronous on the context's stream, allocate nothing and read nothing back. B >= 0.
+ * All six entries are asynchronous on the context's stream, allocate nothing and read nothing back. B >= 0.
  *
  * deepim_selfcheck_philox: out[i] = Philox4x32-10(ctr[i], key[i]), the generator alone (known-answer tests). */
 int deepim_selfcheck_philox(deepim_ctx* ctx, unsigned int* out /*n,4 dev*/, const unsigned int* ctr /*n,4 dev*/,
@@ -1098,6 +1128,15 @@ int deepim_sample_rendered_poses(deepim_ctx* ctx, float* pose_out /*B,3,4*/, int
  * randint(max_thickness) + 1 (max_thickness >= 1) in the order of the file's four blocks; a side is 0 where the file skips it
  * for the direction. thickness must be 16-byte aligned. */
 int deepim_sample_mask_dilate(deepim_ctx* ctx, int32_t* thickness /*B,4 dev*/, int max_thickness, unsigned long long seed,
+                              unsigned long long draw_base, const unsigned long long* draw_ids, int B);
+/* The background draws of lib/utils/image.py:97-116 for B pairs, as deepim_ingest_bgr8_pool takes them, from the stream-3 call
+ * with attempt 0: word 0 as the uniform u stands for the np.random.rand() of :99, word 1 mapped to [0, pool_size) for
+ * random.randint's choice of the image (:113):
+ *   use_bg[b]   = (always != NULL && always[b] != 0) || u < ratio ? 1 : 0      always: the pairs' data_syn flags (:98)
+ *   bg_index[b] = (uint64(word 1) pool_size) >> 32                             drawn for every pair, used or not
+ * ratio: TRAIN.REPLACE_OBSERVED_BG_RATIO in [0, 1] (0: never, since u > 0; 1: always, since u < 1); pool_size >= 1. */
+int deepim_sample_backgrounds(deepim_ctx* ctx, int32_t* use_bg /*B dev*/, int32_t* bg_index /*B dev*/,
+                              const int32_t* always /*B dev or NULL*/, double ratio, int pool_size, unsigned long long seed,
                               unsigned long long draw_base, const unsigned long long* draw_ids, int B);
 /* The loader's running counts, kept on the device: totals[0] += B, totals[1] += the sum of attempts, totals[2] += the pairs with
  * attempts == 0 (exhausted). */

@@ -20,7 +20,13 @@ Pair p of epoch e has draw id e·M·R + p wherever the shuffle puts it, so its p
 (seed, e, p) alone. The rendered side is the unquantised float render the batch updater produces between iterations, not the
 8-bit / 16-bit files of the reference.
 
-Not part of this loader and refused: backgrounds (bg_image), TRAIN.MASK_SYN, resizing (a frame that is not config.SCALES[0]),
+`backgrounds`: a lib/utils/background.BackgroundPool built for the frames' (H, W), or None. With it the observed image gets the
+background replacement of image.py:96-155 on the device: the frames flagged in `data_syn` ((M) bool, optional) always, the
+others with probability TRAIN.REPLACE_OBSERVED_BG_RATIO, on a pool image chosen by the pair's own draw (stream 3 of its draw
+id), cropped, resized and composited by one kernel (deepim_ingest_bgr8_pool). Like the pose, the background of pair p in epoch
+e depends on (seed, e, p) alone. Without it every batch is what it was before backgrounds existed.
+
+Not part of this loader and refused: ready-made backgrounds (bg_image: the pool is the loader's way), TRAIN.MASK_SYN, resizing (a frame that is not config.SCALES[0]),
 shared-frame batches (frame_index), device-resident datasets.
 """
 import numpy as np
@@ -28,6 +34,7 @@ import numpy as np
 from ..lib.pair_matching import data_pair
 from ..lib.pair_matching.pose_sampler import pose_noise, sample_rendered_poses
 from ..lib.utils import image as _image
+from ..lib.utils.background import background_draws_device
 from ..lib.utils.mask_dilate import mask_dilate_draws_device
 from ..runtime import DeviceArray, lib
 
@@ -51,7 +58,7 @@ def epoch_plan(M, R, batch_size, shuffle, rng, epoch):
 
 class TrainDataLoader(object):
     def __init__(self, observed, config, render_machine, batch_size=1, shuffle=False, seed=0, num_rendered_per_observed=1,
-                 points=None, noise=None):
+                 points=None, noise=None, backgrounds=None, data_syn=None):
         self.config, self.render_machine, self.ctx = config, render_machine, render_machine.ctx
         self.batch_size, self.shuffle, self.seed = int(batch_size), bool(shuffle), int(seed)
         self.R = int(num_rendered_per_observed)
@@ -61,7 +68,8 @@ class TrainDataLoader(object):
                 raise TypeError("TrainDataLoader: observed['%s'] is a device array; the dataset is host numpy arrays, a batch is "
                                 "gathered on the host and uploaded" % k)
         if observed.get("bg_image") is not None:
-            raise NotImplementedError("TrainDataLoader: backgrounds (bg_image, image.py:108-155) are not part of this loader")
+            raise NotImplementedError("TrainDataLoader: ready-made backgrounds (bg_image) are not part of this loader; pass "
+                                      "backgrounds=BackgroundPool(...) and they are drawn, cropped and resized on the device")
         if observed.get("frame_index") is not None:
             raise NotImplementedError("TrainDataLoader: shared frames (frame_index) are a test-phase input; the training loader is "
                                       "per pair")
@@ -88,6 +96,12 @@ class TrainDataLoader(object):
             if self.observed[k].shape != (self.M, H, W):
                 raise ValueError("observed['%s'] has shape %s; %s expected" % (k, self.observed[k].shape, (self.M, H, W)))
         self.height, self.width = H, W
+        if backgrounds is not None and (backgrounds.height, backgrounds.width) != (H, W):
+            raise ValueError("the background pool was built for %dx%d frames, the frames are %dx%d"
+                             % (backgrounds.height, backgrounds.width, H, W))
+        self.backgrounds = backgrounds
+        self.bg_ratio = float(config.TRAIN.get("REPLACE_OBSERVED_BG_RATIO", 0.0))
+        self.data_syn = None if data_syn is None else np.asarray(data_syn).astype(bool).reshape(self.M)
         self.pose_observed = np.ascontiguousarray(observed["pose_observed"], dtype=np.float32).reshape(self.M, 3, 4)
         self.mask_idx = np.asarray(observed["mask_idx"]).astype(np.int32).reshape(self.M)
         self.class_index = np.asarray(observed["class_index"]).astype(np.int32).reshape(self.M)
@@ -124,6 +138,17 @@ class TrainDataLoader(object):
         t = self._totals.asnumpy()
         return {"pairs": int(t[0]), "attempts": int(t[1]), "exhausted": int(t[2])}
 
+    def _image_observed(self, frames, m, ids):
+        """image_observed of the batch; with a background pool, on the backgrounds image.py:96-155 gives it: a data_syn frame
+        always, a real one with probability TRAIN.REPLACE_OBSERVED_BG_RATIO, both from the pair's own draw (stream 3)."""
+        ctx, means = self.ctx, _image._means_rgb(self.config)
+        if self.backgrounds is None:
+            return _image.transform_batch(ctx, frames["image_observed"], means)
+        use_bg, bg_index = background_draws_device(ctx, len(m), self.seed, ids, self.bg_ratio, len(self.backgrounds),
+                                                   always=None if self.data_syn is None else self.data_syn[m])
+        return _image.transform_batch_pool(ctx, frames["image_observed"], means, frames["mask_gt_observed"], use_bg, bg_index,
+                                           self.backgrounds)
+
     def make_batch(self, pairs, draw_ids):
         """(data, label) of the given pairs (p = m·R + r) with the given draw ids."""
         ctx, cfg = self.ctx, self.config
@@ -131,7 +156,8 @@ class TrainDataLoader(object):
         B = len(m)
         frames = {k: ctx.array(self.observed[k][m], dtype=_DTYPES[k]) for k in self.keys}      # 1 or 2 bytes per value cross PCIe
         frames["mask_idx"] = ctx.array(self.mask_idx[m], dtype=np.int32)
-        batch = {"image_observed": _image.transform_batch(ctx, frames["image_observed"], _image._means_rgb(cfg)),
+        ids = ctx.array(np.asarray(draw_ids).reshape(B), dtype=np.uint64)
+        batch = {"image_observed": self._image_observed(frames, m, ids),
                  "depth_gt_observed": _image._depth(ctx, frames, "depth_gt_observed", cfg),
                  "mask_gt_observed": _image.label_mask(ctx, frames, "mask_gt_observed"),
                  "pose_observed": ctx.array(self.pose_observed[m]),
@@ -139,7 +165,6 @@ class TrainDataLoader(object):
         if cfg.network.INPUT_DEPTH:       # get_pair_depth, train phase: zeroed outside the pair's label with MASK_INPUTS
             batch["depth_observed"] = _image._depth(ctx, frames, "depth_observed", cfg,
                                                     "mask_gt_observed" if cfg.network.get("MASK_INPUTS", False) else None)
-        ids = ctx.array(np.asarray(draw_ids).reshape(B), dtype=np.uint64)
         batch["pose_rendered"], attempts = sample_rendered_poses(batch["pose_observed"], self.K, self.width, self.height, self.seed,
                                                                  draw_ids=ids, noise=self.noise)
         lib.deepim_sample_stats_accumulate(ctx.handle, self._totals, attempts, B)

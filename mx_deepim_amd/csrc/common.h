@@ -19,6 +19,7 @@ constexpr int DI_STATUS_GROUP_RANGE = 2;      // GroupPicker index out of range
 constexpr int DI_STATUS_X3_SATURATED = 8;     // split-fp16 conv: a value left fp16's range after scaling and was clamped (results invalid)
 constexpr int DI_STATUS_MASK_BOX_EMPTY = 4;   // mask_box / fused re-render: empty mask (data_pair.py:98 np.min raises)
 constexpr int DI_STATUS_FRAME_RANGE = 16;     // shared-frame entries: a device-resident frame_index outside [0, N) (that pair sees an empty frame)
+constexpr int DI_STATUS_BG_RANGE = 32;        // deepim_ingest_bgr8_pool: a device-resident bg_index outside [0, P) (that pair gets a black background)
 
 // deepim_set_option(ctx, "f16_dev_flags", 0 or DI_F16_NO_PP): the 4-wave kernel of csrc/conv_f16.hip is the ping-pong kernel's
 // bit-exact reference in the tests

@@ -26,6 +26,28 @@ __device__ __forceinline__ void next_pixel(long hw, long& b, long& q) {
   if (++q == hw) { q = 0; ++b; }
 }
 
+// the tail of the BGR kernels: px[tensor channel][pixel] less the channel's mean, to the three planes of each pixel's sample
+template <bool VEC_OUT>
+__device__ __forceinline__ void store_planes(float* __restrict__ out, float (&px)[3][4], const Vec3& means, const long (&bs)[4],
+                                             const long (&qs)[4], long hw, int cnt) {
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) px[c][j] -= means.v[c];
+  if (VEC_OUT) {   // hw % 4 == 0: the four pixels share a sample and cnt == 4
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+      *reinterpret_cast<float4*>(out + (bs[0] * 3 + c) * hw + qs[0]) = make_float4(px[c][0], px[c][1], px[c][2], px[c][3]);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (j < cnt) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) out[(bs[j] * 3 + c) * hw + qs[j]] = px[c][j];
+      }
+  }
+}
+
 // VEC_IN: every input pointer is dword-aligned (12-byte loads); VEC_OUT: hw % 4 == 0 and `out` 16-byte aligned (float4 stores)
 template <bool VEC_IN, bool VEC_OUT>
 __global__ __launch_bounds__(256) void ingest_bgr8_kernel(float* __restrict__ out, const uint8_t* __restrict__ frames,
@@ -71,22 +93,163 @@ __global__ __launch_bounds__(256) void ingest_bgr8_kernel(float* __restrict__ ou
       }
     }
   }
+  store_planes<VEC_OUT>(out, px, means, bs, qs, hw, cnt);
+}
+
+// The background pool of deepim_ingest_bgr8_pool (lib/utils/background.py builds it once): P decoded BGR images back to back,
+// and per image everything image.py:108-145 derives from its size and the frame's — the crop, cv2.resize's INTER_LINEAR taps
+// and 11-bit weights, the size of the resized image — so that the kernel is integer arithmetic on four gathered taps.
+struct BgPool {
+  const uint8_t* pixels;     // dword-aligned, every image's start too, 12 readable bytes behind the last image
+  const int64_t* desc;       // (P,4): byte offset of the image, its row stride in bytes, oh, ow (the resized image's size)
+  const uint32_t* xtab;      // (P,W): output column x as x0 << 13 | (x1 != x0) << 12 | a1, with a0 = 2048 - a1; zeros from ow on
+  const uint32_t* ytab;      // (P,H): output row y the same way: y0, y1 = y0 or y0 + 1, b1, b0 = 2048 - b1; zeros from oh on
+  const int32_t* bg_index;   // (B)
+  int* status;
+  int P, H, W;
+};
+// what pair b draws from: on = it composites a pool image (use_bg[b] != 0), live = that image exists (bg_index[b] in [0, P)).
+// Without a live image the pointers are the pool's own with an empty oh x ow: every pixel is outside it, and the loads a lane
+// issues for such a pixel (entry 0 of the first tables, the pool's first bytes) stay inside the pool.
+struct BgImage {
+  const uint8_t* px;
+  const uint32_t *xt, *yt;
+  int stride, oh, ow;
+  bool on, live;
+};
+__device__ __forceinline__ BgImage bg_image_of(const BgPool& pool, const int32_t* __restrict__ use_bg, long b) {
+  BgImage im;
+  im.on = !use_bg || use_bg[b] != 0;
+  const int id = im.on ? pool.bg_index[b] : -1;
+  im.live = id >= 0 && id < pool.P;
+  const int k = im.live ? id : 0;
+  const int64_t* d = pool.desc + (long)k * 4;
+  im.px = pool.pixels + d[0];
+  im.stride = (int)d[1];
+  im.oh = im.live ? (int)d[2] : 0;
+  im.ow = im.live ? (int)d[3] : 0;
+  im.xt = pool.xtab + (long)k * pool.W;
+  im.yt = pool.ytab + (long)k * pool.H;
+  return im;
+}
+// ONE aligned 12-byte window covers the six bytes from byte address a on whatever a's alignment, so the two taps of a row
+// cost one load instead of six
+__device__ __forceinline__ Bytes12 load_window(const uint8_t* a) {
+  return *reinterpret_cast<const Bytes12*>((uintptr_t)a & ~(uintptr_t)3);
+}
+// the BGR pixel at byte `at` (0..3) of the window (t0) and, with `next`, the one three bytes on (t1, else t0 again), as 0x00RRGGBB
+__device__ __forceinline__ void taps_of(const Bytes12& w, int at, bool next, uint32_t& t0, uint32_t& t1) {
+  const uint32_t d0 = (uint32_t)((((uint64_t)w.w[1] << 32) | w.w[0]) >> (8 * at));   // bytes 0..3 from a
+  const uint32_t d1 = (uint32_t)((((uint64_t)w.w[2] << 32) | w.w[1]) >> (8 * at));   // bytes 4..7
+  t0 = d0 & 0xffffffu;
+  t1 = next ? (d0 >> 24) | ((d1 & 0xffffu) << 8) : t0;
+}
+// cv2.resize INTER_LINEAR on 8-bit pixels (the generic path: 11-bit weights, a horizontal pass kept at 15 bits, a rounded
+// vertical pass) from the windows of the two source rows and the column's and the row's table entries, as 0x00RRGGBB
+__device__ __forceinline__ uint32_t bg_resample(const Bytes12& w0, const Bytes12& w1, int at0, int at1, uint32_t ex, uint32_t ey) {
+  const int a1 = (int)(ex & 0xfffu), a0 = 2048 - a1, b1 = (int)(ey & 0xfffu), b0 = 2048 - b1;
+  uint32_t p00, p01, p10, p11;
+  taps_of(w0, at0, (ex & 0x1000u) != 0, p00, p01);
+  taps_of(w1, at1, (ex & 0x1000u) != 0, p10, p11);
+  uint32_t r = 0;
 #pragma unroll
-  for (int c = 0; c < 3; ++c)
+  for (int c = 0; c < 3; ++c) {
+    const int r0 = (int)((p00 >> (8 * c)) & 0xffu) * a0 + (int)((p01 >> (8 * c)) & 0xffu) * a1;
+    const int r1 = (int)((p10 >> (8 * c)) & 0xffu) * a0 + (int)((p11 >> (8 * c)) & 0xffu) * a1;
+    const int v = (((b0 * (r0 >> 4)) >> 16) + ((b1 * (r1 >> 4)) >> 16) + 2) >> 2;
+    r |= (uint32_t)min(max(v, 0), 255) << (8 * c);
+  }
+  return r;
+}
+
+// ingest_bgr8_kernel with the background made on the fly: same flat walk, same loads of the frame and its labels, same
+// stores. A pixel whose label is 0, in a pair with use_bg != 0, is the pool image's resampled pixel inside oh x ow and black
+// outside (image.py:118,145: the resized crop is pasted at the top-left of a black frame); a pair whose bg_index is outside
+// [0, P) is black everywhere and reported through DI_STATUS_BG_RANGE by the lane that owns the pair's first pixel.
+// Lanes without a label-0 pixel read nothing of the pool. The others work in stages without a branch in between, so that
+// the loads of a stage are in flight together: the descriptor (once per lane; once per pixel only where H·W % 4 != 0 lets a
+// lane's pixels cross into the next pair), the four pixels' table entries, their eight windows, the arithmetic. A pixel that
+// takes no background rides along on entry 0 and the image's first bytes, and its result is dropped.
+template <bool VEC_IN, bool VEC_OUT>
+__global__ __launch_bounds__(256) void ingest_bgr8_pool_kernel(float* __restrict__ out, const uint8_t* __restrict__ frames,
+                                                               const uint8_t* __restrict__ fg,
+                                                               const int32_t* __restrict__ use_bg, BgPool pool, Vec3 means,
+                                                               long hw, long n) {
+  const long p0 = ((long)blockIdx.x * 256 + threadIdx.x) * 4;
+  if (p0 >= n) return;
+  const int cnt = (int)min(4L, n - p0);
+  long bs[4], qs[4];
+  locate_pixel(p0, hw, n, bs[0], qs[0]);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) px[c][j] -= means.v[c];
-  if (VEC_OUT) {   // hw % 4 == 0: the four pixels share a sample and cnt == 4
+  for (int j = 1; j < 4; ++j) { bs[j] = bs[j - 1]; qs[j] = qs[j - 1]; next_pixel(hw, bs[j], qs[j]); }
+  uint32_t pix[4], lab[4];   // 0x00RRGGBB of the frame; the label
+  if (VEC_IN && cnt == 4) {
+    const Bytes12 v = *reinterpret_cast<const Bytes12*>(frames + p0 * 3);
+    const uint32_t l = *reinterpret_cast<const uint32_t*>(fg + p0);
+    pix[0] = v.w[0] & 0xffffffu;
+    pix[1] = (v.w[0] >> 24) | ((v.w[1] & 0xffffu) << 8);
+    pix[2] = (v.w[1] >> 16) | ((v.w[2] & 0xffu) << 16);
+    pix[3] = v.w[2] >> 8;
 #pragma unroll
-    for (int c = 0; c < 3; ++c)
-      *reinterpret_cast<float4*>(out + (bs[0] * 3 + c) * hw + qs[0]) = make_float4(px[c][0], px[c][1], px[c][2], px[c][3]);
+    for (int j = 0; j < 4; ++j) lab[j] = (l >> (8 * j)) & 0xffu;
   } else {
 #pragma unroll
-    for (int j = 0; j < 4; ++j)
+    for (int j = 0; j < 4; ++j) {
+      pix[j] = 0; lab[j] = 1;
       if (j < cnt) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) out[(bs[j] * 3 + c) * hw + qs[j]] = px[c][j];
+        const uint8_t* s = frames + (p0 + j) * 3;
+        pix[j] = (uint32_t)s[0] | ((uint32_t)s[1] << 8) | ((uint32_t)s[2] << 16);
+        lab[j] = fg[p0 + j];
       }
+    }
   }
+  bool any = false;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) any |= j < cnt && (lab[j] == 0 || qs[j] == 0);
+  if (any) {
+    int ys[4], xs[4];
+    ys[0] = (int)((uint32_t)qs[0] / (uint32_t)pool.W);   // hw < 2^31 (checked by the launcher)
+    xs[0] = (int)qs[0] - ys[0] * pool.W;
+#pragma unroll
+    for (int j = 1; j < 4; ++j) {
+      xs[j] = xs[j - 1] + 1; ys[j] = ys[j - 1];
+      if (xs[j] == pool.W) { xs[j] = 0; if (++ys[j] == pool.H) ys[j] = 0; }
+    }
+    BgImage im[4];
+    im[0] = bg_image_of(pool, use_bg, bs[0]);
+#pragma unroll
+    for (int j = 1; j < 4; ++j) im[j] = VEC_OUT || j >= cnt ? im[0] : bg_image_of(pool, use_bg, bs[j]);
+    bool take[4], in[4];   // the pixel is background; it lies inside the resized image
+    uint32_t ex[4], ey[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (j < cnt && qs[j] == 0 && im[j].on && !im[j].live) atomicOr(pool.status, DI_STATUS_BG_RANGE);
+      take[j] = j < cnt && lab[j] == 0 && im[j].on;
+      in[j] = take[j] && ys[j] < im[j].oh && xs[j] < im[j].ow;
+      ex[j] = im[j].xt[in[j] ? xs[j] : 0];
+      ey[j] = im[j].yt[in[j] ? ys[j] : 0];
+    }
+    Bytes12 win[4][2];
+    int at[4][2];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const uint8_t* r0 = im[j].px + (long)(ey[j] >> 13) * im[j].stride + (ex[j] >> 13) * 3;
+      const uint8_t* r1 = (ey[j] & 0x1000u) ? r0 + im[j].stride : r0;
+      win[j][0] = load_window(r0); at[j][0] = (int)((uintptr_t)r0 & 3);
+      win[j][1] = load_window(r1); at[j][1] = (int)((uintptr_t)r1 & 3);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const uint32_t v = bg_resample(win[j][0], win[j][1], at[j][0], at[j][1], ex[j], ey[j]);
+      if (take[j]) pix[j] = in[j] ? v : 0u;
+    }
+  }
+  float px[3][4];   // [tensor channel][pixel]
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) px[c][j] = (float)((pix[j] >> (8 * (2 - c))) & 0xffu);
+  store_planes<VEC_OUT>(out, px, means, bs, qs, hw, cnt);
 }
 
 // Shared frames (the *_frames entries): the input of pair b is frame frame_index[b] of N, not sample b. The ids live on the
@@ -290,6 +453,39 @@ extern "C" int deepim_ingest_bgr8(deepim_ctx* ctx, float* out, const uint8_t* fr
   else if (vout) DI_INGEST_BGR(false, true);
   else DI_INGEST_BGR(false, false);
 #undef DI_INGEST_BGR
+  DI_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int deepim_ingest_bgr8_pool(deepim_ctx* ctx, float* out, const uint8_t* frames, const uint8_t* fg_labels,
+                                       const int32_t* use_bg, const int32_t* bg_index, const uint8_t* pool_pixels,
+                                       const int64_t* pool_desc, const int32_t* xtab, const int32_t* ytab, int P,
+                                       const float* means_rgb, int B, int H, int W) {
+  DI_DEVICE(ctx);
+  DI_REQUIRE(B >= 0 && H >= 0 && W >= 0, "ingest_bgr8_pool: negative size");
+  const long hw = (long)H * W, n = (long)B * hw;
+  DI_REQUIRE(hw <= 0x7fffffffL, "ingest_bgr8_pool: frame too large");
+  if (n == 0) return 0;
+  DI_REQUIRE(out && frames && fg_labels && bg_index, "ingest_bgr8_pool: out, frames, fg_labels and bg_index are required");
+  DI_REQUIRE(P >= 1 && pool_pixels && pool_desc && xtab && ytab, "ingest_bgr8_pool: the pool, its tables and P >= 1 are required");
+  DI_REQUIRE(aligned_to(pool_pixels, 4) && aligned_to(pool_desc, 8) && aligned_to(xtab, 4) && aligned_to(ytab, 4) &&
+                 aligned_to(bg_index, 4) && (!use_bg || aligned_to(use_bg, 4)),
+             "ingest_bgr8_pool: pool_desc must be 8-byte aligned, pool_pixels, the tables and the draws 4-byte aligned");
+  Vec3 means = {{0.f, 0.f, 0.f}};
+  if (means_rgb) for (int i = 0; i < 3; ++i) means.v[i] = means_rgb[i];
+  const BgPool pool = {pool_pixels, pool_desc, reinterpret_cast<const uint32_t*>(xtab), reinterpret_cast<const uint32_t*>(ytab),
+                       bg_index, ctx->status, P, H, W};
+  const bool vin = aligned_to(frames, 4) && aligned_to(fg_labels, 4);
+  const bool vout = hw % 4 == 0 && aligned_to(out, 16);
+  const dim3 grid(di_div_up(di_div_up(n, 4), 256)), block(256);
+#define DI_INGEST_POOL(VI, VO)                                                                                          \
+  hipLaunchKernelGGL((ingest_bgr8_pool_kernel<VI, VO>), grid, block, 0, ctx->stream, out, frames, fg_labels, use_bg, pool, \
+                     means, hw, n)
+  if (vin && vout) DI_INGEST_POOL(true, true);
+  else if (vin) DI_INGEST_POOL(true, false);
+  else if (vout) DI_INGEST_POOL(false, true);
+  else DI_INGEST_POOL(false, false);
+#undef DI_INGEST_POOL
   DI_LAUNCH_CHECK();
   return 0;
 }

@@ -2,10 +2,11 @@
 //   Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11) as a counter-based generator
 //   the rendered-pose rule of toolkit/LM6d_1_gen_rendered_pose.py:80-107 on top of it
 //   the draws of lib/utils/mask_dilate.py:19-47
+//   the background draws of lib/utils/image.py:97-116
 //
 // Every draw is a pure function of (seed, draw id, attempt, stream): key = (seed lo, seed hi), counter = (id lo, id hi, attempt,
-// stream). Streams 0 and 1 are the two blocks of a pose draw, stream 2 is the mask-dilate draw. Nothing depends on the batch
-// size, on a pair's position in the batch or on the order of launches.
+// stream). Streams 0 and 1 are the two blocks of a pose draw, stream 2 is the mask-dilate draw, stream 3 the background draw.
+// Nothing depends on the batch size, on a pair's position in the batch or on the order of launches.
 //
 // The kernels run one thread per pair; every array below is indexed by constants after unrolling, so nothing lives in
 // private memory. Arithmetic is float64 throughout (full rate on CDNA4, a few hundred flops per candidate).
@@ -210,6 +211,21 @@ __global__ __launch_bounds__(256) void sample_mask_dilate_kernel(int* __restrict
   reinterpret_cast<int4*>(thickness)[b] = t;
 }
 
+// The background draws of image.py:97-116 from stream 3, attempt 0: word 0 as a uniform is the np.random.rand() held against
+// TRAIN.REPLACE_OBSERVED_BG_RATIO (:99), which a data_syn frame (`always`) does not need (:98); word 1 is random.randint's
+// choice among the pool's images (:113). Both are drawn for every pair, used or not.
+__global__ __launch_bounds__(256) void sample_backgrounds_kernel(int* __restrict__ use_bg, int* __restrict__ bg_index,
+                                                                 const int* __restrict__ always, double ratio, int pool_size,
+                                                                 unsigned long long seed, unsigned long long draw_base,
+                                                                 const unsigned long long* __restrict__ draw_ids, int B) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= B) return;
+  const unsigned long long id = draw_ids ? draw_ids[b] : draw_base + (unsigned long long)b;
+  const Philox4 c = philox_draw(seed, id, 0u, 3u);
+  use_bg[b] = ((always && always[b] != 0) || word_uniform(c.w[0]) < ratio) ? 1 : 0;
+  bg_index[b] = word_below(c.w[1], pool_size);
+}
+
 // totals[0] += B, totals[1] += sum of attempts, totals[2] += pairs with attempts == 0. One block: integer sums, any order.
 __global__ __launch_bounds__(256) void sample_stats_kernel(unsigned long long* __restrict__ totals, const int* __restrict__ attempts,
                                                            int B) {
@@ -299,6 +315,21 @@ extern "C" int deepim_sample_mask_dilate(deepim_ctx* ctx, int32_t* thickness, in
   DI_REQUIRE(thickness, "sample_mask_dilate: NULL argument");
   hipLaunchKernelGGL(sample_mask_dilate_kernel, dim3(di_div_up(B, 256)), dim3(256), 0, ctx->stream, thickness, max_thickness, seed,
                      draw_base, draw_ids, B);
+  DI_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int deepim_sample_backgrounds(deepim_ctx* ctx, int32_t* use_bg, int32_t* bg_index, const int32_t* always, double ratio,
+                                         int pool_size, unsigned long long seed, unsigned long long draw_base,
+                                         const unsigned long long* draw_ids, int B) {
+  DI_DEVICE(ctx);
+  DI_REQUIRE(B >= 0, "sample_backgrounds: B must be >= 0");
+  DI_REQUIRE(pool_size >= 1, "sample_backgrounds: pool_size must be >= 1");
+  DI_REQUIRE(ratio >= 0.0 && ratio <= 1.0, "sample_backgrounds: ratio must lie in [0, 1]");
+  if (B == 0) return 0;
+  DI_REQUIRE(use_bg && bg_index, "sample_backgrounds: NULL argument");
+  hipLaunchKernelGGL(sample_backgrounds_kernel, dim3(di_div_up(B, 256)), dim3(256), 0, ctx->stream, use_bg, bg_index, always, ratio,
+                     pool_size, seed, draw_base, draw_ids, B);
   DI_LAUNCH_CHECK();
   return 0;
 }

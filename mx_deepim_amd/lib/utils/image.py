@@ -13,6 +13,10 @@ numpy array (uploaded as it is, never converted on the host), for a batch of B p
     depth_observed, depth_rendered, depth_gt_observed     (B,H,W) uint16
     mask_gt_observed, mask_observed, mask_observed_est    (B,H,W) uint8 label maps
     mask_idx                              (B) int32: the pair's label value (pair_rec["mask_idx"])
+    bg_pool, bg_index                     instead of bg_image: a lib/utils/background.BackgroundPool of decoded images of any
+                                          sizes, uploaded once, and (B) int32, the image each pair composites (with use_bg
+                                          as above). The crop, the resize and the padding of image.py:108-145 happen inside the
+                                          composite (deepim_ingest_bgr8_pool): no resized background exists in memory
     mask_dilate_thickness                 (B,4) int32 from lib/utils/mask_dilate.mask_dilate_draws, for MASK_DILATE
 
 A dict that carries `frame_index` is a SHARED-FRAME batch: several objects in one camera frame (Occluded LINEMOD, YCB-style
@@ -32,8 +36,10 @@ numpy frame_index is range-checked on the host before anything is launched (Valu
 be: a pair whose id is outside [0, N) sees an empty frame and sets bit 4 of the status word. Shared frames are test-phase only:
 `get_pair_image` (which would have to make the fp32 copies), bg_image and the training loader refuse them.
 
-File decoding, the cv2 resize (:552-580) and the choice of a background are the caller's: a frame whose size is not
-config.SCALES[0] is refused. The test phase's `np.sum(depth_rendered) == 0` guard (:301-303) is a host decision per pair and is
+File decoding and the cv2 resize (:552-580) of the observed and rendered frames are the caller's: a frame whose size is not
+config.SCALES[0] is refused. A background is cropped and resized on the device from a bg_pool (lib/utils/background.py, which
+also draws use_bg and bg_index for the training loader); a bg_image is taken as the caller made it. A bg_index is never read
+by the host: one outside the pool gives that pair a black background and sets bit 5 of the status word. The test phase's `np.sum(depth_rendered) == 0` guard (:301-303) is a host decision per pair and is
 the caller's too; an empty rectangle source gives zeros and sets bit 2 of the status word (deepim_zoom_status).
 
 The kernels are asynchronous on the context's stream. These wrappers stay asynchronous when frames, ids and draws are device
@@ -191,6 +197,20 @@ def transform_batch(ctx, frames_bgr, means_rgb=None, bg=None, fg=None, use_bg=No
     return out
 
 
+def transform_batch_pool(ctx, frames_bgr, means_rgb, fg, use_bg, bg_index, pool):
+    """transform_batch with the background of image.py:108-155 from a BackgroundPool: where fg (B,H,W) uint8 is 0, in the pairs
+    with use_bg != 0 (device int32 (B), None: every pair), the pixel is image bg_index[b] (device int32 (B)) of the pool,
+    cropped, resized and padded to the frame inside the kernel."""
+    B, H, W, _ = frames_bgr.shape
+    if (pool.height, pool.width) != (H, W):
+        raise ValueError("the background pool was built for %dx%d frames, these are %dx%d" % (pool.height, pool.width, H, W))
+    out = ctx.empty((B, 3, H, W))
+    means = None if means_rgb is None else np.ascontiguousarray(means_rgb, dtype=np.float32).reshape(3)
+    lib.deepim_ingest_bgr8_pool(ctx.handle, out, frames_bgr, fg, use_bg, bg_index, pool.pixels, pool.desc, pool.xtab, pool.ytab,
+                                len(pool), means, B, H, W)
+    return out
+
+
 def transform(im, pixel_means):
     """image.py:583-594: im [height, width, channel] uint8 in BGR, pixel_means in the image's BGR order → numpy
     [1, channel, height, width] in RGB order, computed on the default device in fp32 (the reference computes in float64)."""
@@ -208,7 +228,8 @@ def _means_rgb(config):
 
 def get_pair_image(frames, config, phase="train"):
     """image.py:58-163 → (image_observed, image_rendered), device (B,3,H,W). In the train phase, frames with a "bg_image" get the
-    observed background replaced where mask_gt_observed == 0 (:147-155)."""
+    observed background replaced where mask_gt_observed == 0 (:147-155); frames with a "bg_pool" and a "bg_index" get it from the
+    pool's image bg_index[b], cropped and resized as :108-145 do (transform_batch_pool)."""
     if is_shared(frames):
         raise NotImplementedError("get_pair_image would make B fp32 copies of the shared frames (frames['frame_index']): use "
                                   "observed_frames for the observed side and get_rendered_image for image_rendered")
@@ -221,6 +242,17 @@ def get_pair_image(frames, config, phase="train"):
         raise ValueError("image_rendered %s and image_observed %s differ in shape" % (ren.shape, obs.shape))
     means = _means_rgb(config)
     bg = fg = use_bg = None
+    if frames.get("bg_pool") is not None:
+        if frames.get("bg_image") is not None:
+            raise ValueError("frames carry both a bg_image and a bg_pool: one background per pair")
+        if phase == "train":
+            fg = _frame(ctx, frames, "mask_gt_observed", np.uint8)
+            if fg.shape != obs.shape[:3]:
+                raise ValueError("mask_gt_observed does not match image_observed's shape")
+            if frames.get("use_bg") is not None:
+                use_bg = _ids(ctx, frames, "use_bg", B)
+            observed = transform_batch_pool(ctx, obs, means, fg, use_bg, _ids(ctx, frames, "bg_index", B), frames["bg_pool"])
+            return observed, transform_batch(ctx, ren, means)
     if phase == "train" and frames.get("bg_image") is not None:
         bg = _frame(ctx, frames, "bg_image", np.uint8, (3,))
         fg = _frame(ctx, frames, "mask_gt_observed", np.uint8)
