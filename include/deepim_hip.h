@@ -995,6 +995,30 @@ int deepim_render_classes_forward(deepim_ctx* ctx, float* image, float* depth, f
                                   const float* K_host, const float* pixel_means_host, const float* light_offset_host /*or NULL*/,
                                   const float* light_intensity /*device (B,3) or NULL*/, float brightness_ratio, int B, int H,
                                   int W, float znear, float zfar);
+/* The lit mesh-table draw of deepim_render_classes_forward for SYNTHETIC OBSERVED FRAMES (toolkit/LM6d_ds_1_gen_observed.py:
+ * 116-159): every sample has its own light, and the result is written as the decoded frames the I-group entries below read, not
+ * as network tensors. The same project and raster passes; the resolve pass differs in two ways:
+ *   light    light_offset (B,3), light_intensity (B,3), brightness_ratio (B): DEVICE float arrays, one row per sample (what
+ *            deepim_sample_lights draws). The per-pixel arithmetic is that of the lit draw: sample b has the levels
+ *            deepim_render_classes_forward gives with B = 1, its own offset / intensity / ratio and pixel_means NULL.
+ *   outputs  image (N,H,W,3) uint8 BGR = the lit level rint(clamp(colour) 255), 0 on the background
+ *            depth (N,H,W) uint16 = (uint16)(depth * depth_factor): the float32 product truncated (:156); zfar * depth_factor
+ *                  must stay below 65536
+ *            label (N,H,W) uint8 = label_value[b] (device int32 (B), NULL = 1; its low byte) where depth != 0, else 0 (:151-153)
+ *   rows     device int32 (B) or NULL = the identity: sample b is written to row rows[b] of the three outputs, N >= B rows.
+ *            Rows not named are not touched; a sample whose row is outside [0, N) is not written. Two samples naming one row
+ *            race. The loader places its synthetic frames among the real ones of a batch this way.
+ * normals is required (the draw is lit). A lane stores four consecutive pixels with dword stores when H*W % 4 == 0 and the three
+ * outputs are 8-byte aligned, single pixels otherwise: the bytes are the same. A class id outside [0, n_classes) gives an empty
+ * frame (zeros). Asynchronous, allocates like the other draws (scratch and z-buffer grow outside a capture only). */
+int deepim_render_observed_forward(deepim_ctx* ctx, uint8_t* image /*N,H,W,3*/, uint16_t* depth /*N,H,W*/, uint8_t* label /*N,H,W*/,
+                                   const int32_t* rows /*device (B) or NULL*/, int N, const int32_t* label_value /*device (B) or NULL*/,
+                                   float depth_factor, const int32_t* class_index /*device (B)*/,
+                                   const int32_t* mesh_desc /*device (n_classes,8)*/, int n_classes, int max_V, int max_F,
+                                   const float* vertices, const float* vertex_attr, const float* normals, const int32_t* faces,
+                                   const float* textures /*or NULL*/, const float* poses, const float* K_host,
+                                   const float* light_offset /*device (B,3)*/, const float* light_intensity /*device (B,3)*/,
+                                   const float* brightness_ratio /*device (B)*/, int B, int H, int W, float znear, float zfar);
 
 /* ------------------------------------------- I-group: ingest of decoded frames -- */
 /* csrc/ingest.hip. What lib/utils/image.py does on the host between cv2.imread and the tensors of a batch, on frames that
@@ -1093,13 +1117,14 @@ int deepim_l2_norms_multi(deepim_ctx* ctx, float* out /*rows*/, const uint64_t* 
  * function of (seed, draw id, attempt, stream):
  *   key     = (seed low word, seed high word)
  *   counter = (draw id low, draw id high, attempt, stream)      streams 0, 1: the two blocks of a pose draw; 2: mask dilate;
- *                                                               3: background
+ *                                                               3: background; 4, 5: the two blocks of an observed-pose draw;
+ *                                                               6: light
  * so a pair's draw does not depend on the batch size, its position in the batch or the order of launches. The draw id of pair b
  * is draw_ids[b] where draw_ids (device, B) is given, else draw_base + b (draw_base is not added to given ids).
  * A 32-bit word x becomes the uniform u = (x + 0.5) 2^-32 in double, strictly inside (0,1); six normals come pairwise from the
  * first six of a candidate's eight words by Box-Muller in double, r = sqrt(-2 ln u0), z0 = r cos 2 pi u1, z1 = r sin 2 pi u1
  * (block 0: z0..z3, block 1: z4, z5). A word maps to [0, n) as (uint64(x) n) >> 32: the bias is at most n 2^-32.
- * All six entries are asynchronous on the context's stream, allocate nothing and read nothing back. B >= 0.
+ * All entries of this group are asynchronous on the context's stream, allocate nothing and read nothing back. B >= 0.
  *
  * deepim_selfcheck_philox: out[i] = Philox4x32-10(ctr[i], key[i]), the generator alone (known-answer tests). */
 int deepim_selfcheck_philox(deepim_ctx* ctx, unsigned int* out /*n,4 dev*/, const unsigned int* ctr /*n,4 dev*/,
@@ -1141,6 +1166,42 @@ int deepim_sample_backgrounds(deepim_ctx* ctx, int32_t* use_bg /*B dev*/, int32_
 /* The loader's running counts, kept on the device: totals[0] += B, totals[1] += the sum of attempts, totals[2] += the pairs with
  * attempts == 0 (exhausted). */
 int deepim_sample_stats_accumulate(deepim_ctx* ctx, unsigned long long* totals /*3 dev*/, const int32_t* attempts /*B dev*/, int B);
+/* Synthetic observed poses: the rule of toolkit/LM6d_ds_0_gen_observed_poses.py:200-250, one thread per pair, in double.
+ * table (n_classes,22) double, device, one row per class (lib/pair_matching/pose_sampler.pack_observed_table):
+ *   trans_mean[3], trans_std[3], pz_mean[3], angle_max (degrees), fallback pose [12]
+ * Candidate a of a draw id: stream 4, attempt a gives four normals (both Box-Muller pairs), stream 5, attempt a three (the first
+ * pair and the first normal of the second).
+ *   tgt_quat = the first four normalised, negated if w < 0      tgt_trans = trans_mean + z[4:7] trans_std
+ *   R = quat2mat(tgt_quat) in RT_transform.quat2mat's expression order
+ *   deg = the angle of R e_z to pz_mean as :74-78 (clip, arccos, degrees)      (cx, cy) = the projection of tgt_trans through K
+ *   accept iff deg <= angle_max and border < cx < width - border and border < cy < height - border and tgt_trans.z > 0
+ * (z > 0 is not the toolkit's, which divides by z unguarded; border is the file's 48 at 640 x 480). The first accepted candidate of
+ * attempts 0 .. max_attempts-1 is the pose; attempts[b] = the candidates drawn, normals_out[b] / stat_out[b] (both may be NULL)
+ * = its seven normals / deg, cx, cy, 1. None accepted: pose = the class's fallback row, attempts[b] = 0, zeros in normals_out
+ * and stat_out (the toolkit loops for ever). class_index[b] outside [0, n_classes): an all-zero pose, attempts[b] = -1, the table
+ * is not read; the draws render such a pair as an empty frame. deepim_sample_stats_accumulate adds attempts as they are, so
+ * a caller that feeds it keeps -1 out (core/loader.py checks its class ids on the host when it is built). K: 9 HOST floats. */
+int deepim_sample_observed_poses(deepim_ctx* ctx, float* pose_out /*B,3,4*/, int32_t* attempts /*B dev*/,
+                                 double* normals_out /*B,7 or NULL*/, double* stat_out /*B,4 or NULL*/,
+                                 const int32_t* class_index /*B dev*/, const double* table /*n_classes,22 dev*/, int n_classes,
+                                 const float* K, int width, int height, float border, int max_attempts, unsigned long long seed,
+                                 unsigned long long draw_base, const unsigned long long* draw_ids /*B dev or NULL*/, int B);
+/* One candidate of that rule from GIVEN normals (B,7), accepted or not, as deepim_pose_perturb is to the rendered-pose rule:
+ * pose_out = the candidate rounded to float, stat_out (or NULL) = deg, cx, cy, accept flag. A class id outside the table: zeros. */
+int deepim_observed_pose_candidate(deepim_ctx* ctx, float* pose_out /*B,3,4*/, double* stat_out /*B,4 or NULL*/,
+                                   const int32_t* class_index /*B dev*/, const double* table /*n_classes,22 dev*/, int n_classes,
+                                   const double* normals /*B,7 dev*/, const float* K, int width, int height, float border, int B);
+/* The light of toolkit/LM6d_ds_1_gen_observed.py:116-144 for B frames, as deepim_render_observed_forward takes it; the draw id
+ * stands for the frame's running index:
+ *   light_offset[b]     = 0.5 x row (draw id mod 6) of [1,0,1], [1,1,1], [0,1,1], [-1,1,1], [-1,0,1], [0,0,1]; the draw adds
+ *                         (t_x, -t_y, -t_z) of the sample's pose itself (:133-135)
+ *   light_intensity[b]  = colour * (0.9 + 0.2 u[0:3]): stream 6, attempt 0, words 0-2 as uniforms, word 3 mapped to [0, 7) picks
+ *                         the colour row of [0,0,1], [0,1,0], [0,1,1], [1,0,0], [1,0,1], [1,1,0], [1,1,1] (:138-141)
+ *   brightness_ratio[b] = ratios[k], k = word 0 of stream 6, attempt 1 mapped to [0, n_ratios) (:144)
+ * ratios: 1 to 8 HOST floats in [0, 1] (the file's are 0.2, 0.25, 0.3, 0.35, 0.4). All outputs float32, device. */
+int deepim_sample_lights(deepim_ctx* ctx, float* light_offset /*B,3*/, float* light_intensity /*B,3*/,
+                         float* brightness_ratio /*B*/, const float* ratios /*host*/, int n_ratios, unsigned long long seed,
+                         unsigned long long draw_base, const unsigned long long* draw_ids /*B dev or NULL*/, int B);
 
 #ifdef __cplusplus
 }

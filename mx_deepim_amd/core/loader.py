@@ -26,8 +26,20 @@ others with probability TRAIN.REPLACE_OBSERVED_BG_RATIO, on a pool image chosen 
 id), cropped, resized and composited by one kernel (deepim_ingest_bgr8_pool). Like the pose, the background of pair p in epoch
 e depends on (seed, e, p) alone. Without it every batch is what it was before backgrounds existed.
 
+`synthetic`: a lib/utils/synthetic_observed.SyntheticObserved built for the frames' (H, W), or None. With it an epoch is the M·R
+real pairs plus `num_synthetic` fresh synthetic ones (LM6D_REFINE_SYN.py: data_syn = True, mask_idx = 1): n = M·R + S pairs,
+pair p >= M·R being synthetic pair s = p − M·R of class synthetic_classes[s mod len(synthetic_classes)] (default: the classes of
+the observed set, in order). Every pair, real or synthetic, has draw id e·n + p. A synthetic pair's observed pose and light are
+drawn (streams 4-6 of that draw id under the generator's own seed) and its frame is rendered on the device straight into the batch's uint8 / uint16 arrays (deepim_render_observed_forward
+through `rows`), next to the uploaded real rows; its rendered pose is then drawn around that observed pose like any other pair's
+(streams 0/1 of the same draw id). It counts as data_syn: with a pool it always gets a pool background. Its depth_observed is
+its own depth and its mask_idx 1. The synthetic classes are checked against the generator's tables here, on the host, so no
+pair can come out with attempts = −1 and the observed attempts feed deepim_sample_stats_accumulate as they are. Without
+`synthetic` every batch, draw id and byte is what it is without the argument.
+
 Not part of this loader and refused: ready-made backgrounds (bg_image: the pool is the loader's way), TRAIN.MASK_SYN, resizing (a frame that is not config.SCALES[0]),
-shared-frame batches (frame_index), device-resident datasets.
+shared-frame batches (frame_index), device-resident datasets, synthetic frames with more than one object or with occluders
+(LM6D_OCC), and a synthetic set kept across epochs (SyntheticObserved.to_host makes a fixed one for the `observed` argument).
 """
 import numpy as np
 
@@ -36,20 +48,23 @@ from ..lib.pair_matching.pose_sampler import pose_noise, sample_rendered_poses
 from ..lib.utils import image as _image
 from ..lib.utils.background import background_draws_device
 from ..lib.utils.mask_dilate import mask_dilate_draws_device
+from ..lib.utils.synthetic_observed import runs
 from ..runtime import DeviceArray, lib
 
 _DTYPES = {"image_observed": np.uint8, "depth_gt_observed": np.uint16, "mask_gt_observed": np.uint8, "depth_observed": np.uint16}
 
 
-def epoch_plan(M, R, batch_size, shuffle, rng, epoch):
+def epoch_plan(M, R, batch_size, shuffle, rng, epoch, num_synthetic=0):
     """The batches of one epoch over M observed frames with R rendered poses each, no device needed →
     (pairs (n_batches, batch_size) int64, draw_ids (n_batches, batch_size) uint64, dropped).
     pairs holds p = m·R + r in epoch order: arange(M·R), or rng.permutation(M·R) with `shuffle` (rng: a RandomState, consumed
-    once per call); the trailing M·R mod batch_size pairs are dropped. draw_ids = epoch·M·R + pairs."""
-    M, R, batch_size, epoch = int(M), int(R), int(batch_size), int(epoch)
-    if M < 1 or R < 1 or batch_size < 1 or epoch < 0:
-        raise ValueError("epoch_plan: M, R, batch_size must be >= 1 and epoch >= 0")
-    n = M * R
+    once per call); the trailing M·R mod batch_size pairs are dropped. draw_ids = epoch·M·R + pairs.
+    With num_synthetic = S > 0 the epoch has n = M·R + S pairs, p >= M·R being synthetic pair p − M·R, and n stands for M·R
+    in the order, the drop and the draw ids."""
+    M, R, batch_size, epoch, S = int(M), int(R), int(batch_size), int(epoch), int(num_synthetic)
+    if M < 1 or R < 1 or batch_size < 1 or epoch < 0 or S < 0:
+        raise ValueError("epoch_plan: M, R, batch_size must be >= 1 and epoch, num_synthetic >= 0")
+    n = M * R + S
     order = rng.permutation(n).astype(np.int64) if shuffle else np.arange(n, dtype=np.int64)
     n_batches = n // batch_size
     pairs = order[:n_batches * batch_size].reshape(n_batches, batch_size)
@@ -58,7 +73,7 @@ def epoch_plan(M, R, batch_size, shuffle, rng, epoch):
 
 class TrainDataLoader(object):
     def __init__(self, observed, config, render_machine, batch_size=1, shuffle=False, seed=0, num_rendered_per_observed=1,
-                 points=None, noise=None, backgrounds=None, data_syn=None):
+                 points=None, noise=None, backgrounds=None, data_syn=None, synthetic=None, num_synthetic=0, synthetic_classes=None):
         self.config, self.render_machine, self.ctx = config, render_machine, render_machine.ctx
         self.batch_size, self.shuffle, self.seed = int(batch_size), bool(shuffle), int(seed)
         self.R = int(num_rendered_per_observed)
@@ -105,24 +120,42 @@ class TrainDataLoader(object):
         self.pose_observed = np.ascontiguousarray(observed["pose_observed"], dtype=np.float32).reshape(self.M, 3, 4)
         self.mask_idx = np.asarray(observed["mask_idx"]).astype(np.int32).reshape(self.M)
         self.class_index = np.asarray(observed["class_index"]).astype(np.int32).reshape(self.M)
+        self.synthetic, self.S = synthetic, int(num_synthetic) if synthetic is not None else 0
+        if synthetic is None and (num_synthetic or synthetic_classes is not None):
+            raise ValueError("TrainDataLoader: num_synthetic / synthetic_classes need synthetic=SyntheticObserved(...)")
+        self.synthetic_classes = np.zeros(0, np.int32)
+        if synthetic is not None:
+            if self.S < 0:
+                raise ValueError("TrainDataLoader: num_synthetic must be >= 0")
+            if (synthetic.height, synthetic.width) != (H, W):
+                raise ValueError("the synthetic generator draws %dx%d, the frames are %dx%d" % (synthetic.height, synthetic.width, H, W))
+            if synthetic.ctx is not self.ctx:
+                raise ValueError("TrainDataLoader: the synthetic generator lives on another context")
+            classes = sorted(set(self.class_index.tolist())) if synthetic_classes is None else synthetic_classes
+            self.synthetic_classes = np.asarray(classes).astype(np.int32).reshape(-1)
+            if self.S and self.synthetic_classes.size == 0:
+                raise ValueError("TrainDataLoader: synthetic_classes is empty")
+            synthetic.check_classes(self.synthetic_classes)         # on the host: no pair can draw attempts = -1
         self.points = None
         if config.train_iter.SE3_PM_LOSS:
             if points is None:
                 raise ValueError("TrainDataLoader: train_iter.SE3_PM_LOSS needs `points` = {class id: (model points, weights)}")
             self.points = {int(c): (np.ascontiguousarray(p, np.float32), np.ascontiguousarray(w, np.float32)) for c, (p, w) in points.items()}
-            missing = sorted(set(self.class_index.tolist()) - set(self.points))
+            missing = sorted((set(self.class_index.tolist()) | (set(self.synthetic_classes.tolist()) if self.S else set())) - set(self.points))
             if missing:
                 raise KeyError("TrainDataLoader: no model points for class ids {}".format(missing))
-        if self.M * self.R < self.batch_size:
-            raise ValueError("TrainDataLoader: %d pairs do not fill one batch of %d" % (self.M * self.R, self.batch_size))
+        if self.M * self.R + self.S < self.batch_size:
+            raise ValueError("TrainDataLoader: %d pairs do not fill one batch of %d" % (self.M * self.R + self.S, self.batch_size))
         self.K = np.ascontiguousarray(config.dataset.INTRINSIC_MATRIX, np.float32).reshape(3, 3)
         self._rng = np.random.RandomState(self.seed)
-        self._totals = self.ctx.zeros((3,), np.uint64)      # pairs drawn, sum of attempts, exhausted pairs: device-resident
+        # pairs drawn, sum of attempts, exhausted pairs: device-resident; with `synthetic` the same three of the observed-pose draws
+        self._totals = self.ctx.zeros((3,) if synthetic is None else (6,), np.uint64)
         self.epoch = 0
         self._plan()
 
     def _plan(self):
-        self.pairs, self.draw_ids, self.dropped = epoch_plan(self.M, self.R, self.batch_size, self.shuffle, self._rng, self.epoch)
+        self.pairs, self.draw_ids, self.dropped = epoch_plan(self.M, self.R, self.batch_size, self.shuffle, self._rng, self.epoch,
+                                                             self.S)
 
     def __len__(self):
         return len(self.pairs)
@@ -134,34 +167,68 @@ class TrainDataLoader(object):
 
     def stats(self):
         """One read-back: {"pairs": pairs drawn, "attempts": candidates drawn for them, "exhausted": pairs for which none of
-        max_attempts candidates was accepted (they train on a zero delta)} since construction."""
+        max_attempts candidates was accepted (they train on a zero delta)} since construction. With `synthetic`, from the same
+        read-back, also {"observed_pairs", "observed_attempts", "observed_exhausted"}: the synthetic pairs drawn, the observed-pose
+        candidates drawn for them and the pairs that fell back to their class's fallback pose."""
         t = self._totals.asnumpy()
-        return {"pairs": int(t[0]), "attempts": int(t[1]), "exhausted": int(t[2])}
+        out = {"pairs": int(t[0]), "attempts": int(t[1]), "exhausted": int(t[2])}
+        if self.synthetic is not None:
+            out.update(observed_pairs=int(t[3]), observed_attempts=int(t[4]), observed_exhausted=int(t[5]))
+        return out
 
-    def _image_observed(self, frames, m, ids):
+    def _image_observed(self, frames, always, ids):
         """image_observed of the batch; with a background pool, on the backgrounds image.py:96-155 gives it: a data_syn frame
-        always, a real one with probability TRAIN.REPLACE_OBSERVED_BG_RATIO, both from the pair's own draw (stream 3)."""
+        (`always`: the batch's flags, None = none) always, a real one with probability TRAIN.REPLACE_OBSERVED_BG_RATIO, both
+        from the pair's own draw (stream 3)."""
         ctx, means = self.ctx, _image._means_rgb(self.config)
         if self.backgrounds is None:
             return _image.transform_batch(ctx, frames["image_observed"], means)
-        use_bg, bg_index = background_draws_device(ctx, len(m), self.seed, ids, self.bg_ratio, len(self.backgrounds),
-                                                   always=None if self.data_syn is None else self.data_syn[m])
+        use_bg, bg_index = background_draws_device(ctx, ids.size, self.seed, ids, self.bg_ratio, len(self.backgrounds), always=always)
         return _image.transform_batch_pool(ctx, frames["image_observed"], means, frames["mask_gt_observed"], use_bg, bg_index,
                                            self.backgrounds)
 
+    def _upload(self, key, m, real):
+        """The batch's (B,H,W[,3]) device array of observed[key]: row b is frame m[b] where real[b]; the synthetic rows are left
+        for the generator. A batch of real rows is one upload, as without synthetic pairs; else one upload per run of real rows."""
+        src = self.observed[key]
+        if real.all():
+            return self.ctx.array(src[m], dtype=_DTYPES[key])      # 1 or 2 bytes per value cross PCIe
+        out = self.ctx.empty((len(m),) + src.shape[1:], _DTYPES[key])
+        for j0, j1, r0 in runs(np.nonzero(real)[0]):
+            out[r0:r0 + (j1 - j0)].copyfrom(src[m[r0:r0 + (j1 - j0)]])
+        return out
+
     def make_batch(self, pairs, draw_ids):
-        """(data, label) of the given pairs (p = m·R + r) with the given draw ids."""
+        """(data, label) of the given pairs (p = m·R + r, or M·R + s for synthetic pair s) with the given draw ids."""
         ctx, cfg = self.ctx, self.config
-        m = np.asarray(pairs, np.int64) // self.R
+        pairs = np.asarray(pairs, np.int64)
+        real = pairs < self.M * self.R
+        m = np.where(real, pairs // self.R, 0)
         B = len(m)
-        frames = {k: ctx.array(self.observed[k][m], dtype=_DTYPES[k]) for k in self.keys}      # 1 or 2 bytes per value cross PCIe
-        frames["mask_idx"] = ctx.array(self.mask_idx[m], dtype=np.int32)
+        syn = np.nonzero(~real)[0]
+        mask_idx, cls, pose = self.mask_idx[m], self.class_index[m], self.pose_observed[m]
+        always = None if self.data_syn is None else self.data_syn[m]
+        if syn.size:
+            cls_syn = self.synthetic_classes[(pairs[syn] - self.M * self.R) % len(self.synthetic_classes)]
+            mask_idx[syn], cls[syn], pose[syn] = 1, cls_syn, 0.0
+            always = np.zeros(B, bool) if always is None else always.copy()
+            always[syn] = True
+        frames = {k: self._upload(k, m, real) for k in self.keys}
+        frames["mask_idx"] = ctx.array(mask_idx, dtype=np.int32)
         ids = ctx.array(np.asarray(draw_ids).reshape(B), dtype=np.uint64)
-        batch = {"image_observed": self._image_observed(frames, m, ids),
+        pose_observed = ctx.array(pose)
+        if syn.size:      # the synthetic rows: poses, lights and frames made on the device, straight into the batch's arrays
+            drawn = self.synthetic.frames(cls_syn, np.asarray(draw_ids).reshape(B)[syn], rows=syn,
+                                          out=dict(frames, pose_observed=pose_observed))
+            lib.deepim_sample_stats_accumulate(ctx.handle, self._totals[3:6], drawn["attempts"], int(syn.size))
+            if cfg.network.INPUT_DEPTH:       # their depth_observed is their own depth
+                for j0, j1, r0 in runs(syn):
+                    frames["depth_observed"][r0:r0 + (j1 - j0)].copyfrom(frames["depth_gt_observed"][r0:r0 + (j1 - j0)])
+        batch = {"image_observed": self._image_observed(frames, always, ids),
                  "depth_gt_observed": _image._depth(ctx, frames, "depth_gt_observed", cfg),
                  "mask_gt_observed": _image.label_mask(ctx, frames, "mask_gt_observed"),
-                 "pose_observed": ctx.array(self.pose_observed[m]),
-                 "class_index": ctx.array(self.class_index[m], dtype=np.int32)}
+                 "pose_observed": pose_observed,
+                 "class_index": ctx.array(cls, dtype=np.int32)}
         if cfg.network.INPUT_DEPTH:       # get_pair_depth, train phase: zeroed outside the pair's label with MASK_INPUTS
             batch["depth_observed"] = _image._depth(ctx, frames, "depth_observed", cfg,
                                                     "mask_gt_observed" if cfg.network.get("MASK_INPUTS", False) else None)
@@ -172,7 +239,6 @@ class TrainDataLoader(object):
         if cfg.TRAIN.get("MASK_DILATE", False):
             batch["mask_dilate_thickness"] = mask_dilate_draws_device(ctx, B, self.seed, draw_ids=ids)
         if self.points is not None:
-            cls = self.class_index[m]
             batch["point_cloud_model"] = ctx.array(np.stack([self.points[int(c)][0] for c in cls]))
             batch["point_cloud_weights"] = ctx.array(np.stack([self.points[int(c)][1] for c in cls]))
         out = data_pair.get_data_pair_train_batch(batch, cfg)

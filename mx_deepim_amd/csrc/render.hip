@@ -16,6 +16,7 @@
 //             covered pixel on the key (float_bits(Z) << 32 | triangle id) — first triangle wins exact ties
 //   resolve:  one thread per pixel: re-derives the barycentrics of the winning triangle, shades, writes the
 //             network tensors directly: image (B,3,H,W) RGB mean-subtracted, depth (B,1,H,W), 0 = background
+//             (resolve_frames_kernel: the same fragment with a light per sample, stored as uint8 / uint16 frames)
 #include "common.h"
 #include <limits.h>
 
@@ -185,24 +186,34 @@ struct LitParams {
   const float* intensity;  // (B,3) device, or nullptr = (1,1,1)
   Vec3 light_offset;       // 0.5·(0,1,1) in the reference's loops
   float ratio;             // brightness_ratio (0.7)
+  __device__ __forceinline__ float offset(int, int r) const { return light_offset.v[r]; }
+  __device__ __forceinline__ float inten(int b, int c) const { return intensity ? intensity[b * 3 + c] : 1.f; }
+  __device__ __forceinline__ float rat(int) const { return ratio; }
 };
 
-template <class Src>
-__global__ __launch_bounds__(256) void resolve_kernel(float* __restrict__ image, float* __restrict__ depth,
-                                                      unsigned long long* __restrict__ zbuf,
-                                                      const PV* __restrict__ pv_all, Src src, Vec3 means, int H, int W,
-                                                      float znear, float* __restrict__ mask, float mask_thresh,
-                                                      int* __restrict__ box_words, LitParams lit) {
-  const int b = blockIdx.y;
-  const long p = (long)blockIdx.x * 256 + threadIdx.x;
-  const long plane = (long)H * W;
-  const bool inside = p < plane;
-  const unsigned long long key = inside ? zbuf[(long)b * plane + p] : ~0ull;
-  if (inside && key != ~0ull) zbuf[(long)b * plane + p] = ~0ull;      // the z-buffer leaves the call as it entered it: all-ones
+// Light source of deepim_render_observed_forward: every sample has its own light (LM6d_ds_1_gen_observed.py:116-144), three
+// device arrays with one row per sample. b is blockIdx.y, so these are scalar loads.
+struct LitPerSample {
+  const float* poses;      // (B,3,4)
+  const float* off;        // (B,3)
+  const float* intensity;  // (B,3)
+  const float* ratio;      // (B)
+  __device__ __forceinline__ float offset(int b, int r) const { return off[b * 3 + r]; }
+  __device__ __forceinline__ float inten(int b, int c) const { return intensity[b * 3 + c]; }
+  __device__ __forceinline__ float rat(int b) const { return ratio[b]; }
+};
+
+// The fragment of pixel p of sample b from its z-buffer key (hit = the key is not all-ones): depth z (0 = background) and colour
+// levels rgb (the lit stage's are whole numbers in 0..255). One text for every resolve kernel, whatever it stores (tensors or
+// frames) and wherever its light comes from (Lit: LitParams or LitPerSample).
+struct Frag { float rgb[3]; float z; };
+template <class Src, class Lit>
+__device__ __forceinline__ Frag resolve_pixel(bool hit, unsigned long long key, int b, long p, const PV* pv_all,
+                                               const Src& src, int W, float znear, const Lit& lit) {
   float rgb[3] = {0.f, 0.f, 0.f};
   float z = 0.f;
   MeshRef m;
-  if (key != ~0ull && src.mesh(b, m)) {      // only a sample with a mesh ever rasterised a key
+  if (hit && src.mesh(b, m)) {      // only a sample with a mesh ever rasterised a key
     const float* __restrict__ attr = m.attr;
     const float* __restrict__ tex = m.tex;
     const int f = (int)(unsigned)(key & 0xffffffffu);
@@ -239,7 +250,7 @@ __global__ __launch_bounds__(256) void resolve_kernel(float* __restrict__ image,
         const float sgn = r == 0 ? 1.f : -1.f;     // yz_flip of _get_view_mtx
         pos[r] = sgn * ((((P[r * 4] * mp[0] + P[r * 4 + 1] * mp[1]) + P[r * 4 + 2] * mp[2])) + P[r * 4 + 3]);
         nrm[r] = sgn * ((P[r * 4] * mn[0] + P[r * 4 + 1] * mn[1]) + P[r * 4 + 2] * mn[2]);
-        s2l[r] = (lit.light_offset.v[r] + sgn * P[r * 4 + 3]) - pos[r];
+        s2l[r] = (lit.offset(b, r) + sgn * P[r * 4 + 3]) - pos[r];
       }
       const float dotp = (nrm[0] * s2l[0] + nrm[1] * s2l[1]) + nrm[2] * s2l[2];
       const float ls = sqrtf((s2l[0] * s2l[0] + s2l[1] * s2l[1]) + s2l[2] * s2l[2]);
@@ -247,16 +258,37 @@ __global__ __launch_bounds__(256) void resolve_kernel(float* __restrict__ image,
       float br = dotp / (ls * ln);
       br = fmaxf(fminf(br, 1.f), 0.f);             // max(min(x, 1), 0): a NaN (degenerate normal) becomes 0, as in GLSL on most drivers
       if (!(br == br)) br = 0.f;
-      const float shade = (1.f - lit.ratio) + lit.ratio * br;
+      const float ratio = lit.rat(b);
+      const float shade = (1.f - ratio) + ratio * br;
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
-        const float inten = lit.intensity ? lit.intensity[b * 3 + c] : 1.f;
+        const float inten = lit.inten(b, c);
         float col = (rgb[c] / 255.f) * (shade * inten);
         col = fminf(fmaxf(col, 0.f), 1.f);
         rgb[c] = rintf(col * 255.f);               // np.round(rgb * 255).astype(uint8)
       }
     }
   }
+  Frag o;
+  o.rgb[0] = rgb[0]; o.rgb[1] = rgb[1]; o.rgb[2] = rgb[2]; o.z = z;
+  return o;
+}
+
+template <class Src>
+__global__ __launch_bounds__(256) void resolve_kernel(float* __restrict__ image, float* __restrict__ depth,
+                                                      unsigned long long* __restrict__ zbuf,
+                                                      const PV* __restrict__ pv_all, Src src, Vec3 means, int H, int W,
+                                                      float znear, float* __restrict__ mask, float mask_thresh,
+                                                      int* __restrict__ box_words, LitParams lit) {
+  const int b = blockIdx.y;
+  const long p = (long)blockIdx.x * 256 + threadIdx.x;
+  const long plane = (long)H * W;
+  const bool inside = p < plane;
+  const unsigned long long key = inside ? zbuf[(long)b * plane + p] : ~0ull;
+  const bool hit = key != ~0ull;
+  if (inside && hit) zbuf[(long)b * plane + p] = ~0ull;      // the z-buffer leaves the call as it entered it: all-ones
+  const Frag fr = resolve_pixel(hit, key, b, p, pv_all, src, W, znear, lit);
+  const float* rgb = fr.rgb; const float z = fr.z;
   if (inside) {
 #pragma unroll
     for (int c = 0; c < 3; ++c) image[((long)b * 3 + c) * plane + p] = rgb[c] - means.v[c];
@@ -282,17 +314,91 @@ __global__ __launch_bounds__(256) void resolve_kernel(float* __restrict__ image,
   }
 }
 
+// Destination of deepim_render_observed_forward: decoded frames as lib/utils/image.py reads them from the PNGs of
+// LM6d_ds_1_gen_observed.py:149-159, sample b in row rows[b] (nullptr: b) of N rows. 6 bytes per pixel.
+struct FrameOut {
+  unsigned char* image;         // (N,H,W,3) BGR levels
+  unsigned short* depth;        // (N,H,W) (uint16)(depth * depth_factor), the float32 product truncated
+  unsigned char* label;         // (N,H,W) label_value[b] where depth != 0, else 0
+  const int* rows;              // (B) or nullptr
+  const int* label_value;       // (B) or nullptr = 1
+  float depth_factor;
+  int N;
+};
+
+// Resolve pass of the frame draw: lane g of a sample owns the PX consecutive pixels PX g .. PX g + PX - 1.
+// PX = 4 (the plane is a multiple of 4 pixels and the three outputs are 8-byte aligned): the lane stores its 12 image bytes as
+// three dwords, its four depths as one 8-byte store and its four labels as one dword, so a wave writes 768 + 512 + 256
+// contiguous bytes with no partial dwords. PX = 1: single byte / short stores, any size. A sample whose row is outside [0, N)
+// stores nothing; its z-buffer entries are still put back.
+template <class Src, int PX>
+__global__ __launch_bounds__(256) void resolve_frames_kernel(FrameOut out, unsigned long long* __restrict__ zbuf,
+                                                             const PV* __restrict__ pv_all, Src src, int H, int W, float znear,
+                                                             LitPerSample lit) {
+  const int b = blockIdx.y;
+  const long plane = (long)H * W;
+  const long p0 = ((long)blockIdx.x * 256 + threadIdx.x) * PX;
+  if (p0 >= plane) return;                       // PX = 4: plane % 4 == 0, so a lane owns four pixels or none
+  const int row = out.rows ? out.rows[b] : b;
+  const bool store = (unsigned)row < (unsigned)out.N;
+  const unsigned lab = (unsigned)(out.label_value ? out.label_value[b] : 1) & 0xffu;
+  unsigned long long* zb = zbuf + (long)b * plane + p0;
+  unsigned bgr[PX * 3], d16[PX], l8[PX];
+  unsigned long long keys[PX];
+  if constexpr (PX == 4) {                       // the lane's four keys are 32 contiguous, 32-byte aligned bytes: two 16-byte loads
+    const ulonglong2 k01 = reinterpret_cast<const ulonglong2*>(zb)[0], k23 = reinterpret_cast<const ulonglong2*>(zb)[1];
+    keys[0] = k01.x; keys[1] = k01.y; keys[2] = k23.x; keys[3] = k23.y;
+    if ((k01.x & k01.y & k23.x & k23.y) != ~0ull) {      // the z-buffer leaves the call as it entered it: all-ones
+      const ulonglong2 ones = {~0ull, ~0ull};
+      reinterpret_cast<ulonglong2*>(zb)[0] = ones;
+      reinterpret_cast<ulonglong2*>(zb)[1] = ones;
+    }
+  } else {
+    keys[0] = zb[0];
+    if (keys[0] != ~0ull) zb[0] = ~0ull;
+  }
+#pragma unroll
+  for (int i = 0; i < PX; ++i) {
+    const unsigned long long key = keys[i];
+    const bool hit = key != ~0ull;
+    const Frag fr = resolve_pixel(hit, key, b, p0 + i, pv_all, src, W, znear, lit);
+    const float* rgb = fr.rgb; const float z = fr.z;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) bgr[i * 3 + c] = (unsigned)(int)rgb[2 - c];      // whole numbers in 0..255 from the lit stage
+    d16[i] = (unsigned)(int)(z * out.depth_factor) & 0xffffu;
+    l8[i] = z != 0.f ? lab : 0u;
+  }
+  if (!store) return;
+  const long q = (long)row * plane + p0;
+  if constexpr (PX == 4) {
+    uint3 w;
+    w.x = bgr[0] | bgr[1] << 8 | bgr[2] << 16 | bgr[3] << 24;
+    w.y = bgr[4] | bgr[5] << 8 | bgr[6] << 16 | bgr[7] << 24;
+    w.z = bgr[8] | bgr[9] << 8 | bgr[10] << 16 | bgr[11] << 24;
+    unsigned* img = reinterpret_cast<unsigned*>(out.image + q * 3);
+    img[0] = w.x; img[1] = w.y; img[2] = w.z;
+    uint2 d;
+    d.x = d16[0] | d16[1] << 16;
+    d.y = d16[2] | d16[3] << 16;
+    *reinterpret_cast<uint2*>(out.depth + q) = d;
+    *reinterpret_cast<unsigned*>(out.label + q) = l8[0] | l8[1] << 8 | l8[2] << 16 | l8[3] << 24;
+  } else {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) out.image[q * 3 + c] = (unsigned char)bgr[c];
+    out.depth[q] = (unsigned short)d16[0];
+    out.label[q] = (unsigned char)l8[0];
+  }
+}
+
 }  // namespace
 
-// The launch group of every entry: project (grid (ceil(max_V/256), B)), raster (grid (ceil(max_F/256), B)), resolve, box fill.
-// max_V / max_F: the largest mesh `src` can select; the projected-vertex scratch is B x max_V records.
+// The front of every entry's launch group: project (grid (ceil(max_V/256), B)) and raster (grid (ceil(max_F/256), B)) into the
+// context's z-buffer, which is left dirty: the caller launches a resolve pass next and clears ctx->zbuf_dirty.
+// max_V / max_F: the largest mesh `src` can select; the projected-vertex scratch (*pv_out) is B x max_V records.
 template <class Src>
-static int render_launch(deepim_ctx* ctx, float* image, float* depth, float* mask, float* mask_box, float mask_thresh,
-                         const Src& src, int max_V, int max_F, const float* poses, const float* K_host,
-                         const float* pixel_means_host, int B, int H, int W, float znear, float zfar,
-                         const float* light_offset_host, const float* light_intensity, float ratio) {
+static int render_front(deepim_ctx* ctx, const Src& src, int max_V, int max_F, const float* poses, const float* K_host, int B, int H,
+                        int W, float znear, float zfar, int* words, PV** pv_out) {
   DI_REQUIRE(znear > 0.f && zfar > znear, "render: need 0 < zNear < zFar");
-  DI_REQUIRE(mask_box == nullptr || (mask != nullptr && B <= DI_MAX_BOX_SAMPLES), "render: mask_box needs mask, B <= 4096");
   const size_t zbytes = (size_t)B * H * W * sizeof(unsigned long long);
   const size_t pbytes = (size_t)B * max_V * sizeof(PV);
   void* scratch;
@@ -314,20 +420,34 @@ static int render_launch(deepim_ctx* ctx, float* image, float* depth, float* mas
     DI_CHECK(hipMemsetAsync(ctx->zbuf, 0xff, ctx->zbuf_bytes, ctx->stream));
     ctx->zbuf_dirty = 0;
   }
-  unsigned long long* zbuf = ctx->zbuf;
   PV* pv = (PV*)scratch;
   Mat3 K;
   for (int i = 0; i < 9; ++i) K.v[i] = K_host[i];
+  hipLaunchKernelGGL(project_kernel<Src>, dim3(di_div_up(max_V, 256), B), dim3(256), 0, ctx->stream, pv, src, poses, K, words);
+  DI_LAUNCH_CHECK();
+  ctx->zbuf_dirty = 1;
+  hipLaunchKernelGGL(raster_kernel<Src>, dim3(di_div_up(max_F, 256), B), dim3(256), 0, ctx->stream, ctx->zbuf, pv, src, H, W, znear,
+                     zfar);
+  *pv_out = pv;
+  return 0;
+}
+
+// The launch group of the tensor entries: the front, resolve, box fill.
+template <class Src>
+static int render_launch(deepim_ctx* ctx, float* image, float* depth, float* mask, float* mask_box, float mask_thresh,
+                         const Src& src, int max_V, int max_F, const float* poses, const float* K_host,
+                         const float* pixel_means_host, int B, int H, int W, float znear, float zfar,
+                         const float* light_offset_host, const float* light_intensity, float ratio) {
+  DI_REQUIRE(mask_box == nullptr || (mask != nullptr && B <= DI_MAX_BOX_SAMPLES), "render: mask_box needs mask, B <= 4096");
   Vec3 means = {{0, 0, 0}};
   if (pixel_means_host) for (int i = 0; i < 3; ++i) means.v[i] = pixel_means_host[i];
   int* words = mask_box ? ctx->box_words : nullptr;
   LitParams lit = {poses, light_intensity, {{0, 0, 0}}, ratio};
   if (light_offset_host) for (int i = 0; i < 3; ++i) lit.light_offset.v[i] = light_offset_host[i];
-  hipLaunchKernelGGL(project_kernel<Src>, dim3(di_div_up(max_V, 256), B), dim3(256), 0, ctx->stream, pv, src, poses, K, words);
-  DI_LAUNCH_CHECK();
-  ctx->zbuf_dirty = 1;
-  hipLaunchKernelGGL(raster_kernel<Src>, dim3(di_div_up(max_F, 256), B), dim3(256), 0, ctx->stream, zbuf, pv, src, H, W, znear,
-                     zfar);
+  PV* pv;
+  int rc = render_front(ctx, src, max_V, max_F, poses, K_host, B, H, W, znear, zfar, words, &pv);
+  if (rc) return rc;
+  unsigned long long* zbuf = ctx->zbuf;
   hipLaunchKernelGGL(resolve_kernel<Src>, dim3(di_div_up((long)H * W, 256), B), dim3(256), 0, ctx->stream, image, depth, zbuf,
                      pv, src, means, H, W, znear, mask, mask_thresh, words, lit);
   DI_LAUNCH_CHECK();
@@ -412,4 +532,41 @@ extern "C" int deepim_render_classes_forward(deepim_ctx* ctx, float* image, floa
                          textures, n_classes, max_V, max_F};
   return render_launch(ctx, image, depth, mask_rendered, mask_box, mask_thresh, src, max_V, max_F, poses, K_host,
                        pixel_means_host, B, H, W, znear, zfar, light_offset_host, light_intensity, brightness_ratio);
+}
+
+// The mesh-table draw, lit, with one light per sample, written as decoded frames (layout: include/deepim_hip.h).
+extern "C" int deepim_render_observed_forward(deepim_ctx* ctx, uint8_t* image, uint16_t* depth, uint8_t* label, const int32_t* rows,
+                                              int N, const int32_t* label_value, float depth_factor, const int32_t* class_index,
+                                              const int32_t* mesh_desc, int n_classes, int max_V, int max_F, const float* vertices,
+                                              const float* vertex_attr, const float* normals, const int32_t* faces,
+                                              const float* textures, const float* poses, const float* K_host,
+                                              const float* light_offset, const float* light_intensity,
+                                              const float* brightness_ratio, int B, int H, int W, float znear, float zfar) {
+  DI_DEVICE(ctx);
+  DI_REQUIRE(B >= 0 && N >= B, "render_observed: the outputs need N >= B >= 0 rows");
+  if (B == 0) return 0;
+  DI_REQUIRE(n_classes > 0 && max_V > 0 && max_F > 0 && H > 0 && W > 0, "render_observed: empty mesh table or image");
+  DI_REQUIRE(image && depth && label, "render_observed: image, depth and label are required");
+  DI_REQUIRE(class_index != nullptr && mesh_desc != nullptr, "render_observed: class_index and mesh_desc are required");
+  DI_REQUIRE(normals != nullptr && light_offset != nullptr && light_intensity != nullptr && brightness_ratio != nullptr,
+             "render_observed: the lit draw needs normals and the three per-sample light arrays");
+  DI_REQUIRE(depth_factor > 0.f && zfar * depth_factor < 65536.f, "render_observed: zFar * depth_factor must stay below 65536");
+  const MeshTable src = {(const int*)class_index, (const int*)mesh_desc, vertices, vertex_attr, normals, (const int*)faces,
+                         textures, n_classes, max_V, max_F};
+  PV* pv;
+  int rc = render_front(ctx, src, max_V, max_F, poses, K_host, B, H, W, znear, zfar, nullptr, &pv);
+  if (rc) return rc;
+  const FrameOut out = {image, depth, label, (const int*)rows, (const int*)label_value, depth_factor, N};
+  const LitPerSample lit = {poses, light_offset, light_intensity, brightness_ratio};
+  const long plane = (long)H * W;
+  const bool quad = plane % 4 == 0 && (((uintptr_t)image | (uintptr_t)depth | (uintptr_t)label) & 7) == 0;
+  if (quad)
+    hipLaunchKernelGGL((resolve_frames_kernel<MeshTable, 4>), dim3(di_div_up(plane / 4, 256), B), dim3(256), 0, ctx->stream, out,
+                       ctx->zbuf, pv, src, H, W, znear, lit);
+  else
+    hipLaunchKernelGGL((resolve_frames_kernel<MeshTable, 1>), dim3(di_div_up(plane, 256), B), dim3(256), 0, ctx->stream, out,
+                       ctx->zbuf, pv, src, H, W, znear, lit);
+  DI_LAUNCH_CHECK();
+  ctx->zbuf_dirty = 0;
+  return 0;
 }

@@ -3,9 +3,12 @@
 //   the rendered-pose rule of toolkit/LM6d_1_gen_rendered_pose.py:80-107 on top of it
 //   the draws of lib/utils/mask_dilate.py:19-47
 //   the background draws of lib/utils/image.py:97-116
+//   the synthetic observed poses of toolkit/LM6d_ds_0_gen_observed_poses.py:200-250 and the lights of
+//   toolkit/LM6d_ds_1_gen_observed.py:116-144
 //
 // Every draw is a pure function of (seed, draw id, attempt, stream): key = (seed lo, seed hi), counter = (id lo, id hi, attempt,
-// stream). Streams 0 and 1 are the two blocks of a pose draw, stream 2 is the mask-dilate draw, stream 3 the background draw.
+// stream). Streams 0 and 1 are the two blocks of a pose draw, stream 2 is the mask-dilate draw, stream 3 the background draw,
+// streams 4 and 5 the quaternion and translation blocks of an observed-pose draw, stream 6 the light draw.
 // Nothing depends on the batch size, on a pair's position in the batch or on the order of launches.
 //
 // The kernels run one thread per pair; every array below is indexed by constants after unrolling, so nothing lives in
@@ -251,6 +254,197 @@ __global__ __launch_bounds__(256) void sample_stats_kernel(unsigned long long* _
   }
 }
 
+// ---- synthetic observed frames: the pose of LM6d_ds_0_gen_observed_poses.py and the light of LM6d_ds_1_gen_observed.py
+
+constexpr int OBS_ROW = 22;      // a class's row: trans_mean[3], trans_std[3], pz_mean[3], angle_max (degrees), fallback pose [12]
+
+struct ObservedRule {
+  Mat3 K;
+  float border;
+  int width, height;
+};
+
+// the seven normals of one candidate: stream 4 gives z0..z3 (the quaternion), stream 5 z4..z6 (the translation; the second
+// normal of its second pair is not used)
+__device__ __forceinline__ void observed_normals(unsigned long long seed, unsigned long long id, unsigned int attempt, double* z) {
+  const Philox4 a = philox_draw(seed, id, attempt, 4u);
+  const Philox4 b = philox_draw(seed, id, attempt, 5u);
+  double unused;
+  box_muller(a.w[0], a.w[1], z[0], z[1]);
+  box_muller(a.w[2], a.w[3], z[2], z[3]);
+  box_muller(b.w[0], b.w[1], z[4], z[5]);
+  box_muller(b.w[2], b.w[3], z[6], unused);
+}
+
+// One candidate of LM6d_ds_0_gen_observed_poses.py:203-220 from given normals, in float64:
+//   tgt_quat = z[0:4] / |z[0:4]|, negated if w < 0      tgt_trans = trans_mean + z[4:7] trans_std (np.random.normal(mean, std))
+//   R = quat2mat(tgt_quat) in the expression order of RT_transform.quat2mat
+//   deg = angle(R e_z, pz_mean) as :74-78: arccos(clip(u.v / (|u| |v|), -1, 1)) in degrees
+//   (cx, cy) = the projection of tgt_trans through K
+//   accept iff deg <= angle_max and border < cx < W - border and border < cy < H - border and tgt_trans.z > 0
+// The z > 0 clause is not the reference's, which divides by z unguarded (as in pose_perturb_one).
+// row: the class's table row; pose: the candidate [R | t] in double (12); stat: deg, cx, cy. Returns the accept flag.
+__device__ __forceinline__ bool observed_pose_one(const double* __restrict__ row, const double* z, const ObservedRule& p, double* pose,
+                                                  double* stat) {
+  const double n = sqrt(((z[0] * z[0] + z[1] * z[1]) + z[2] * z[2]) + z[3] * z[3]);
+  double w = z[0] / n, x = z[1] / n, y = z[2] / n, q = z[3] / n;
+  if (w < 0.0) { w = -w; x = -x; y = -y; q = -q; }
+  const double Nq = ((w * w + x * x) + y * y) + q * q;
+  double R[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
+  if (!(Nq < 2.220446049250313e-16)) {
+    const double s = 2.0 / Nq;
+    const double X = x * s, Y = y * s, Z = q * s;
+    const double wX = w * X, wY = w * Y, wZ = w * Z;
+    const double xX = x * X, xY = x * Y, xZ = x * Z;
+    const double yY = y * Y, yZ = y * Z, zZ = q * Z;
+    R[0] = 1.0 - (yY + zZ); R[1] = xY - wZ; R[2] = xZ + wY;
+    R[3] = xY + wZ; R[4] = 1.0 - (xX + zZ); R[5] = yZ - wX;
+    R[6] = xZ - wY; R[7] = yZ + wX; R[8] = 1.0 - (xX + yY);
+  }
+  const double tx = row[0] + z[4] * row[3];
+  const double ty = row[1] + z[5] * row[4];
+  const double tz = row[2] + z[6] * row[5];
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) pose[i * 4 + j] = R[i * 3 + j];
+  pose[3] = tx; pose[7] = ty; pose[11] = tz;
+  const double ux = R[2], uy = R[5], uz = R[8], vx = row[6], vy = row[7], vz = row[8];
+  const double c = ((ux * vx + uy * vy) + uz * vz) / (sqrt((ux * ux + uy * uy) + uz * uz) * sqrt((vx * vx + vy * vy) + vz * vz));
+  const double deg = acos(fmin(fmax(c, -1.0), 1.0)) / 3.141592653589793 * 180.0;      // a NaN (zero pz_mean) stays NaN: rejected
+  const double px = ((double)p.K.v[0] * tx + (double)p.K.v[1] * ty) + (double)p.K.v[2] * tz;
+  const double py = ((double)p.K.v[3] * tx + (double)p.K.v[4] * ty) + (double)p.K.v[5] * tz;
+  const double pz = ((double)p.K.v[6] * tx + (double)p.K.v[7] * ty) + (double)p.K.v[8] * tz;
+  const double cx = px / pz, cy = py / pz;
+  stat[0] = c == c ? deg : c; stat[1] = cx; stat[2] = cy;
+  const double lo = (double)p.border;
+  return c == c && deg <= row[9] && lo < cx && cx < (double)p.width - lo && lo < cy && cy < (double)p.height - lo && tz > 0.0;
+}
+
+// The candidate of GIVEN normals for every pair, accepted or not (the replay of a golden run). A class id outside the table:
+// zeros in pose_out and stat_out.
+__global__ __launch_bounds__(256) void observed_pose_kernel(float* __restrict__ pose_out, double* __restrict__ stat_out,
+                                                            const int* __restrict__ class_index, const double* __restrict__ table,
+                                                            int n_classes, const double* __restrict__ normals, ObservedRule p, int B) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= B) return;
+  const int cls = class_index[b];
+  double z[7], pose[12], stat[3];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) pose[i] = 0.0;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) stat[i] = 0.0;
+  bool ok = false;
+  if ((unsigned)cls < (unsigned)n_classes) {
+#pragma unroll
+    for (int i = 0; i < 7; ++i) z[i] = normals[(long)b * 7 + i];
+    ok = observed_pose_one(table + (long)cls * OBS_ROW, z, p, pose, stat);
+  }
+#pragma unroll
+  for (int i = 0; i < 12; ++i) pose_out[(long)b * 12 + i] = (float)pose[i];
+  if (stat_out) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) stat_out[(long)b * 4 + i] = stat[i];
+    stat_out[(long)b * 4 + 3] = ok ? 1.0 : 0.0;
+  }
+}
+
+// The attempt loop of LM6d_ds_0_gen_observed_poses.py:203-236 with a bound: the first accepted candidate of attempts
+// 0 .. max_attempts-1, attempts[b] = candidates drawn (1 .. max_attempts). None accepted: the class's fallback pose,
+// attempts[b] = 0, zeros in normals_out and stat_out (the reference loops for ever there). A class id outside the table:
+// an all-zero pose and attempts[b] = -1; the table is not read.
+__global__ __launch_bounds__(256) void sample_observed_poses_kernel(float* __restrict__ pose_out, int* __restrict__ attempts,
+                                                                    double* __restrict__ normals_out, double* __restrict__ stat_out,
+                                                                    const int* __restrict__ class_index,
+                                                                    const double* __restrict__ table, int n_classes, ObservedRule p,
+                                                                    int max_attempts, unsigned long long seed,
+                                                                    unsigned long long draw_base,
+                                                                    const unsigned long long* __restrict__ draw_ids, int B) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= B) return;
+  const unsigned long long id = draw_ids ? draw_ids[b] : draw_base + (unsigned long long)b;
+  const int cls = class_index[b];
+  const bool known = (unsigned)cls < (unsigned)n_classes;
+  const double* __restrict__ row = table + (long)(known ? cls : 0) * OBS_ROW;
+  float out[12];
+  double zk[7], sk[4];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) out[i] = known ? (float)row[10 + i] : 0.f;
+#pragma unroll
+  for (int i = 0; i < 7; ++i) zk[i] = 0.0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) sk[i] = 0.0;
+  int used = known ? 0 : -1;
+  for (int a = 0; known && a < max_attempts; ++a) {
+    double z[7], pose[12], stat[3];
+    observed_normals(seed, id, (unsigned int)a, z);
+    if (observed_pose_one(row, z, p, pose, stat)) {
+#pragma unroll
+      for (int i = 0; i < 12; ++i) out[i] = (float)pose[i];
+#pragma unroll
+      for (int i = 0; i < 7; ++i) zk[i] = z[i];
+#pragma unroll
+      for (int i = 0; i < 3; ++i) sk[i] = stat[i];
+      sk[3] = 1.0;
+      used = a + 1;
+      break;
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 12; ++i) pose_out[(long)b * 12 + i] = out[i];
+  attempts[b] = used;
+  if (normals_out) {
+#pragma unroll
+    for (int i = 0; i < 7; ++i) normals_out[(long)b * 7 + i] = zk[i];
+  }
+  if (stat_out) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) stat_out[(long)b * 4 + i] = sk[i];
+  }
+}
+
+struct Ratios { float v[8]; };
+
+// The light of LM6d_ds_1_gen_observed.py:116-144 for the frame whose running index is the draw id:
+//   light_offset = 0.5 x row (id mod 6) of [1,0,1], [1,1,1], [0,1,1], [-1,1,1], [-1,0,1], [0,0,1]   (:117-131; the absolute
+//       position of :133-135 adds (t_x, -t_y, -t_z), which the lit draw does itself)
+//   stream 6, attempt 0: words 0-2 -> intensity[c] = 0.9 + 0.2 u (np.random.uniform(0.9, 1.1), :139); word 3 -> one of the seven
+//       colour rows [0,0,1] .. [1,1,1] (:138,140), row k being the bits of k + 1; light_intensity = colour * intensity (:141)
+//   stream 6, attempt 1: word 0 -> one of the n_ratios brightness ratios (:144)
+__global__ __launch_bounds__(256) void sample_lights_kernel(float* __restrict__ light_offset, float* __restrict__ light_intensity,
+                                                            float* __restrict__ brightness_ratio, Ratios ratios, int n_ratios,
+                                                            unsigned long long seed, unsigned long long draw_base,
+                                                            const unsigned long long* __restrict__ draw_ids, int B) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= B) return;
+  const unsigned long long id = draw_ids ? draw_ids[b] : draw_base + (unsigned long long)b;
+  const int m = (int)(id % 6ull);
+  light_offset[(long)b * 3 + 0] = 0.5f * (m < 2 ? 1.f : (m == 2 || m == 5) ? 0.f : -1.f);
+  light_offset[(long)b * 3 + 1] = 0.5f * ((m >= 1 && m <= 3) ? 1.f : 0.f);
+  light_offset[(long)b * 3 + 2] = 0.5f;
+  const Philox4 c0 = philox_draw(seed, id, 0u, 6u);
+  const Philox4 c1 = philox_draw(seed, id, 1u, 6u);
+  const int colour = word_below(c0.w[3], 7) + 1;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const double inten = 0.9 + 0.2 * word_uniform(c0.w[c]);
+    light_intensity[(long)b * 3 + c] = ((colour >> (2 - c)) & 1) ? (float)inten : 0.f;
+  }
+  const int k = word_below(c1.w[0], n_ratios);
+  float r = ratios.v[0];
+#pragma unroll
+  for (int i = 1; i < 8; ++i) r = k == i ? ratios.v[i] : r;
+  brightness_ratio[b] = r;
+}
+
+int observed_rule_from(ObservedRule* p, const float* K_host, int width, int height, float border) {
+  DI_REQUIRE(K_host, "observed poses: K is a host array, not NULL");
+  for (int i = 0; i < 9; ++i) p->K.v[i] = K_host[i];
+  DI_REQUIRE(width > 0 && height > 0, "observed poses: width and height must be positive");
+  p->border = border; p->width = width; p->height = height;
+  return 0;
+}
+
 int pose_noise_from(PoseNoise* p, const float* K_host, const float* noise_host, int width, int height, float border) {
   DI_REQUIRE(K_host && noise_host, "pose sampler: K and noise are host arrays, not NULL");
   for (int i = 0; i < 9; ++i) p->K.v[i] = K_host[i];
@@ -330,6 +524,57 @@ extern "C" int deepim_sample_backgrounds(deepim_ctx* ctx, int32_t* use_bg, int32
   DI_REQUIRE(use_bg && bg_index, "sample_backgrounds: NULL argument");
   hipLaunchKernelGGL(sample_backgrounds_kernel, dim3(di_div_up(B, 256)), dim3(256), 0, ctx->stream, use_bg, bg_index, always, ratio,
                      pool_size, seed, draw_base, draw_ids, B);
+  DI_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int deepim_observed_pose_candidate(deepim_ctx* ctx, float* pose_out, double* stat_out, const int32_t* class_index,
+                                              const double* table, int n_classes, const double* normals, const float* K, int width,
+                                              int height, float border, int B) {
+  DI_DEVICE(ctx);
+  DI_REQUIRE(B >= 0, "observed_pose_candidate: B must be >= 0");
+  DI_REQUIRE(n_classes >= 1, "observed_pose_candidate: n_classes must be >= 1");
+  ObservedRule p;
+  if (observed_rule_from(&p, K, width, height, border)) return -1;
+  if (B == 0) return 0;
+  DI_REQUIRE(pose_out && class_index && table && normals, "observed_pose_candidate: NULL argument");
+  hipLaunchKernelGGL(observed_pose_kernel, dim3(di_div_up(B, 256)), dim3(256), 0, ctx->stream, pose_out, stat_out,
+                     (const int*)class_index, table, n_classes, normals, p, B);
+  DI_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int deepim_sample_observed_poses(deepim_ctx* ctx, float* pose_out, int32_t* attempts, double* normals_out, double* stat_out,
+                                            const int32_t* class_index, const double* table, int n_classes, const float* K, int width,
+                                            int height, float border, int max_attempts, unsigned long long seed,
+                                            unsigned long long draw_base, const unsigned long long* draw_ids, int B) {
+  DI_DEVICE(ctx);
+  DI_REQUIRE(B >= 0, "sample_observed_poses: B must be >= 0");
+  DI_REQUIRE(max_attempts >= 1, "sample_observed_poses: max_attempts must be >= 1");
+  DI_REQUIRE(n_classes >= 1, "sample_observed_poses: n_classes must be >= 1");
+  ObservedRule p;
+  if (observed_rule_from(&p, K, width, height, border)) return -1;
+  if (B == 0) return 0;
+  DI_REQUIRE(pose_out && attempts && class_index && table, "sample_observed_poses: NULL argument");
+  hipLaunchKernelGGL(sample_observed_poses_kernel, dim3(di_div_up(B, 256)), dim3(256), 0, ctx->stream, pose_out, (int*)attempts,
+                     normals_out, stat_out, (const int*)class_index, table, n_classes, p, max_attempts, seed, draw_base, draw_ids, B);
+  DI_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int deepim_sample_lights(deepim_ctx* ctx, float* light_offset, float* light_intensity, float* brightness_ratio,
+                                    const float* ratios_host, int n_ratios, unsigned long long seed, unsigned long long draw_base,
+                                    const unsigned long long* draw_ids, int B) {
+  DI_DEVICE(ctx);
+  DI_REQUIRE(B >= 0, "sample_lights: B must be >= 0");
+  DI_REQUIRE(ratios_host && n_ratios >= 1 && n_ratios <= 8, "sample_lights: 1 to 8 brightness ratios, a host array");
+  Ratios r;
+  for (int i = 0; i < 8; ++i) r.v[i] = i < n_ratios ? ratios_host[i] : 0.f;
+  for (int i = 0; i < n_ratios; ++i) DI_REQUIRE(r.v[i] >= 0.f && r.v[i] <= 1.f, "sample_lights: brightness ratios in [0, 1]");
+  if (B == 0) return 0;
+  DI_REQUIRE(light_offset && light_intensity && brightness_ratio, "sample_lights: NULL argument");
+  hipLaunchKernelGGL(sample_lights_kernel, dim3(di_div_up(B, 256)), dim3(256), 0, ctx->stream, light_offset, light_intensity,
+                     brightness_ratio, r, n_ratios, seed, draw_base, draw_ids, B);
   DI_LAUNCH_CHECK();
   return 0;
 }

@@ -63,3 +63,84 @@ def sample_rendered_poses(pose_observed, K, width, height, seed, draw_base=0, dr
                                      ctypes.c_float(n["border"]), int(n["max_attempts"]), ctypes.c_ulonglong(int(seed) & U64),
                                      ctypes.c_ulonglong(int(draw_base) & U64), device_draw_ids(ctx, draw_ids, B), B)
     return (pose, attempts, normals) if with_normals else (pose, attempts)
+
+
+# ---- synthetic observed poses: toolkit/LM6d_ds_0_gen_observed_poses.py ------------------------------------------------------
+OBSERVED_TABLE_COLUMNS = 22      # trans_mean[3], trans_std[3], pz_mean[3], angle_max (degrees), fallback pose [12]
+BRIGHTNESS_RATIOS = (0.2, 0.25, 0.3, 0.35, 0.4)      # toolkit/LM6d_ds_1_gen_observed.py:86
+
+
+def _angle(u, v):
+    """LM6d_ds_0_gen_observed_poses.py:74-78."""
+    c = np.dot(u, v) / (np.linalg.norm(u) * np.linalg.norm(v))
+    return np.arccos(np.clip(c, -1, 1)) / np.pi * 180
+
+
+def observed_pose_stats(poses_by_class):
+    """stat_poses() of LM6d_ds_0_gen_observed_poses.py:81-180 in float64 numpy, no device needed. poses_by_class: {class id:
+    (n,3,4) training poses} -> {class id: dict(trans_mean (3), trans_std (3) (np.std: population), pz_mean (3) = the mean of
+    R e_z, angle_max = the largest angle in degrees of any training pose's R e_z to pz_mean, fallback (3,4) = the training pose
+    whose R e_z is closest to pz_mean (what an exhausted draw falls back to; the toolkit loops for ever instead))}."""
+    out = {}
+    for c, poses in poses_by_class.items():
+        poses = np.asarray(poses, np.float64).reshape(-1, 3, 4)
+        if len(poses) == 0:
+            raise ValueError("observed_pose_stats: class {} has no poses".format(c))
+        pz = np.dot(poses[:, :, :3], np.array([0.0, 0.0, 1.0]))
+        pz_mean = np.mean(pz, 0)
+        deg = np.array([_angle(pz_mean, p) for p in pz])
+        out[c] = {"trans_mean": np.mean(poses[:, :, 3], 0), "trans_std": np.std(poses[:, :, 3], 0), "pz_mean": pz_mean,
+                  "angle_max": float(np.max(deg)), "fallback": poses[int(np.argmin(deg))].copy()}
+    return out
+
+
+def pack_observed_table(stats, n_classes=None):
+    """The device table of deepim_sample_observed_poses: (n_classes, 22) float64, row c = stats[c] (trans_mean, trans_std,
+    pz_mean, angle_max, fallback rounded to float32). A class without stats gets angle_max = -1 and a zero fallback: every
+    candidate is rejected and its pairs come out exhausted, on a zero pose."""
+    n = (max(stats) + 1) if n_classes is None else int(n_classes)
+    table = np.zeros((n, OBSERVED_TABLE_COLUMNS), np.float64)
+    table[:, 9] = -1.0
+    for c, s in stats.items():
+        if not 0 <= int(c) < n:
+            raise ValueError("pack_observed_table: class id {} outside [0, {})".format(c, n))
+        if np.any(np.asarray(s["trans_std"], np.float64) < 0):
+            raise ValueError("pack_observed_table: trans_std must be >= 0")
+        table[int(c)] = np.concatenate([np.asarray(s["trans_mean"], np.float64).reshape(3), np.asarray(s["trans_std"], np.float64).reshape(3),
+                                        np.asarray(s["pz_mean"], np.float64).reshape(3), [float(s["angle_max"])],
+                                        np.asarray(s["fallback"], np.float32).astype(np.float64).reshape(12)])
+    return table
+
+
+def sample_observed_poses(class_index, table, K, width, height, seed, draw_base=0, draw_ids=None, border=48.0, max_attempts=100,
+                          with_normals=False, with_stat=False):
+    """class_index: device (B) int32; table: device (n_classes,22) float64 (pack_observed_table); K: host 3x3.
+    -> (pose_observed (B,3,4) float32, attempts (B) int32 [, normals (B,7) float64] [, stat (B,4) float64]), device arrays.
+    attempts[b]: the candidates drawn; 0 = none accepted (the pose is the class's fallback); -1 = class id outside the table (a
+    zero pose, which the render machine draws as an empty frame). deepim_sample_stats_accumulate counts a pair with attempts
+    == 0 as exhausted and adds the values as they are, so callers that feed it keep -1 out: core/loader.TrainDataLoader checks
+    its synthetic_classes against the table on the host when it is built, and no pair of its batches can carry -1."""
+    if not isinstance(class_index, DeviceArray) or class_index.dtype != np.int32:
+        raise TypeError("sample_observed_poses: class_index is a device int32 array")
+    if not isinstance(table, DeviceArray) or table.dtype != np.float64 or table.ndim != 2 or table.shape[1] != OBSERVED_TABLE_COLUMNS:
+        raise TypeError("sample_observed_poses: table is a device float64 (n_classes,22) array")
+    ctx, B = class_index.context, class_index.size
+    K = np.ascontiguousarray(K, dtype=np.float32).reshape(3, 3)
+    pose, attempts = ctx.empty((B, 3, 4)), ctx.empty((B,), np.int32)
+    normals = ctx.empty((B, 7), np.float64) if with_normals else None
+    stat = ctx.empty((B, 4), np.float64) if with_stat else None
+    lib.deepim_sample_observed_poses(ctx.handle, pose, attempts, normals, stat, class_index, table, table.shape[0], K, int(width),
+                                     int(height), ctypes.c_float(border), int(max_attempts), ctypes.c_ulonglong(int(seed) & U64),
+                                     ctypes.c_ulonglong(int(draw_base) & U64), device_draw_ids(ctx, draw_ids, B), B)
+    return (pose, attempts) + ((normals,) if with_normals else ()) + ((stat,) if with_stat else ())
+
+
+def sample_lights(ctx, B, seed, draw_base=0, draw_ids=None, brightness_ratios=BRIGHTNESS_RATIOS):
+    """The light of LM6d_ds_1_gen_observed.py:116-144 for B pairs -> device float32 (light_offset (B,3), light_intensity (B,3),
+    brightness_ratio (B)): the offset is 0.5 x row (draw id mod 6) of the file's six positions, the intensity one of its seven
+    colour rows times U(0.9, 1.1) per channel, the ratio one of `brightness_ratios` (at most 8)."""
+    ratios = np.ascontiguousarray(brightness_ratios, np.float32).reshape(-1)
+    offset, intensity, ratio = ctx.empty((B, 3)), ctx.empty((B, 3)), ctx.empty((B,))
+    lib.deepim_sample_lights(ctx.handle, offset, intensity, ratio, ratios, len(ratios), ctypes.c_ulonglong(int(seed) & U64),
+                             ctypes.c_ulonglong(int(draw_base) & U64), device_draw_ids(ctx, draw_ids, B), B)
+    return offset, intensity, ratio
