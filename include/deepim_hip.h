@@ -107,6 +107,21 @@ int deepim_graph_begin(deepim_ctx* ctx);
 int deepim_graph_end(deepim_ctx* ctx, int* graph_id);
 int deepim_graph_launch(deepim_ctx* ctx, int graph_id);
 
+/* Per-pair cameras. K_table: device (n,3,3) float32 row-major intrinsics, or NULL to unbind. The context stores (pointer, n) and
+ * nothing else: no copy, no launch, no derived table, no allocation — the memory stays the caller's and must outlive its use. The
+ * kernels read the rows when they run, so a captured graph of an iteration replays for any later batch's cameras, as it does for
+ * any batch's class ids.
+ * THE K_host RULE. In every entry whose K_host is marked "or NULL: camera table" — the zoom front ends, the five draws,
+ * deepim_pose_error, deepim_calc_KT, deepim_flow_epe, deepim_pair_flow_labels — K_host == NULL means "sample b of this call reads
+ * row b of the bound table". With K_host != NULL the entry does what it always did, whatever is bound. NULL with nothing bound, or
+ * with n < B, fails on the host before any launch with a message naming the entry. A call on the slice [b0, b1) of a batch binds
+ * K_table + 9*b0 with n = b1 - b0 first. A sample computed from row b has the bits of the same call with K_host = that row (the
+ * inverse intrinsics of the flow entries included: the device inverts in double as the host does). A row is data, not an index:
+ * a non-finite or singular one gives its sample the NaN zoom factor or empty draw of a bad pose, and no address depends on it.
+ * Every other entry that takes a K (deepim_flow_updater_forward, deepim_pose_perturb, the pose samplers) requires it: NULL is an
+ * error code, not a table read. */
+int deepim_bind_cameras(deepim_ctx* ctx, const float* K_table /*device (n,3,3) row-major, or NULL = unbind*/, int n);
+
 /* ------------------------------------------------ multi-GPU: pose all-gather over RCCL/xGMI -- */
 /* pairs shard across GPUs with no data-path collective except ONE all-gather of the refined poses per
  * refinement iteration, so that every rank/host holds all poses for the next render/update — the role of the per-device
@@ -162,7 +177,7 @@ int deepim_calc_flow_forward(deepim_ctx* ctx, float* flow /*B,H,W,2*/, float* vi
  * weight_type 0 'all', 1 'viz', 2 'valid', tiled over the two channels. Poses (B,3,4) device, K host. */
 int deepim_pair_flow_labels(deepim_ctx* ctx, float* flow /*B,2,H,W*/, float* flow_weights /*B,2,H,W*/,
                             const float* depth_rendered, const float* depth_observed, const float* pose_rendered,
-                            const float* pose_observed, const float* K_host, float thresh, int standard_rep,
+                            const float* pose_observed, const float* K_host /*or NULL: camera table*/, float thresh, int standard_rep,
                             int weight_type, int B, int H, int W);
 /* Flow EPE of the test loop, fused (deepim/core/tester.py:366-378: par_generate_gt :530-569 + calc_EPE_one_pair :572-589):
  * per pixel of pair b the float64 ground truth of calc_flow(depth_rendered, pose_rendered, pose_observed, K, depth_observed,
@@ -177,7 +192,7 @@ int deepim_pair_flow_labels(deepim_ctx* ctx, float* flow /*B,2,H,W*/, float* flo
  * call only, outside a capture; legal inside deepim_graph_begin/end (K_host, thresh and standard_rep are baked in). */
 int deepim_flow_epe(deepim_ctx* ctx, double* out /*B,6*/, double* totals /*6, accumulated; or NULL*/,
                     const float* flow_est /*B,2,H,W*/, const float* depth_rendered, const float* depth_observed,
-                    const float* pose_rendered, const float* pose_observed /*B,3,4*/, const float* K_host,
+                    const float* pose_rendered, const float* pose_observed /*B,3,4*/, const float* K_host /*or NULL: camera table*/,
                     const int32_t* skip /*device (B) or NULL*/, float thresh, int standard_rep, int B, int H, int W);
 /* image.py:381-387: mask_rendered = depth_rendered with values > thresh set to 1 (others kept) */
 int deepim_depth_clip_mask(deepim_ctx* ctx, float* mask, const float* depth, float thresh, size_t n);
@@ -186,12 +201,12 @@ int deepim_depth_clip_mask(deepim_ctx* ctx, float* mask, const float* depth, flo
 int deepim_flow_updater_forward(deepim_ctx* ctx, float* flow /*B,2,H,W*/, float* flow_weights /*B,2,H,W*/,
                                 const float* depth_src, const float* depth_tgt,
                                 const float* pose_src, const float* pose_tgt,
-                                const float* K_host, float thresh, int wh_rep,
+                                const float* K_host /*required*/, float thresh, int wh_rep,
                                 int B, int H, int W);
 /* batch_updater_py_multi.py:255-265: KT = K·(pose_tgt ∘ pose_src⁻¹) and
  * mask_rendered = depth_rendered > 0.2 */
 int deepim_calc_KT(deepim_ctx* ctx, float* KT /*B,3,4*/, const float* pose_src,
-                   const float* pose_tgt, const float* K_host, int B);
+                   const float* pose_tgt, const float* K_host /*or NULL: camera table*/, int B);
 int deepim_depth_to_mask(deepim_ctx* ctx, float* mask, const float* depth, float thresh, size_t n);
 /* "box_rendered" / "box_observed" rectangle of a mask (lib/pair_matching/data_pair.py:94-116, the INIT_MASK twin at
  * lib/utils/image.py:355-374): 1 inside [y_start:y_end, x_start:x_end] with start/end = first/last row and column holding a
@@ -205,7 +220,7 @@ int deepim_mask_box_forward(deepim_ctx* ctx, float* box, const float* mask, int 
 int deepim_zoom_mask_forward(deepim_ctx* ctx,
                              const float* mask_observed, const float* mask_gt_observed,
                              const float* mask_rendered, const float* src_pose /*B,3,4*/,
-                             const float* K_host,
+                             const float* K_host /*or NULL: camera table*/,
                              float* zoom_mask_observed, float* zoom_mask_gt_observed,
                              float* zoom_mask_rendered, float* zoom_factor /*B,4*/,
                              int B, int H, int W);
@@ -213,7 +228,7 @@ int deepim_zoom_mask_forward(deepim_ctx* ctx,
  * in the channel order of the image tensor. */
 int deepim_zoom_image_forward(deepim_ctx* ctx,
                               const float* image_observed, const float* image_rendered,
-                              const float* src_pose, const float* K_host,
+                              const float* src_pose, const float* K_host /*or NULL: camera table*/,
                               const float* pixel_means_host,
                               float* zoom_image_observed, float* zoom_image_rendered,
                               float* zoom_factor, int B, int H, int W);
@@ -258,7 +273,7 @@ int deepim_zoom_concat_forward(deepim_ctx* ctx,
                                const float* image_observed, const float* image_rendered,
                                const float* mask_observed, const float* mask_rendered,
                                const float* depth_observed, const float* depth_rendered,
-                               const float* src_pose, const float* K_host,
+                               const float* src_pose, const float* K_host /*or NULL: camera table*/,
                                const float* pixel_means_host,
                                float* net_input, float* zoom_factor,
                                int B, int H, int W);
@@ -267,14 +282,14 @@ int deepim_zoom_concat_forward(deepim_ctx* ctx,
  * element values identical to deepim_zoom_concat_forward's (B,8,H,W) */
 int deepim_zoom_concat_forward_nc8(deepim_ctx* ctx, const float* image_observed, const float* image_rendered,
                                    const float* mask_observed, const float* mask_rendered, const float* src_pose,
-                                   const float* K_host, const float* pixel_means_host, float* net_input_nc8,
+                                   const float* K_host /*or NULL: camera table*/, const float* pixel_means_host, float* net_input_nc8,
                                    float* zoom_factor, int B, int H, int W);
 /* the front end of the fp16 conv path (config 5): the same values rounded once to fp16 and written as the pixel records
  * deepim_conv1_f16_h16_forward reads — main8 (B,H,W,8 halves) = net-input channels 0-7; with depth_* set (INPUT_DEPTH, C = 10)
  * extra2 (B,H,W,2 halves) = channels 8-9 (the masks). depth_observed, depth_rendered and extra2 are all NULL or all set. */
 int deepim_zoom_concat_forward_h16(deepim_ctx* ctx, const float* image_observed, const float* image_rendered,
                                    const float* mask_observed, const float* mask_rendered, const float* depth_observed,
-                                   const float* depth_rendered, const float* src_pose, const float* K_host,
+                                   const float* depth_rendered, const float* src_pose, const float* K_host /*or NULL: camera table*/,
                                    const float* pixel_means_host, void* main8, void* extra2, float* zoom_factor, int B,
                                    int H, int W);
 /* deepim_zoom_concat_forward for a batch whose pairs look at SHARED camera frames (several objects in one frame): the observed
@@ -300,7 +315,7 @@ int deepim_zoom_concat_frames_forward(deepim_ctx* ctx, const uint8_t* frames_bgr
                                       const uint16_t* depth_frames16 /*N,H,W or NULL*/,
                                       const uint8_t* depth_labels /*N,H,W or NULL*/,
                                       const int32_t* mask_idx /*device (B) or NULL*/, float depth_factor,
-                                      const float* depth_rendered /*or NULL*/, const float* src_pose, const float* K_host,
+                                      const float* depth_rendered /*or NULL*/, const float* src_pose, const float* K_host /*or NULL: camera table*/,
                                       const float* pixel_means_host, float* net_input, float* zoom_factor, int B, int H,
                                       int W);
 /* the shared-frame front end of the fp16 conv path: the observed channels as in deepim_zoom_concat_frames_forward, the outputs
@@ -313,14 +328,14 @@ int deepim_zoom_concat_frames_forward_h16(deepim_ctx* ctx, const uint8_t* frames
                                           const uint8_t* depth_labels /*N,H,W or NULL*/,
                                           const int32_t* mask_idx /*device (B) or NULL*/, float depth_factor,
                                           const float* depth_rendered /*or NULL*/, const float* src_pose,
-                                          const float* K_host, const float* pixel_means_host, void* main8, void* extra2,
+                                          const float* K_host /*or NULL: camera table*/, const float* pixel_means_host, void* main8, void* extra2,
                                           float* zoom_factor, int B, int H, int W);
 /* the same front end in the TRAINING graph (deepIM_flownet.py:392-412): the zoom region comes from mask_gt_observed
  * (B,1,H,W; NULL = mask_observed, i.e. the test graph) */
 int deepim_zoom_concat_train_forward(deepim_ctx* ctx, const float* image_observed, const float* image_rendered,
                                      const float* mask_observed, const float* mask_gt_observed, const float* mask_rendered,
                                      const float* depth_observed, const float* depth_rendered, const float* src_pose,
-                                     const float* K_host, const float* pixel_means_host, float* net_input,
+                                     const float* K_host /*or NULL: camera table*/, const float* pixel_means_host, float* net_input,
                                      float* zoom_factor, int B, int H, int W);
 /* parity hook: runs all 2^32 float bit patterns through the kernel's 5-op replacement of `v / 255.0f`
  * (deepIM_flownet.py:35-36 divides the zoomed images by 255) against the IEEE division on the device and returns the
@@ -655,7 +670,7 @@ int deepim_calc_se3(deepim_ctx* ctx, float* rotm, float* t, const float* pose_sr
  * KD-tree), arp_2d (:36-52, mean reprojection distance in pixels) }. points: (B,3,N) model points or, with
  * points_shared != 0, one (3,N) set for all pairs. float64 accumulation, float32 results (B,5). */
 int deepim_pose_error(deepim_ctx* ctx, float* out /*B,5*/, const float* pose_est, const float* pose_gt,
-                      const float* points, int points_shared, const float* K_host, int B, int N);
+                      const float* points, int points_shared, const float* K_host /*or NULL: camera table*/, int B, int N);
 /* Transform3D forward/backward (deepim/operator_py/transform3d.py:34-151) */
 int deepim_transform3d_forward(deepim_ctx* ctx, float* out /*B,3,N*/, const float* points /*B,3,N*/,
                                const float* rotation /*B,4*/, const float* translation /*B,3*/,
@@ -938,7 +953,7 @@ int deepim_x3_weight_range_check(deepim_ctx* ctx, const float* w, long n, float 
  *   K_host: 9 floats, row-major intrinsics. */
 int deepim_render_forward(deepim_ctx* ctx, float* image, float* depth, const float* vertices,
                           const float* vertex_attr, const int32_t* faces, const float* texture,
-                          int tex_h, int tex_w, const float* poses, const float* K_host,
+                          int tex_h, int tex_w, const float* poses, const float* K_host /*or NULL: camera table*/,
                           const float* pixel_means_host, int V, int F, int B, int H, int W, float znear,
                           float zfar);
 /* The same draw fused with the rest of the test-loop update (deepim/core/tester.py:437-449,
@@ -948,7 +963,7 @@ int deepim_render_forward(deepim_ctx* ctx, float* image, float* depth, const flo
 int deepim_render_update_forward(deepim_ctx* ctx, float* image, float* depth, float* mask_rendered,
                                  float* mask_box /*or NULL*/, float mask_thresh, const float* vertices,
                                  const float* vertex_attr, const int32_t* faces, const float* texture,
-                                 int tex_h, int tex_w, const float* poses, const float* K_host,
+                                 int tex_h, int tex_w, const float* poses, const float* K_host /*or NULL: camera table*/,
                                  const float* pixel_means_host, int V, int F, int B, int H, int W,
                                  float znear, float zfar);
 /* The draw of the ModelNet loops (BASELINE config 5): lib/render_glumpy/render_py_light_modelnet_multi.py:36-80,170-188 — the
@@ -963,7 +978,7 @@ int deepim_render_update_forward(deepim_ctx* ctx, float* image, float* depth, fl
 int deepim_render_lit_forward(deepim_ctx* ctx, float* image, float* depth, float* mask_rendered /*or NULL*/,
                               float* mask_box /*or NULL*/, float mask_thresh, const float* vertices,
                               const float* vertex_attr, const float* normals, const int32_t* faces, const float* texture,
-                              int tex_h, int tex_w, const float* poses, const float* K_host, const float* pixel_means_host,
+                              int tex_h, int tex_w, const float* poses, const float* K_host /*or NULL: camera table*/, const float* pixel_means_host,
                               const float* light_offset_host, const float* light_intensity /*device (B,3) or NULL*/,
                               float brightness_ratio, int V, int F, int B, int H, int W, float znear, float zfar);
 /* The three draws above for a batch whose samples belong to DIFFERENT meshes (BASELINE config 3: all 13 LINEMOD objects in one
@@ -992,7 +1007,7 @@ int deepim_render_classes_forward(deepim_ctx* ctx, float* image, float* depth, f
                                   const int32_t* mesh_desc /*device (n_classes,8)*/, int n_classes, int max_V, int max_F,
                                   const float* vertices, const float* vertex_attr, const float* normals /*or NULL*/,
                                   const int32_t* faces, const float* textures /*or NULL*/, const float* poses,
-                                  const float* K_host, const float* pixel_means_host, const float* light_offset_host /*or NULL*/,
+                                  const float* K_host /*or NULL: camera table*/, const float* pixel_means_host, const float* light_offset_host /*or NULL*/,
                                   const float* light_intensity /*device (B,3) or NULL*/, float brightness_ratio, int B, int H,
                                   int W, float znear, float zfar);
 /* The lit mesh-table draw of deepim_render_classes_forward for SYNTHETIC OBSERVED FRAMES (toolkit/LM6d_ds_1_gen_observed.py:
@@ -1016,7 +1031,7 @@ int deepim_render_observed_forward(deepim_ctx* ctx, uint8_t* image /*N,H,W,3*/, 
                                    float depth_factor, const int32_t* class_index /*device (B)*/,
                                    const int32_t* mesh_desc /*device (n_classes,8)*/, int n_classes, int max_V, int max_F,
                                    const float* vertices, const float* vertex_attr, const float* normals, const int32_t* faces,
-                                   const float* textures /*or NULL*/, const float* poses, const float* K_host,
+                                   const float* textures /*or NULL*/, const float* poses, const float* K_host /*or NULL: camera table*/,
                                    const float* light_offset /*device (B,3)*/, const float* light_intensity /*device (B,3)*/,
                                    const float* brightness_ratio /*device (B)*/, int B, int H, int W, float znear, float zfar);
 

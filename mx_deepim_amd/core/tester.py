@@ -19,6 +19,14 @@ Differences from the reference:
   * the data / net / calc_gt times of the progress line are host times of asynchronous launches (only the per-batch read-back
     waits for the device).
   * pred_eval returns what it computed (the reference returns None).
+  * per-pair cameras: a pair record may carry "K" (3,3). tester.py:424-426 loads a pair's `-K.txt` only for the re-render and
+    then leaves that K in the loop variable for every later pair that has no file. Here a pair's K is that pair's camera
+    everywhere — zoom centre, re-render, flow ground truth and arp_2d — and it does not leak to other pairs: a record without a
+    K gets config.dataset.INTRINSIC_MATRIX. When any record of a batch has one, the batch's (B,3,3) table (cameras.camera_table)
+    is uploaded once, set as data["intrinsics"] and bound as the context's camera table (Context.bind_cameras); the K of every
+    stored pose is collected in `all_K[cls]`, parallel to all_poses_gt[cls][0], handed to the evaluation and cached in the
+    sidecar `<name>_pose_iter<N>_K.pkl` next to the reference's four containers (written only when cameras were used). The
+    caller decodes the `-K.txt` files, as it decodes the frames.
 """
 from __future__ import print_function, division, absolute_import
 
@@ -29,6 +37,7 @@ import time
 
 import numpy as np
 
+from ..cameras import camera_table, has_cameras
 from ..lib.pair_matching.batch_updater_py_multi import update_test_batch
 from ..lib.utils import image as _image
 from ..runtime import DeviceArray, lib
@@ -71,15 +80,23 @@ def _poses(ctx, p, B):
     return ctx.array(np.asarray(p, dtype=np.float32).reshape(B, 3, 4))
 
 
-def calc_EPE_batch(config, flow_est, flow_gt, pose_rendered, pose_observed, skip=None, totals=None, out=None):
+def calc_EPE_batch(config, flow_est, flow_gt, pose_rendered, pose_observed, skip=None, totals=None, out=None, K=None):
     """tester.py:559-589 for a batch, one deepim_flow_epe call and no host round trip: flow_est (B,2,H,W) device (the graph's
     flow_est_crop), flow_gt from par_generate_gt, poses (B,3,4). Returns the device float64 (B,6) array of EPE_KEYS per pair.
-    skip: device int32 (B), pairs to leave out; totals: device float64 (6), running sums the rows are added to."""
+    skip: device int32 (B), pairs to leave out; totals: device float64 (6), running sums the rows are added to.
+    K: None (config.dataset.INTRINSIC_MATRIX), a host (3,3), or a DeviceArray (B,3,3) of per-pair cameras (bound as the context's
+    camera table; each pair's ground truth then comes from its own K and its inverse)."""
     ctx = flow_est.context
     B, _, H, W = flow_est.shape
     if out is None:
         out = ctx.empty((B, 6), dtype=np.float64)
-    K = np.ascontiguousarray(config.dataset.INTRINSIC_MATRIX, dtype=np.float32).reshape(3, 3)
+    if isinstance(K, DeviceArray):
+        if K.shape != (B, 3, 3):
+            raise ValueError("calc_EPE_batch: a device K must be (%d,3,3), got %s" % (B, K.shape))
+        ctx.bind_cameras(K)
+        K = None
+    else:
+        K = np.ascontiguousarray(config.dataset.INTRINSIC_MATRIX if K is None else K, dtype=np.float32).reshape(3, 3)
     lib.deepim_flow_epe(ctx.handle, out, totals, flow_est, flow_gt["depth_rendered"], flow_gt["depth_observed"],
                         _poses(ctx, pose_rendered, B), _poses(ctx, pose_observed, B), K, skip, ctypes.c_float(FLOW_THRESH),
                         1 if config.network.get("STANDARD_FLOW_REP", False) else 0, B, H, W)
@@ -104,15 +121,46 @@ def _as_array(lists):
         return np.array(lists, dtype=object)
 
 
-def _evaluate(config, imdb_test, all_poses_est, all_poses_gt):
-    res = {"pose": imdb_test.evaluate_pose(config, all_poses_est, all_poses_gt)}
+def _evaluate(config, imdb_test, all_poses_est, all_poses_gt, all_K=None):
+    cams = {} if all_K is None else {"all_K": all_K}      # per-pair cameras (module docstring); without them the reference's calls
+    res = {"pose": imdb_test.evaluate_pose(config, all_poses_est, all_poses_gt, **cams)}
     pose_add_plots_dir = os.path.join(imdb_test.result_path, "add_plots")
     _mkdir_p(pose_add_plots_dir)
-    res["add"] = imdb_test.evaluate_pose_add(config, all_poses_est, all_poses_gt, output_dir=pose_add_plots_dir)
+    res["add"] = imdb_test.evaluate_pose_add(config, all_poses_est, all_poses_gt, output_dir=pose_add_plots_dir, **cams)
     pose_arp2d_plots_dir = os.path.join(imdb_test.result_path, "arp_2d_plots")
     _mkdir_p(pose_arp2d_plots_dir)
-    res["arp_2d"] = imdb_test.evaluate_pose_arp_2d(config, all_poses_est, all_poses_gt, output_dir=pose_arp2d_plots_dir)
+    res["arp_2d"] = imdb_test.evaluate_pose_arp_2d(config, all_poses_est, all_poses_gt, output_dir=pose_arp2d_plots_dir, **cams)
     return res
+
+
+def camera_cache_file(pose_err_file):
+    """The sidecar of the result cache that keeps all_K: `<name>_pose_iter<N>_K.pkl` next to `<name>_pose_iter<N>.pkl`."""
+    return pose_err_file[:-len(".pkl")] + "_K.pkl"
+
+
+def save_result_cache(pose_err_file, containers, all_K=None):
+    """The reference's four containers to `pose_err_file`; all_K to the sidecar when per-pair cameras were used — and no
+    sidecar otherwise: one left by an earlier run is removed, it would give the cached poses another run's cameras."""
+    with open(pose_err_file, "wb") as f:
+        pickle.dump(list(containers), f, protocol=2)
+    side = camera_cache_file(pose_err_file)
+    if all_K is not None:
+        with open(side, "wb") as f:
+            pickle.dump(all_K, f, protocol=2)
+    elif os.path.exists(side):
+        os.remove(side)
+
+
+def load_result_cache(pose_err_file):
+    """-> ([all_rot_err, all_trans_err, all_poses_est, all_poses_gt], all_K or None): the cache and, when it exists, its sidecar."""
+    with open(pose_err_file, "rb") as fid:
+        containers = pickle.load(fid, encoding="latin1")
+    all_K = None
+    side = camera_cache_file(pose_err_file)
+    if os.path.exists(side):
+        with open(side, "rb") as fid:
+            all_K = pickle.load(fid, encoding="latin1")
+    return containers, all_K
 
 
 def pred_eval(config, predictor, test_data, imdb_test, vis=False, ignore_cache=None, logger=None, pairdb=None,
@@ -122,7 +170,8 @@ def pred_eval(config, predictor, test_data, imdb_test, vis=False, ignore_cache=N
     :param imdb_test: lib/dataset/LM6D_REFINE with `name` and `result_path`
     :param ignore_cache: ignore the saved cache file
     :param render_machine: lib/render_glumpy Render_Py (or the lit ModelNet machine); needed from test_iter = 2 on
-    Returns a dict: the four cached containers, sum_PoseErr, num_inst, "epe" (the six totals and the three means) and "tables"."""
+    Returns a dict: the four cached containers, "all_K" (None unless a pair record carried a "K"), sum_PoseErr, num_inst, "epe"
+    (the six totals and the three means) and "tables"."""
     for key, lines in (("VISUALIZE", ":112, :411-421"), ("PRECOMPUTED_ICP", ":193-242"), ("BEFORE_ICP", ":244-279")):
         if config.TEST.get(key, False):
             raise NotImplementedError("TEST.%s (deepim/core/tester.py%s) reads files and draws figures; it is not part of "
@@ -132,11 +181,10 @@ def pred_eval(config, predictor, test_data, imdb_test, vis=False, ignore_cache=N
     logger.info("test iter size: {}".format(test_iter))
     pose_err_file = os.path.join(imdb_test.result_path, imdb_test.name + "_pose_iter{}.pkl".format(test_iter))
     if os.path.exists(pose_err_file) and not ignore_cache and not vis:
-        with open(pose_err_file, "rb") as fid:
-            [all_rot_err, all_trans_err, all_poses_est, all_poses_gt] = pickle.load(fid, encoding="latin1")
-        tables = _evaluate(config, imdb_test, all_poses_est, all_poses_gt)
+        [all_rot_err, all_trans_err, all_poses_est, all_poses_gt], all_K = load_result_cache(pose_err_file)
+        tables = _evaluate(config, imdb_test, all_poses_est, all_poses_gt, all_K)
         return {"all_rot_err": all_rot_err, "all_trans_err": all_trans_err, "all_poses_est": all_poses_est,
-                "all_poses_gt": all_poses_gt, "tables": tables, "from_cache": True}
+                "all_poses_gt": all_poses_gt, "all_K": all_K, "tables": tables, "from_cache": True}
 
     if test_iter > 1 and render_machine is None:
         raise ValueError("pred_eval: TEST.test_iter = %d re-renders between the iterations: pass render_machine" % test_iter)
@@ -155,6 +203,8 @@ def pred_eval(config, predictor, test_data, imdb_test, vis=False, ignore_cache=N
     all_trans_err = [[[] for _ in range(test_iter)] for _ in range(num_cls)]
     all_poses_est = [[[] for _ in range(test_iter)] for _ in range(num_cls)]
     all_poses_gt = [[[] for _ in range(test_iter)] for _ in range(num_cls)]
+    all_K = [[] for _ in range(num_cls)]        # the camera of every stored pose, parallel to all_poses_gt[cls][0]
+    cameras_used = False
     num_inst = np.zeros(num_cls + 1)
     K = np.ascontiguousarray(config.dataset.INTRINSIC_MATRIX, dtype=np.float32).reshape(3, 3)
     one_point = ctx.zeros((3, 1))       # deepim_pose_error's re / te need no model points; its add / adi / arp_2d go unused
@@ -169,6 +219,13 @@ def pred_eval(config, predictor, test_data, imdb_test, vis=False, ignore_cache=N
         pose_observed = np.stack([np.asarray(r["pose_observed"], np.float32).reshape(3, 4) for r in pair_records])
         no_point = np.array([np.sum(r["pose_rendered"]) == -12 for r in pair_records])      # NO POINT VALID IN INIT POSE
         class_ids = [imdb_test.classes.index(r["gt_class"]) for r in pair_records]
+        cams = None                                 # the batch's (B,3,3) table: host copy here, cams_d on the device
+        if has_cameras(pair_records):
+            cams = camera_table(pair_records, K)
+            cameras_used = True
+        elif data.get("intrinsics") is not None:
+            raise ValueError("pred_eval: the batch carries data['intrinsics'] but no pair record has a 'K': the evaluation "
+                             "would silently use another camera")
         for b in np.nonzero(no_point)[0]:
             print(pairs_done + b)
             print("in test: NO POINT_VALID IN rendered")
@@ -176,6 +233,9 @@ def pred_eval(config, predictor, test_data, imdb_test, vis=False, ignore_cache=N
             poses_host = errs_host = None
         else:
             data = dict(data)
+            cams_d = None
+            if cams is not None:
+                cams_d = data["intrinsics"] = ctx.array(cams)       # uploaded once per batch
             skip = None
             if no_point.any():
                 skip = ctx.array(no_point.astype(np.int32), dtype=np.int32)
@@ -200,7 +260,7 @@ def pred_eval(config, predictor, test_data, imdb_test, vis=False, ignore_cache=N
             if do_epe:      # evaluate optical flow: once per pair, from the first forward (:366-378)
                 flow_gt = par_generate_gt(config, frames)
                 calc_EPE_batch(config, output_all[0]["flow_est_crop_output"], flow_gt, pose_rendered_d, pose_observed_d,
-                               skip=skip, totals=epe_totals)
+                               skip=skip, totals=epe_totals, K=cams_d)
             post_time += time.time() - t
 
             for pose_iter_idx in range(test_iter):      # iterative refine se3 estimation
@@ -210,7 +270,10 @@ def pred_eval(config, predictor, test_data, imdb_test, vis=False, ignore_cache=N
                 if skip is not None:
                     for b in np.nonzero(no_point)[0]:                                 # keep the parked rows parked
                         cur[int(b)].copyfrom(pose_observed_d[int(b)])
-                lib.deepim_pose_error(ctx.handle, errs_d[pose_iter_idx], cur, pose_observed_d, one_point, 1, K, B, 1)   # :401
+                if cams_d is not None:
+                    ctx.bind_cameras(cams_d)
+                lib.deepim_pose_error(ctx.handle, errs_d[pose_iter_idx], cur, pose_observed_d, one_point, 1,
+                                      None if cams_d is not None else K, B, 1)   # :401
                 post_time += time.time() - t
                 if pose_iter_idx < test_iter - 1:       # if more than one iteration
                     t = time.time()
@@ -227,6 +290,7 @@ def pred_eval(config, predictor, test_data, imdb_test, vis=False, ignore_cache=N
 
         for b, rec in enumerate(pair_records):          # the containers, pair by pair in the reference's order
             class_id = class_ids[b]
+            all_K[class_id].append(K.copy() if cams is None else cams[b].copy())
             if not no_point[b]:
                 num_inst[class_id] += 1
                 num_inst[-1] += 1
@@ -254,10 +318,11 @@ def pred_eval(config, predictor, test_data, imdb_test, vis=False, ignore_cache=N
 
     # save inference results
     _mkdir_p(imdb_test.result_path)
-    with open(pose_err_file, "wb") as f:
-        logger.info("saving result cache to {}".format(pose_err_file))
-        pickle.dump([all_rot_err, all_trans_err, all_poses_est, all_poses_gt], f, protocol=2)
-        logger.info("done")
+    if not cameras_used:
+        all_K = None
+    logger.info("saving result cache to {}".format(pose_err_file))
+    save_result_cache(pose_err_file, [all_rot_err, all_trans_err, all_poses_est, all_poses_gt], all_K)
+    logger.info("done")
 
     epe = None
     if config.network.PRED_FLOW:
@@ -271,8 +336,8 @@ def pred_eval(config, predictor, test_data, imdb_test, vis=False, ignore_cache=N
         logger.info("EPE visible: {}".format(epe["EPE_visible"]))
 
     logger.info("evaluate pose:")
-    tables = _evaluate(config, imdb_test, all_poses_est, all_poses_gt)
+    tables = _evaluate(config, imdb_test, all_poses_est, all_poses_gt, all_K)
     logger.info("using {} seconds in total".format(time.time() - t_start))
     return {"all_rot_err": all_rot_err, "all_trans_err": all_trans_err, "all_poses_est": all_poses_est,
-            "all_poses_gt": all_poses_gt, "sum_PoseErr": sum_PoseErr, "num_inst": num_inst, "epe": epe, "tables": tables,
+            "all_poses_gt": all_poses_gt, "all_K": all_K, "sum_PoseErr": sum_PoseErr, "num_inst": num_inst, "epe": epe, "tables": tables,
             "from_cache": False}

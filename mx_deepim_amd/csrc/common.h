@@ -77,6 +77,8 @@ struct deepim_ctx {
   void* wino_counters;   // arrival counters of the Winograd kernels' in-kernel finish, one per tile block (deepim_create; zero between launches)
   int f16_dev_flags;     // 0 (default) or DI_F16_NO_PP: fp16 layers stay off the ping-pong kernel
   std::vector<const void*> attr_done;  // hipFuncSetAttribute groups already applied on THIS context's device (di_attr_needed)
+  const float* cam_table;   // deepim_bind_cameras: device (cam_n,3,3) intrinsics read by the entries called with K_host == NULL
+  int cam_n;                // (the caller's memory: only the pointer is kept, so a captured graph sees the table's later contents)
 };
 
 // true the first time `tag` is seen on this context: guards one-off hipFuncSetAttribute calls (per device, hence per context)
@@ -139,3 +141,60 @@ static inline int di_div_up(long a, long b) { return (int)((a + b - 1) / b); }
 // small by-value attribute blocks passed as kernel arguments (live in SGPRs)
 struct Mat3 { float v[9]; };
 struct Vec3 { float v[3]; };
+
+// Where a kernel's camera comes from (the K_host rule of include/deepim_hip.h): one matrix by value for the whole launch, or
+// row b of the table bound with deepim_bind_cameras. Kernels that read K are templated on it; both sources hand the same
+// operations the same values, so a sample computed from table row b has the bits of a call with K_host = that row.
+struct CamOne {
+  Mat3 K;
+  __device__ __forceinline__ const Mat3& at(int) const { return K; }
+};
+struct CamTable {
+  const float* rows;
+  __device__ __forceinline__ Mat3 at(int b) const {
+    Mat3 m;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) m.v[i] = rows[(long)b * 9 + i];
+    return m;
+  }
+};
+static inline CamOne cam_one(const float* K_host) {
+  CamOne c;
+  for (int i = 0; i < 9; ++i) c.K.v[i] = K_host[i];
+  return c;
+}
+
+// 3x3 inverse in double (adjugate) — for intrinsics this matches numpy's LU result to f64 ulps. Host and device run the same
+// IEEE double operations in the same order (no contraction), so both give the same bits.
+__host__ __device__ inline void inv3d(const float* K, double* o) {
+  double a = K[0], b = K[1], c = K[2], d = K[3], e = K[4], f = K[5], g = K[6], h = K[7], i = K[8];
+  double A = e * i - f * h, Bc = -(d * i - f * g), C = d * h - e * g;
+  double det = a * A + b * Bc + c * C;
+  o[0] = A / det; o[1] = -(b * i - c * h) / det; o[2] = (b * f - c * e) / det;
+  o[3] = Bc / det; o[4] = (a * i - c * g) / det; o[5] = -(a * f - c * d) / det;
+  o[6] = C / det; o[7] = -(a * h - b * g) / det; o[8] = (a * e - b * d) / det;
+}
+// np.linalg.inv(np.matrix(K)) of a float32 K: the double inverse rounded to float32
+__host__ __device__ inline Mat3 inv3_f32(const float* K) {
+  double kinv[9];
+  inv3d(K, kinv);
+  Mat3 m;
+  for (int i = 0; i < 9; ++i) m.v[i] = (float)kinv[i];
+  return m;
+}
+// The inverse intrinsics of the flow kernels: computed once on the host, or by each block from its pair's table row
+struct KinvOne {
+  Mat3 Kinv;
+  __device__ __forceinline__ const Mat3& at(int) const { return Kinv; }
+};
+struct KinvTable {
+  const float* rows;
+  __device__ __forceinline__ Mat3 at(int b) const { return inv3_f32(rows + (long)b * 9); }
+};
+
+// The K_host rule on the host, before any launch: K_host, else the bound table with at least B rows, else an error naming `entry`
+int deepim_camera_check(deepim_ctx* ctx, const float* K_host, int B, const char* entry);
+#define DI_CAMERA(ctx, K_host, B, entry)                                   \
+  do {                                                                     \
+    if (deepim_camera_check((ctx), (K_host), (B), (entry)) != 0) return -1; \
+  } while (0)

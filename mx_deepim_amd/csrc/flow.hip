@@ -167,15 +167,18 @@ __global__ __launch_bounds__(256) void calc_flow_kernel(float* __restrict__ flow
 // Loader-side flow labels, lib/utils/image.py:402-450 (get_pair_flow): calc_flow per pair, flow.transpose((2,0,1)) →
 // (B,2,H,W), weights by TRAIN.FLOW_WEIGHT_TYPE — 0 'all' (ones), 1 'viz' (visible), 2 'valid' (depth_rendered == 0 or
 // visible) — tiled over the two channels. One pass: 8 B read + 16 B written per pixel.
+// Kin: KinvOne (the host's inverse by value) or KinvTable (the block inverts row b = blockIdx.y of the bound table: uniform)
+template <class Kin>
 __global__ __launch_bounds__(256) void pair_flow_labels_kernel(float* __restrict__ flow, float* __restrict__ weights,
                                                                const float* __restrict__ depth_src,
                                                                const float* __restrict__ depth_tgt,
-                                                               const float* __restrict__ KT_all, Mat3 Kinv, float thresh,
+                                                               const float* __restrict__ KT_all, Kin kin, float thresh,
                                                                int standard_rep, int weight_type, int height, int width) {
   const int b = blockIdx.y;
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
   const int plane = height * width;
   if (p >= plane) return;
+  const auto& Kinv = kin.at(b);
   float dsf;
   const CalcFlowOut o = calc_flow_pixel(b, p, depth_src, depth_tgt, KT_all, Kinv, thresh, standard_rep, height, width, &dsf);
   const float wgt = weight_type == 0 ? 1.f : (weight_type == 1 ? o.vis : ((dsf == 0.f || o.vis == 1.f) ? 1.f : 0.f));
@@ -215,15 +218,18 @@ constexpr int EPE_MAX_ITERS = 8;   // quads per lane: the launcher picks 1 … 8
 
 // grid (ceil(quads / (256·iters)), B), 256 threads. Block x owns the quads [x·256·iters, (x + 1)·256·iters) of its pair and walks
 // them in `iters` coalesced steps of 256 quads, so that the reduction below is paid once per 4·iters pixels of a lane.
+// Kin: KinvOne or KinvTable, as in pair_flow_labels_kernel
+template <class Kin>
 __global__ __launch_bounds__(256) void flow_epe_partial_kernel(EpePartial* __restrict__ partials,
                                                                const float* __restrict__ flow_est,
                                                                const float* __restrict__ depth_src,
                                                                const float* __restrict__ depth_tgt,
-                                                               const float* __restrict__ KT_all, Mat3 Kinv,
+                                                               const float* __restrict__ KT_all, Kin kin,
                                                                const int32_t* __restrict__ skip, float thresh,
                                                                int standard_rep, int height, int width, int iters) {
   const int b = blockIdx.y;
   if (skip && skip[b] != 0) return;          // block-uniform: the finish pass writes the zero row
+  const auto& Kinv = kin.at(b);
   const int plane = height * width;
   const float* KT = KT_all + b * 12;
   const float* tgt = depth_tgt + (size_t)b * plane;
@@ -368,10 +374,13 @@ __global__ __launch_bounds__(256) void flow_updater_kernel(float* __restrict__ f
 }
 
 // calc_se3 (RT_transform.py:176-187 → projection.py:12-43, f32 results) then K·se3 (f32).
+// Cam: CamOne (K by value) or CamTable (pair b reads row b of the bound table)
+template <class Cam>
 __global__ void calc_KT_kernel(float* __restrict__ KT, const float* __restrict__ pose_src,
-                               const float* __restrict__ pose_tgt, Mat3 K, int B) {
+                               const float* __restrict__ pose_tgt, Cam cam, int B) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
+  const auto& K = cam.at(b);
   const float* S = pose_src + b * 12;
   const float* T = pose_tgt + b * 12;
   // se3_inverse(src): Rinv = R^T ; tinv = -1 * (R^T · t)
@@ -445,14 +454,16 @@ Mat3 load_mat3(const float* h) {
   return m;
 }
 
-// 3x3 inverse in double (adjugate) — for intrinsics this matches numpy's LU result to f64 ulps
-void inv3d(const float* K, double* o) {
-  double a = K[0], b = K[1], c = K[2], d = K[3], e = K[4], f = K[5], g = K[6], h = K[7], i = K[8];
-  double A = e * i - f * h, Bc = -(d * i - f * g), C = d * h - e * g;
-  double det = a * A + b * Bc + c * C;
-  o[0] = A / det; o[1] = -(b * i - c * h) / det; o[2] = (b * f - c * e) / det;
-  o[3] = Bc / det; o[4] = (a * i - c * g) / det; o[5] = -(a * f - c * d) / det;
-  o[6] = C / det; o[7] = -(a * h - b * g) / det; o[8] = (a * e - b * d) / det;
+// the K·T scratch rows of the entries below; K_host == NULL: the bound camera table (the entry has checked it with DI_CAMERA)
+int launch_calc_KT(deepim_ctx* ctx, float* KT, const float* pose_src, const float* pose_tgt, const float* K_host, int B) {
+  if (K_host)
+    hipLaunchKernelGGL(calc_KT_kernel<CamOne>, dim3(di_div_up(B, 64)), dim3(64), 0, ctx->stream, KT, pose_src, pose_tgt,
+                       cam_one(K_host), B);
+  else
+    hipLaunchKernelGGL(calc_KT_kernel<CamTable>, dim3(di_div_up(B, 64)), dim3(64), 0, ctx->stream, KT, pose_src, pose_tgt,
+                       CamTable{ctx->cam_table}, B);
+  DI_LAUNCH_CHECK();
+  return 0;
 }
 
 }  // namespace
@@ -562,20 +573,21 @@ extern "C" int deepim_pair_flow_labels(deepim_ctx* ctx, float* flow, float* flow
                                        int weight_type, int B, int H, int W) {
   DI_DEVICE(ctx);
   if (B == 0) return 0;
+  DI_CAMERA(ctx, K_host, B, "deepim_pair_flow_labels");
   DI_REQUIRE(weight_type >= 0 && weight_type <= 2, "pair_flow_labels: unknown FLOW_WEIGHT_TYPE");
   void* scratch;
   int rc = deepim_scratch(ctx, (size_t)B * 48, &scratch);
   if (rc) return rc;
   float* KT = (float*)scratch;
-  rc = deepim_calc_KT(ctx, KT, pose_rendered, pose_observed, K_host, B);   // np.matmul(K, se3_mul(tgt, se3_inverse(src))), f32
+  rc = launch_calc_KT(ctx, KT, pose_rendered, pose_observed, K_host, B);   // np.matmul(K, se3_mul(tgt, se3_inverse(src))), f32
   if (rc) return rc;
-  double kinv[9];
-  inv3d(K_host, kinv);                    // np.linalg.inv(np.matrix(K)): float32 result for a float32 K
-  Mat3 Kinv;
-  for (int i = 0; i < 9; ++i) Kinv.v[i] = (float)kinv[i];
   dim3 grid(di_div_up((long)W * H, 256), B);
-  hipLaunchKernelGGL(pair_flow_labels_kernel, grid, dim3(256), 0, ctx->stream, flow, flow_weights, depth_rendered,
-                     depth_observed, KT, Kinv, thresh, standard_rep, weight_type, H, W);
+  if (K_host)                             // np.linalg.inv(np.matrix(K)): float32 result for a float32 K
+    hipLaunchKernelGGL(pair_flow_labels_kernel<KinvOne>, grid, dim3(256), 0, ctx->stream, flow, flow_weights, depth_rendered,
+                       depth_observed, KT, KinvOne{inv3_f32(K_host)}, thresh, standard_rep, weight_type, H, W);
+  else                                    // the same inverse, by each block from its pair's row
+    hipLaunchKernelGGL(pair_flow_labels_kernel<KinvTable>, grid, dim3(256), 0, ctx->stream, flow, flow_weights, depth_rendered,
+                       depth_observed, KT, KinvTable{ctx->cam_table}, thresh, standard_rep, weight_type, H, W);
   DI_LAUNCH_CHECK();
   return 0;
 }
@@ -589,6 +601,7 @@ extern "C" int deepim_flow_epe(deepim_ctx* ctx, double* out, double* totals, con
   DI_REQUIRE(B <= 65535, "flow_epe: batch too large");
   DI_REQUIRE((long)H * W <= (1L << 30), "flow_epe: frame too large");
   if (B == 0) return 0;
+  DI_CAMERA(ctx, K_host, B, "deepim_flow_epe");
   const int plane = H * W;
   const int quads = di_div_up(plane, 4);
   const int iters = std::min(EPE_MAX_ITERS, std::max(1, di_div_up(quads, 64 * 256)));   // 480x640: 5, so 60 blocks per pair
@@ -599,14 +612,14 @@ extern "C" int deepim_flow_epe(deepim_ctx* ctx, double* out, double* totals, con
   if (rc) return rc;
   float* KT = (float*)scratch;
   EpePartial* partials = (EpePartial*)((char*)scratch + (size_t)B * 48);
-  rc = deepim_calc_KT(ctx, KT, pose_rendered, pose_observed, K_host, B);   // np.matmul(K, se3_mul(tgt, se3_inverse(src))), f32
+  rc = launch_calc_KT(ctx, KT, pose_rendered, pose_observed, K_host, B);   // np.matmul(K, se3_mul(tgt, se3_inverse(src))), f32
   if (rc) return rc;
-  double kinv[9];
-  inv3d(K_host, kinv);                    // np.linalg.inv(np.matrix(K)): float32 result for a float32 K
-  Mat3 Kinv;
-  for (int i = 0; i < 9; ++i) Kinv.v[i] = (float)kinv[i];
-  hipLaunchKernelGGL(flow_epe_partial_kernel, dim3(nblk, B), dim3(256), 0, ctx->stream, partials, flow_est, depth_rendered,
-                     depth_observed, KT, Kinv, skip, thresh, standard_rep, H, W, iters);
+  if (K_host)                             // np.linalg.inv(np.matrix(K)): float32 result for a float32 K
+    hipLaunchKernelGGL(flow_epe_partial_kernel<KinvOne>, dim3(nblk, B), dim3(256), 0, ctx->stream, partials, flow_est,
+                       depth_rendered, depth_observed, KT, KinvOne{inv3_f32(K_host)}, skip, thresh, standard_rep, H, W, iters);
+  else                                    // the same inverse, by each block from its pair's row
+    hipLaunchKernelGGL(flow_epe_partial_kernel<KinvTable>, dim3(nblk, B), dim3(256), 0, ctx->stream, partials, flow_est,
+                       depth_rendered, depth_observed, KT, KinvTable{ctx->cam_table}, skip, thresh, standard_rep, H, W, iters);
   hipLaunchKernelGGL(flow_epe_finish_kernel, dim3(1), dim3(256), 0, ctx->stream, out, totals, partials, skip, nblk, B, plane);
   DI_LAUNCH_CHECK();
   return 0;
@@ -625,22 +638,21 @@ extern "C" int deepim_calc_KT(deepim_ctx* ctx, float* KT, const float* pose_src,
                               const float* K_host, int B) {
   DI_DEVICE(ctx);
   if (B == 0) return 0;
-  hipLaunchKernelGGL(calc_KT_kernel, dim3(di_div_up(B, 64)), dim3(64), 0, ctx->stream, KT, pose_src, pose_tgt,
-                     load_mat3(K_host), B);
-  DI_LAUNCH_CHECK();
-  return 0;
+  DI_CAMERA(ctx, K_host, B, "deepim_calc_KT");
+  return launch_calc_KT(ctx, KT, pose_src, pose_tgt, K_host, B);
 }
 
 extern "C" int deepim_flow_updater_forward(deepim_ctx* ctx, float* flow, float* flow_weights, const float* depth_src,
                                            const float* depth_tgt, const float* pose_src, const float* pose_tgt,
                                            const float* K_host, float thresh, int wh_rep, int B, int H, int W) {
   DI_DEVICE(ctx);
+  DI_REQUIRE(K_host != nullptr, "deepim_flow_updater_forward: K_host is required (this entry reads no camera table)");
   if (B == 0) return 0;
   void* scratch;
   int rc = deepim_scratch(ctx, (size_t)B * 48, &scratch);
   if (rc) return rc;
   float* KT = (float*)scratch;
-  rc = deepim_calc_KT(ctx, KT, pose_src, pose_tgt, K_host, B);
+  rc = launch_calc_KT(ctx, KT, pose_src, pose_tgt, K_host, B);
   if (rc) return rc;
   Mat3d Kinv;
   inv3d(K_host, Kinv.v);

@@ -73,8 +73,10 @@ struct MeshTable {
   __device__ __forceinline__ int pv_stride() const { return max_V; }
 };
 
-template <class Src>
-__global__ __launch_bounds__(256) void project_kernel(PV* __restrict__ pv, Src src, const float* __restrict__ poses, Mat3 K,
+// Cam: CamOne (K by value) or CamTable (sample b = blockIdx.y reads row b of the bound table: a uniform load). A non-finite row
+// projects its sample to non-finite vertices, which the raster pass drops: an empty draw, and no address depends on the row.
+template <class Src, class Cam>
+__global__ __launch_bounds__(256) void project_kernel(PV* __restrict__ pv, Src src, const float* __restrict__ poses, Cam cam,
                                                       int* __restrict__ box_words) {
   const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
   // arm this sample's bbox accumulator for the resolve pass of THIS call, in stream order (two launches earlier):
@@ -88,6 +90,7 @@ __global__ __launch_bounds__(256) void project_kernel(PV* __restrict__ pv, Src s
   const float X = ((P[0] * x + P[1] * y) + P[2] * z) + P[3];
   const float Y = ((P[4] * x + P[5] * y) + P[6] * z) + P[7];
   const float Z = ((P[8] * x + P[9] * y) + P[10] * z) + P[11];
+  const auto& K = cam.at(b);
   PV o;
   o.u = K.v[0] * X / Z + K.v[2];
   o.v = K.v[4] * Y / Z + K.v[5];
@@ -421,9 +424,12 @@ static int render_front(deepim_ctx* ctx, const Src& src, int max_V, int max_F, c
     ctx->zbuf_dirty = 0;
   }
   PV* pv = (PV*)scratch;
-  Mat3 K;
-  for (int i = 0; i < 9; ++i) K.v[i] = K_host[i];
-  hipLaunchKernelGGL(project_kernel<Src>, dim3(di_div_up(max_V, 256), B), dim3(256), 0, ctx->stream, pv, src, poses, K, words);
+  if (K_host)
+    hipLaunchKernelGGL((project_kernel<Src, CamOne>), dim3(di_div_up(max_V, 256), B), dim3(256), 0, ctx->stream, pv, src, poses,
+                       cam_one(K_host), words);
+  else      // the bound camera table (the entry has checked it with DI_CAMERA)
+    hipLaunchKernelGGL((project_kernel<Src, CamTable>), dim3(di_div_up(max_V, 256), B), dim3(256), 0, ctx->stream, pv, src, poses,
+                       CamTable{ctx->cam_table}, words);
   DI_LAUNCH_CHECK();
   ctx->zbuf_dirty = 1;
   hipLaunchKernelGGL(raster_kernel<Src>, dim3(di_div_up(max_F, 256), B), dim3(256), 0, ctx->stream, ctx->zbuf, pv, src, H, W, znear,
@@ -474,6 +480,7 @@ extern "C" int deepim_render_forward(deepim_ctx* ctx, float* image, float* depth
                                      const float* pixel_means_host, int V, int F, int B, int H, int W, float znear,
                                      float zfar) {
   DI_DEVICE(ctx);
+  DI_CAMERA(ctx, K_host, B, "deepim_render_forward");
   return render_impl(ctx, image, depth, nullptr, nullptr, 0.f, vertices, vertex_attr, faces, texture, tex_h, tex_w, poses,
                      K_host, pixel_means_host, V, F, B, H, W, znear, zfar);
 }
@@ -485,6 +492,7 @@ extern "C" int deepim_render_update_forward(deepim_ctx* ctx, float* image, float
                                             const float* pixel_means_host, int V, int F, int B, int H, int W,
                                             float znear, float zfar) {
   DI_DEVICE(ctx);
+  DI_CAMERA(ctx, K_host, B, "deepim_render_update_forward");
   DI_REQUIRE(mask_rendered != nullptr, "render_update: mask_rendered is NULL");
   return render_impl(ctx, image, depth, mask_rendered, mask_box, mask_thresh, vertices, vertex_attr, faces, texture, tex_h,
                      tex_w, poses, K_host, pixel_means_host, V, F, B, H, W, znear, zfar);
@@ -499,6 +507,7 @@ extern "C" int deepim_render_lit_forward(deepim_ctx* ctx, float* image, float* d
                                          const float* light_offset_host, const float* light_intensity,
                                          float brightness_ratio, int V, int F, int B, int H, int W, float znear, float zfar) {
   DI_DEVICE(ctx);
+  DI_CAMERA(ctx, K_host, B, "deepim_render_lit_forward");
   DI_REQUIRE(normals != nullptr && light_offset_host != nullptr, "render_lit: normals and light offset are required");
   DI_REQUIRE(brightness_ratio >= 0.f && brightness_ratio <= 1.f, "render_lit: brightness_ratio in [0, 1]");
   DI_REQUIRE(mask_box == nullptr || mask_rendered != nullptr, "render_lit: mask_box needs mask_rendered");
@@ -519,6 +528,7 @@ extern "C" int deepim_render_classes_forward(deepim_ctx* ctx, float* image, floa
                                              float znear, float zfar) {
   DI_DEVICE(ctx);
   if (B == 0) return 0;
+  DI_CAMERA(ctx, K_host, B, "deepim_render_classes_forward");
   DI_REQUIRE(n_classes > 0 && max_V > 0 && max_F > 0 && H > 0 && W > 0, "render_classes: empty mesh table or image");
   DI_REQUIRE(class_index != nullptr && mesh_desc != nullptr, "render_classes: class_index and mesh_desc are required");
   DI_REQUIRE(mask_box == nullptr || mask_rendered != nullptr, "render_classes: mask_box needs mask_rendered");
@@ -545,6 +555,7 @@ extern "C" int deepim_render_observed_forward(deepim_ctx* ctx, uint8_t* image, u
   DI_DEVICE(ctx);
   DI_REQUIRE(B >= 0 && N >= B, "render_observed: the outputs need N >= B >= 0 rows");
   if (B == 0) return 0;
+  DI_CAMERA(ctx, K_host, B, "deepim_render_observed_forward");
   DI_REQUIRE(n_classes > 0 && max_V > 0 && max_F > 0 && H > 0 && W > 0, "render_observed: empty mesh table or image");
   DI_REQUIRE(image && depth && label, "render_observed: image, depth and label are required");
   DI_REQUIRE(class_index != nullptr && mesh_desc != nullptr, "render_observed: class_index and mesh_desc are required");

@@ -53,6 +53,8 @@ extern "C" int deepim_create(int device_id, deepim_ctx** out) {
   c->comm = nullptr;
   c->comm_rank = 0;
   c->comm_world = 1;
+  c->cam_table = nullptr;
+  c->cam_n = 0;
   deepim_ctx_default_options(c);
   hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
   if (e != hipSuccess) {
@@ -256,6 +258,26 @@ extern "C" int deepim_get_option(deepim_ctx* ctx, const char* name, int* value) 
   deepim_set_error_msg("deepim_get_option: unknown option");
   return -1;
 }
+// Per-pair cameras: the context remembers (pointer, n) and nothing else — no copy, no launch, no allocation. The kernels read the
+// rows when they run, so a captured graph replays for whatever the table holds then.
+extern "C" int deepim_bind_cameras(deepim_ctx* ctx, const float* K_table, int n) {
+  DI_REQUIRE(ctx != nullptr, "deepim_bind_cameras: ctx is NULL");
+  DI_REQUIRE(K_table == nullptr || n >= 1, "deepim_bind_cameras: a table needs n >= 1 rows");
+  ctx->cam_table = K_table;
+  ctx->cam_n = K_table ? n : 0;
+  return 0;
+}
+int deepim_camera_check(deepim_ctx* ctx, const float* K_host, int B, const char* entry) {
+  if (K_host != nullptr || B <= 0) return 0;
+  if (ctx->cam_table != nullptr && ctx->cam_n >= B) return 0;
+  if (ctx->cam_table == nullptr)
+    snprintf(g_err, sizeof(g_err), "%s: K_host is NULL and no camera table is bound (deepim_bind_cameras)", entry);
+  else
+    snprintf(g_err, sizeof(g_err), "%s: K_host is NULL and the bound camera table has %d rows for a batch of %d", entry,
+             ctx->cam_n, B);
+  return -1;
+}
+
 extern "C" int deepim_sync(deepim_ctx* ctx) {
   DI_DEVICE(ctx);
   DI_CHECK(hipStreamSynchronize(ctx->stream));

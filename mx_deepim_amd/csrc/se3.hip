@@ -496,10 +496,13 @@ __device__ __forceinline__ double wave_sum_d(double v) {
 
 // one block per pair; est/gt transformed points staged in LDS tiles for the brute-force nearest neighbour
 constexpr int PE_TILE = 1024;
+// Cam: CamOne (K by value) or CamTable (pair b = blockIdx.x reads row b of the bound table, for arp_2d's projection)
+template <class Cam>
 __global__ __launch_bounds__(256) void pose_error_kernel(float* __restrict__ out, const float* __restrict__ pose_est,
                                                          const float* __restrict__ pose_gt, const float* __restrict__ pts,
-                                                         long pts_bstride, Mat3 K, int N) {
+                                                         long pts_bstride, Cam cam, int N) {
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const auto& K = cam.at(b);
   const float* E = pose_est + b * 12;
   const float* G = pose_gt + b * 12;
   const float* p = pts + (long)b * pts_bstride;
@@ -685,11 +688,14 @@ extern "C" int deepim_pose_error(deepim_ctx* ctx, float* out, const float* pose_
                                  const float* points, int points_shared, const float* K_host, int B, int N) {
   DI_DEVICE(ctx);
   if (B == 0) return 0;
+  DI_CAMERA(ctx, K_host, B, "deepim_pose_error");
   DI_REQUIRE(N > 0, "pose_error: need at least one model point");
-  Mat3 K;
-  for (int i = 0; i < 9; ++i) K.v[i] = K_host[i];
-  hipLaunchKernelGGL(pose_error_kernel, dim3(B), dim3(256), 0, ctx->stream, out, pose_est, pose_gt, points,
-                     points_shared ? 0L : (long)3 * N, K, N);
+  if (K_host)
+    hipLaunchKernelGGL(pose_error_kernel<CamOne>, dim3(B), dim3(256), 0, ctx->stream, out, pose_est, pose_gt, points,
+                       points_shared ? 0L : (long)3 * N, cam_one(K_host), N);
+  else
+    hipLaunchKernelGGL(pose_error_kernel<CamTable>, dim3(B), dim3(256), 0, ctx->stream, out, pose_est, pose_gt, points,
+                       points_shared ? 0L : (long)3 * N, CamTable{ctx->cam_table}, N);
   DI_LAUNCH_CHECK();
   return 0;
 }

@@ -87,8 +87,11 @@ __global__ __launch_bounds__(256) void bbox_kernel(int* __restrict__ box, const 
 // tx = cx / W * 2 - 1 — rounded once when stored to the float32 zoom_factor.
 // rearm: the accumulators are the context's persistent ones — put them back to "empty" once read, so that the NEXT zoom-factor
 // computation needs no init launch (they are armed at context creation; every consumer re-arms exactly what it read)
+// Cam: CamOne (K by value) or CamTable (pair b reads row b of the bound table); the row is data — a non-finite or singular one
+// gives its pair a NaN factor, and no address depends on it
+template <class Cam>
 __global__ void zoom_factor_kernel(float* __restrict__ zoom_factor, int* __restrict__ status,
-                                   int* __restrict__ box, const float* __restrict__ src_pose, Mat3 K, int B,
+                                   int* __restrict__ box, const float* __restrict__ src_pose, Cam cam, int B,
                                    int H, int W, int rearm) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
@@ -109,6 +112,7 @@ __global__ void zoom_factor_kernel(float* __restrict__ zoom_factor, int* __restr
   const double rsx = real[0], rex = real[1], rsy = real[2], rey = real[3];
   const float* t = src_pose + b * 12;
   const float t0 = t[3], t1 = t[7], t2 = t[11];
+  const auto& K = cam.at(b);
   const float c0 = K.v[0] * t0 + K.v[1] * t1 + K.v[2] * t2;
   const float c1 = K.v[3] * t0 + K.v[4] * t1 + K.v[5] * t2;
   const float c2 = K.v[6] * t0 + K.v[7] * t1 + K.v[8] * t2;
@@ -648,9 +652,8 @@ Chan make_chan(const float* src, float* dst, long sb, long db, float mean, int f
   return c;
 }
 
-Mat3 mat3_from(const float* h) { Mat3 m; for (int i = 0; i < 9; ++i) m.v[i] = h[i]; return m; }
-
 // boxes + factor; scratch layout: [B*2*4 int boxes]; status word lives in ctx->status
+// K_host == NULL: the bound camera table (the entry has checked it with DI_CAMERA)
 int compute_zoom_factor(deepim_ctx* ctx, float* zoom_factor, const float* map0, const float* map1, int mode0, int mode1,
                         const float* means3, const float* src_pose, const float* K_host, int B, int H, int W) {
   // up to DI_MAX_BOX_SAMPLES pairs the accumulators are the context's persistent, self-re-arming ones (no init launch: one of the
@@ -676,8 +679,12 @@ int compute_zoom_factor(deepim_ctx* ctx, float* zoom_factor, const float* map0, 
   if (persistent) ctx->zoom_box_dirty = 1;
   hipLaunchKernelGGL(bbox_kernel, grid, dim3(256), 0, ctx->stream, box, map0, map1, mode0, mode1, means, H, W);
   DI_LAUNCH_CHECK();
-  hipLaunchKernelGGL(zoom_factor_kernel, dim3(di_div_up(B, 64)), dim3(64), 0, ctx->stream, zoom_factor, status, box,
-                     src_pose, mat3_from(K_host), B, H, W, persistent ? 1 : 0);
+  if (K_host)
+    hipLaunchKernelGGL(zoom_factor_kernel<CamOne>, dim3(di_div_up(B, 64)), dim3(64), 0, ctx->stream, zoom_factor, status, box,
+                       src_pose, cam_one(K_host), B, H, W, persistent ? 1 : 0);
+  else
+    hipLaunchKernelGGL(zoom_factor_kernel<CamTable>, dim3(di_div_up(B, 64)), dim3(64), 0, ctx->stream, zoom_factor, status, box,
+                       src_pose, CamTable{ctx->cam_table}, B, H, W, persistent ? 1 : 0);
   DI_LAUNCH_CHECK();
   if (persistent) ctx->zoom_box_dirty = 0;   // the consumer is queued: it resets what it reads
   return 0;
@@ -691,6 +698,7 @@ extern "C" int deepim_zoom_mask_forward(deepim_ctx* ctx, const float* mask_obser
                                         float* zoom_mask_rendered, float* zoom_factor, int B, int H, int W) {
   DI_DEVICE(ctx);
   if (B == 0) return 0;
+  DI_CAMERA(ctx, K_host, B, "deepim_zoom_mask_forward");
   int rc = compute_zoom_factor(ctx, zoom_factor, mask_gt_observed, mask_rendered, BB_MASK_GT, BB_MASK_RENDERED, nullptr,
                                src_pose, K_host, B, H, W);
   if (rc) return rc;
@@ -717,6 +725,7 @@ extern "C" int deepim_zoom_image_forward(deepim_ctx* ctx, const float* image_obs
                                          int B, int H, int W) {
   DI_DEVICE(ctx);
   if (B == 0) return 0;
+  DI_CAMERA(ctx, K_host, B, "deepim_zoom_image_forward");
   int rc = compute_zoom_factor(ctx, zoom_factor, image_observed, image_rendered, BB_IMAGE, BB_IMAGE, pixel_means_host,
                                src_pose, K_host, B, H, W);
   if (rc) return rc;
@@ -821,6 +830,7 @@ struct FrontEnd {
   bool frames;                // false: g.image_observed / g.depth_observed
   const float* box_observed;  // ZoomMask's observed map; NULL: g.mask_observed, and the two images when there are no masks
   FrontForm form;
+  const char* entry;          // the C entry's name, for the camera rule's error
   const char* need_masks;     // the entry's wording of its three refusals (need_together: NULL = nothing to check)
   const char* need_together;
   const char* need_aligned;
@@ -853,6 +863,7 @@ static int launch_front_end(deepim_ctx* ctx, FrontEnd e, const float* src_pose, 
                             const float* pixel_means_host, float* zoom_factor, int B, int H, int W) {
   DI_DEVICE(ctx);
   if (B == 0) return 0;
+  DI_CAMERA(ctx, K_host, B, e.entry);
   ConcatArgs& g = e.g;
   const FrameArgs& f = e.f;
   const bool with_mask = g.mask_observed != nullptr;
@@ -918,14 +929,28 @@ static int launch_front_end(deepim_ctx* ctx, FrontEnd e, const float* src_pose, 
   return 0;
 }
 
+// the planes front end from per-pair tensors: the test graph (mask_gt_observed NULL) and the training graph
+static int planes_front_end(deepim_ctx* ctx, const char* entry, const float* image_observed, const float* image_rendered,
+                            const float* mask_observed, const float* mask_gt_observed, const float* mask_rendered,
+                            const float* depth_observed, const float* depth_rendered, const float* src_pose,
+                            const float* K_host, const float* pixel_means_host, float* net_input, float* zoom_factor, int B,
+                            int H, int W) {
+  FrontEnd e = front_end(image_observed, image_rendered, mask_observed, mask_rendered, depth_observed, depth_rendered);
+  e.box_observed = mask_gt_observed;
+  e.form = FORM_PLANES; e.g.net_input = net_input;
+  e.entry = entry;
+  e.need_masks = "zoom_concat: pass both masks or neither";
+  return launch_front_end(ctx, e, src_pose, K_host, pixel_means_host, zoom_factor, B, H, W);
+}
+
 extern "C" int deepim_zoom_concat_forward(deepim_ctx* ctx, const float* image_observed, const float* image_rendered,
                                           const float* mask_observed, const float* mask_rendered,
                                           const float* depth_observed, const float* depth_rendered,
                                           const float* src_pose, const float* K_host, const float* pixel_means_host,
                                           float* net_input, float* zoom_factor, int B, int H, int W) {
-  return deepim_zoom_concat_train_forward(ctx, image_observed, image_rendered, mask_observed, nullptr, mask_rendered,
-                                          depth_observed, depth_rendered, src_pose, K_host, pixel_means_host, net_input,
-                                          zoom_factor, B, H, W);
+  return planes_front_end(ctx, "deepim_zoom_concat_forward", image_observed, image_rendered, mask_observed, nullptr,
+                          mask_rendered, depth_observed, depth_rendered, src_pose, K_host, pixel_means_host, net_input,
+                          zoom_factor, B, H, W);
 }
 
 // the shipped 8-channel front end (masks, no depth) writing channel-blocked records (B,H,W,8) for conv1's NC8 kernel
@@ -935,6 +960,7 @@ extern "C" int deepim_zoom_concat_forward_nc8(deepim_ctx* ctx, const float* imag
                                               float* zoom_factor, int B, int H, int W) {
   FrontEnd e = front_end(image_observed, image_rendered, mask_observed, mask_rendered, nullptr, nullptr);
   e.form = FORM_NC8; e.g.net_input = net_input_nc8;
+  e.entry = "deepim_zoom_concat_forward_nc8";
   e.need_masks = "zoom_concat_nc8: the 8-channel input needs both masks";
   e.need_aligned = "zoom_concat_nc8: W % 4 == 0 and a 16-byte aligned output";
   return launch_front_end(ctx, e, src_pose, K_host, pixel_means_host, zoom_factor, B, H, W);
@@ -948,6 +974,7 @@ extern "C" int deepim_zoom_concat_forward_h16(deepim_ctx* ctx, const float* imag
                                               float* zoom_factor, int B, int H, int W) {
   FrontEnd e = front_end(image_observed, image_rendered, mask_observed, mask_rendered, depth_observed, depth_rendered);
   e.form = FORM_H16; e.main8 = (_Float16*)main8; e.extra2 = (_Float16*)extra2;
+  e.entry = "deepim_zoom_concat_forward_h16";
   e.need_masks = "zoom_concat_h16: needs both masks (8- or 10-channel input)";
   e.need_together = "zoom_concat_h16: depth pair and extra2 go together";
   e.need_aligned = "zoom_concat_h16: W % 4 == 0, 16-byte aligned outputs";
@@ -980,6 +1007,7 @@ extern "C" int deepim_zoom_concat_frames_forward(deepim_ctx* ctx, const uint8_t*
   FrontEnd e = frames_front_end(ctx, frames_bgr8, frame_index, N, image_rendered, mask_observed, mask_rendered, depth_frames16,
                                 depth_labels, mask_idx, depth_factor, depth_rendered);
   e.form = FORM_PLANES; e.g.net_input = net_input;
+  e.entry = "deepim_zoom_concat_frames_forward";
   e.need_aligned = "zoom_concat_frames: W % 4 == 0 and 16-byte aligned outputs";
   return launch_front_end(ctx, e, src_pose, K_host, pixel_means_host, zoom_factor, B, H, W);
 }
@@ -994,6 +1022,7 @@ extern "C" int deepim_zoom_concat_frames_forward_h16(deepim_ctx* ctx, const uint
   FrontEnd e = frames_front_end(ctx, frames_bgr8, frame_index, N, image_rendered, mask_observed, mask_rendered, depth_frames16,
                                 depth_labels, mask_idx, depth_factor, depth_rendered);
   e.form = FORM_H16; e.main8 = (_Float16*)main8; e.extra2 = (_Float16*)extra2;
+  e.entry = "deepim_zoom_concat_frames_forward_h16";
   e.need_together = "zoom_concat_frames_h16: depth pair and extra2 go together";
   e.need_aligned = "zoom_concat_frames_h16: W % 4 == 0 and 16-byte aligned outputs";
   return launch_front_end(ctx, e, src_pose, K_host, pixel_means_host, zoom_factor, B, H, W);
@@ -1007,11 +1036,9 @@ extern "C" int deepim_zoom_concat_train_forward(deepim_ctx* ctx, const float* im
                                                 const float* depth_rendered, const float* src_pose, const float* K_host,
                                                 const float* pixel_means_host, float* net_input, float* zoom_factor, int B,
                                                 int H, int W) {
-  FrontEnd e = front_end(image_observed, image_rendered, mask_observed, mask_rendered, depth_observed, depth_rendered);
-  e.box_observed = mask_gt_observed;
-  e.form = FORM_PLANES; e.g.net_input = net_input;
-  e.need_masks = "zoom_concat: pass both masks or neither";
-  return launch_front_end(ctx, e, src_pose, K_host, pixel_means_host, zoom_factor, B, H, W);
+  return planes_front_end(ctx, "deepim_zoom_concat_train_forward", image_observed, image_rendered, mask_observed,
+                          mask_gt_observed, mask_rendered, depth_observed, depth_rendered, src_pose, K_host, pixel_means_host,
+                          net_input, zoom_factor, B, H, W);
 }
 
 extern "C" int deepim_selfcheck_div255(deepim_ctx* ctx, unsigned long long* mismatches_host) {

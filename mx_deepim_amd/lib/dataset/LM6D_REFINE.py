@@ -56,7 +56,8 @@ class LM6D_REFINE(object):
 
     # ------------------------------------------------------------------------------------------ per-pose metrics
     def _device_metrics(self, cls_name, est, gt, K):
-        """est, gt (n,3,4) → (n,5) [re°, te, add, adi, arp_2d] from ONE deepim_pose_error launch."""
+        """est, gt (n,3,4) → (n,5) [re°, te, add, adi, arp_2d] from ONE deepim_pose_error launch. K: (3,3), one camera for all
+        poses, or (n,3,3), pose b's own (bound as the context's camera table; only arp_2d reads it)."""
         from ...runtime import Context, lib
         if self._ctx is None:
             self._ctx = Context.default()
@@ -64,17 +65,28 @@ class LM6D_REFINE(object):
         n = len(est)
         pts = np.ascontiguousarray(np.asarray(self._points[cls_name], np.float32).T)          # (3,N)
         out = ctx.empty((n, 5))
-        lib.deepim_pose_error(ctx.handle, out, ctx.array(np.ascontiguousarray(est, np.float32)),
-                              ctx.array(np.ascontiguousarray(gt, np.float32)), ctx.array(pts), 1,
-                              np.ascontiguousarray(K, np.float32), n, pts.shape[1])
-        return out.asnumpy().astype(np.float64)
+        K = np.ascontiguousarray(K, np.float32)
+        if K.ndim == 3:
+            if len(K) != n:
+                raise ValueError("one camera per pose: %d cameras for %d poses" % (len(K), n))
+            ctx.bind_cameras(K)
+            K = None
+        try:
+            lib.deepim_pose_error(ctx.handle, out, ctx.array(np.ascontiguousarray(est, np.float32)),
+                                  ctx.array(np.ascontiguousarray(gt, np.float32)), ctx.array(pts), 1, K, n, pts.shape[1])
+            return out.asnumpy().astype(np.float64)
+        finally:
+            if K is None:
+                ctx.bind_cameras(None)      # the table was this call's own
 
-    def pose_metrics(self, config, all_poses_est, all_poses_gt):
+    def pose_metrics(self, config, all_poses_est, all_poses_gt, all_K=None):
         """name → (num_iter, n, 4) float64: [rot° , trans m] as evaluate_pose uses them (eggbox half-turn rule on
         calc_rt_dist_m > 90°, :304-309), the ADD / ADD-S error as evaluate_pose_add uses it (:423-428: ADI for
-        eggbox/glue/bowl/cup, no half-turn rule), arp_2d as evaluate_pose_arp_2d uses it (rule on re > 90°, :563-571)."""
+        eggbox/glue/bowl/cup, no half-turn rule), arp_2d as evaluate_pose_arp_2d uses it (rule on re > 90°, :563-571).
+        all_K (per-pair cameras of the test loop): all_K[cls] is parallel to all_poses_gt[cls][0], one (3,3) per pose; arp_2d of
+        a pose is then taken with its own camera — tiled over the iterations as the ground truth is, and the flipped rows'
+        cameras for the eggbox re-evaluation. None: config.dataset.INTRINSIC_MATRIX for every pose."""
         num_iter = config.TEST.test_iter
-        K = config.dataset.INTRINSIC_MATRIX
         res = {}
         for ci, name in enumerate(self.classes):
             if not (len(all_poses_est[ci][0]) and len(all_poses_gt[ci][0])):
@@ -83,21 +95,28 @@ class LM6D_REFINE(object):
             n = len(gt)
             est = np.asarray([all_poses_est[ci][it] for it in range(num_iter)], np.float32).reshape(num_iter * n, 3, 4)
             gtt = np.tile(gt, (num_iter, 1, 1))
+            if all_K is None:
+                K = config.dataset.INTRINSIC_MATRIX
+            else:
+                K = np.asarray(all_K[ci], np.float32).reshape(-1, 3, 3)
+                if len(K) != n:
+                    raise ValueError("all_K[%d] holds %d cameras for %d poses" % (ci, len(K), n))
+                K = np.tile(K, (num_iter, 1, 1))
             m = self._device_metrics(name, est, gtt, K)
             out = np.stack([m[:, 0], m[:, 1], m[:, 3] if name in SYM_ADI else m[:, 2], m[:, 4]], 1)
             if name == "eggbox":
                 flip = m[:, 0] > 90
                 if flip.any():
-                    ms = self._device_metrics(name, _turn_z(est[flip]), gtt[flip], K)
+                    ms = self._device_metrics(name, _turn_z(est[flip]), gtt[flip], K if all_K is None else K[flip])
                     out[flip, 0], out[flip, 1], out[flip, 3] = ms[:, 0], ms[:, 1], ms[:, 4]
             res[name] = out.reshape(num_iter, n, 4)
         return res
 
     # ------------------------------------------------------------------------------- (n°, n cm), :278-370
-    def evaluate_pose(self, config, all_poses_est, all_poses_gt, metrics=None):
+    def evaluate_pose(self, config, all_poses_est, all_poses_gt, metrics=None, all_K=None):
         log = self.logger
         log.info("evaluating pose")
-        metrics = metrics if metrics is not None else self.pose_metrics(config, all_poses_est, all_poses_gt)
+        metrics = metrics if metrics is not None else self.pose_metrics(config, all_poses_est, all_poses_gt, all_K)
         rot_thresh_list = np.arange(1, 11, 1)
         trans_thresh_list = np.arange(0.01, 0.11, 0.01)
         num_metric = len(rot_thresh_list)
@@ -216,9 +235,9 @@ class LM6D_REFINE(object):
                 "num_valid_class": num_valid_class}
 
     # ------------------------------------------------------------------------------- ADD / ADD-S, :372-512
-    def evaluate_pose_add(self, config, all_poses_est, all_poses_gt, output_dir=None, metrics=None):
+    def evaluate_pose_add(self, config, all_poses_est, all_poses_gt, output_dir=None, metrics=None, all_K=None):
         self.logger.info("evaluating pose add")
-        metrics = metrics if metrics is not None else self.pose_metrics(config, all_poses_est, all_poses_gt)
+        metrics = metrics if metrics is not None else self.pose_metrics(config, all_poses_est, all_poses_gt, all_K)
         eval_method = "adi" if any(c in SYM_ADI for c in self.classes if c in metrics) else "add"     # :381, :426 (sticky)
         return self._threshold_tables(
             config, metrics, 2, {"0.02": 0.02, "0.05": 0.05, "0.10": 0.10}, np.arange(0, 0.1, 0.0001), 0.0001,
@@ -226,9 +245,9 @@ class LM6D_REFINE(object):
             "---------- add performance over {} classes -----------", False, output_dir, "{}_xys.pkl".format(eval_method))
 
     # ------------------------------------------------------------------------------- arp 2D, :514-674
-    def evaluate_pose_arp_2d(self, config, all_poses_est, all_poses_gt, output_dir=None, metrics=None):
+    def evaluate_pose_arp_2d(self, config, all_poses_est, all_poses_gt, output_dir=None, metrics=None, all_K=None):
         self.logger.info("evaluating pose average re-projection 2d error")
-        metrics = metrics if metrics is not None else self.pose_metrics(config, all_poses_est, all_poses_gt)
+        metrics = metrics if metrics is not None else self.pose_metrics(config, all_poses_est, all_poses_gt, all_K)
         return self._threshold_tables(
             config, metrics, 3, {"2": 2.0, "5": 5.0, "10": 10.0, "20": 20.0}, np.arange(0, 50, 0.1), 0.1, lambda c: 1.0,
             "threshold=[0, 50]", 50.0, 100.0,

@@ -123,8 +123,11 @@ def update_test_batch(cfg, data, render_machine, refined_pose, class_index=None,
     With the lit ModelNet render machine (tester.py:114-172) `light_intensity` = device (B,3) per-sample light colour (the
     reference draws U(0.9, 1.1) per render; None = 1.0).
     `class_index`: None, a scalar or a host sequence of B ids (one launch group per run of equal ids), or a device int32 array
-    of B ids (one launch group for the whole batch, no read-back)."""
+    of B ids (one launch group for the whole batch, no read-back).
+    data["intrinsics"] (DeviceArray (B,3,3), per-pair cameras) goes to the render machine as `K=` — its [b0:b1] slice to each run
+    on the host-id path — and stays in the returned batch; without it the machine draws with its own K."""
     ctx = refined_pose.context
+    cams = data.get("intrinsics")
     B, H, W = refined_pose.shape[0], render_machine.height, render_machine.width
     out = out or {}
     image = out.get("image_rendered") or ctx.empty((B, 3, H, W))
@@ -143,7 +146,7 @@ def update_test_batch(cfg, data, render_machine, refined_pose, class_index=None,
     if is_device_ids(class_index) and class_index.size == B:
         # class ids resident on the device: ONE fused pass (draw, mask_rendered = depth > 0.2, rectangle) over the whole mixed
         # batch; the host never reads the ids, so a captured graph of the iteration replays for any batch's objects
-        render_machine.render_classes_into(image, depth, class_index, refined_pose, mask_rendered=mask, mask_box=box,
+        render_machine.render_classes_into(image, depth, class_index, refined_pose, K=cams, mask_rendered=mask, mask_box=box,
                                            mask_thresh=0.2, light_intensity=light_intensity)
         return _updated(cfg, new, image, depth, mask, box, refined_pose)
     # host ids: one fused pass per run of equal class ids
@@ -156,6 +159,7 @@ def update_test_batch(cfg, data, render_machine, refined_pose, class_index=None,
         while b1 < B and ids[b1] == ids[b0]:
             b1 += 1
         render_machine.render_into(image[b0:b1], depth[b0:b1], ids[b0], refined_pose[b0:b1],
+                                   K=None if cams is None else cams[b0:b1],
                                    mask_rendered=None if mask is None else mask[b0:b1],
                                    mask_box=None if box is None else box[b0:b1], mask_thresh=0.2,
                                    light_intensity=None if light_intensity is None else light_intensity[b0:b1])

@@ -18,6 +18,7 @@ import ctypes
 
 import numpy as np
 
+from ...cameras import validate_cameras
 from ...runtime import DeviceArray, lib
 from ..utils import image as _image
 from ..utils.mask_dilate import mask_dilate_batch
@@ -95,7 +96,9 @@ def get_data_pair_test_batch(frames, config):
     image_observed [and depth_observed] are replaced by ONE entry, data["observed_frames"] (lib/utils/image.ObservedFrames): the
     uint8 / uint16 frames on the device with the device frame_index [, the label maps, mask_idx and DEPTH_FACTOR of the observed
     depth], which the network's zoom front end reads in place. A numpy frame_index outside [0, N) raises ValueError before
-    anything is uploaded or launched."""
+    anything is uploaded or launched.
+    frames["intrinsics"] — per-pair cameras, a (B,3,3) numpy array (validated and uploaded once) or a DeviceArray — is passed
+    through as data["intrinsics"]: the zoom front end and the re-render then take pair b's camera from row b."""
     data = {}
     shared = _image.is_shared(frames)
     if shared:
@@ -115,6 +118,13 @@ def get_data_pair_test_batch(frames, config):
         pose = ctx.array(np.asarray(pose, dtype=np.float32).reshape(B, 3, 4))
     data["src_pose"] = pose
     data["class_index"] = frames.get("class_index")
+    cams = frames.get("intrinsics")
+    if cams is not None:
+        if not isinstance(cams, DeviceArray):
+            cams = ctx.array(validate_cameras(cams))
+        if cams.shape != (B, 3, 3):
+            raise ValueError("frames['intrinsics'] must be (%d,3,3), got %s" % (B, cams.shape))
+        data["intrinsics"] = cams
     if config.network.INPUT_DEPTH and shared:
         data["depth_rendered"] = _image._depth(ctx, frames, "depth_rendered", config)
     elif config.network.INPUT_DEPTH:

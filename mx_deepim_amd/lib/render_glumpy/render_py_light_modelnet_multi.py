@@ -91,9 +91,9 @@ class Render_Py_Light_ModelNet_Multi(Render_Py):
     def render_into(self, image, depth, cls_idx, poses, K=None, pixel_means="default", mask_rendered=None, mask_box=None,
                     mask_thresh=0.2, light_offset=None, light_intensity=None, brightness_k=0):
         """As Render_Py.render_into, lit: light at `light_offset` (default 0.5·[0,1,1]) + (t_x, −t_y, −t_z) of every sample's
-        pose, `light_intensity` = device (n,3) or None (white, 1.0)."""
+        pose, `light_intensity` = device (n,3) or None (white, 1.0). `K`: as in Render_Py.render_into."""
         m, nrm = self.mesh_list[int(cls_idx)], self.normal_list[int(cls_idx)]
-        K = self.K if K is None else np.ascontiguousarray(K, dtype=np.float32).reshape(3, 3)
+        K = self._camera(K, poses.shape[0])
         means = self.pixel_means if isinstance(pixel_means, str) else pixel_means
         off = np.ascontiguousarray(LIGHT_OFFSET if light_offset is None else light_offset, np.float32).reshape(3)
         lib.deepim_render_lit_forward(self.ctx.handle, image, depth, mask_rendered, mask_box, ctypes.c_float(mask_thresh), m.vertices,

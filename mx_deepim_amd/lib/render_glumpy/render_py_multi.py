@@ -22,7 +22,7 @@ import os
 
 import numpy as np
 
-from ...runtime import Context, lib
+from ...runtime import Context, DeviceArray, lib
 
 
 def quat2mat(q):
@@ -191,15 +191,29 @@ class Render_Py(object):
                                         texture=load_texture(os.path.join(folder, "texture_map.png"))))
 
     # -- device API ----------------------------------------------------------------------------------------------
+    def _camera(self, K, n):
+        """`K=` of the draw methods → the C entry's K_host: the machine's K (None), a host (3,3), or — for a DeviceArray (n,3,3)
+        whose leading axis is the call's batch, sample b drawn with row b — NULL after binding it as the context's camera table
+        (a leading-axis slice binds with its offset)."""
+        if K is None:
+            return self.K
+        if isinstance(K, DeviceArray):
+            if K.ndim != 3 or K.shape[0] != n:
+                raise ValueError("a device K must be (n,3,3) with n = the call's batch (%d), got %s" % (n, K.shape))
+            self.ctx.bind_cameras(K)
+            return None
+        return np.ascontiguousarray(K, dtype=np.float32).reshape(3, 3)
+
     def render_into(self, image, depth, cls_idx, poses, K=None, pixel_means="default", mask_rendered=None, mask_box=None,
                     mask_thresh=0.2, light_intensity=None):
         """image (n,3,H,W), depth (n,1,H,W), poses (n,3,4): all device arrays; one mesh. With `mask_rendered` (n,1,H,W)
         the same pass also writes depth > mask_thresh, and with `mask_box` its box_rendered rectangle. (`light_intensity` belongs
-        to the lit ModelNet machine, render_py_light_modelnet_multi.py; this unlit draw ignores it.)"""
+        to the lit ModelNet machine, render_py_light_modelnet_multi.py; this unlit draw ignores it.) `K`: None (the machine's), a
+        host (3,3), or a DeviceArray (n,3,3) of per-sample cameras (`_camera`)."""
         m = self.mesh_list[int(cls_idx)]
-        K = self.K if K is None else np.ascontiguousarray(K, dtype=np.float32).reshape(3, 3)
-        means = self.pixel_means if isinstance(pixel_means, str) else pixel_means
         n = poses.shape[0]
+        K = self._camera(K, n)
+        means = self.pixel_means if isinstance(pixel_means, str) else pixel_means
         tail = (m.vertices, m.attr, m.faces, m.texture, m.tex_h, m.tex_w, poses, K, means, m.V, m.F, n, self.height,
                 self.width, ctypes.c_float(self.zNear), ctypes.c_float(self.zFar))
         if mask_rendered is None:
@@ -225,7 +239,7 @@ class Render_Py(object):
         if mask_rendered is None and mask_box is not None:
             raise ValueError("mask_box needs mask_rendered")
         t = self.mesh_table()
-        K = self.K if K is None else np.ascontiguousarray(K, dtype=np.float32).reshape(3, 3)
+        K = self._camera(K, poses.shape[0])
         means = self.pixel_means if isinstance(pixel_means, str) else pixel_means
         lib.deepim_render_classes_forward(self.ctx.handle, image, depth, mask_rendered, mask_box, ctypes.c_float(mask_thresh),
                                           class_index, t.mesh_desc, t.n_classes, t.max_V, t.max_F, t.vertices, t.vertex_attr,
@@ -245,7 +259,8 @@ class Render_Py(object):
         Host ids: samples of the same class in consecutive runs are drawn by one launch group each. A DEVICE int32 array of B ids:
         the whole batch is one launch group (`render_classes_into`) and the ids are never read back. (A device array of another
         dtype is read back and split into runs like host ids.) `out` = (image, depth) preallocated device tensors;
-        `mask_rendered` (B,1,H,W): also written, = depth > mask_thresh, by the same pass."""
+        `mask_rendered` (B,1,H,W): also written, = depth > mask_thresh, by the same pass. `K`: as in `render_into`; a device
+        (B,3,3) table is sliced with the runs on the host-id path."""
         B = poses.shape[0]
         image, depth = out if out is not None else (self.ctx.empty((B, 3, self.height, self.width)),
                                                     self.ctx.empty((B, 1, self.height, self.width)))
@@ -263,7 +278,7 @@ class Render_Py(object):
             b1 = b0 + 1
             while b1 < B and ids[b1] == ids[b0]:
                 b1 += 1
-            self.render_into(image[b0:b1], depth[b0:b1], ids[b0], poses[b0:b1], K=K,
+            self.render_into(image[b0:b1], depth[b0:b1], ids[b0], poses[b0:b1], K=K[b0:b1] if isinstance(K, DeviceArray) else K,
                              mask_rendered=None if mask_rendered is None else mask_rendered[b0:b1], mask_thresh=mask_thresh,
                              light_intensity=None if light_intensity is None else light_intensity[b0:b1])
             b0 = b1

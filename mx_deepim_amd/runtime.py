@@ -214,6 +214,26 @@ class Context:
     def sync(self):
         lib.deepim_sync(self.handle)
 
+    # -- per-pair cameras (deepim_bind_cameras): entries called with K_host = None read row b of the bound table for sample b
+    def bind_cameras(self, table):
+        """table: DeviceArray (n,3,3) float32 (a leading-axis slice binds with its offset), a numpy (n,3,3) — validated on the
+        host (finite, K[2,2] != 0, non-singular: ValueError) and uploaded — or None to unbind. The library keeps only the
+        pointer, so the context keeps the array alive. Returns the DeviceArray (None after an unbind)."""
+        if table is None:
+            lib.deepim_bind_cameras(self.handle, None, 0)
+            self.cameras = None
+            return None
+        if not isinstance(table, DeviceArray):
+            from .cameras import validate_cameras
+            table = self.array(validate_cameras(table))
+        if table.dtype != np.float32 or table.ndim != 3 or table.shape[1:] != (3, 3) or table.shape[0] < 1:
+            raise ValueError("bind_cameras: the table must be float32 (n,3,3) with n >= 1, got %s %s" % (table.dtype, table.shape))
+        lib.deepim_bind_cameras(self.handle, table, table.shape[0])
+        self.cameras = table
+        return table
+
+    cameras = None      # what bind_cameras bound last (kept alive here: the library holds a bare pointer)
+
     # -- HIP-event stopwatch on the context stream
     def timer(self):
         t = ctypes.c_int()

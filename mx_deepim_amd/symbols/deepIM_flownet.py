@@ -585,8 +585,17 @@ class deepIM_flownet(TrainGraph):
         whose observed image [and depth] are gathered from the N uint8 / uint16 frames through the device frame_index; the library
         refuses the mask-less ZoomImage configuration there.
         Output form: conv1's fp16 pixel records on the fused fp16 path, the opt-in NC8 records (_conv1_from_nc8; per-pair tensors
-        only, there is no shared-frame variant), else the NCHW net input that the fp32, x3 and two-step fp16 encoders read."""
+        only, there is no shared-frame variant), else the NCHW net input that the fp32, x3 and two-step fp16 encoders read.
+        Camera: the run's `self.K`, or — with data["intrinsics"], a DeviceArray (B,3,3) — pair b's own row: the table is bound
+        (Context.bind_cameras) and the entry gets NULL, in every form."""
         A, h, raw = self.act, self.ctx.handle, dict.__getitem__
+        K = self.K
+        cams = data.get("intrinsics")
+        if cams is not None:
+            if not isinstance(cams, DeviceArray) or cams.shape != (self.B, 3, 3):
+                raise ValueError("data['intrinsics'] must be a DeviceArray (%d,3,3)" % self.B)
+            self.ctx.bind_cameras(cams)
+            K = None
         of = data.get("observed_frames")
         if of is not None and of.n_pairs != self.B:
             raise ValueError("observed_frames index %d pairs; the network is bound for %d" % (of.n_pairs, self.B))
@@ -614,7 +623,7 @@ class deepIM_flownet(TrainGraph):
                      "nchw": lib.deepim_zoom_concat_forward}[form]
             depths = () if form == "nc8" else (data.get("depth_observed") if self.input_depth else None, depth_rendered)
             src = (data["image_observed"], data["image_rendered"]) + masks + depths
-        entry(h, *(src + (data["src_pose"], self.K, self.pixel_means) + out + (A["zoom_factor"], self.B, self.H, self.W)))
+        entry(h, *(src + (data["src_pose"], K, self.pixel_means) + out + (A["zoom_factor"], self.B, self.H, self.W)))
 
     def encoder_fp16(self):
         """Same 10 layers on the fp16 matrix cores: NCHW fp32 net input → NHWC fp16 → convs → conv6_1 back to
