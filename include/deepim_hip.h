@@ -1034,6 +1034,28 @@ int deepim_render_observed_forward(deepim_ctx* ctx, uint8_t* image /*N,H,W,3*/, 
                                    const float* textures /*or NULL*/, const float* poses, const float* K_host /*or NULL: camera table*/,
                                    const float* light_offset /*device (B,3)*/, const float* light_intensity /*device (B,3)*/,
                                    const float* brightness_ratio /*device (B)*/, int B, int H, int W, float znear, float zfar);
+/* The UNLIT mesh-table draw of deepim_render_classes_forward (normals NULL) for the INITIAL POSES OF THE TEST PHASE
+ * (toolkit/LM6d_3_gen_PoseCNN_pred_rendered.py:149-155 writes them to disk once), stored the way deepim_render_observed_forward
+ * stores: rows of decoded frames, not tensors. The same project and raster passes, K_host or NULL = the bound camera table, an
+ * id outside [0, n_classes) = an empty frame; rows, N, the out-of-range-row rule, the two store paths and the z-buffer left
+ * all-ones are those of the observed entry. The outputs:
+ *   image    (N,H,W,3) uint8 BGR = rint(clamp(level, 0, 255)) of the unlit level deepim_render_classes_forward gives with
+ *            pixel_means NULL: cv2.imwrite of the float image saturates and rounds to nearest even. 0 on the background
+ *   depth    (N,H,W) uint16 = (uint16)(depth * depth_factor), the float32 product truncated (:151); zfar * depth_factor must
+ *            stay below 65536 (a host error before any launch)
+ *   label    (N,H,W) uint8 as in the observed entry, or NULL: not stored
+ *   covered  device int32 (B) or NULL: covered[b] = the number of pixels of sample b whose stored uint16 depth is non-zero,
+ *            whether or not the sample's row is stored. The call WRITES it (it is zeroed on the stream first and never
+ *            accumulates across calls): one atomic add per wave of the resolve pass. It is what np.sum(depth_rendered) == 0 of
+ *            lib/utils/image.py:301-303 asks, kept on the device for deepim_mask_gate; the host never reads it.
+ * B <= 65535, H*W < 2^31. Asynchronous, allocates like the other draws (scratch and z-buffer grow outside a capture only). */
+int deepim_render_frames_forward(deepim_ctx* ctx, uint8_t* image /*N,H,W,3*/, uint16_t* depth /*N,H,W*/, uint8_t* label /*N,H,W or NULL*/,
+                                 int32_t* covered /*device (B) or NULL*/, const int32_t* rows /*device (B) or NULL*/, int N,
+                                 const int32_t* label_value /*device (B) or NULL*/, float depth_factor,
+                                 const int32_t* class_index /*device (B)*/, const int32_t* mesh_desc /*device (n_classes,8)*/,
+                                 int n_classes, int max_V, int max_F, const float* vertices, const float* vertex_attr,
+                                 const int32_t* faces, const float* textures /*or NULL*/, const float* poses,
+                                 const float* K_host /*or NULL: camera table*/, int B, int H, int W, float znear, float zfar);
 
 /* ------------------------------------------- I-group: ingest of decoded frames -- */
 /* csrc/ingest.hip. What lib/utils/image.py does on the host between cv2.imread and the tensors of a batch, on frames that
@@ -1105,6 +1127,10 @@ int deepim_ingest_label_mask_frames(deepim_ctx* ctx, float* out /*B,1,H,W*/, con
  * out == mask is refused: the gather cannot run in place. */
 int deepim_mask_dilate(deepim_ctx* ctx, float* out /*B,1,H,W*/, const float* mask /*B,1,H,W*/,
                        const int32_t* thickness /*device (B,4)*/, int B, int H, int W);
+/* lib/utils/image.py:301-303 (test phase) for a batch, in place: the planes mask[b] of the samples with covered[b] == 0 (what
+ * deepim_render_frames_forward counted: an empty initial render) become zero, whatever TEST.INIT_MASK made them; the other
+ * planes are neither read nor written. Asynchronous, allocates nothing, legal inside a capture. B <= 65535. */
+int deepim_mask_gate(deepim_ctx* ctx, float* mask /*B,1,H,W, in place*/, const int32_t* covered /*device (B)*/, int B, int H, int W);
 
 /* ------------------------------------------------ training metrics (csrc/metric.hip) -- */
 /* The sums the reference's metrics take on the host once per batch (deepim/core/metric.py:51-137), as one fused reduction.

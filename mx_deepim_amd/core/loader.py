@@ -1,4 +1,7 @@
-"""The training iterator: TrainDataLoader (deepim/core/loader.py:111-262) over the device's own random draws.
+"""The data iterators of deepim/core/loader.py. TestDataLoader (:17-108), which draws every pair's initial pose as decoded
+frames on the device, is at the end of this file with its own description; first
+
+The training iterator: TrainDataLoader (deepim/core/loader.py:111-262) over the device's own random draws.
 
 The reference's loader reads, for every observed frame, ten rendered images and poses that toolkit/LM6d_1_gen_rendered_pose.py
 and LM6d_2_gen_rendered.py wrote to disk once. This one needs no such dataset: it takes the observed frames and their
@@ -43,6 +46,7 @@ shared-frame batches (frame_index), device-resident datasets, synthetic frames w
 """
 import numpy as np
 
+from ..cameras import camera_table, has_cameras
 from ..lib.pair_matching import data_pair
 from ..lib.pair_matching.pose_sampler import pose_noise, sample_rendered_poses
 from ..lib.utils import image as _image
@@ -247,3 +251,199 @@ class TrainDataLoader(object):
     def __iter__(self):
         for pairs, ids in zip(self.pairs, self.draw_ids):
             yield self.make_batch(pairs, ids)
+
+
+# ---------------------------------------------------------------------------------------------------------- the test phase --
+_TEST_DTYPES = {"image_observed": np.uint8, "depth_observed": np.uint16, "depth_gt_observed": np.uint16,
+                "mask_gt_observed": np.uint8, "mask_observed": np.uint8, "mask_observed_est": np.uint8}
+# TEST.INIT_MASK → the label map lib/utils/image.get_pair_mask reads for it (box_rendered reads the rendered depth alone)
+_INIT_MASK_SOURCE = {"mask_gt_observed": "mask_gt_observed", "box_gt_observed": "mask_gt_observed", "mask_observed": "mask_observed",
+                     "box_": "mask_observed", "box_rendered": None}
+
+
+def observed_keys_of_test(config, have=()):
+    """The observed arrays the test phase of `config` reads, no device needed: image_observed always; depth_observed with
+    network.INPUT_DEPTH (and, with MASK_INPUTS, the label map get_pair_depth zeroes it with); the label map of TEST.INIT_MASK with
+    network.INPUT_MASK; for the flow EPE (network.PRED_FLOW and not TEST.FAST_TEST) mask_gt_observed and depth_gt_observed — or
+    depth_observed when `have` (the keys on offer) holds no depth_gt_observed (tester.py:541-547)."""
+    n = config.network
+    keys = ["image_observed"]
+    if n.INPUT_DEPTH:
+        keys.append("depth_observed")
+        if n.get("MASK_INPUTS", False):
+            keys.append("mask_gt_observed" if config.dataset.get("MASK_GT", False) else "mask_observed_est")
+    if n.INPUT_MASK:
+        init = config.TEST.INIT_MASK
+        if init not in _INIT_MASK_SOURCE:
+            raise Exception("Unknown init mask type: {}".format(init))
+        if _INIT_MASK_SOURCE[init] is not None:
+            keys.append(_INIT_MASK_SOURCE[init])
+    if n.PRED_FLOW and not config.TEST.FAST_TEST:
+        keys.append("depth_gt_observed" if ("depth_gt_observed" in have or "depth_observed" not in have) else "depth_observed")
+        keys.append("mask_gt_observed")
+    return list(dict.fromkeys(keys))
+
+
+def plan_test_batches(P, batch_size, shuffle, rng):
+    """The batches of one pass over P pairs, no device needed → (pairs (n_batches, batch_size) int64, pad). The order is
+    arange(P), or rng.permutation(P) with `shuffle` (rng: a RandomState, consumed once per call). No pair is dropped: the last
+    batch is filled up with `pad` = n_batches·batch_size − P repeats of its last pair."""
+    P, batch_size = int(P), int(batch_size)
+    if P < 1 or batch_size < 1:
+        raise ValueError("plan_test_batches: P and batch_size must be >= 1")
+    order = rng.permutation(P).astype(np.int64) if shuffle else np.arange(P, dtype=np.int64)
+    n_batches = -(-P // batch_size)
+    pad = n_batches * batch_size - P
+    order = np.concatenate([order, np.full(pad, order[-1], np.int64)])
+    return order.reshape(n_batches, batch_size), pad
+
+
+def batch_frames(frame_ids):
+    """The frames a shared-frame batch uploads, no device needed → (frames (N,) ascending distinct ids, frame_index (B,) int32):
+    pair b looks at row frame_index[b] of the N <= B uploaded frames."""
+    uniq, inv = np.unique(np.asarray(frame_ids, np.int64).reshape(-1), return_inverse=True)
+    return uniq, inv.reshape(-1).astype(np.int32)
+
+
+class TestDataLoader(object):
+    """The test iterator: TestDataLoader (deepim/core/loader.py:17-108) from observed frames and initial poses alone.
+
+        loader = TestDataLoader(observed, pairdb, config, render_machine, batch_size=2)
+        pred_eval(config, Predictor(config, net), loader, imdb, logger=logger, render_machine=render_machine)
+
+    The reference reads, for every pair, the render of its initial pose that toolkit/LM6d_3_gen_PoseCNN_pred_rendered.py:149-155
+    wrote to disk once. This one DRAWS it: every batch's initial poses are rendered on the device straight into uint8 / uint16
+    frames with the bytes those files hold (Render_Py.render_frames_into), next to each pair's count of covered pixels.
+
+    `observed`: host numpy arrays for the F camera frames as the decoder left them (observed_keys_of_test says which the
+    configuration reads): image_observed (F,H,W,3) uint8 BGR; depth_observed / depth_gt_observed (F,H,W) uint16;
+    mask_gt_observed / mask_observed / mask_observed_est (F,H,W) uint8 label maps. H x W is config.SCALES[0].
+    `pairdb`: a list of P dicts with frame (index into the F frames), gt_class, mask_idx, pose_observed (3,4), pose_rendered
+    (3,4) — the initial estimate, all −1 where the detector found nothing (tester.py:285-310) — and optionally K (3,3).
+
+    Every batch is (data, frames, pair_records) as core/tester.pred_eval takes it. With `shared_frames` the distinct frames of
+    the batch are uploaded once (N <= B rows) and the pairs name them through a frame_index; without, one row per pair. mask_idx,
+    the render machine's class ids and the poses are uploaded; when a record has a K, the batch's (B,3,3) camera table too
+    (frames["intrinsics"]), and the draw uses it. frames["rendered_covered"] lets get_pair_mask zero mask_observed of a pair whose
+    draw is empty (image.py:301-303) on the device. With TEST.MASK_DILATE the thicknesses come from the device generator with
+    the pair's index in `pairdb` as its draw id: a pair's draw depends on (seed, pair) alone. Nothing is read back.
+
+    Differences from the reference: one upload per frame, not per pair; batch_size > 1; the last batch is filled up by repeating
+    its last pair, and the repeats' records are copies carrying "pad": True, which pred_eval leaves out of everything it counts
+    (the reference hands the pad count to DataBatch); the mask-dilate draws are the device generator's; the empty-draw rule is
+    applied on the device and not printed. Order: arange(P), or with `shuffle` a permutation from RandomState(seed), drawn anew
+    at each reset().
+
+    Refused: device-resident datasets, a frame that is not config.SCALES[0] or not the render machine's size, a pair whose frame
+    is outside [0, F) or whose gt_class the render machine does not know, and shared_frames with network.INPUT_MASK off (the
+    library's shared-frame zoom front end has no mask-less variant: pass shared_frames=False)."""
+    __test__ = False          # a data iterator named after the reference's, not a pytest class
+
+    def __init__(self, observed, pairdb, config, render_machine, batch_size=1, shuffle=False, seed=0, shared_frames=True):
+        self.config, self.render_machine = config, render_machine
+        self.batch_size, self.shuffle, self.seed, self.shared_frames = int(batch_size), bool(shuffle), int(seed), bool(shared_frames)
+        if self.batch_size < 1:
+            raise ValueError("TestDataLoader: batch_size must be >= 1")
+        for k, v in observed.items():
+            if isinstance(v, DeviceArray):
+                raise TypeError("TestDataLoader: observed['%s'] is a device array; the dataset is host numpy arrays, a batch's "
+                                "frames are gathered on the host and uploaded" % k)
+        if self.shared_frames and not config.network.INPUT_MASK:
+            raise NotImplementedError("TestDataLoader: shared_frames needs network.INPUT_MASK — the shared-frame zoom front end "
+                                      "has no mask-less variant; pass shared_frames=False")
+        self.keys = observed_keys_of_test(config, [k for k, v in observed.items() if v is not None])
+        self.observed = {}
+        for k in self.keys:
+            if observed.get(k) is None:
+                raise KeyError("TestDataLoader: observed carries no '%s'" % k)
+            v = np.asarray(observed[k])
+            if v.dtype != np.dtype(_TEST_DTYPES[k]):
+                raise TypeError("observed['%s'] is %s; the decoded %s frame is expected" % (k, v.dtype, np.dtype(_TEST_DTYPES[k])))
+            self.observed[k] = v
+        img = self.observed["image_observed"]
+        if img.ndim != 4 or img.shape[3] != 3 or img.shape[0] < 1:
+            raise ValueError("observed['image_observed'] has shape %s; (F,H,W,3) expected" % (img.shape,))
+        self.F, H, W = img.shape[0], img.shape[1], img.shape[2]
+        _image._check_size(config, H, W)
+        if (render_machine.height, render_machine.width) != (H, W):
+            raise ValueError("the render machine draws %dx%d, the frames are %dx%d" % (render_machine.height, render_machine.width, H, W))
+        for k in self.keys[1:]:
+            if self.observed[k].shape != (self.F, H, W):
+                raise ValueError("observed['%s'] has shape %s; %s expected" % (k, self.observed[k].shape, (self.F, H, W)))
+        self.height, self.width = H, W
+        self.pairdb = list(pairdb)
+        self.size = len(self.pairdb)
+        if self.size < 1:
+            raise ValueError("TestDataLoader: the pairdb is empty")
+        classes = list(render_machine.classes)
+        self.frame, self.mask_idx = np.zeros(self.size, np.int64), np.zeros(self.size, np.int32)
+        self.class_index, self.pose_rendered = np.zeros(self.size, np.int32), np.zeros((self.size, 3, 4), np.float32)
+        for p, rec in enumerate(self.pairdb):
+            for k in ("frame", "gt_class", "mask_idx", "pose_observed", "pose_rendered"):
+                if rec.get(k) is None:
+                    raise KeyError("TestDataLoader: pair %d carries no '%s'" % (p, k))
+            f = int(rec["frame"])
+            if not 0 <= f < self.F:
+                raise ValueError("TestDataLoader: pair %d looks at frame %d, outside the %d observed frame%s"
+                                 % (p, f, self.F, "" if self.F == 1 else "s"))
+            if rec["gt_class"] not in classes:
+                raise ValueError("TestDataLoader: pair %d is of class %r, which the render machine (%s) does not draw"
+                                 % (p, rec["gt_class"], ", ".join(map(str, classes))))
+            if np.shape(rec["pose_rendered"]) != (3, 4) or np.shape(rec["pose_observed"]) != (3, 4):
+                raise ValueError("TestDataLoader: pair %d: pose_rendered and pose_observed must be (3,4)" % p)
+            self.frame[p], self.mask_idx[p], self.class_index[p] = f, int(rec["mask_idx"]), classes.index(rec["gt_class"])
+            self.pose_rendered[p] = np.asarray(rec["pose_rendered"], np.float32)
+        self.ctx = render_machine.ctx          # touched last: every refusal above needs no device
+        self.K = np.ascontiguousarray(config.dataset.INTRINSIC_MATRIX, np.float32).reshape(3, 3)
+        self.depth_factor = float(config.dataset.get("DEPTH_FACTOR", 1000))
+        self.dilate = bool(config.network.INPUT_MASK and config.TEST.get("MASK_DILATE", False))
+        self._rng = np.random.RandomState(self.seed)
+        self._plan()
+
+    def _plan(self):
+        self.pairs, self.pad = plan_test_batches(self.size, self.batch_size, self.shuffle, self._rng)
+
+    def __len__(self):
+        return len(self.pairs)
+
+    def reset(self):
+        """The next pass: with shuffle, the next permutation of the loader's RandomState."""
+        self._plan()
+
+    def getpad(self):
+        """How many repeats of its last pair fill up the last batch of a pass (their records carry "pad": True)."""
+        return self.pad
+
+    def make_batch(self, pairs, pad=0):
+        """(data, frames, pair_records) of the pairs `pairs` (indices into the pairdb), the last `pad` of them padding."""
+        ctx, cfg = self.ctx, self.config
+        pairs = np.asarray(pairs, np.int64).reshape(-1)
+        B, H, W = len(pairs), self.height, self.width
+        records = [self.pairdb[p] if b < B - pad else dict(self.pairdb[p], pad=True) for b, p in enumerate(pairs)]
+        frames = {}
+        if self.shared_frames:
+            rows, index = batch_frames(self.frame[pairs])
+            frames["frame_index"] = ctx.array(index, dtype=np.int32)
+        else:
+            rows = self.frame[pairs]
+        for k in self.keys:
+            frames[k] = ctx.array(self.observed[k][rows], dtype=_TEST_DTYPES[k])       # 1 or 2 bytes per value cross PCIe
+        frames["mask_idx"] = ctx.array(self.mask_idx[pairs], dtype=np.int32)
+        frames["class_index"] = ctx.array(self.class_index[pairs], dtype=np.int32)
+        frames["pose_rendered"] = ctx.array(self.pose_rendered[pairs])
+        cams = None
+        if has_cameras(records):
+            cams = frames["intrinsics"] = ctx.array(camera_table(records, self.K))
+        frames["image_rendered"] = ctx.empty((B, H, W, 3), np.uint8)
+        frames["depth_rendered"] = ctx.empty((B, H, W), np.uint16)
+        frames["rendered_covered"] = ctx.empty((B,), np.int32)
+        self.render_machine.render_frames_into(frames["image_rendered"], frames["depth_rendered"], frames["class_index"],
+                                               frames["pose_rendered"], K=cams, covered=frames["rendered_covered"],
+                                               depth_factor=self.depth_factor)
+        if self.dilate:
+            frames["mask_dilate_thickness"] = mask_dilate_draws_device(ctx, B, self.seed, draw_ids=pairs.astype(np.uint64))
+        return data_pair.get_data_pair_test_batch(frames, cfg), frames, records
+
+    def __iter__(self):
+        for i, pairs in enumerate(self.pairs):
+            yield self.make_batch(pairs, self.pad if i == len(self.pairs) - 1 else 0)

@@ -27,6 +27,9 @@ Differences from the reference:
     stored pose is collected in `all_K[cls]`, parallel to all_poses_gt[cls][0], handed to the evaluation and cached in the
     sidecar `<name>_pose_iter<N>_K.pkl` next to the reference's four containers (written only when cameras were used). The
     caller decodes the `-K.txt` files, as it decodes the frames.
+  * `test_data` may be a core/loader.TestDataLoader, which makes the batches from observed frames and initial poses alone and
+    fills up its last batch by repeating the last pair. Such a record carries "pad": True (the reference's DataBatch.pad): it
+    rides through the network like its original and enters no container, no num_inst, no sum, no EPE total and no pair count.
 """
 from __future__ import print_function, division, absolute_import
 
@@ -41,6 +44,7 @@ from ..cameras import camera_table, has_cameras
 from ..lib.pair_matching.batch_updater_py_multi import update_test_batch
 from ..lib.utils import image as _image
 from ..runtime import DeviceArray, lib
+from .loader import TestDataLoader
 
 EPE_KEYS = ("epe_all", "num_all", "epe_viz", "num_viz", "epe_vizbg", "num_vizbg")     # tester.py:581-588
 FLOW_THRESH = 3e-3                                                                   # calc_flow's default, flow.py:12
@@ -194,6 +198,7 @@ def pred_eval(config, predictor, test_data, imdb_test, vis=False, ignore_cache=N
     class_name = list(config.dataset.get("class_name", imdb_test.classes))
     do_epe = bool(config.network.PRED_FLOW and not config.TEST.FAST_TEST)
     num_pairs = len(pairdb) if pairdb is not None else (
+        test_data.size if isinstance(test_data, TestDataLoader) else
         sum(len(t[2]) for t in test_data) if isinstance(test_data, (list, tuple)) else -1)
 
     data_time, net_time, post_time = 0.0, 0.0, 0.0
@@ -218,6 +223,7 @@ def pred_eval(config, predictor, test_data, imdb_test, vis=False, ignore_cache=N
         pose_rendered = np.stack([np.asarray(r["pose_rendered"], np.float32).reshape(3, 4) for r in pair_records])
         pose_observed = np.stack([np.asarray(r["pose_observed"], np.float32).reshape(3, 4) for r in pair_records])
         no_point = np.array([np.sum(r["pose_rendered"]) == -12 for r in pair_records])      # NO POINT VALID IN INIT POSE
+        pad = np.array([bool(r.get("pad", False)) for r in pair_records])                   # a loader's filler: counted nowhere
         class_ids = [imdb_test.classes.index(r["gt_class"]) for r in pair_records]
         cams = None                                 # the batch's (B,3,3) table: host copy here, cams_d on the device
         if has_cameras(pair_records):
@@ -226,7 +232,7 @@ def pred_eval(config, predictor, test_data, imdb_test, vis=False, ignore_cache=N
         elif data.get("intrinsics") is not None:
             raise ValueError("pred_eval: the batch carries data['intrinsics'] but no pair record has a 'K': the evaluation "
                              "would silently use another camera")
-        for b in np.nonzero(no_point)[0]:
+        for b in np.nonzero(no_point & ~pad)[0]:
             print(pairs_done + b)
             print("in test: NO POINT_VALID IN rendered")
         if no_point.all():
@@ -237,8 +243,9 @@ def pred_eval(config, predictor, test_data, imdb_test, vis=False, ignore_cache=N
             if cams is not None:
                 cams_d = data["intrinsics"] = ctx.array(cams)       # uploaded once per batch
             skip = None
+            if (no_point | pad).any():
+                skip = ctx.array((no_point | pad).astype(np.int32), dtype=np.int32)
             if no_point.any():
-                skip = ctx.array(no_point.astype(np.int32), dtype=np.int32)
                 parked = np.where(no_point[:, None, None], pose_observed, pose_rendered)
                 data["src_pose"] = ctx.array(parked)
             pose_rendered_d = ctx.array(pose_rendered)
@@ -289,6 +296,8 @@ def pred_eval(config, predictor, test_data, imdb_test, vis=False, ignore_cache=N
             post_time += time.time() - t
 
         for b, rec in enumerate(pair_records):          # the containers, pair by pair in the reference's order
+            if pad[b]:
+                continue
             class_id = class_ids[b]
             all_K[class_id].append(K.copy() if cams is None else cams[b].copy())
             if not no_point[b]:
@@ -306,11 +315,12 @@ def pred_eval(config, predictor, test_data, imdb_test, vis=False, ignore_cache=N
                 all_trans_err[class_id][pose_iter_idx].append(t_dist)
                 sum_PoseErr[pose_iter_idx][class_id, :] += np.array([r_dist, t_dist])
                 sum_PoseErr[pose_iter_idx][-1, :] += np.array([r_dist, t_dist])
-        pairs_done += B
+        first_pair = pairs_done + 1
+        pairs_done += B - int(pad.sum())
 
         if idx % 50 == 0:       # post process
             logger.info("testing {}/{} data {:.4f}s net {:.4f}s calc_gt {:.4f}s".format(
-                pairs_done - B + 1, num_pairs, data_time / pairs_done, net_time / pairs_done, post_time / pairs_done))
+                first_pair, num_pairs, data_time / pairs_done, net_time / pairs_done, post_time / pairs_done))
         t = time.time()
 
     all_rot_err = _as_array(all_rot_err)

@@ -427,6 +427,22 @@ __global__ __launch_bounds__(256) void mask_dilate_kernel(float* __restrict__ ou
   }
 }
 
+// image.py:301-303 for a batch: the planes of the samples whose initial render covered no pixel become zero, the others are
+// not touched (no load, no store). covered[b] depends on blockIdx.y only: a scalar load and a uniform exit.
+template <bool VEC>
+__global__ __launch_bounds__(256) void mask_gate_kernel(float* __restrict__ mask, const int32_t* __restrict__ covered, long hw) {
+  const int b = blockIdx.y;
+  if (covered[b] != 0) return;
+  float* o = mask + b * hw;
+  if (VEC) {
+    const long p0 = ((long)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (p0 < hw) *reinterpret_cast<float4*>(o + p0) = make_float4(0.f, 0.f, 0.f, 0.f);
+  } else {
+    const long p = (long)blockIdx.x * 256 + threadIdx.x;
+    if (p < hw) o[p] = 0.f;
+  }
+}
+
 inline bool aligned_to(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
 }  // namespace
@@ -580,6 +596,20 @@ extern "C" int deepim_mask_dilate(deepim_ctx* ctx, float* out, const float* mask
   else
     hipLaunchKernelGGL(mask_dilate_kernel<false>, dim3(di_div_up(hw, 256), B), dim3(256), 0, ctx->stream, out, mask,
                        thickness, H, W);
+  DI_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int deepim_mask_gate(deepim_ctx* ctx, float* mask, const int32_t* covered, int B, int H, int W) {
+  DI_DEVICE(ctx);
+  DI_REQUIRE(B >= 0 && H >= 0 && W >= 0, "mask_gate: negative size");
+  DI_REQUIRE(B <= 65535, "mask_gate: batch too large");
+  const long hw = (long)H * W;
+  if (B == 0 || hw == 0) return 0;
+  DI_REQUIRE(mask && covered, "mask_gate: NULL argument");
+  const bool vec = hw % 4 == 0 && aligned_to(mask, 16);
+  if (vec) hipLaunchKernelGGL(mask_gate_kernel<true>, dim3(di_div_up(hw / 4, 256), B), dim3(256), 0, ctx->stream, mask, covered, hw);
+  else hipLaunchKernelGGL(mask_gate_kernel<false>, dim3(di_div_up(hw, 256), B), dim3(256), 0, ctx->stream, mask, covered, hw);
   DI_LAUNCH_CHECK();
   return 0;
 }

@@ -189,6 +189,7 @@ struct LitParams {
   const float* intensity;  // (B,3) device, or nullptr = (1,1,1)
   Vec3 light_offset;       // 0.5·(0,1,1) in the reference's loops
   float ratio;             // brightness_ratio (0.7)
+  static constexpr bool lit = true;
   __device__ __forceinline__ float offset(int, int r) const { return light_offset.v[r]; }
   __device__ __forceinline__ float inten(int b, int c) const { return intensity ? intensity[b * 3 + c] : 1.f; }
   __device__ __forceinline__ float rat(int) const { return ratio; }
@@ -201,9 +202,20 @@ struct LitPerSample {
   const float* off;        // (B,3)
   const float* intensity;  // (B,3)
   const float* ratio;      // (B)
+  static constexpr bool lit = true;
   __device__ __forceinline__ float offset(int b, int r) const { return off[b * 3 + r]; }
   __device__ __forceinline__ float inten(int b, int c) const { return intensity[b * 3 + c]; }
   __device__ __forceinline__ float rat(int b) const { return ratio[b]; }
+  // the stored byte of a level: the lit stage's levels are whole numbers in 0..255 already
+  static __device__ __forceinline__ unsigned level(float v) { return (unsigned)(int)v; }
+};
+
+// Light source of deepim_render_frames_forward: none. The lit stage is compiled out and a level is the unlit one (texture or
+// vertex colour, any float), stored as cv2.imwrite converts a float image (toolkit/LM6d_3_gen_PoseCNN_pred_rendered.py:149-155): saturated,
+// rounded to nearest even.
+struct Unlit {
+  static constexpr bool lit = false;
+  static __device__ __forceinline__ unsigned level(float v) { return (unsigned)(int)rintf(fminf(fmaxf(v, 0.f), 255.f)); }
 };
 
 // The fragment of pixel p of sample b from its z-buffer key (hit = the key is not all-ones): depth z (0 = background) and colour
@@ -239,7 +251,7 @@ __device__ __forceinline__ Frag resolve_pixel(bool hit, unsigned long long key, 
 #pragma unroll
       for (int c = 0; c < 3; ++c) rgb[c] = tex_bilinear(tex, m.TH, m.TW, c, u, v);
     }
-    if (m.normals != nullptr) {
+    if constexpr (Lit::lit) if (m.normals != nullptr) {
       const float* P = lit.poses + b * 12;
       float mp[3], mn[3];      // perspective-correct model-space position and normal of the fragment (GL varyings)
 #pragma unroll
@@ -317,12 +329,13 @@ __global__ __launch_bounds__(256) void resolve_kernel(float* __restrict__ image,
   }
 }
 
-// Destination of deepim_render_observed_forward: decoded frames as lib/utils/image.py reads them from the PNGs of
-// LM6d_ds_1_gen_observed.py:149-159, sample b in row rows[b] (nullptr: b) of N rows. 6 bytes per pixel.
+// Destination of deepim_render_observed_forward / deepim_render_frames_forward: decoded frames as lib/utils/image.py reads them
+// from the PNGs of LM6d_ds_1_gen_observed.py:149-159, sample b in row rows[b] (nullptr: b) of N rows. 6 bytes per pixel.
 struct FrameOut {
   unsigned char* image;         // (N,H,W,3) BGR levels
   unsigned short* depth;        // (N,H,W) (uint16)(depth * depth_factor), the float32 product truncated
-  unsigned char* label;         // (N,H,W) label_value[b] where depth != 0, else 0
+  unsigned char* label;         // (N,H,W) label_value[b] where depth != 0, else 0; nullptr: not stored
+  int* covered;                 // (B) zeroed before the launch: += the sample's pixels with a non-zero stored depth; or nullptr
   const int* rows;              // (B) or nullptr
   const int* label_value;       // (B) or nullptr = 1
   float depth_factor;
@@ -333,11 +346,13 @@ struct FrameOut {
 // PX = 4 (the plane is a multiple of 4 pixels and the three outputs are 8-byte aligned): the lane stores its 12 image bytes as
 // three dwords, its four depths as one 8-byte store and its four labels as one dword, so a wave writes 768 + 512 + 256
 // contiguous bytes with no partial dwords. PX = 1: single byte / short stores, any size. A sample whose row is outside [0, N)
-// stores nothing; its z-buffer entries are still put back.
-template <class Src, int PX>
+// stores nothing; its z-buffer entries are still put back and its pixels still counted. Lit: LitPerSample or Unlit, which also
+// says how a level becomes a byte. The lanes past the plane are the tail of the grid's last waves, so lane 0 of a wave with any
+// live lane is live: it adds the wave's count (ballots over the live lanes) to out.covered[b] with one atomic.
+template <class Src, int PX, class Lit>
 __global__ __launch_bounds__(256) void resolve_frames_kernel(FrameOut out, unsigned long long* __restrict__ zbuf,
                                                              const PV* __restrict__ pv_all, Src src, int H, int W, float znear,
-                                                             LitPerSample lit) {
+                                                             Lit lit) {
   const int b = blockIdx.y;
   const long plane = (long)H * W;
   const long p0 = ((long)blockIdx.x * 256 + threadIdx.x) * PX;
@@ -367,9 +382,15 @@ __global__ __launch_bounds__(256) void resolve_frames_kernel(FrameOut out, unsig
     const Frag fr = resolve_pixel(hit, key, b, p0 + i, pv_all, src, W, znear, lit);
     const float* rgb = fr.rgb; const float z = fr.z;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) bgr[i * 3 + c] = (unsigned)(int)rgb[2 - c];      // whole numbers in 0..255 from the lit stage
+    for (int c = 0; c < 3; ++c) bgr[i * 3 + c] = Lit::level(rgb[2 - c]);
     d16[i] = (unsigned)(int)(z * out.depth_factor) & 0xffffu;
     l8[i] = z != 0.f ? lab : 0u;
+  }
+  if (out.covered != nullptr) {
+    int n = 0;
+#pragma unroll
+    for (int i = 0; i < PX; ++i) n += __popcll(__ballot(d16[i] != 0u));
+    if (n != 0 && (threadIdx.x & 63) == 0) atomicAdd(out.covered + b, n);
   }
   if (!store) return;
   const long q = (long)row * plane + p0;
@@ -384,12 +405,12 @@ __global__ __launch_bounds__(256) void resolve_frames_kernel(FrameOut out, unsig
     d.x = d16[0] | d16[1] << 16;
     d.y = d16[2] | d16[3] << 16;
     *reinterpret_cast<uint2*>(out.depth + q) = d;
-    *reinterpret_cast<unsigned*>(out.label + q) = l8[0] | l8[1] << 8 | l8[2] << 16 | l8[3] << 24;
+    if (out.label != nullptr) *reinterpret_cast<unsigned*>(out.label + q) = l8[0] | l8[1] << 8 | l8[2] << 16 | l8[3] << 24;
   } else {
 #pragma unroll
     for (int c = 0; c < 3; ++c) out.image[q * 3 + c] = (unsigned char)bgr[c];
     out.depth[q] = (unsigned short)d16[0];
-    out.label[q] = (unsigned char)l8[0];
+    if (out.label != nullptr) out.label[q] = (unsigned char)l8[0];
   }
 }
 
@@ -544,6 +565,26 @@ extern "C" int deepim_render_classes_forward(deepim_ctx* ctx, float* image, floa
                        pixel_means_host, B, H, W, znear, zfar, light_offset_host, light_intensity, brightness_ratio);
 }
 
+// The launch group of the frame entries: the front, then the frame resolve pass with the light source `lit`.
+template <class Lit>
+static int frames_launch(deepim_ctx* ctx, const FrameOut& out, const MeshTable& src, const Lit& lit, int max_V, int max_F,
+                         const float* poses, const float* K_host, int B, int H, int W, float znear, float zfar) {
+  PV* pv;
+  int rc = render_front(ctx, src, max_V, max_F, poses, K_host, B, H, W, znear, zfar, nullptr, &pv);
+  if (rc) return rc;
+  const long plane = (long)H * W;
+  const bool quad = plane % 4 == 0 && (((uintptr_t)out.image | (uintptr_t)out.depth | (uintptr_t)out.label) & 7) == 0;
+  if (quad)
+    hipLaunchKernelGGL((resolve_frames_kernel<MeshTable, 4, Lit>), dim3(di_div_up(plane / 4, 256), B), dim3(256), 0, ctx->stream,
+                       out, ctx->zbuf, pv, src, H, W, znear, lit);
+  else
+    hipLaunchKernelGGL((resolve_frames_kernel<MeshTable, 1, Lit>), dim3(di_div_up(plane, 256), B), dim3(256), 0, ctx->stream, out,
+                       ctx->zbuf, pv, src, H, W, znear, lit);
+  DI_LAUNCH_CHECK();
+  ctx->zbuf_dirty = 0;
+  return 0;
+}
+
 // The mesh-table draw, lit, with one light per sample, written as decoded frames (layout: include/deepim_hip.h).
 extern "C" int deepim_render_observed_forward(deepim_ctx* ctx, uint8_t* image, uint16_t* depth, uint8_t* label, const int32_t* rows,
                                               int N, const int32_t* label_value, float depth_factor, const int32_t* class_index,
@@ -564,20 +605,32 @@ extern "C" int deepim_render_observed_forward(deepim_ctx* ctx, uint8_t* image, u
   DI_REQUIRE(depth_factor > 0.f && zfar * depth_factor < 65536.f, "render_observed: zFar * depth_factor must stay below 65536");
   const MeshTable src = {(const int*)class_index, (const int*)mesh_desc, vertices, vertex_attr, normals, (const int*)faces,
                          textures, n_classes, max_V, max_F};
-  PV* pv;
-  int rc = render_front(ctx, src, max_V, max_F, poses, K_host, B, H, W, znear, zfar, nullptr, &pv);
-  if (rc) return rc;
-  const FrameOut out = {image, depth, label, (const int*)rows, (const int*)label_value, depth_factor, N};
+  const FrameOut out = {image, depth, label, nullptr, (const int*)rows, (const int*)label_value, depth_factor, N};
   const LitPerSample lit = {poses, light_offset, light_intensity, brightness_ratio};
-  const long plane = (long)H * W;
-  const bool quad = plane % 4 == 0 && (((uintptr_t)image | (uintptr_t)depth | (uintptr_t)label) & 7) == 0;
-  if (quad)
-    hipLaunchKernelGGL((resolve_frames_kernel<MeshTable, 4>), dim3(di_div_up(plane / 4, 256), B), dim3(256), 0, ctx->stream, out,
-                       ctx->zbuf, pv, src, H, W, znear, lit);
-  else
-    hipLaunchKernelGGL((resolve_frames_kernel<MeshTable, 1>), dim3(di_div_up(plane, 256), B), dim3(256), 0, ctx->stream, out,
-                       ctx->zbuf, pv, src, H, W, znear, lit);
-  DI_LAUNCH_CHECK();
-  ctx->zbuf_dirty = 0;
-  return 0;
+  return frames_launch(ctx, out, src, lit, max_V, max_F, poses, K_host, B, H, W, znear, zfar);
+}
+
+// The mesh-table draw, unlit, written as decoded frames with the per-sample count of covered pixels (layout: include/deepim_hip.h).
+extern "C" int deepim_render_frames_forward(deepim_ctx* ctx, uint8_t* image, uint16_t* depth, uint8_t* label, int32_t* covered,
+                                            const int32_t* rows, int N, const int32_t* label_value, float depth_factor,
+                                            const int32_t* class_index, const int32_t* mesh_desc, int n_classes, int max_V, int max_F,
+                                            const float* vertices, const float* vertex_attr, const int32_t* faces,
+                                            const float* textures, const float* poses, const float* K_host, int B, int H, int W,
+                                            float znear, float zfar) {
+  DI_DEVICE(ctx);
+  DI_REQUIRE(B >= 0 && N >= B, "render_frames: the outputs need N >= B >= 0 rows");
+  if (B == 0) return 0;
+  DI_CAMERA(ctx, K_host, B, "deepim_render_frames_forward");
+  DI_REQUIRE(n_classes > 0 && max_V > 0 && max_F > 0 && H > 0 && W > 0, "render_frames: empty mesh table or image");
+  DI_REQUIRE(image && depth, "render_frames: image and depth are required");
+  DI_REQUIRE(class_index != nullptr && mesh_desc != nullptr, "render_frames: class_index and mesh_desc are required");
+  DI_REQUIRE(depth_factor > 0.f && zfar * depth_factor < 65536.f, "render_frames: zFar * depth_factor must stay below 65536");
+  DI_REQUIRE((long)H * W <= 0x7fffffffL, "render_frames: frame too large for the int32 pixel count");
+  DI_REQUIRE(B <= 65535, "render_frames: batch too large");
+  const MeshTable src = {(const int*)class_index, (const int*)mesh_desc, vertices, vertex_attr, nullptr, (const int*)faces,
+                         textures, n_classes, max_V, max_F};
+  // the call WRITES covered: zeroed in stream order ahead of the resolve pass's adds (a memset node inside a capture)
+  if (covered) DI_CHECK(hipMemsetAsync(covered, 0, (size_t)B * sizeof(int32_t), ctx->stream));
+  const FrameOut out = {image, depth, label, (int*)covered, (const int*)rows, (const int*)label_value, depth_factor, N};
+  return frames_launch(ctx, out, src, Unlit{}, max_V, max_F, poses, K_host, B, H, W, znear, zfar);
 }

@@ -254,6 +254,36 @@ class Render_Py(object):
         [0, len(classes)) comes out as an empty frame (see include/deepim_hip.h). (`light_intensity`: ignored, as in `render_into`.)"""
         self._draw_classes(image, depth, class_index, poses, K, pixel_means, mask_rendered, mask_box, mask_thresh)
 
+    def render_frames_into(self, image_u8, depth_u16, class_index_dev, poses, K=None, rows=None, label=None, label_value=None,
+                           covered=None, depth_factor=1000.0):
+        """The unlit mixed-class draw stored as DECODED frames (`deepim_render_frames_forward`): what the reference's
+        toolkit/LM6d_3_gen_PoseCNN_pred_rendered.py writes to disk for every initial pose and lib/utils/image.py reads back.
+        image_u8 (N,H,W,3) uint8 BGR = rint(clip(level, 0, 255)), depth_u16 (N,H,W) uint16 = the float32 depth * depth_factor
+        truncated, label (N,H,W) uint8 or None = label_value[b] (device int32 (n), None = 1) where the depth is non-zero.
+        Sample b goes to row rows[b] (device int32 (n), None = b) of the N >= n rows. covered: device int32 (n) or None, written
+        with each sample's count of non-zero depth pixels (never read here). `K`: as in `render_into`."""
+        if not is_device_ids(class_index_dev):
+            raise TypeError("render_frames_into needs class_index as a device int32 array")
+        n, H, W = poses.shape[0], self.height, self.width
+        if image_u8.dtype != np.uint8 or image_u8.ndim != 4 or image_u8.shape[1:] != (H, W, 3):
+            raise TypeError("render_frames_into: image must be uint8 (N,%d,%d,3), got %s %s" % (H, W, image_u8.dtype, image_u8.shape))
+        N = image_u8.shape[0]
+        if depth_u16.dtype != np.uint16 or depth_u16.shape != (N, H, W):
+            raise TypeError("render_frames_into: depth must be uint16 %s, got %s %s" % ((N, H, W), depth_u16.dtype, depth_u16.shape))
+        if label is not None and (label.dtype != np.uint8 or label.shape != (N, H, W)):
+            raise TypeError("render_frames_into: label must be uint8 %s, got %s %s" % ((N, H, W), label.dtype, label.shape))
+        for name, a in (("rows", rows), ("label_value", label_value), ("covered", covered)):
+            if a is not None and (not is_device_ids(a) or a.size != n):
+                raise TypeError("render_frames_into: %s must be a device int32 array of %d values" % (name, n))
+        if class_index_dev.size != n:
+            raise TypeError("render_frames_into: %d class ids for %d poses" % (class_index_dev.size, n))
+        t = self.mesh_table()
+        K = self._camera(K, n)
+        lib.deepim_render_frames_forward(self.ctx.handle, image_u8, depth_u16, label, covered, rows, N, label_value,
+                                         ctypes.c_float(depth_factor), class_index_dev, t.mesh_desc, t.n_classes, t.max_V, t.max_F,
+                                         t.vertices, t.vertex_attr, t.faces, t.textures, poses, K, n, H, W,
+                                         ctypes.c_float(self.zNear), ctypes.c_float(self.zFar))
+
     def render_batch(self, class_index, poses, K=None, out=None, mask_rendered=None, mask_thresh=0.2, light_intensity=None):
         """poses (B,3,4) device; class_index: scalar, host sequence of B class ids, None (= class 0), or a device array.
         Host ids: samples of the same class in consecutive runs are drawn by one launch group each. A DEVICE int32 array of B ids:

@@ -40,7 +40,10 @@ File decoding and the cv2 resize (:552-580) of the observed and rendered frames 
 config.SCALES[0] is refused. A background is cropped and resized on the device from a bg_pool (lib/utils/background.py, which
 also draws use_bg and bg_index for the training loader); a bg_image is taken as the caller made it. A bg_index is never read
 by the host: one outside the pool gives that pair a black background and sets bit 5 of the status word. The test phase's `np.sum(depth_rendered) == 0` guard (:301-303) is a host decision per pair and is
-the caller's too; an empty rectangle source gives zeros and sets bit 2 of the status word (deepim_zoom_status).
+the caller's too — unless the frames carry "rendered_covered" (device int32 (B): each pair's count of non-zero depth_rendered
+pixels, which Render_Py.render_frames_into writes next to the frames it draws; core/loader.TestDataLoader hands it over): then
+`get_pair_mask` zeroes mask_observed of the pairs with a count of 0 on the device (deepim_mask_gate), before TEST.MASK_DILATE.
+An empty rectangle source gives zeros and sets bit 2 of the status word (deepim_zoom_status).
 
 The kernels are asynchronous on the context's stream. These wrappers stay asynchronous when frames, ids and draws are device
 arrays; a numpy input is uploaded with a synchronous copy into a temporary whose release synchronises the stream again.
@@ -370,6 +373,13 @@ def get_pair_mask(frames, config, phase="train", depth_rendered=None):
         mask_observed = _box(ctx, fg)
     else:
         raise Exception("Unknown init mask type: {}".format(init))
+    if frames.get("rendered_covered") is not None:
+        # :301-303: `np.sum(depth_rendered) == 0` gives a zero mask_observed whatever INIT_MASK says — decided on the device from
+        # the draw's own per-pair count of covered pixels (deepim_render_frames_forward), never read back and not printed
+        covered = frames["rendered_covered"]
+        if not isinstance(covered, DeviceArray) or covered.dtype != np.int32 or covered.size != B:
+            raise TypeError("frames['rendered_covered'] must be a device int32 array of %d values" % B)
+        lib.deepim_mask_gate(ctx.handle, mask_observed, covered, B, H, W)
     if config.TEST.get("MASK_DILATE", False):
         if frames.get("mask_dilate_thickness") is None:
             raise NotImplementedError("TEST.MASK_DILATE: the frames carry no 'mask_dilate_thickness' — the random draws are the "
