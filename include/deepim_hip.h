@@ -356,7 +356,8 @@ int deepim_zoom_inverse_factor(deepim_ctx* ctx, const float* zoom_factor, float*
  * bit3 (8) = split-fp16 conv path: a value left fp16's range after scaling (|v·scale| > 60000 or NaN) and was clamped — the
  *            results of that call are not fp32-grade; lower the activation scale or use the fp32 path
  * bit4 (16) = a shared-frame entry (deepim_zoom_concat_frames_forward[_h16], deepim_ingest_*_frames) met a frame_index outside
- *            [0, N): that pair's observed channels / output plane are those of an empty frame
+ *            [0, N): that pair's observed channels / output plane are those of an empty frame; or deepim_gather_rows met an
+ *            index outside [0, n_rows): that row is zeros
  * bit5 (32) = deepim_ingest_bgr8_pool met a bg_index outside [0, P) in a pair that composites a background: that pair's
  *            background is black */
 int deepim_zoom_status(deepim_ctx* ctx, int* status);
@@ -1120,6 +1121,30 @@ int deepim_ingest_depth16_frames(deepim_ctx* ctx, float* out /*B,1,H,W*/, const 
 int deepim_ingest_label_mask_frames(deepim_ctx* ctx, float* out /*B,1,H,W*/, const uint8_t* labels /*N,H,W*/,
                                     const int32_t* frame_index /*device (B)*/, const int32_t* mask_idx /*device (B)*/, int N,
                                     int B, int H, int W);
+/* deepim_ingest_bgr8 (without a ready-made background) and deepim_ingest_bgr8_pool for frames read THROUGH AN INDEX: frames is
+ * (N,H,W,3), fg_labels (N,H,W), and pair b reads frame frame_index[b] of both; use_bg and bg_index stay per pair. N may be a
+ * whole device-resident dataset (core/resident.ResidentObserved): every offset into the arrays is 64-bit. out has the bits the
+ * per-sample entry gives on frames[frame_index] (and fg_labels[frame_index]). A pair whose index is outside [0, N) reads
+ * nothing outside the arrays, gets the empty-frame value (0 - mean) in all three planes, composites no background and sets
+ * bit 4 (16) of the status word; the other pairs are unaffected. No LDS, nothing allocated, legal inside a capture; the host
+ * never reads frame_index. The 12-byte loads need a dword-aligned base and H*W % 4 == 0 (frame f starts at byte 3 H W f);
+ * otherwise every pixel is read on its own, each from its own pair's frame. */
+int deepim_ingest_bgr8_frames(deepim_ctx* ctx, float* out /*B,3,H,W*/, const uint8_t* frames /*N,H,W,3*/,
+                              const int32_t* frame_index /*device (B)*/, int N, const float* means_rgb /*host 3 or NULL*/,
+                              int B, int H, int W);
+int deepim_ingest_bgr8_pool_frames(deepim_ctx* ctx, float* out /*B,3,H,W*/, const uint8_t* frames /*N,H,W,3*/,
+                                   const uint8_t* fg_labels /*N,H,W*/, const int32_t* frame_index /*device (B)*/, int N,
+                                   const int32_t* use_bg /*device (B) or NULL*/, const int32_t* bg_index /*device (B)*/,
+                                   const uint8_t* pool_pixels, const int64_t* pool_desc, const int32_t* xtab /*P,W*/,
+                                   const int32_t* ytab /*P,H*/, int P, const float* means_rgb /*host 3 or NULL*/, int B, int H,
+                                   int W);
+/* out[b] = table[index[b]] for b < B: rows of row_words 4-byte words (any type), table of n_rows rows, index device int32 (B)
+ * the host never reads. One lane per 16 bytes when row_words % 4 == 0 and out and table are 16-byte aligned, else per word;
+ * every pointer 4-byte aligned, out != table. An index outside [0, n_rows) reads nothing, gives a zero row and sets bit 4 (16)
+ * of the status word. The table offset is 64-bit (rows may be whole frames of a resident set). Asynchronous, allocates
+ * nothing, legal inside a capture. */
+int deepim_gather_rows(deepim_ctx* ctx, void* out, const void* table, const int32_t* index /*device (B)*/, int n_rows,
+                       long row_words, int B);
 /* lib/utils/mask_dilate.py:19-47 with the random draws handed in: thickness (B,4) int32, columns in the order of the file's
  * four blocks — the origin mask shifted down (:24), up (:30), right (:36), left (:42) by that many pixels; 0 = that side is
  * not dilated. Where mask != 0 the output is mask, clamped to 1 where it exceeds 1; elsewhere 1 if an enabled side has a

@@ -40,8 +40,17 @@ its own depth and its mask_idx 1. The synthetic classes are checked against the 
 pair can come out with attempts = −1 and the observed attempts feed deepim_sample_stats_accumulate as they are. Without
 `synthetic` every batch, draw id and byte is what it is without the argument.
 
+`observed` = core/resident.ResidentObserved(observed, ctx, spare_rows=batch_size, points=points): the set uploaded once. The
+plan, the draw ids, the seeds and every refusal are the same and so is every byte of every batch, but a batch is made from
+indices alone: frame_index (B int32), the draw ids (B uint64) and, with synthetic pairs, their positions and class ids go up;
+image_observed is read in place by deepim_ingest_bgr8_frames (_pool_frames with `backgrounds`), the depth and label maps by the
+deepim_ingest_*_frames entries, and pose_observed, mask_idx, class_index, the data_syn flags and the point clouds are rows
+of resident tables gathered by deepim_gather_rows. The synthetic pair at batch position b is drawn into spare row M + b of the
+set (resident.batch_rows), which the loader claims when it is built: safe on one stream, since batch k's ingest is queued
+before batch k+1's draw and a batch keeps fp32 copies only. A dict holding a DeviceArray is still refused.
+
 Not part of this loader and refused: ready-made backgrounds (bg_image: the pool is the loader's way), TRAIN.MASK_SYN, resizing (a frame that is not config.SCALES[0]),
-shared-frame batches (frame_index), device-resident datasets, synthetic frames with more than one object or with occluders
+shared-frame batches (frame_index), synthetic frames with more than one object or with occluders
 (LM6D_OCC), and a synthetic set kept across epochs (SyntheticObserved.to_host makes a fixed one for the `observed` argument).
 """
 import numpy as np
@@ -54,6 +63,7 @@ from ..lib.utils.background import background_draws_device
 from ..lib.utils.mask_dilate import mask_dilate_draws_device
 from ..lib.utils.synthetic_observed import runs
 from ..runtime import DeviceArray, lib
+from .resident import ResidentObserved, batch_rows          # noqa: F401 (re-exported: the set both loaders take)
 
 _DTYPES = {"image_observed": np.uint8, "depth_gt_observed": np.uint16, "mask_gt_observed": np.uint8, "depth_observed": np.uint16}
 
@@ -82,10 +92,20 @@ class TrainDataLoader(object):
         self.batch_size, self.shuffle, self.seed = int(batch_size), bool(shuffle), int(seed)
         self.R = int(num_rendered_per_observed)
         self.noise = pose_noise(noise)
+        self.resident = res = observed if isinstance(observed, ResidentObserved) else None
+        if res is not None:        # the host side of the set: its small tables; the frames stay on the device
+            if res.ctx is not self.ctx:
+                raise ValueError("TrainDataLoader: the resident set lives on another context")
+            for k in ("pose_observed", "mask_idx", "class_index"):
+                if k not in res.host_tables:
+                    raise KeyError("TrainDataLoader: the resident set was built without '%s'" % k)
+            observed = dict(res.host_tables)
+            if data_syn is None:
+                data_syn = observed.get("data_syn")
         for k, v in observed.items():
             if isinstance(v, DeviceArray):
-                raise TypeError("TrainDataLoader: observed['%s'] is a device array; the dataset is host numpy arrays, a batch is "
-                                "gathered on the host and uploaded" % k)
+                raise TypeError("TrainDataLoader: observed['%s'] is a device array; the dataset is host numpy arrays (a batch is "
+                                "gathered on the host and uploaded) or a ResidentObserved" % k)
         if observed.get("bg_image") is not None:
             raise NotImplementedError("TrainDataLoader: ready-made backgrounds (bg_image) are not part of this loader; pass "
                                       "backgrounds=BackgroundPool(...) and they are drawn, cropped and resized on the device")
@@ -98,21 +118,28 @@ class TrainDataLoader(object):
         self.keys = ["image_observed", "depth_gt_observed", "mask_gt_observed"] + (["depth_observed"] if n.INPUT_DEPTH else [])
         self.observed = {}
         for k in self.keys:
+            if res is not None:             # dtypes, shapes and equal M were checked when the set was built
+                if k not in res.arrays:
+                    raise KeyError("TrainDataLoader: the resident set holds no '%s'" % k)
+                continue
             if observed.get(k) is None:
                 raise KeyError("TrainDataLoader: observed carries no '%s'" % k)
             v = np.asarray(observed[k])
             if v.dtype != np.dtype(_DTYPES[k]):
                 raise TypeError("observed['%s'] is %s; the decoded %s frame is expected" % (k, v.dtype, np.dtype(_DTYPES[k])))
             self.observed[k] = v
-        img = self.observed["image_observed"]
-        if img.ndim != 4 or img.shape[3] != 3:
-            raise ValueError("observed['image_observed'] has shape %s; (M,H,W,3) expected" % (img.shape,))
-        self.M, H, W = img.shape[0], img.shape[1], img.shape[2]
+        if res is not None:
+            self.M, H, W = res.M, res.height, res.width
+        else:
+            img = self.observed["image_observed"]
+            if img.ndim != 4 or img.shape[3] != 3:
+                raise ValueError("observed['image_observed'] has shape %s; (M,H,W,3) expected" % (img.shape,))
+            self.M, H, W = img.shape[0], img.shape[1], img.shape[2]
         _image._check_size(config, H, W)             # the resize of image.py:552-580 is the caller's
         if (render_machine.height, render_machine.width) != (H, W):
             raise ValueError("the render machine draws %dx%d, the frames are %dx%d" % (render_machine.height, render_machine.width, H, W))
         for k in self.keys[1:]:
-            if self.observed[k].shape != (self.M, H, W):
+            if res is None and self.observed[k].shape != (self.M, H, W):
                 raise ValueError("observed['%s'] has shape %s; %s expected" % (k, self.observed[k].shape, (self.M, H, W)))
         self.height, self.width = H, W
         if backgrounds is not None and (backgrounds.height, backgrounds.width) != (H, W):
@@ -142,14 +169,24 @@ class TrainDataLoader(object):
             synthetic.check_classes(self.synthetic_classes)         # on the host: no pair can draw attempts = -1
         self.points = None
         if config.train_iter.SE3_PM_LOSS:
-            if points is None:
+            if points is None and (res is None or res.point_tables is None):
                 raise ValueError("TrainDataLoader: train_iter.SE3_PM_LOSS needs `points` = {class id: (model points, weights)}")
-            self.points = {int(c): (np.ascontiguousarray(p, np.float32), np.ascontiguousarray(w, np.float32)) for c, (p, w) in points.items()}
+            if res is not None and res.point_tables is None:
+                res.set_points(points)           # once: the per-class tables are gathered on the device from then on
+            self.points = res.point_classes if res is not None else {
+                int(c): (np.ascontiguousarray(p, np.float32), np.ascontiguousarray(w, np.float32)) for c, (p, w) in points.items()}
             missing = sorted((set(self.class_index.tolist()) | (set(self.synthetic_classes.tolist()) if self.S else set())) - set(self.points))
             if missing:
                 raise KeyError("TrainDataLoader: no model points for class ids {}".format(missing))
         if self.M * self.R + self.S < self.batch_size:
             raise ValueError("TrainDataLoader: %d pairs do not fill one batch of %d" % (self.M * self.R + self.S, self.batch_size))
+        if res is not None:
+            if self.S:               # synthetic pair at batch position b is drawn into spare row M + b
+                res.claim_spare_rows(self, self.batch_size)
+            if self.backgrounds is not None and (self.data_syn is not None or self.S):
+                want = np.zeros(self.M, bool) if self.data_syn is None else self.data_syn
+                if "data_syn" not in res.tables or not np.array_equal(res.host_tables["data_syn"], want):
+                    res.set_data_syn(want)
         self.K = np.ascontiguousarray(config.dataset.INTRINSIC_MATRIX, np.float32).reshape(3, 3)
         self._rng = np.random.RandomState(self.seed)
         # pairs drawn, sum of attempts, exhausted pairs: device-resident; with `synthetic` the same three of the observed-pose draws
@@ -206,6 +243,8 @@ class TrainDataLoader(object):
         """(data, label) of the given pairs (p = m·R + r, or M·R + s for synthetic pair s) with the given draw ids."""
         ctx, cfg = self.ctx, self.config
         pairs = np.asarray(pairs, np.int64)
+        if self.resident is not None:
+            return self._make_batch_resident(pairs, draw_ids)
         real = pairs < self.M * self.R
         m = np.where(real, pairs // self.R, 0)
         B = len(m)
@@ -236,17 +275,69 @@ class TrainDataLoader(object):
         if cfg.network.INPUT_DEPTH:       # get_pair_depth, train phase: zeroed outside the pair's label with MASK_INPUTS
             batch["depth_observed"] = _image._depth(ctx, frames, "depth_observed", cfg,
                                                     "mask_gt_observed" if cfg.network.get("MASK_INPUTS", False) else None)
+        if self.points is not None:
+            batch["point_cloud_model"] = ctx.array(np.stack([self.points[int(c)][0] for c in cls]))
+            batch["point_cloud_weights"] = ctx.array(np.stack([self.points[int(c)][1] for c in cls]))
+        return self._finish(batch, ids, B)
+
+    def _finish(self, batch, ids, B):
+        """The rendered side and the labels of a batch whose observed side is made: the same for both kinds of set."""
+        ctx, cfg = self.ctx, self.config
         batch["pose_rendered"], attempts = sample_rendered_poses(batch["pose_observed"], self.K, self.width, self.height, self.seed,
                                                                  draw_ids=ids, noise=self.noise)
         lib.deepim_sample_stats_accumulate(ctx.handle, self._totals, attempts, B)
         batch["image_rendered"], batch["depth_rendered"] = self.render_machine.render_batch(batch["class_index"], batch["pose_rendered"])
         if cfg.TRAIN.get("MASK_DILATE", False):
             batch["mask_dilate_thickness"] = mask_dilate_draws_device(ctx, B, self.seed, draw_ids=ids)
-        if self.points is not None:
-            batch["point_cloud_model"] = ctx.array(np.stack([self.points[int(c)][0] for c in cls]))
-            batch["point_cloud_weights"] = ctx.array(np.stack([self.points[int(c)][1] for c in cls]))
         out = data_pair.get_data_pair_train_batch(batch, cfg)
         return out["data"], out["label"]
+
+    def _make_batch_resident(self, pairs, draw_ids):
+        """make_batch over a ResidentObserved: frame_index, the draw ids and, with synthetic pairs, their positions and class
+        ids go up; every row of the batch is read in place or gathered on the device."""
+        ctx, cfg, res = self.ctx, self.config, self.resident
+        rows, syn = batch_rows(pairs, self.M, self.R)
+        B = len(rows)
+        fi = ctx.array(rows, dtype=np.int32)
+        ids = ctx.array(np.asarray(draw_ids).reshape(B), dtype=np.uint64)
+        if syn.size:       # drawn into spare row M + b; class, pose (and mask_idx = data_syn = 1, set once) land in the tables' row
+            cls_syn = ctx.array(self.synthetic_classes[(pairs[syn] - self.M * self.R) % len(self.synthetic_classes)], dtype=np.int32)
+            if syn.size == B:
+                ids_syn, rows_syn = ids, fi
+            else:
+                at = ctx.array(syn, dtype=np.int32)
+                ids_syn = res.gather(ids.reshape((B, 1)), at, syn.size).reshape((syn.size,))
+                rows_syn = res.gather(fi, at, syn.size)
+            drawn = self.synthetic.frames(cls_syn, ids_syn, rows=rows[syn], rows_device=rows_syn,
+                                          out=dict(res.arrays, pose_observed=res.tables["pose_observed"]))
+            lib.deepim_sample_stats_accumulate(ctx.handle, self._totals[3:6], drawn["attempts"], int(syn.size))
+            for j0, j1, r0 in runs(rows[syn]):
+                res.tables["class_index"][r0:r0 + (j1 - j0)].copyfrom(cls_syn[j0:j1])
+                if cfg.network.INPUT_DEPTH:       # their depth_observed is their own depth
+                    res.arrays["depth_observed"][r0:r0 + (j1 - j0)].copyfrom(res.arrays["depth_gt_observed"][r0:r0 + (j1 - j0)])
+        frames = {k: res.arrays[k] for k in self.keys}
+        frames["frame_index"] = fi
+        frames["mask_idx"] = res.gather(res.tables["mask_idx"], fi, B)
+        means = _image._means_rgb(cfg)
+        if self.backgrounds is None:
+            image = _image.transform_batch_frames(ctx, frames["image_observed"], fi, means)
+        else:
+            always = res.gather(res.tables["data_syn"], fi, B) if (self.data_syn is not None or self.S) else None
+            use_bg, bg_index = background_draws_device(ctx, B, self.seed, ids, self.bg_ratio, len(self.backgrounds), always=always)
+            image = _image.transform_batch_frames(ctx, frames["image_observed"], fi, means, frames["mask_gt_observed"], use_bg,
+                                                  bg_index, self.backgrounds)
+        batch = {"image_observed": image,
+                 "depth_gt_observed": _image._depth(ctx, frames, "depth_gt_observed", cfg),
+                 "mask_gt_observed": _image.label_mask(ctx, frames, "mask_gt_observed"),
+                 "pose_observed": res.gather(res.tables["pose_observed"], fi, B),
+                 "class_index": res.gather(res.tables["class_index"], fi, B)}
+        if cfg.network.INPUT_DEPTH:
+            batch["depth_observed"] = _image._depth(ctx, frames, "depth_observed", cfg,
+                                                    "mask_gt_observed" if cfg.network.get("MASK_INPUTS", False) else None)
+        if self.points is not None:
+            batch["point_cloud_model"] = res.gather(res.point_tables[0], batch["class_index"], B)
+            batch["point_cloud_weights"] = res.gather(res.point_tables[1], batch["class_index"], B)
+        return self._finish(batch, ids, B)
 
     def __iter__(self):
         for pairs, ids in zip(self.pairs, self.draw_ids):
@@ -334,7 +425,11 @@ class TestDataLoader(object):
     applied on the device and not printed. Order: arange(P), or with `shuffle` a permutation from RandomState(seed), drawn anew
     at each reset().
 
-    Refused: device-resident datasets, a frame that is not config.SCALES[0] or not the render machine's size, a pair whose frame
+    `observed` = core/resident.ResidentObserved(observed, ctx): the F frames uploaded once. With `shared_frames` a batch's
+    frames dict holds the set's own arrays (N = F) and frame_index = frame[pairs]; without, the per-pair rows are gathered on
+    the device by deepim_gather_rows (a frame that is not a multiple of 4 bytes is refused). Only ids, poses and cameras go up.
+
+    Refused: a dict holding a device array, a frame that is not config.SCALES[0] or not the render machine's size, a pair whose frame
     is outside [0, F) or whose gt_class the render machine does not know, and shared_frames with network.INPUT_MASK off (the
     library's shared-frame zoom front end has no mask-less variant: pass shared_frames=False)."""
     __test__ = False          # a data iterator named after the reference's, not a pytest class
@@ -344,10 +439,16 @@ class TestDataLoader(object):
         self.batch_size, self.shuffle, self.seed, self.shared_frames = int(batch_size), bool(shuffle), int(seed), bool(shared_frames)
         if self.batch_size < 1:
             raise ValueError("TestDataLoader: batch_size must be >= 1")
-        for k, v in observed.items():
-            if isinstance(v, DeviceArray):
-                raise TypeError("TestDataLoader: observed['%s'] is a device array; the dataset is host numpy arrays, a batch's "
-                                "frames are gathered on the host and uploaded" % k)
+        self.resident = res = observed if isinstance(observed, ResidentObserved) else None
+        if res is not None:
+            if res.ctx is not render_machine.ctx:
+                raise ValueError("TestDataLoader: the resident set lives on another context")
+            observed = res.arrays           # checked when the set was built; read below for its keys alone
+        else:
+            for k, v in observed.items():
+                if isinstance(v, DeviceArray):
+                    raise TypeError("TestDataLoader: observed['%s'] is a device array; the dataset is host numpy arrays (a batch's "
+                                    "frames are gathered on the host and uploaded) or a ResidentObserved" % k)
         if self.shared_frames and not config.network.INPUT_MASK:
             raise NotImplementedError("TestDataLoader: shared_frames needs network.INPUT_MASK — the shared-frame zoom front end "
                                       "has no mask-less variant; pass shared_frames=False")
@@ -356,19 +457,27 @@ class TestDataLoader(object):
         for k in self.keys:
             if observed.get(k) is None:
                 raise KeyError("TestDataLoader: observed carries no '%s'" % k)
+            if res is not None:
+                if not self.shared_frames and (res.arrays[k].nbytes // res.rows) % 4:
+                    raise ValueError("TestDataLoader: a '%s' frame of %d bytes is not a multiple of 4 bytes; the per-pair rows of "
+                                     "a resident set are gathered in 4-byte words" % (k, res.arrays[k].nbytes // res.rows))
+                continue
             v = np.asarray(observed[k])
             if v.dtype != np.dtype(_TEST_DTYPES[k]):
                 raise TypeError("observed['%s'] is %s; the decoded %s frame is expected" % (k, v.dtype, np.dtype(_TEST_DTYPES[k])))
             self.observed[k] = v
-        img = self.observed["image_observed"]
-        if img.ndim != 4 or img.shape[3] != 3 or img.shape[0] < 1:
-            raise ValueError("observed['image_observed'] has shape %s; (F,H,W,3) expected" % (img.shape,))
-        self.F, H, W = img.shape[0], img.shape[1], img.shape[2]
+        if res is not None:
+            self.F, H, W = res.M, res.height, res.width
+        else:
+            img = self.observed["image_observed"]
+            if img.ndim != 4 or img.shape[3] != 3 or img.shape[0] < 1:
+                raise ValueError("observed['image_observed'] has shape %s; (F,H,W,3) expected" % (img.shape,))
+            self.F, H, W = img.shape[0], img.shape[1], img.shape[2]
         _image._check_size(config, H, W)
         if (render_machine.height, render_machine.width) != (H, W):
             raise ValueError("the render machine draws %dx%d, the frames are %dx%d" % (render_machine.height, render_machine.width, H, W))
         for k in self.keys[1:]:
-            if self.observed[k].shape != (self.F, H, W):
+            if res is None and self.observed[k].shape != (self.F, H, W):
                 raise ValueError("observed['%s'] has shape %s; %s expected" % (k, self.observed[k].shape, (self.F, H, W)))
         self.height, self.width = H, W
         self.pairdb = list(pairdb)
@@ -421,13 +530,20 @@ class TestDataLoader(object):
         B, H, W = len(pairs), self.height, self.width
         records = [self.pairdb[p] if b < B - pad else dict(self.pairdb[p], pad=True) for b, p in enumerate(pairs)]
         frames = {}
-        if self.shared_frames:
-            rows, index = batch_frames(self.frame[pairs])
-            frames["frame_index"] = ctx.array(index, dtype=np.int32)
+        if self.resident is not None:       # the ids go up; the frames are the set's own (shared) or gathered on the device
+            index = ctx.array(self.frame[pairs], dtype=np.int32)
+            if self.shared_frames:
+                frames["frame_index"] = index
+            for k in self.keys:
+                frames[k] = self.resident.arrays[k] if self.shared_frames else self.resident.gather(self.resident.arrays[k], index, B)
         else:
-            rows = self.frame[pairs]
-        for k in self.keys:
-            frames[k] = ctx.array(self.observed[k][rows], dtype=_TEST_DTYPES[k])       # 1 or 2 bytes per value cross PCIe
+            if self.shared_frames:
+                rows, index = batch_frames(self.frame[pairs])
+                frames["frame_index"] = ctx.array(index, dtype=np.int32)
+            else:
+                rows = self.frame[pairs]
+            for k in self.keys:
+                frames[k] = ctx.array(self.observed[k][rows], dtype=_TEST_DTYPES[k])       # 1 or 2 bytes per value cross PCIe
         frames["mask_idx"] = ctx.array(self.mask_idx[pairs], dtype=np.int32)
         frames["class_index"] = ctx.array(self.class_index[pairs], dtype=np.int32)
         frames["pose_rendered"] = ctx.array(self.pose_rendered[pairs])

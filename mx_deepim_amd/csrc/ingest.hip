@@ -48,11 +48,38 @@ __device__ __forceinline__ void store_planes(float* __restrict__ out, float (&px
   }
 }
 
-// VEC_IN: every input pointer is dword-aligned (12-byte loads); VEC_OUT: hw % 4 == 0 and `out` 16-byte aligned (float4 stores)
-template <bool VEC_IN, bool VEC_OUT>
+// Frames through an index (the *_frames entries): the input of pair b is frame frame_index[b] of N, not sample b. The ids live
+// on the device: one outside [0, N) reads nothing (the pair's output is that of an empty frame) and is reported through
+// DI_STATUS_FRAME_RANGE by the lane that owns the pair's first pixel. Unused (and never read) by the per-sample entries.
+// N may be a whole resident dataset: every offset into the frames is 64-bit (frame 2 331 of a 480x640 BGR set starts past 2^31).
+struct FrameSel {
+  const int32_t* frame_index;   // (B)
+  int* status;
+  int N;
+};
+// input offset, in pixels, of in-sample pixel q of pair b (flat pixel p of the batch), or -1 for a pair without a frame
+template <bool FRAMES>
+__device__ __forceinline__ long source_pixel(const FrameSel& fs, long p, long b, long q, long hw) {
+  if (!FRAMES) return p;
+  const int id = fs.frame_index[b];
+  if (id < 0 || id >= fs.N) {
+    if (q == 0) atomicOr(fs.status, DI_STATUS_FRAME_RANGE);
+    return -1;
+  }
+  return (long)id * hw + q;
+}
+
+// VEC_IN: every input pointer is dword-aligned (12-byte loads); VEC_OUT: hw % 4 == 0 and `out` 16-byte aligned (float4 stores).
+// FRAMES (deepim_ingest_bgr8_frames): `frames` and `fg` are (N,H,W[,3]) and pair b reads frame frame_index[b]; `bg` stays per
+// pair. Per sample the 12-byte loads are dword-aligned for any W because the batch is one flat run; through an index frame f
+// starts at byte 3·hw·f and a lane's four pixels must share a frame, so VEC_IN then also needs hw % 4 == 0 (the launcher's
+// rule) — otherwise the scalar path, where a lane's four pixels may belong to two pairs naming different frames and each
+// pixel takes its own pair's frame. A pair without a frame is (0 - mean) and composites no background.
+template <bool VEC_IN, bool VEC_OUT, bool FRAMES>
 __global__ __launch_bounds__(256) void ingest_bgr8_kernel(float* __restrict__ out, const uint8_t* __restrict__ frames,
                                                           const uint8_t* __restrict__ bg, const uint8_t* __restrict__ fg,
-                                                          const int32_t* __restrict__ use_bg, Vec3 means, long hw, long n) {
+                                                          const int32_t* __restrict__ use_bg, Vec3 means, long hw, long n,
+                                                          FrameSel fs) {
   const long p0 = ((long)blockIdx.x * 256 + threadIdx.x) * 4;
   if (p0 >= n) return;
   const int cnt = (int)min(4L, n - p0);
@@ -62,10 +89,13 @@ __global__ __launch_bounds__(256) void ingest_bgr8_kernel(float* __restrict__ ou
 #pragma unroll
   for (int j = 1; j < 4; ++j) { bs[j] = bs[j - 1]; qs[j] = qs[j - 1]; next_pixel(hw, bs[j], qs[j]); }
   if (VEC_IN && cnt == 4) {
-    Bytes12 v = *reinterpret_cast<const Bytes12*>(frames + p0 * 3);
-    if (bg) {
+    const long s0 = source_pixel<FRAMES>(fs, p0, bs[0], qs[0], hw);
+    const bool have = !FRAMES || s0 >= 0;
+    Bytes12 v = {{0u, 0u, 0u}};
+    if (have) v = *reinterpret_cast<const Bytes12*>(frames + s0 * 3);
+    if (bg && have) {
       const Bytes12 g = *reinterpret_cast<const Bytes12*>(bg + p0 * 3);
-      const uint32_t l = *reinterpret_cast<const uint32_t*>(fg + p0);
+      const uint32_t l = *reinterpret_cast<const uint32_t*>(fg + s0);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const bool take_bg = ((l >> (8 * j)) & 0xffu) == 0 && (!use_bg || use_bg[bs[j]] != 0);
@@ -81,15 +111,17 @@ __global__ __launch_bounds__(256) void ingest_bgr8_kernel(float* __restrict__ ou
   } else {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) px[c][j] = 0.f;
       if (j < cnt) {
         const long p = p0 + j;
-        const bool take_bg = bg && fg[p] == 0 && (!use_bg || use_bg[bs[j]] != 0);
-        const uint8_t* s = (take_bg ? bg : frames) + p * 3;
+        const long sp = source_pixel<FRAMES>(fs, p, bs[j], qs[j], hw);
+        if (!FRAMES || sp >= 0) {
+          const bool take_bg = bg && fg[sp] == 0 && (!use_bg || use_bg[bs[j]] != 0);
+          const uint8_t* s = take_bg ? bg + p * 3 : frames + sp * 3;
 #pragma unroll
-        for (int c = 0; c < 3; ++c) px[c][j] = (float)s[2 - c];
-      } else {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) px[c][j] = 0.f;
+          for (int c = 0; c < 3; ++c) px[c][j] = (float)s[2 - c];
+        }
       }
     }
   }
@@ -170,11 +202,14 @@ __device__ __forceinline__ uint32_t bg_resample(const Bytes12& w0, const Bytes12
 // the loads of a stage are in flight together: the descriptor (once per lane; once per pixel only where H·W % 4 != 0 lets a
 // lane's pixels cross into the next pair), the four pixels' table entries, their eight windows, the arithmetic. A pixel that
 // takes no background rides along on entry 0 and the image's first bytes, and its result is dropped.
-template <bool VEC_IN, bool VEC_OUT>
+// FRAMES (deepim_ingest_bgr8_pool_frames): `frames` and `fg` are (N,H,W[,3]) and pair b reads frame frame_index[b] of both,
+// under ingest_bgr8_kernel's alignment rule; use_bg and bg_index stay per pair. A pair without a frame is black with a
+// non-zero label everywhere: (0 - mean), no background.
+template <bool VEC_IN, bool VEC_OUT, bool FRAMES>
 __global__ __launch_bounds__(256) void ingest_bgr8_pool_kernel(float* __restrict__ out, const uint8_t* __restrict__ frames,
                                                                const uint8_t* __restrict__ fg,
                                                                const int32_t* __restrict__ use_bg, BgPool pool, Vec3 means,
-                                                               long hw, long n) {
+                                                               long hw, long n, FrameSel fs) {
   const long p0 = ((long)blockIdx.x * 256 + threadIdx.x) * 4;
   if (p0 >= n) return;
   const int cnt = (int)min(4L, n - p0);
@@ -184,8 +219,13 @@ __global__ __launch_bounds__(256) void ingest_bgr8_pool_kernel(float* __restrict
   for (int j = 1; j < 4; ++j) { bs[j] = bs[j - 1]; qs[j] = qs[j - 1]; next_pixel(hw, bs[j], qs[j]); }
   uint32_t pix[4], lab[4];   // 0x00RRGGBB of the frame; the label
   if (VEC_IN && cnt == 4) {
-    const Bytes12 v = *reinterpret_cast<const Bytes12*>(frames + p0 * 3);
-    const uint32_t l = *reinterpret_cast<const uint32_t*>(fg + p0);
+    const long s0 = source_pixel<FRAMES>(fs, p0, bs[0], qs[0], hw);
+    Bytes12 v = {{0u, 0u, 0u}};
+    uint32_t l = 0x01010101u;
+    if (!FRAMES || s0 >= 0) {
+      v = *reinterpret_cast<const Bytes12*>(frames + s0 * 3);
+      l = *reinterpret_cast<const uint32_t*>(fg + s0);
+    }
     pix[0] = v.w[0] & 0xffffffu;
     pix[1] = (v.w[0] >> 24) | ((v.w[1] & 0xffffu) << 8);
     pix[2] = (v.w[1] >> 16) | ((v.w[2] & 0xffu) << 16);
@@ -197,9 +237,12 @@ __global__ __launch_bounds__(256) void ingest_bgr8_pool_kernel(float* __restrict
     for (int j = 0; j < 4; ++j) {
       pix[j] = 0; lab[j] = 1;
       if (j < cnt) {
-        const uint8_t* s = frames + (p0 + j) * 3;
-        pix[j] = (uint32_t)s[0] | ((uint32_t)s[1] << 8) | ((uint32_t)s[2] << 16);
-        lab[j] = fg[p0 + j];
+        const long sp = source_pixel<FRAMES>(fs, p0 + j, bs[j], qs[j], hw);
+        if (!FRAMES || sp >= 0) {
+          const uint8_t* s = frames + sp * 3;
+          pix[j] = (uint32_t)s[0] | ((uint32_t)s[1] << 8) | ((uint32_t)s[2] << 16);
+          lab[j] = fg[sp];
+        }
       }
     }
   }
@@ -250,26 +293,6 @@ __global__ __launch_bounds__(256) void ingest_bgr8_pool_kernel(float* __restrict
 #pragma unroll
     for (int c = 0; c < 3; ++c) px[c][j] = (float)((pix[j] >> (8 * (2 - c))) & 0xffu);
   store_planes<VEC_OUT>(out, px, means, bs, qs, hw, cnt);
-}
-
-// Shared frames (the *_frames entries): the input of pair b is frame frame_index[b] of N, not sample b. The ids live on the
-// device: one outside [0, N) reads nothing (the pair's output is zeros) and is reported through DI_STATUS_FRAME_RANGE by the
-// lane that owns the pair's first pixel. Unused (and never read) by the per-sample entries.
-struct FrameSel {
-  const int32_t* frame_index;   // (B)
-  int* status;
-  int N;
-};
-// input offset of in-sample pixel q of pair b, or -1 for a pair without a frame
-template <bool FRAMES>
-__device__ __forceinline__ long source_pixel(const FrameSel& fs, long p, long b, long q, long hw) {
-  if (!FRAMES) return p;
-  const int id = fs.frame_index[b];
-  if (id < 0 || id >= fs.N) {
-    if (q == 0) atomicOr(fs.status, DI_STATUS_FRAME_RANGE);
-    return -1;
-  }
-  return (long)id * hw + q;
 }
 
 // out (B,1,H,W) is as flat as the inputs: pixel p of the batch goes to out[p]. VEC with FRAMES: hw % 4 == 0 as well, so that
@@ -443,27 +466,44 @@ __global__ __launch_bounds__(256) void mask_gate_kernel(float* __restrict__ mask
   }
 }
 
+// deepim_gather_rows: out[b] = table[index[b]] for rows of `row_units` units T (uint4 where the row length and the three
+// pointers allow 16-byte accesses, else one 4-byte word), one lane per unit of the B·row_units flat run. An index outside
+// [0, n_rows) reads nothing: the row is zeros, reported through DI_STATUS_FRAME_RANGE by the lane that owns its first unit.
+// Rows may be whole frames of a resident set: the table offset is 64-bit.
+template <class T>
+__global__ __launch_bounds__(256) void gather_rows_kernel(T* __restrict__ out, const T* __restrict__ table,
+                                                          const int32_t* __restrict__ index, int n_rows, long row_units, long n,
+                                                          int* status) {
+  const long u = (long)blockIdx.x * 256 + threadIdx.x;
+  if (u >= n) return;
+  long b, r;
+  locate_pixel(u, row_units, n, b, r);
+  const int id = index[b];
+  T v = T();
+  if (id >= 0 && id < n_rows) v = table[(long)id * row_units + r];
+  else if (r == 0) atomicOr(status, DI_STATUS_FRAME_RANGE);
+  out[u] = v;
+}
+
 inline bool aligned_to(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
-}  // namespace
-
-extern "C" int deepim_ingest_bgr8(deepim_ctx* ctx, float* out, const uint8_t* frames, const uint8_t* bg_frames,
-                                  const uint8_t* fg_labels, const int32_t* use_bg, const float* means_rgb, int B, int H,
-                                  int W) {
-  DI_DEVICE(ctx);
-  DI_REQUIRE(B >= 0 && H >= 0 && W >= 0, "ingest_bgr8: negative size");
-  DI_REQUIRE((bg_frames == NULL) == (fg_labels == NULL), "ingest_bgr8: bg_frames and fg_labels come together or not at all");
-  DI_REQUIRE(bg_frames != NULL || use_bg == NULL, "ingest_bgr8: use_bg without bg_frames");
-  const long hw = (long)H * W, n = (long)B * hw;
-  if (n == 0) return 0;
+// the launch of both BGR entries: fs = NULL reads sample b (deepim_ingest_bgr8), else frame fs->frame_index[b]
+int launch_ingest_bgr8(deepim_ctx* ctx, float* out, const uint8_t* frames, const uint8_t* bg_frames, const uint8_t* fg_labels,
+                       const int32_t* use_bg, const float* means_rgb, long hw, long n, const FrameSel* fs) {
   Vec3 means = {{0.f, 0.f, 0.f}};
   if (means_rgb) for (int i = 0; i < 3; ++i) means.v[i] = means_rgb[i];
-  const bool vin = aligned_to(frames, 4) && (!bg_frames || (aligned_to(bg_frames, 4) && aligned_to(fg_labels, 4)));
+  const bool vin = aligned_to(frames, 4) && (!bg_frames || (aligned_to(bg_frames, 4) && aligned_to(fg_labels, 4))) &&
+                   (!fs || hw % 4 == 0);
   const bool vout = hw % 4 == 0 && aligned_to(out, 16);
   const dim3 grid(di_div_up(di_div_up(n, 4), 256)), block(256);
-#define DI_INGEST_BGR(VI, VO)                                                                                            \
-  hipLaunchKernelGGL((ingest_bgr8_kernel<VI, VO>), grid, block, 0, ctx->stream, out, frames, bg_frames, fg_labels, use_bg, \
-                     means, hw, n)
+  const FrameSel sel = fs ? *fs : FrameSel{NULL, NULL, 0};
+#define DI_INGEST_BGR(VI, VO)                                                                                              \
+  do {                                                                                                                     \
+    if (fs) hipLaunchKernelGGL((ingest_bgr8_kernel<VI, VO, true>), grid, block, 0, ctx->stream, out, frames, bg_frames,    \
+                               fg_labels, use_bg, means, hw, n, sel);                                                      \
+    else hipLaunchKernelGGL((ingest_bgr8_kernel<VI, VO, false>), grid, block, 0, ctx->stream, out, frames, bg_frames,      \
+                            fg_labels, use_bg, means, hw, n, sel);                                                         \
+  } while (0)
   if (vin && vout) DI_INGEST_BGR(true, true);
   else if (vin) DI_INGEST_BGR(true, false);
   else if (vout) DI_INGEST_BGR(false, true);
@@ -473,12 +513,10 @@ extern "C" int deepim_ingest_bgr8(deepim_ctx* ctx, float* out, const uint8_t* fr
   return 0;
 }
 
-extern "C" int deepim_ingest_bgr8_pool(deepim_ctx* ctx, float* out, const uint8_t* frames, const uint8_t* fg_labels,
-                                       const int32_t* use_bg, const int32_t* bg_index, const uint8_t* pool_pixels,
-                                       const int64_t* pool_desc, const int32_t* xtab, const int32_t* ytab, int P,
-                                       const float* means_rgb, int B, int H, int W) {
-  DI_DEVICE(ctx);
-  DI_REQUIRE(B >= 0 && H >= 0 && W >= 0, "ingest_bgr8_pool: negative size");
+// the launch of both pool entries, after their argument checks
+int launch_ingest_bgr8_pool(deepim_ctx* ctx, float* out, const uint8_t* frames, const uint8_t* fg_labels, const int32_t* use_bg,
+                            const int32_t* bg_index, const uint8_t* pool_pixels, const int64_t* pool_desc, const int32_t* xtab,
+                            const int32_t* ytab, int P, const float* means_rgb, int B, int H, int W, const FrameSel* fs) {
   const long hw = (long)H * W, n = (long)B * hw;
   DI_REQUIRE(hw <= 0x7fffffffL, "ingest_bgr8_pool: frame too large");
   if (n == 0) return 0;
@@ -491,17 +529,95 @@ extern "C" int deepim_ingest_bgr8_pool(deepim_ctx* ctx, float* out, const uint8_
   if (means_rgb) for (int i = 0; i < 3; ++i) means.v[i] = means_rgb[i];
   const BgPool pool = {pool_pixels, pool_desc, reinterpret_cast<const uint32_t*>(xtab), reinterpret_cast<const uint32_t*>(ytab),
                        bg_index, ctx->status, P, H, W};
-  const bool vin = aligned_to(frames, 4) && aligned_to(fg_labels, 4);
+  const bool vin = aligned_to(frames, 4) && aligned_to(fg_labels, 4) && (!fs || hw % 4 == 0);
   const bool vout = hw % 4 == 0 && aligned_to(out, 16);
   const dim3 grid(di_div_up(di_div_up(n, 4), 256)), block(256);
-#define DI_INGEST_POOL(VI, VO)                                                                                          \
-  hipLaunchKernelGGL((ingest_bgr8_pool_kernel<VI, VO>), grid, block, 0, ctx->stream, out, frames, fg_labels, use_bg, pool, \
-                     means, hw, n)
+  const FrameSel sel = fs ? *fs : FrameSel{NULL, NULL, 0};
+#define DI_INGEST_POOL(VI, VO)                                                                                               \
+  do {                                                                                                                       \
+    if (fs) hipLaunchKernelGGL((ingest_bgr8_pool_kernel<VI, VO, true>), grid, block, 0, ctx->stream, out, frames, fg_labels, \
+                               use_bg, pool, means, hw, n, sel);                                                             \
+    else hipLaunchKernelGGL((ingest_bgr8_pool_kernel<VI, VO, false>), grid, block, 0, ctx->stream, out, frames, fg_labels,   \
+                            use_bg, pool, means, hw, n, sel);                                                                \
+  } while (0)
   if (vin && vout) DI_INGEST_POOL(true, true);
   else if (vin) DI_INGEST_POOL(true, false);
   else if (vout) DI_INGEST_POOL(false, true);
   else DI_INGEST_POOL(false, false);
 #undef DI_INGEST_POOL
+  DI_LAUNCH_CHECK();
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int deepim_ingest_bgr8(deepim_ctx* ctx, float* out, const uint8_t* frames, const uint8_t* bg_frames,
+                                  const uint8_t* fg_labels, const int32_t* use_bg, const float* means_rgb, int B, int H,
+                                  int W) {
+  DI_DEVICE(ctx);
+  DI_REQUIRE(B >= 0 && H >= 0 && W >= 0, "ingest_bgr8: negative size");
+  DI_REQUIRE((bg_frames == NULL) == (fg_labels == NULL), "ingest_bgr8: bg_frames and fg_labels come together or not at all");
+  DI_REQUIRE(bg_frames != NULL || use_bg == NULL, "ingest_bgr8: use_bg without bg_frames");
+  const long hw = (long)H * W, n = (long)B * hw;
+  if (n == 0) return 0;
+  return launch_ingest_bgr8(ctx, out, frames, bg_frames, fg_labels, use_bg, means_rgb, hw, n, NULL);
+}
+
+extern "C" int deepim_ingest_bgr8_frames(deepim_ctx* ctx, float* out, const uint8_t* frames, const int32_t* frame_index, int N,
+                                         const float* means_rgb, int B, int H, int W) {
+  DI_DEVICE(ctx);
+  DI_REQUIRE(B >= 0 && H >= 0 && W >= 0, "ingest_bgr8_frames: negative size");
+  const long hw = (long)H * W, n = (long)B * hw;
+  if (n == 0) return 0;
+  DI_REQUIRE(N >= 1 && out && frames && frame_index, "ingest_bgr8_frames: out, frames, frame_index and N >= 1 are required");
+  DI_REQUIRE(aligned_to(frame_index, 4), "ingest_bgr8_frames: frame_index must be 4-byte aligned");
+  const FrameSel fs = {frame_index, ctx->status, N};
+  return launch_ingest_bgr8(ctx, out, frames, NULL, NULL, NULL, means_rgb, hw, n, &fs);
+}
+
+extern "C" int deepim_ingest_bgr8_pool(deepim_ctx* ctx, float* out, const uint8_t* frames, const uint8_t* fg_labels,
+                                       const int32_t* use_bg, const int32_t* bg_index, const uint8_t* pool_pixels,
+                                       const int64_t* pool_desc, const int32_t* xtab, const int32_t* ytab, int P,
+                                       const float* means_rgb, int B, int H, int W) {
+  DI_DEVICE(ctx);
+  DI_REQUIRE(B >= 0 && H >= 0 && W >= 0, "ingest_bgr8_pool: negative size");
+  return launch_ingest_bgr8_pool(ctx, out, frames, fg_labels, use_bg, bg_index, pool_pixels, pool_desc, xtab, ytab, P, means_rgb,
+                                 B, H, W, NULL);
+}
+
+extern "C" int deepim_ingest_bgr8_pool_frames(deepim_ctx* ctx, float* out, const uint8_t* frames, const uint8_t* fg_labels,
+                                              const int32_t* frame_index, int N, const int32_t* use_bg, const int32_t* bg_index,
+                                              const uint8_t* pool_pixels, const int64_t* pool_desc, const int32_t* xtab,
+                                              const int32_t* ytab, int P, const float* means_rgb, int B, int H, int W) {
+  DI_DEVICE(ctx);
+  DI_REQUIRE(B >= 0 && H >= 0 && W >= 0, "ingest_bgr8_pool_frames: negative size");
+  if ((long)B * H * W == 0) return 0;
+  DI_REQUIRE(N >= 1 && frame_index && aligned_to(frame_index, 4),
+             "ingest_bgr8_pool_frames: a 4-byte aligned frame_index and N >= 1 are required");
+  const FrameSel fs = {frame_index, ctx->status, N};
+  return launch_ingest_bgr8_pool(ctx, out, frames, fg_labels, use_bg, bg_index, pool_pixels, pool_desc, xtab, ytab, P, means_rgb,
+                                 B, H, W, &fs);
+}
+
+extern "C" int deepim_gather_rows(deepim_ctx* ctx, void* out, const void* table, const int32_t* index, int n_rows,
+                                  long row_words, int B) {
+  DI_DEVICE(ctx);
+  DI_REQUIRE(B >= 0 && row_words >= 0 && n_rows >= 0, "gather_rows: negative size");
+  if (B == 0 || row_words == 0) return 0;
+  DI_REQUIRE(out && table && index && n_rows >= 1, "gather_rows: out, table, index and n_rows >= 1 are required");
+  DI_REQUIRE(aligned_to(out, 4) && aligned_to(table, 4) && aligned_to(index, 4), "gather_rows: every pointer must be 4-byte aligned");
+  DI_REQUIRE(out != table, "gather_rows: out == table (a gather cannot run in place)");
+  if (row_words % 4 == 0 && aligned_to(out, 16) && aligned_to(table, 16)) {
+    const long units = row_words / 4, n = (long)B * units;
+    DI_REQUIRE(n <= 0x7fffffffL * 256L, "gather_rows: batch too large");
+    hipLaunchKernelGGL(gather_rows_kernel<uint4>, dim3(di_div_up(n, 256)), dim3(256), 0, ctx->stream, static_cast<uint4*>(out),
+                       static_cast<const uint4*>(table), index, n_rows, units, n, ctx->status);
+  } else {
+    const long n = (long)B * row_words;
+    DI_REQUIRE(n <= 0x7fffffffL * 256L, "gather_rows: batch too large");
+    hipLaunchKernelGGL(gather_rows_kernel<uint32_t>, dim3(di_div_up(n, 256)), dim3(256), 0, ctx->stream,
+                       static_cast<uint32_t*>(out), static_cast<const uint32_t*>(table), index, n_rows, row_words, n, ctx->status);
+  }
   DI_LAUNCH_CHECK();
   return 0;
 }

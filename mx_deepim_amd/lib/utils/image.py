@@ -214,6 +214,28 @@ def transform_batch_pool(ctx, frames_bgr, means_rgb, fg, use_bg, bg_index, pool)
     return out
 
 
+def transform_batch_frames(ctx, frames_bgr, frame_index, means_rgb=None, fg=None, use_bg=None, bg_index=None, pool=None):
+    """transform_batch / transform_batch_pool (with `pool`) of frames_bgr[frame_index] without the gather: frames_bgr (N,H,W,3)
+    uint8 and fg (N,H,W) uint8 stay where they are — a whole device-resident set, say — and pair b reads frame frame_index[b]
+    (device int32 (B), never read by the host) → (B,3,H,W) fp32. use_bg and bg_index stay per pair."""
+    N, H, W, _ = frames_bgr.shape
+    if frame_index.dtype != np.int32:
+        raise TypeError("transform_batch_frames: frame_index on the device must be int32")
+    B = frame_index.size
+    out = ctx.empty((B, 3, H, W))
+    means = None if means_rgb is None else np.ascontiguousarray(means_rgb, dtype=np.float32).reshape(3)
+    if pool is None:
+        lib.deepim_ingest_bgr8_frames(ctx.handle, out, frames_bgr, frame_index, N, means, B, H, W)
+        return out
+    if (pool.height, pool.width) != (H, W):
+        raise ValueError("the background pool was built for %dx%d frames, these are %dx%d" % (pool.height, pool.width, H, W))
+    if fg is None or fg.shape != (N, H, W):
+        raise ValueError("transform_batch_frames: the pool composite needs fg labels of shape %s" % ((N, H, W),))
+    lib.deepim_ingest_bgr8_pool_frames(ctx.handle, out, frames_bgr, fg, frame_index, N, use_bg, bg_index, pool.pixels, pool.desc,
+                                       pool.xtab, pool.ytab, len(pool), means, B, H, W)
+    return out
+
+
 def transform(im, pixel_means):
     """image.py:583-594: im [height, width, channel] uint8 in BGR, pixel_means in the image's BGR order → numpy
     [1, channel, height, width] in RGB order, computed on the default device in fp32 (the reference computes in float64)."""

@@ -77,7 +77,7 @@ class SyntheticObserved(object):
                                            brightness_ratio, B, self.height, self.width, ctypes.c_float(rm.zNear),
                                            ctypes.c_float(rm.zFar))
 
-    def frames(self, class_index, draw_ids, out=None, rows=None):
+    def frames(self, class_index, draw_ids, out=None, rows=None, rows_device=None):
         """class_index: device int32 (B) or host ids; draw_ids: device uint64 (B) or host integers. -> dict of device arrays:
         image_observed (N,H,W,3) uint8 BGR, depth_gt_observed (N,H,W) uint16, mask_gt_observed (N,H,W) uint8 (1 on the object),
         pose_observed, attempts (B) int32 (pose_sampler.sample_observed_poses), light_offset, light_intensity (B,3),
@@ -87,7 +87,7 @@ class SyntheticObserved(object):
         batch's own arrays of N >= B rows and sample b goes to row rows[b] (a HOST sequence: the caller planned the batch);
         the other rows are not touched. The frames are written in place by the draw; the poses are placed by one device copy
         per run of consecutive rows. The returned dict holds `out`'s arrays, pose_observed included when it was given (else the
-        compact (B,3,4) one)."""
+        compact (B,3,4) one). `rows_device`: `rows` as a device int32 (B) array the caller already holds, instead of an upload."""
         ctx = self.ctx
         if not isinstance(class_index, DeviceArray):
             class_index = ctx.array(np.asarray(class_index).reshape(-1), dtype=np.int32)
@@ -108,7 +108,7 @@ class SyntheticObserved(object):
             N = out["image_observed"].shape[0]
             if B and (rows.min() < 0 or rows.max() >= N or len(set(rows.tolist())) != B):
                 raise ValueError("frames: rows must be distinct and inside [0, %d)" % N)
-            rows_dev = ctx.array(rows, dtype=np.int32)
+            rows_dev = ctx.array(rows, dtype=np.int32) if rows_device is None else rows_device
         self.draw_into(out["image_observed"], out["depth_gt_observed"], out["mask_gt_observed"], class_index, pose, off, inten,
                        ratio, rows=rows_dev)
         res = {k: out[k] for k, _dt, _inner in FRAME_KEYS}
