@@ -1058,6 +1058,33 @@ int deepim_render_frames_forward(deepim_ctx* ctx, uint8_t* image /*N,H,W,3*/, ui
                                  const int32_t* faces, const float* textures /*or NULL*/, const float* poses,
                                  const float* K_host /*or NULL: camera table*/, int B, int H, int W, float znear, float zfar);
 
+/* The lit mesh-table draw of deepim_render_observed_forward for a SCENE: S slots (1..8) per frame share one z-buffer plane, so
+ * that objects hide one another. Ours: the reference has no generator for occluded scenes. Sample d = f S + s (frame f < B,
+ * slot s < S) has its own class_index[d], poses[d] and label_value[d] (NULL = s + 1); a class id outside the table is an empty
+ * slot. The light is per FRAME, light_offset (B,3), light_intensity (B,3), brightness_ratio (B), moved to each slot's own pose as
+ * lib/render_glumpy/render_py_light_multi_program.py:370-396 lights the objects of a scene: slot s is shaded exactly as the
+ * observed entry shades a sample with that light and the slot's pose, L = offset + (t_x, -t_y, -t_z).
+ *   key      float_bits(Z) << 32 | s << 24 | triangle (max_F <= 2^24). Within a slot the winner is the single-object draw's;
+ *            between slots the nearer fragment wins and an exact depth tie goes to the LOWER slot.
+ *   outputs  row rows[f] (device int32 (B), NULL = f) of image / depth / label (N rows), stored as the observed entry stores
+ *            them, four pixels per lane or one; label = the winning slot's label value where depth != 0. Rows not named are not
+ *            touched and a frame whose row is outside [0, N) is not written (its pixels are still counted).
+ *   visible  device int32 (B,S) or NULL: visible[f,s] = the pixels of frame f won by slot s with a non-zero stored depth. The call
+ *            WRITES it (zeroed on the stream first). With S = 1 it is what covered is in deepim_render_frames_forward.
+ * With S = 1 the three outputs are the bytes of deepim_render_observed_forward. The z-buffer holds B planes and leaves the call
+ * all-ones; the projected-vertex scratch is B S x max_V records. Host errors before any launch: S outside 1..8, B S > 65535,
+ * max_F > 2^24, zfar * depth_factor >= 65536, K_host NULL (the bound camera table is per pair, not per slot). Asynchronous,
+ * allocates like the other draws (scratch and z-buffer grow outside a capture only). */
+int deepim_render_scene_forward(deepim_ctx* ctx, uint8_t* image /*N,H,W,3*/, uint16_t* depth /*N,H,W*/, uint8_t* label /*N,H,W*/,
+                                int32_t* visible /*device (B,S) or NULL*/, const int32_t* rows /*device (B) or NULL*/, int N,
+                                const int32_t* label_value /*device (B,S) or NULL*/, float depth_factor,
+                                const int32_t* class_index /*device (B,S)*/, const int32_t* mesh_desc /*device (n_classes,8)*/,
+                                int n_classes, int max_V, int max_F, const float* vertices, const float* vertex_attr,
+                                const float* normals, const int32_t* faces, const float* textures /*or NULL*/,
+                                const float* poses /*device (B,S,3,4)*/, const float* K_host, const float* light_offset /*device (B,3)*/,
+                                const float* light_intensity /*device (B,3)*/, const float* brightness_ratio /*device (B)*/, int B,
+                                int S, int H, int W, float znear, float zfar);
+
 /* ------------------------------------------- I-group: ingest of decoded frames -- */
 /* csrc/ingest.hip. What lib/utils/image.py does on the host between cv2.imread and the tensors of a batch, on frames that
  * are already on the device as the camera / decoder left them (uint8 / uint16): 1 or 2 bytes per value cross PCIe, not 4.
@@ -1184,7 +1211,8 @@ int deepim_l2_norms_multi(deepim_ctx* ctx, float* out /*rows*/, const uint64_t* 
  *   key     = (seed low word, seed high word)
  *   counter = (draw id low, draw id high, attempt, stream)      streams 0, 1: the two blocks of a pose draw; 2: mask dilate;
  *                                                               3: background; 4, 5: the two blocks of an observed-pose draw;
- *                                                               6: light
+ *                                                               6: light; 7, 8: the placement and rotation blocks of a
+ *                                                               scene's occluders (attempt = the slot)
  * so a pair's draw does not depend on the batch size, its position in the batch or the order of launches. The draw id of pair b
  * is draw_ids[b] where draw_ids (device, B) is given, else draw_base + b (draw_base is not added to given ids).
  * A 32-bit word x becomes the uniform u = (x + 0.5) 2^-32 in double, strictly inside (0,1); six normals come pairwise from the
@@ -1268,6 +1296,37 @@ int deepim_observed_pose_candidate(deepim_ctx* ctx, float* pose_out /*B,3,4*/, d
 int deepim_sample_lights(deepim_ctx* ctx, float* light_offset /*B,3*/, float* light_intensity /*B,3*/,
                          float* brightness_ratio /*B*/, const float* ratios /*host*/, int n_ratios, unsigned long long seed,
                          unsigned long long draw_base, const unsigned long long* draw_ids /*B dev or NULL*/, int B);
+
+/* The occluders of a synthetic scene (ours: the reference has no such generator), one thread per pair, in double, rounded to
+ * float. Outputs for S = max_occluders + 1 slots: class_out (B,S) int32, pose_out (B,S,3,4), label_value_out (B,S) = s + 1.
+ * Slot 0 is the target (target_class[b], target_pose[b]) copied through. Streams 7 and 8 of the pair's draw id:
+ *   stream 7, attempt 0, word 0 -> the count n, uniform in [min_occluders, max_occluders] (no draw when max_occluders = 0)
+ *   stream 7, attempt s = 1..n: word 0 -> the class, uniform over occluder_classes (it may be the target's); words 1-3 as
+ *       uniforms -> rho in [lateral_lo, lateral_hi], phi in [0, 2 pi), tau in [toward_lo, toward_hi];
+ *       t = t_target + d (rho cos phi, rho sin phi, -tau), d = diameters[target class] in metres
+ *   stream 8, attempt s: four normals -> the unit quaternion, negated if w < 0 -> quat2mat, as stream 4's
+ * Slots beyond n, and an occluder with t_z <= 0, are empty: class -1 and a zero pose. occluder_classes: device int32
+ * (n_occluder_classes); diameters: device float (n_classes), indexed by class id. 0 <= min <= max <= 7. */
+int deepim_sample_occluders(deepim_ctx* ctx, int32_t* class_out /*B,S dev*/, float* pose_out /*B,S,3,4*/,
+                            int32_t* label_value_out /*B,S dev*/, const int32_t* target_class /*B dev*/,
+                            const float* target_pose /*B,3,4*/, const int32_t* occluder_classes /*dev*/, int n_occluder_classes,
+                            const float* diameters /*n_classes dev*/, int n_classes, int min_occluders, int max_occluders,
+                            float lateral_lo, float lateral_hi, float toward_lo, float toward_hi, unsigned long long seed,
+                            unsigned long long draw_base, const unsigned long long* draw_ids /*B dev or NULL*/, int B);
+/* The fallback for a synthetic scene (csrc/ingest.hip), one launch. visible (B,S): deepim_render_scene_forward's counts of the
+ * scene; full (B): its counts of the target drawn alone (S = 1). Pair b is KEPT iff full[b] > 0 and (double)visible[b,0] >=
+ * (double)min_visible full[b] (lib/utils/mask_augment.py:91-93 falls back below 0.4). With row = rows[b] (device int32, NULL = b)
+ * of the batch arrays (N rows) and the alone frames as B compact rows:
+ *   always      depth_gt[row] <- the alone depth (the flow labels and point clouds are made from the target alone)
+ *   not kept    image[row], label[row] and, where given, depth_observed[row] <- the alone frame's
+ * kept (B) int32 is written. totals (3 device uint64, or NULL) += B, the pairs kept, and the slots s >= 1 of slot_class (B,S, or
+ * NULL) that hold a class (>= 0). A row outside [0, N) is not written. Allocates nothing; legal inside a capture. */
+int deepim_occlusion_gate(deepim_ctx* ctx, uint8_t* image /*N,H,W,3*/, uint16_t* depth_gt /*N,H,W*/, uint8_t* label /*N,H,W*/,
+                          uint16_t* depth_observed /*N,H,W or NULL*/, int32_t* kept /*B dev*/, unsigned long long* totals /*3 dev or NULL*/,
+                          const int32_t* rows /*B dev or NULL*/, int N, const uint8_t* alone_image /*B,H,W,3*/,
+                          const uint16_t* alone_depth /*B,H,W*/, const uint8_t* alone_label /*B,H,W*/, const int32_t* visible /*B,S dev*/,
+                          const int32_t* full /*B dev*/, const int32_t* slot_class /*B,S dev or NULL*/, float min_visible, int B, int S,
+                          int H, int W);
 
 #ifdef __cplusplus
 }

@@ -40,6 +40,13 @@ its own depth and its mask_idx 1. The synthetic classes are checked against the 
 pair can come out with attempts = −1 and the observed attempts feed deepim_sample_stats_accumulate as they are. Without
 `synthetic` every batch, draw id and byte is what it is without the argument.
 
+A `synthetic` built with occluders (SyntheticObserved(..., occluders=OccluderSpec(...))) puts up to max_occluders other objects
+into a synthetic pair's frame (streams 7 and 8 of its draw id). The plan, the draw ids and the real rows do not change. The
+pair's label map shows the visible part of the target only (mask_idx stays 1), its depth_gt_observed stays the target drawn
+alone, and with network.INPUT_DEPTH its depth_observed is the scene's depth, occluders included. A pair whose target keeps less
+than min_visible of its pixels falls back to today's unoccluded frame. stats() then also counts the pairs gated, kept and the
+occluder slots drawn.
+
 `observed` = core/resident.ResidentObserved(observed, ctx, spare_rows=batch_size, points=points): the set uploaded once. The
 plan, the draw ids, the seeds and every refusal are the same and so is every byte of every batch, but a batch is made from
 indices alone: frame_index (B int32), the draw ids (B uint64) and, with synthetic pairs, their positions and class ids go up;
@@ -50,8 +57,7 @@ set (resident.batch_rows), which the loader claims when it is built: safe on one
 before batch k+1's draw and a batch keeps fp32 copies only. A dict holding a DeviceArray is still refused.
 
 Not part of this loader and refused: ready-made backgrounds (bg_image: the pool is the loader's way), TRAIN.MASK_SYN, resizing (a frame that is not config.SCALES[0]),
-shared-frame batches (frame_index), synthetic frames with more than one object or with occluders
-(LM6D_OCC), and a synthetic set kept across epochs (SyntheticObserved.to_host makes a fixed one for the `observed` argument).
+shared-frame batches (frame_index), more than one target per synthetic frame, and a synthetic set kept across epochs (SyntheticObserved.to_host makes a fixed one for the `observed` argument).
 """
 import numpy as np
 
@@ -190,7 +196,9 @@ class TrainDataLoader(object):
         self.K = np.ascontiguousarray(config.dataset.INTRINSIC_MATRIX, np.float32).reshape(3, 3)
         self._rng = np.random.RandomState(self.seed)
         # pairs drawn, sum of attempts, exhausted pairs: device-resident; with `synthetic` the same three of the observed-pose draws
-        self._totals = self.ctx.zeros((3,) if synthetic is None else (6,), np.uint64)
+        # with occluders three more: pairs gated, pairs kept, occluder slots drawn
+        self.occluded = synthetic is not None and getattr(synthetic, "occluders", None) is not None
+        self._totals = self.ctx.zeros((3,) if synthetic is None else (9,) if self.occluded else (6,), np.uint64)
         self.epoch = 0
         self._plan()
 
@@ -215,6 +223,8 @@ class TrainDataLoader(object):
         out = {"pairs": int(t[0]), "attempts": int(t[1]), "exhausted": int(t[2])}
         if self.synthetic is not None:
             out.update(observed_pairs=int(t[3]), observed_attempts=int(t[4]), observed_exhausted=int(t[5]))
+        if self.occluded:
+            out.update(occluded_pairs=int(t[6]), occluded_kept=int(t[7]), occluder_slots=int(t[8]))
         return out
 
     def _image_observed(self, frames, always, ids):
@@ -262,9 +272,9 @@ class TrainDataLoader(object):
         pose_observed = ctx.array(pose)
         if syn.size:      # the synthetic rows: poses, lights and frames made on the device, straight into the batch's arrays
             drawn = self.synthetic.frames(cls_syn, np.asarray(draw_ids).reshape(B)[syn], rows=syn,
-                                          out=dict(frames, pose_observed=pose_observed))
+                                          out=dict(frames, pose_observed=pose_observed), **self._gate_totals())
             lib.deepim_sample_stats_accumulate(ctx.handle, self._totals[3:6], drawn["attempts"], int(syn.size))
-            if cfg.network.INPUT_DEPTH:       # their depth_observed is their own depth
+            if cfg.network.INPUT_DEPTH and not self.occluded:       # their depth_observed is their own depth (occluded: the scene's)
                 for j0, j1, r0 in runs(syn):
                     frames["depth_observed"][r0:r0 + (j1 - j0)].copyfrom(frames["depth_gt_observed"][r0:r0 + (j1 - j0)])
         batch = {"image_observed": self._image_observed(frames, always, ids),
@@ -279,6 +289,10 @@ class TrainDataLoader(object):
             batch["point_cloud_model"] = ctx.array(np.stack([self.points[int(c)][0] for c in cls]))
             batch["point_cloud_weights"] = ctx.array(np.stack([self.points[int(c)][1] for c in cls]))
         return self._finish(batch, ids, B)
+
+    def _gate_totals(self):
+        """The keyword that hands the generator the occlusion gate's three running totals; nothing without occluders."""
+        return {"totals": self._totals[6:9]} if self.occluded else {}
 
     def _finish(self, batch, ids, B):
         """The rendered side and the labels of a batch whose observed side is made: the same for both kinds of set."""
@@ -308,12 +322,13 @@ class TrainDataLoader(object):
                 at = ctx.array(syn, dtype=np.int32)
                 ids_syn = res.gather(ids.reshape((B, 1)), at, syn.size).reshape((syn.size,))
                 rows_syn = res.gather(fi, at, syn.size)
+            out = {k: res.arrays[k] for k in self.keys}       # depth_observed only with INPUT_DEPTH, as over a host set
             drawn = self.synthetic.frames(cls_syn, ids_syn, rows=rows[syn], rows_device=rows_syn,
-                                          out=dict(res.arrays, pose_observed=res.tables["pose_observed"]))
+                                          out=dict(out, pose_observed=res.tables["pose_observed"]), **self._gate_totals())
             lib.deepim_sample_stats_accumulate(ctx.handle, self._totals[3:6], drawn["attempts"], int(syn.size))
             for j0, j1, r0 in runs(rows[syn]):
                 res.tables["class_index"][r0:r0 + (j1 - j0)].copyfrom(cls_syn[j0:j1])
-                if cfg.network.INPUT_DEPTH:       # their depth_observed is their own depth
+                if cfg.network.INPUT_DEPTH and not self.occluded:       # their depth_observed is their own depth (occluded: the scene's)
                     res.arrays["depth_observed"][r0:r0 + (j1 - j0)].copyfrom(res.arrays["depth_gt_observed"][r0:r0 + (j1 - j0)])
         frames = {k: res.arrays[k] for k in self.keys}
         frames["frame_index"] = fi

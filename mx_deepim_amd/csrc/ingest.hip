@@ -485,6 +485,79 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(T* __restrict__ out, c
   out[u] = v;
 }
 
+// deepim_occlusion_gate: the fallback of lib/utils/mask_augment.py:91-93 for the synthetic scenes of deepim_render_scene_forward. Pair
+// b (blockIdx.y: visible, full, the row and the verdict are scalar loads and uniform exits) is kept iff full[b] > 0 and
+// visible[b,0] >= min_visible full[b], in double. Its depth_gt row always becomes the alone depth; a kept pair's blocks stop
+// there, the others copy the alone image and label (and depth_observed) over the scene's. A byte copy: four pixels per lane
+// (three dwords, two, one) or single pixels. Block (0,0) also adds the batch's counts to the running totals: integer sums over
+// visible / full / slot_class, which no block writes, by one block per launch, so plain adds as in sample_stats_kernel.
+struct OcclusionGate {
+  uint8_t* image; uint16_t* depth_gt; uint8_t* label; uint16_t* depth_observed;       // (N,H,W[,3]); depth_observed or NULL
+  const uint8_t* alone_image; const uint16_t* alone_depth; const uint8_t* alone_label;  // (B,H,W[,3])
+  const int32_t* visible; const int32_t* full; const int32_t* slot_class; const int32_t* rows;
+  int32_t* kept;
+  unsigned long long* totals;
+  float min_visible;
+  int N, B, S;
+  long hw;
+  __device__ __forceinline__ bool keep(int b) const {
+    const int f = full[b];
+    return f > 0 && (double)visible[(long)b * S] >= (double)min_visible * (double)f;
+  }
+};
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void occlusion_gate_kernel(OcclusionGate a) {
+  const int b = blockIdx.y;
+  const bool keep = a.keep(b);
+  if (blockIdx.x == 0 && threadIdx.x == 0) a.kept[b] = keep ? 1 : 0;
+  if (a.totals != nullptr && blockIdx.x == 0 && b == 0) {      // uniform per block: the barrier below is reached by all 256 threads
+    __shared__ unsigned long long red[4][2];
+    unsigned long long nk = 0, ns = 0;
+    for (int i = threadIdx.x; i < a.B; i += 256) {
+      nk += a.keep(i) ? 1ull : 0ull;
+      if (a.slot_class != nullptr)
+        for (int s = 1; s < a.S; ++s) ns += a.slot_class[(long)i * a.S + s] >= 0 ? 1ull : 0ull;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      nk += __shfl_xor(nk, off, 64);
+      ns += __shfl_xor(ns, off, 64);
+    }
+    if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6][0] = nk; red[threadIdx.x >> 6][1] = ns; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      a.totals[0] += (unsigned long long)a.B;
+      a.totals[1] += (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]);
+      a.totals[2] += (red[0][1] + red[1][1]) + (red[2][1] + red[3][1]);
+    }
+  }
+  const int row = a.rows ? a.rows[b] : b;
+  if ((unsigned)row >= (unsigned)a.N) return;
+  const long p0 = ((long)blockIdx.x * 256 + threadIdx.x) * (VEC ? 4 : 1);
+  if (p0 >= a.hw) return;
+  const long src = (long)b * a.hw + p0, dst = (long)row * a.hw + p0;
+  if (VEC) {
+    const uint2 d = *reinterpret_cast<const uint2*>(a.alone_depth + src);
+    *reinterpret_cast<uint2*>(a.depth_gt + dst) = d;
+    if (keep) return;
+    const uint32_t* si = reinterpret_cast<const uint32_t*>(a.alone_image + src * 3);
+    uint32_t* di = reinterpret_cast<uint32_t*>(a.image + dst * 3);
+    const uint32_t w0 = si[0], w1 = si[1], w2 = si[2];
+    di[0] = w0; di[1] = w1; di[2] = w2;
+    *reinterpret_cast<uint32_t*>(a.label + dst) = *reinterpret_cast<const uint32_t*>(a.alone_label + src);
+    if (a.depth_observed != nullptr) *reinterpret_cast<uint2*>(a.depth_observed + dst) = d;
+  } else {
+    const uint16_t d = a.alone_depth[src];
+    a.depth_gt[dst] = d;
+    if (keep) return;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) a.image[dst * 3 + c] = a.alone_image[src * 3 + c];
+    a.label[dst] = a.alone_label[src];
+    if (a.depth_observed != nullptr) a.depth_observed[dst] = d;
+  }
+}
+
 inline bool aligned_to(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
 // the launch of both BGR entries: fs = NULL reads sample b (deepim_ingest_bgr8), else frame fs->frame_index[b]
@@ -726,6 +799,30 @@ extern "C" int deepim_mask_gate(deepim_ctx* ctx, float* mask, const int32_t* cov
   const bool vec = hw % 4 == 0 && aligned_to(mask, 16);
   if (vec) hipLaunchKernelGGL(mask_gate_kernel<true>, dim3(di_div_up(hw / 4, 256), B), dim3(256), 0, ctx->stream, mask, covered, hw);
   else hipLaunchKernelGGL(mask_gate_kernel<false>, dim3(di_div_up(hw, 256), B), dim3(256), 0, ctx->stream, mask, covered, hw);
+  DI_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int deepim_occlusion_gate(deepim_ctx* ctx, uint8_t* image, uint16_t* depth_gt, uint8_t* label, uint16_t* depth_observed,
+                                     int32_t* kept, unsigned long long* totals, const int32_t* rows, int N, const uint8_t* alone_image,
+                                     const uint16_t* alone_depth, const uint8_t* alone_label, const int32_t* visible,
+                                     const int32_t* full, const int32_t* slot_class, float min_visible, int B, int S, int H, int W) {
+  DI_DEVICE(ctx);
+  DI_REQUIRE(B >= 0 && N >= B && H >= 0 && W >= 0, "occlusion_gate: the batch arrays need N >= B >= 0 rows");
+  DI_REQUIRE(B <= 65535 && S >= 1 && S <= 8, "occlusion_gate: B <= 65535 and S in 1..8");
+  DI_REQUIRE(min_visible >= 0.f && min_visible <= 1.f, "occlusion_gate: min_visible in [0, 1]");
+  const long hw = (long)H * W;
+  DI_REQUIRE(hw <= 0x7fffffffL, "occlusion_gate: frame too large");
+  if (B == 0 || hw == 0) return 0;
+  DI_REQUIRE(image && depth_gt && label && kept && alone_image && alone_depth && alone_label && visible && full,
+             "occlusion_gate: NULL argument");
+  DI_REQUIRE(image != alone_image && depth_gt != alone_depth && label != alone_label, "occlusion_gate: the alone frames are the batch's own arrays");
+  const OcclusionGate a = {image, depth_gt, label, depth_observed, alone_image, alone_depth, alone_label, visible, full, slot_class,
+                           rows, kept, totals, min_visible, N, B, S, hw};
+  const bool vec = hw % 4 == 0 && aligned_to(image, 4) && aligned_to(alone_image, 4) && aligned_to(label, 4) && aligned_to(alone_label, 4) &&
+                   aligned_to(depth_gt, 8) && aligned_to(alone_depth, 8) && (!depth_observed || aligned_to(depth_observed, 8));
+  if (vec) hipLaunchKernelGGL(occlusion_gate_kernel<true>, dim3(di_div_up(hw / 4, 256), B), dim3(256), 0, ctx->stream, a);
+  else hipLaunchKernelGGL(occlusion_gate_kernel<false>, dim3(di_div_up(hw, 256), B), dim3(256), 0, ctx->stream, a);
   DI_LAUNCH_CHECK();
   return 0;
 }

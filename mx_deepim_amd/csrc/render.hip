@@ -16,7 +16,8 @@
 //             covered pixel on the key (float_bits(Z) << 32 | triangle id) — first triangle wins exact ties
 //   resolve:  one thread per pixel: re-derives the barycentrics of the winning triangle, shades, writes the
 //             network tensors directly: image (B,3,H,W) RGB mean-subtracted, depth (B,1,H,W), 0 = background
-//             (resolve_frames_kernel: the same fragment with a light per sample, stored as uint8 / uint16 frames)
+//             (resolve_frames_kernel: the same fragment with a light per sample, stored as uint8 / uint16 frames;
+//             resolve_scene_kernel: several objects per frame in one z-buffer plane, the key carrying the object's slot)
 #include "common.h"
 #include <limits.h>
 
@@ -138,9 +139,23 @@ __device__ __forceinline__ float pixel_depth(const Tri& t, float w0, float w1, f
   return 1.0f / inv;
 }
 
-template <class Src>
+// Where a sample's fragments go. OwnPlane: sample b owns z-buffer plane b and its keys carry the triangle id alone.
+// ScenePlane (deepim_render_scene_forward): sample d = f S + s is slot s of frame f; the S slots of a frame share plane f and a
+// key carries the slot in bits 24..31 of its low word, above the triangle id (max_F <= 2^24), so that between objects the
+// nearer fragment wins and an exact depth tie goes to the lower slot; within a slot the order is the single-object draw's.
+struct OwnPlane {
+  __device__ __forceinline__ int plane(int b) const { return b; }
+  __device__ __forceinline__ unsigned tag(int) const { return 0u; }
+};
+struct ScenePlane {
+  int S;
+  __device__ __forceinline__ int plane(int d) const { return d / S; }
+  __device__ __forceinline__ unsigned tag(int d) const { return (unsigned)(d % S) << 24; }
+};
+
+template <class Src, class Plane>
 __global__ __launch_bounds__(256) void raster_kernel(unsigned long long* __restrict__ zbuf, const PV* __restrict__ pv_all,
-                                                     Src src, int H, int W, float znear, float zfar) {
+                                                     Src src, Plane plane, int H, int W, float znear, float zfar) {
   const int b = blockIdx.y, f = blockIdx.x * 256 + threadIdx.x;
   MeshRef m;
   if (!src.mesh(b, m) || f >= m.F) return;
@@ -152,14 +167,15 @@ __global__ __launch_bounds__(256) void raster_kernel(unsigned long long* __restr
   if (!(maxx >= 0.f && minx <= (float)(W - 1) && maxy >= 0.f && miny <= (float)(H - 1))) return;
   const int x0 = max(0, (int)ceilf(minx)), x1 = min(W - 1, (int)floorf(maxx));
   const int y0 = max(0, (int)ceilf(miny)), y1 = min(H - 1, (int)floorf(maxy));
-  unsigned long long* zb = zbuf + (long)b * H * W;
+  unsigned long long* zb = zbuf + (long)plane.plane(b) * H * W;
+  const unsigned low = plane.tag(b) | (unsigned)f;
   for (int y = y0; y <= y1; ++y)
     for (int x = x0; x <= x1; ++x) {
       float w0, w1, w2;
       if (!cover(t, (float)x, (float)y, w0, w1, w2)) continue;
       const float z = pixel_depth(t, w0, w1, w2);
       if (!(z > znear && z < zfar)) continue;  // GL clips fragments outside [zNear, zFar]
-      const unsigned long long key = ((unsigned long long)__float_as_uint(z) << 32) | (unsigned)f;
+      const unsigned long long key = ((unsigned long long)__float_as_uint(z) << 32) | low;
       atomicMin(zb + (long)y * W + x, key);
     }
 }
@@ -342,6 +358,48 @@ struct FrameOut {
   int N;
 };
 
+// The two ends of a frame resolve pass, for the PX consecutive pixels a lane owns (PX = 4 or 1).
+// take_keys: the lane's z-buffer keys, put back to all-ones where an object was: the z-buffer leaves the call as it entered it.
+// With PX = 4 the keys are 32 contiguous, 32-byte aligned bytes: two 16-byte loads.
+template <int PX>
+__device__ __forceinline__ void take_keys(unsigned long long* zb, unsigned long long (&keys)[PX]) {
+  if constexpr (PX == 4) {
+    const ulonglong2 k01 = reinterpret_cast<const ulonglong2*>(zb)[0], k23 = reinterpret_cast<const ulonglong2*>(zb)[1];
+    keys[0] = k01.x; keys[1] = k01.y; keys[2] = k23.x; keys[3] = k23.y;
+    if ((k01.x & k01.y & k23.x & k23.y) != ~0ull) {
+      const ulonglong2 ones = {~0ull, ~0ull};
+      reinterpret_cast<ulonglong2*>(zb)[0] = ones;
+      reinterpret_cast<ulonglong2*>(zb)[1] = ones;
+    }
+  } else {
+    keys[0] = zb[0];
+    if (keys[0] != ~0ull) zb[0] = ~0ull;
+  }
+}
+// store_frame_pixels: BGR levels, uint16 depths and labels (label == nullptr: not stored) at pixel q of the (N,H,W[,3]) outputs.
+template <int PX>
+__device__ __forceinline__ void store_frame_pixels(unsigned char* image, unsigned short* depth, unsigned char* label, long q,
+                                                   const unsigned (&bgr)[PX * 3], const unsigned (&d16)[PX], const unsigned (&l8)[PX]) {
+  if constexpr (PX == 4) {
+    uint3 w;
+    w.x = bgr[0] | bgr[1] << 8 | bgr[2] << 16 | bgr[3] << 24;
+    w.y = bgr[4] | bgr[5] << 8 | bgr[6] << 16 | bgr[7] << 24;
+    w.z = bgr[8] | bgr[9] << 8 | bgr[10] << 16 | bgr[11] << 24;
+    unsigned* img = reinterpret_cast<unsigned*>(image + q * 3);
+    img[0] = w.x; img[1] = w.y; img[2] = w.z;
+    uint2 d;
+    d.x = d16[0] | d16[1] << 16;
+    d.y = d16[2] | d16[3] << 16;
+    *reinterpret_cast<uint2*>(depth + q) = d;
+    if (label != nullptr) *reinterpret_cast<unsigned*>(label + q) = l8[0] | l8[1] << 8 | l8[2] << 16 | l8[3] << 24;
+  } else {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) image[q * 3 + c] = (unsigned char)bgr[c];
+    depth[q] = (unsigned short)d16[0];
+    if (label != nullptr) label[q] = (unsigned char)l8[0];
+  }
+}
+
 // Resolve pass of the frame draw: lane g of a sample owns the PX consecutive pixels PX g .. PX g + PX - 1.
 // PX = 4 (the plane is a multiple of 4 pixels and the three outputs are 8-byte aligned): the lane stores its 12 image bytes as
 // three dwords, its four depths as one 8-byte store and its four labels as one dword, so a wave writes 768 + 512 + 256
@@ -363,18 +421,7 @@ __global__ __launch_bounds__(256) void resolve_frames_kernel(FrameOut out, unsig
   unsigned long long* zb = zbuf + (long)b * plane + p0;
   unsigned bgr[PX * 3], d16[PX], l8[PX];
   unsigned long long keys[PX];
-  if constexpr (PX == 4) {                       // the lane's four keys are 32 contiguous, 32-byte aligned bytes: two 16-byte loads
-    const ulonglong2 k01 = reinterpret_cast<const ulonglong2*>(zb)[0], k23 = reinterpret_cast<const ulonglong2*>(zb)[1];
-    keys[0] = k01.x; keys[1] = k01.y; keys[2] = k23.x; keys[3] = k23.y;
-    if ((k01.x & k01.y & k23.x & k23.y) != ~0ull) {      // the z-buffer leaves the call as it entered it: all-ones
-      const ulonglong2 ones = {~0ull, ~0ull};
-      reinterpret_cast<ulonglong2*>(zb)[0] = ones;
-      reinterpret_cast<ulonglong2*>(zb)[1] = ones;
-    }
-  } else {
-    keys[0] = zb[0];
-    if (keys[0] != ~0ull) zb[0] = ~0ull;
-  }
+  take_keys<PX>(zb, keys);
 #pragma unroll
   for (int i = 0; i < PX; ++i) {
     const unsigned long long key = keys[i];
@@ -394,24 +441,85 @@ __global__ __launch_bounds__(256) void resolve_frames_kernel(FrameOut out, unsig
   }
   if (!store) return;
   const long q = (long)row * plane + p0;
-  if constexpr (PX == 4) {
-    uint3 w;
-    w.x = bgr[0] | bgr[1] << 8 | bgr[2] << 16 | bgr[3] << 24;
-    w.y = bgr[4] | bgr[5] << 8 | bgr[6] << 16 | bgr[7] << 24;
-    w.z = bgr[8] | bgr[9] << 8 | bgr[10] << 16 | bgr[11] << 24;
-    unsigned* img = reinterpret_cast<unsigned*>(out.image + q * 3);
-    img[0] = w.x; img[1] = w.y; img[2] = w.z;
-    uint2 d;
-    d.x = d16[0] | d16[1] << 16;
-    d.y = d16[2] | d16[3] << 16;
-    *reinterpret_cast<uint2*>(out.depth + q) = d;
-    if (out.label != nullptr) *reinterpret_cast<unsigned*>(out.label + q) = l8[0] | l8[1] << 8 | l8[2] << 16 | l8[3] << 24;
-  } else {
+  store_frame_pixels<PX>(out.image, out.depth, out.label, q, bgr, d16, l8);
+}
+
+// Light source of deepim_render_scene_forward: one light per FRAME (render_py_light_multi_program.py:370-396 lights the objects of
+// a scene with one light moved to each object's own pose), three device arrays with one row per frame. f is blockIdx.y, so these
+// stay scalar loads; the pose is the slot's own, row d = f S + s of `poses`, and varies per lane.
+struct LitPerFrame {
+  const float* poses;      // (B S,3,4)
+  const float* off;        // (B,3)
+  const float* intensity;  // (B,3)
+  const float* ratio;      // (B)
+  int f;                   // set by the kernel: its frame
+  static constexpr bool lit = true;
+  __device__ __forceinline__ float offset(int, int r) const { return off[f * 3 + r]; }
+  __device__ __forceinline__ float inten(int, int c) const { return intensity[f * 3 + c]; }
+  __device__ __forceinline__ float rat(int) const { return ratio[f]; }
+  static __device__ __forceinline__ unsigned level(float v) { return (unsigned)(int)v; }
+};
+
+// Destination of deepim_render_scene_forward: FrameOut's rows of decoded frames, one per frame f of S slots.
+struct SceneOut {
+  unsigned char* image;         // (N,H,W,3) BGR levels
+  unsigned short* depth;        // (N,H,W)
+  unsigned char* label;         // (N,H,W) label_value[f S + s] of the winning slot s where depth != 0, else 0
+  int* visible;                 // (B,S) zeroed before the launch: += slot s's pixels of frame f with a non-zero stored depth; or nullptr
+  const int* rows;              // (B) or nullptr
+  const int* label_value;       // (B S) or nullptr = s + 1
+  float depth_factor;
+  int N, S;
+};
+
+// Resolve pass of the scene draw: resolve_frames_kernel over the B frames, each pixel shaded as the slot that won it. The slot
+// sits in bits 24..31 of the key's low word (ScenePlane); it is taken out and the remaining key is what the single-object draw of
+// sample f S + s leaves, so resolve_pixel gives that draw's fragment. The mesh row, the pose and the label value belong to the
+// pixel's slot: they vary per lane inside a block and are vector loads here, no longer the scalar loads of the one-object
+// passes; the light and the destination row depend on blockIdx.y alone and stay scalar. HBM-bound like its pattern: 8 B/px of
+// key read (plus the put-back where an object was), 6 B/px stored. out.visible: per slot one ballot per owned pixel and at most
+// one atomic add per wave, by lane 0 (live in every wave with a live lane, as in resolve_frames_kernel).
+template <int PX>
+__global__ __launch_bounds__(256) void resolve_scene_kernel(SceneOut out, unsigned long long* __restrict__ zbuf,
+                                                            const PV* __restrict__ pv_all, MeshTable src, int H, int W, float znear,
+                                                            LitPerFrame lit) {
+  const int f = blockIdx.y, S = out.S;
+  lit.f = f;
+  const long plane = (long)H * W;
+  const long p0 = ((long)blockIdx.x * 256 + threadIdx.x) * PX;
+  if (p0 >= plane) return;                       // PX = 4: plane % 4 == 0, so a lane owns four pixels or none
+  const int row = out.rows ? out.rows[f] : f;
+  const bool store = (unsigned)row < (unsigned)out.N;
+  unsigned long long* zb = zbuf + (long)f * plane + p0;
+  unsigned bgr[PX * 3], d16[PX], l8[PX], slot[PX];
+  unsigned long long keys[PX];
+  take_keys<PX>(zb, keys);
 #pragma unroll
-    for (int c = 0; c < 3; ++c) out.image[q * 3 + c] = (unsigned char)bgr[c];
-    out.depth[q] = (unsigned short)d16[0];
-    if (out.label != nullptr) out.label[q] = (unsigned char)l8[0];
+  for (int i = 0; i < PX; ++i) {
+    const unsigned s = (unsigned)(keys[i] >> 24) & 0xffu;
+    const bool hit = keys[i] != ~0ull && s < (unsigned)S;      // the S slots' raster threads wrote every key: s < S; checked, since s makes addresses
+    const unsigned long long key = keys[i] & ~0xff000000ull;
+    const int d = f * S + (int)s;
+    const Frag fr = resolve_pixel(hit, key, d, p0 + i, pv_all, src, W, znear, lit);
+    const float* rgb = fr.rgb; const float z = fr.z;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) bgr[i * 3 + c] = LitPerFrame::level(rgb[2 - c]);
+    d16[i] = (unsigned)(int)(z * out.depth_factor) & 0xffffu;
+    const unsigned lab = (unsigned)(out.label_value ? (hit ? out.label_value[d] : 0) : (int)s + 1) & 0xffu;
+    l8[i] = z != 0.f ? lab : 0u;
+    slot[i] = s;
   }
+  if (out.visible != nullptr) {
+    for (int s = 0; s < S; ++s) {
+      int n = 0;
+#pragma unroll
+      for (int i = 0; i < PX; ++i) n += __popcll(__ballot(d16[i] != 0u && slot[i] == (unsigned)s));
+      if (n != 0 && (threadIdx.x & 63) == 0) atomicAdd(out.visible + f * S + s, n);
+    }
+  }
+  if (!store) return;
+  const long q = (long)row * plane + p0;
+  store_frame_pixels<PX>(out.image, out.depth, out.label, q, bgr, d16, l8);
 }
 
 }  // namespace
@@ -419,11 +527,12 @@ __global__ __launch_bounds__(256) void resolve_frames_kernel(FrameOut out, unsig
 // The front of every entry's launch group: project (grid (ceil(max_V/256), B)) and raster (grid (ceil(max_F/256), B)) into the
 // context's z-buffer, which is left dirty: the caller launches a resolve pass next and clears ctx->zbuf_dirty.
 // max_V / max_F: the largest mesh `src` can select; the projected-vertex scratch (*pv_out) is B x max_V records.
-template <class Src>
-static int render_front(deepim_ctx* ctx, const Src& src, int max_V, int max_F, const float* poses, const float* K_host, int B, int H,
-                        int W, float znear, float zfar, int* words, PV** pv_out) {
+// plane: where the B samples' fragments go (OwnPlane: `planes` = B; ScenePlane{S}: `planes` = B / S frames).
+template <class Src, class Plane>
+static int render_front(deepim_ctx* ctx, const Src& src, const Plane& plane, int planes, int max_V, int max_F, const float* poses,
+                        const float* K_host, int B, int H, int W, float znear, float zfar, int* words, PV** pv_out) {
   DI_REQUIRE(znear > 0.f && zfar > znear, "render: need 0 < zNear < zFar");
-  const size_t zbytes = (size_t)B * H * W * sizeof(unsigned long long);
+  const size_t zbytes = (size_t)planes * H * W * sizeof(unsigned long long);
   const size_t pbytes = (size_t)B * max_V * sizeof(PV);
   void* scratch;
   int rc = deepim_scratch(ctx, pbytes + 64, &scratch);
@@ -453,8 +562,8 @@ static int render_front(deepim_ctx* ctx, const Src& src, int max_V, int max_F, c
                        CamTable{ctx->cam_table}, words);
   DI_LAUNCH_CHECK();
   ctx->zbuf_dirty = 1;
-  hipLaunchKernelGGL(raster_kernel<Src>, dim3(di_div_up(max_F, 256), B), dim3(256), 0, ctx->stream, ctx->zbuf, pv, src, H, W, znear,
-                     zfar);
+  hipLaunchKernelGGL((raster_kernel<Src, Plane>), dim3(di_div_up(max_F, 256), B), dim3(256), 0, ctx->stream, ctx->zbuf, pv, src, plane,
+                     H, W, znear, zfar);
   *pv_out = pv;
   return 0;
 }
@@ -472,7 +581,7 @@ static int render_launch(deepim_ctx* ctx, float* image, float* depth, float* mas
   LitParams lit = {poses, light_intensity, {{0, 0, 0}}, ratio};
   if (light_offset_host) for (int i = 0; i < 3; ++i) lit.light_offset.v[i] = light_offset_host[i];
   PV* pv;
-  int rc = render_front(ctx, src, max_V, max_F, poses, K_host, B, H, W, znear, zfar, words, &pv);
+  int rc = render_front(ctx, src, OwnPlane{}, B, max_V, max_F, poses, K_host, B, H, W, znear, zfar, words, &pv);
   if (rc) return rc;
   unsigned long long* zbuf = ctx->zbuf;
   hipLaunchKernelGGL(resolve_kernel<Src>, dim3(di_div_up((long)H * W, 256), B), dim3(256), 0, ctx->stream, image, depth, zbuf,
@@ -570,7 +679,7 @@ template <class Lit>
 static int frames_launch(deepim_ctx* ctx, const FrameOut& out, const MeshTable& src, const Lit& lit, int max_V, int max_F,
                          const float* poses, const float* K_host, int B, int H, int W, float znear, float zfar) {
   PV* pv;
-  int rc = render_front(ctx, src, max_V, max_F, poses, K_host, B, H, W, znear, zfar, nullptr, &pv);
+  int rc = render_front(ctx, src, OwnPlane{}, B, max_V, max_F, poses, K_host, B, H, W, znear, zfar, nullptr, &pv);
   if (rc) return rc;
   const long plane = (long)H * W;
   const bool quad = plane % 4 == 0 && (((uintptr_t)out.image | (uintptr_t)out.depth | (uintptr_t)out.label) & 7) == 0;
@@ -633,4 +742,48 @@ extern "C" int deepim_render_frames_forward(deepim_ctx* ctx, uint8_t* image, uin
   if (covered) DI_CHECK(hipMemsetAsync(covered, 0, (size_t)B * sizeof(int32_t), ctx->stream));
   const FrameOut out = {image, depth, label, (int*)covered, (const int*)rows, (const int*)label_value, depth_factor, N};
   return frames_launch(ctx, out, src, Unlit{}, max_V, max_F, poses, K_host, B, H, W, znear, zfar);
+}
+
+// The lit mesh-table draw of a SCENE: S slots per frame share one z-buffer plane (layout: include/deepim_hip.h).
+extern "C" int deepim_render_scene_forward(deepim_ctx* ctx, uint8_t* image, uint16_t* depth, uint8_t* label, int32_t* visible,
+                                           const int32_t* rows, int N, const int32_t* label_value, float depth_factor,
+                                           const int32_t* class_index, const int32_t* mesh_desc, int n_classes, int max_V, int max_F,
+                                           const float* vertices, const float* vertex_attr, const float* normals, const int32_t* faces,
+                                           const float* textures, const float* poses, const float* K_host, const float* light_offset,
+                                           const float* light_intensity, const float* brightness_ratio, int B, int S, int H, int W,
+                                           float znear, float zfar) {
+  DI_DEVICE(ctx);
+  DI_REQUIRE(S >= 1 && S <= 8, "render_scene: S (slots per frame) must lie in 1..8");
+  DI_REQUIRE(B >= 0 && N >= B, "render_scene: the outputs need N >= B >= 0 rows");
+  DI_REQUIRE((long)B * S <= 65535, "render_scene: B * S must stay below 65536");
+  DI_REQUIRE(max_F <= (1 << 24), "render_scene: a mesh of more than 2^24 triangles leaves no room for the slot in the key");
+  DI_REQUIRE(depth_factor > 0.f && zfar * depth_factor < 65536.f, "render_scene: zFar * depth_factor must stay below 65536");
+  if (B == 0) return 0;
+  DI_REQUIRE(K_host != nullptr, "render_scene: K_host is required (the camera table is per pair, not per slot)");
+  DI_REQUIRE(n_classes > 0 && max_V > 0 && max_F > 0 && H > 0 && W > 0, "render_scene: empty mesh table or image");
+  DI_REQUIRE(image && depth && label, "render_scene: image, depth and label are required");
+  DI_REQUIRE(class_index != nullptr && mesh_desc != nullptr && poses != nullptr, "render_scene: class_index, mesh_desc and poses are required");
+  DI_REQUIRE(normals != nullptr && light_offset != nullptr && light_intensity != nullptr && brightness_ratio != nullptr,
+             "render_scene: the lit draw needs normals and the three per-frame light arrays");
+  DI_REQUIRE((long)H * W <= 0x7fffffffL, "render_scene: frame too large for the int32 pixel count");
+  const MeshTable src = {(const int*)class_index, (const int*)mesh_desc, vertices, vertex_attr, normals, (const int*)faces,
+                         textures, n_classes, max_V, max_F};
+  // the call WRITES visible: zeroed in stream order ahead of the resolve pass's adds (a memset node inside a capture)
+  if (visible) DI_CHECK(hipMemsetAsync(visible, 0, (size_t)B * S * sizeof(int32_t), ctx->stream));
+  PV* pv;
+  int rc = render_front(ctx, src, ScenePlane{S}, B, max_V, max_F, poses, K_host, B * S, H, W, znear, zfar, nullptr, &pv);
+  if (rc) return rc;
+  const SceneOut out = {image, depth, label, (int*)visible, (const int*)rows, (const int*)label_value, depth_factor, N, S};
+  const LitPerFrame lit = {poses, light_offset, light_intensity, brightness_ratio, 0};
+  const long plane = (long)H * W;
+  const bool quad = plane % 4 == 0 && (((uintptr_t)image | (uintptr_t)depth | (uintptr_t)label) & 7) == 0;
+  if (quad)
+    hipLaunchKernelGGL(resolve_scene_kernel<4>, dim3(di_div_up(plane / 4, 256), B), dim3(256), 0, ctx->stream, out, ctx->zbuf, pv, src,
+                       H, W, znear, lit);
+  else
+    hipLaunchKernelGGL(resolve_scene_kernel<1>, dim3(di_div_up(plane, 256), B), dim3(256), 0, ctx->stream, out, ctx->zbuf, pv, src, H,
+                       W, znear, lit);
+  DI_LAUNCH_CHECK();
+  ctx->zbuf_dirty = 0;
+  return 0;
 }

@@ -8,7 +8,8 @@
 //
 // Every draw is a pure function of (seed, draw id, attempt, stream): key = (seed lo, seed hi), counter = (id lo, id hi, attempt,
 // stream). Streams 0 and 1 are the two blocks of a pose draw, stream 2 is the mask-dilate draw, stream 3 the background draw,
-// streams 4 and 5 the quaternion and translation blocks of an observed-pose draw, stream 6 the light draw.
+// streams 4 and 5 the quaternion and translation blocks of an observed-pose draw, stream 6 the light draw, streams 7 and 8 the
+// placement and rotation blocks of a scene's occluders (attempt = the slot; attempt 0 of stream 7 is their count).
 // Nothing depends on the batch size, on a pair's position in the batch or on the order of launches.
 //
 // The kernels run one thread per pair; every array below is indexed by constants after unrolling, so nothing lives in
@@ -276,21 +277,13 @@ __device__ __forceinline__ void observed_normals(unsigned long long seed, unsign
   box_muller(b.w[2], b.w[3], z[6], unused);
 }
 
-// One candidate of LM6d_ds_0_gen_observed_poses.py:203-220 from given normals, in float64:
-//   tgt_quat = z[0:4] / |z[0:4]|, negated if w < 0      tgt_trans = trans_mean + z[4:7] trans_std (np.random.normal(mean, std))
-//   R = quat2mat(tgt_quat) in the expression order of RT_transform.quat2mat
-//   deg = angle(R e_z, pz_mean) as :74-78: arccos(clip(u.v / (|u| |v|), -1, 1)) in degrees
-//   (cx, cy) = the projection of tgt_trans through K
-//   accept iff deg <= angle_max and border < cx < W - border and border < cy < H - border and tgt_trans.z > 0
-// The z > 0 clause is not the reference's, which divides by z unguarded (as in pose_perturb_one).
-// row: the class's table row; pose: the candidate [R | t] in double (12); stat: deg, cx, cy. Returns the accept flag.
-__device__ __forceinline__ bool observed_pose_one(const double* __restrict__ row, const double* z, const ObservedRule& p, double* pose,
-                                                  double* stat) {
+// Four normals as a rotation: the quaternion z / |z|, negated if w < 0, through RT_transform.quat2mat in its expression order.
+__device__ __forceinline__ void normals_to_rotation(const double* z, double* R) {
   const double n = sqrt(((z[0] * z[0] + z[1] * z[1]) + z[2] * z[2]) + z[3] * z[3]);
   double w = z[0] / n, x = z[1] / n, y = z[2] / n, q = z[3] / n;
   if (w < 0.0) { w = -w; x = -x; y = -y; q = -q; }
   const double Nq = ((w * w + x * x) + y * y) + q * q;
-  double R[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
+  R[0] = 1.0; R[1] = 0.0; R[2] = 0.0; R[3] = 0.0; R[4] = 1.0; R[5] = 0.0; R[6] = 0.0; R[7] = 0.0; R[8] = 1.0;
   if (!(Nq < 2.220446049250313e-16)) {
     const double s = 2.0 / Nq;
     const double X = x * s, Y = y * s, Z = q * s;
@@ -301,6 +294,20 @@ __device__ __forceinline__ bool observed_pose_one(const double* __restrict__ row
     R[3] = xY + wZ; R[4] = 1.0 - (xX + zZ); R[5] = yZ - wX;
     R[6] = xZ - wY; R[7] = yZ + wX; R[8] = 1.0 - (xX + yY);
   }
+}
+
+// One candidate of LM6d_ds_0_gen_observed_poses.py:203-220 from given normals, in float64:
+//   tgt_quat = z[0:4] / |z[0:4]|, negated if w < 0      tgt_trans = trans_mean + z[4:7] trans_std (np.random.normal(mean, std))
+//   R = quat2mat(tgt_quat) in the expression order of RT_transform.quat2mat
+//   deg = angle(R e_z, pz_mean) as :74-78: arccos(clip(u.v / (|u| |v|), -1, 1)) in degrees
+//   (cx, cy) = the projection of tgt_trans through K
+//   accept iff deg <= angle_max and border < cx < W - border and border < cy < H - border and tgt_trans.z > 0
+// The z > 0 clause is not the reference's, which divides by z unguarded (as in pose_perturb_one).
+// row: the class's table row; pose: the candidate [R | t] in double (12); stat: deg, cx, cy. Returns the accept flag.
+__device__ __forceinline__ bool observed_pose_one(const double* __restrict__ row, const double* z, const ObservedRule& p, double* pose,
+                                                  double* stat) {
+  double R[9];
+  normals_to_rotation(z, R);
   const double tx = row[0] + z[4] * row[3];
   const double ty = row[1] + z[5] * row[4];
   const double tz = row[2] + z[6] * row[5];
@@ -400,6 +407,73 @@ __global__ __launch_bounds__(256) void sample_observed_poses_kernel(float* __res
   if (stat_out) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) stat_out[(long)b * 4 + i] = sk[i];
+  }
+}
+
+// ---- occluders of a synthetic scene (ours: the reference has no generator for occluded scenes)
+
+struct OccluderRule {
+  int min_occluders, max_occluders, n_list, n_classes;
+  float lateral_lo, lateral_hi, toward_lo, toward_hi;      // in diameters of the target's class
+};
+
+// The S = max_occluders + 1 slots of pair b: slot 0 is the target, copied through. Stream 7, attempt 0, word 0 -> the count n in
+// [min, max] (not drawn when max_occluders = 0). Slot s = 1..n: stream 7, attempt s -> word 0 the class out of `list` (it may be
+// the target's), words 1-3 as uniforms rho in lateral, phi in [0, 2 pi), tau in toward: t = t_target + d (rho cos phi,
+// rho sin phi, -tau), d = diameters[target class] (0 for a class id outside the table); stream 8, attempt s -> four normals ->
+// the rotation, as stream 4's. Slots beyond n, and an occluder behind the camera (t_z <= 0): class -1, a zero pose.
+__global__ __launch_bounds__(256) void sample_occluders_kernel(int* __restrict__ class_out, float* __restrict__ pose_out,
+                                                               int* __restrict__ label_out, const int* __restrict__ target_class,
+                                                               const float* __restrict__ target_pose, const int* __restrict__ list,
+                                                               const float* __restrict__ diameters, OccluderRule p,
+                                                               unsigned long long seed, unsigned long long draw_base,
+                                                               const unsigned long long* __restrict__ draw_ids, int B) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= B) return;
+  const unsigned long long id = draw_ids ? draw_ids[b] : draw_base + (unsigned long long)b;
+  const int S = p.max_occluders + 1;
+  const int cls = target_class[b];
+  float T[12];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) T[i] = target_pose[(long)b * 12 + i];
+  class_out[(long)b * S] = cls;
+  label_out[(long)b * S] = 1;
+#pragma unroll
+  for (int i = 0; i < 12; ++i) pose_out[(long)b * S * 12 + i] = T[i];
+  if (S == 1) return;
+  const double d = (unsigned)cls < (unsigned)p.n_classes ? (double)diameters[cls] : 0.0;
+  const int n = p.min_occluders + word_below(philox_draw(seed, id, 0u, 7u).w[0], p.max_occluders - p.min_occluders + 1);
+  for (int s = 1; s < S; ++s) {
+    int c = -1;
+    float out[12];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) out[i] = 0.f;
+    if (s <= n) {
+      const Philox4 a = philox_draw(seed, id, (unsigned int)s, 7u);
+      const Philox4 r = philox_draw(seed, id, (unsigned int)s, 8u);
+      const double rho = (double)p.lateral_lo + ((double)p.lateral_hi - (double)p.lateral_lo) * word_uniform(a.w[1]);
+      const double phi = 6.283185307179586 * word_uniform(a.w[2]);
+      const double tau = (double)p.toward_lo + ((double)p.toward_hi - (double)p.toward_lo) * word_uniform(a.w[3]);
+      const double tx = (double)T[3] + d * (rho * cos(phi));
+      const double ty = (double)T[7] + d * (rho * sin(phi));
+      const double tz = (double)T[11] - d * tau;
+      if (tz > 0.0) {
+        double z[4], R[9];
+        box_muller(r.w[0], r.w[1], z[0], z[1]);
+        box_muller(r.w[2], r.w[3], z[2], z[3]);
+        normals_to_rotation(z, R);
+        c = list[word_below(a.w[0], p.n_list)];
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+          for (int j = 0; j < 3; ++j) out[i * 4 + j] = (float)R[i * 3 + j];
+        out[3] = (float)tx; out[7] = (float)ty; out[11] = (float)tz;
+      }
+    }
+    class_out[(long)b * S + s] = c;
+    label_out[(long)b * S + s] = s + 1;
+#pragma unroll
+    for (int i = 0; i < 12; ++i) pose_out[((long)b * S + s) * 12 + i] = out[i];
   }
 }
 
@@ -575,6 +649,29 @@ extern "C" int deepim_sample_lights(deepim_ctx* ctx, float* light_offset, float*
   DI_REQUIRE(light_offset && light_intensity && brightness_ratio, "sample_lights: NULL argument");
   hipLaunchKernelGGL(sample_lights_kernel, dim3(di_div_up(B, 256)), dim3(256), 0, ctx->stream, light_offset, light_intensity,
                      brightness_ratio, r, n_ratios, seed, draw_base, draw_ids, B);
+  DI_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int deepim_sample_occluders(deepim_ctx* ctx, int32_t* class_out, float* pose_out, int32_t* label_value_out,
+                                       const int32_t* target_class, const float* target_pose, const int32_t* occluder_classes,
+                                       int n_occluder_classes, const float* diameters, int n_classes, int min_occluders,
+                                       int max_occluders, float lateral_lo, float lateral_hi, float toward_lo, float toward_hi,
+                                       unsigned long long seed, unsigned long long draw_base, const unsigned long long* draw_ids, int B) {
+  DI_DEVICE(ctx);
+  DI_REQUIRE(B >= 0, "sample_occluders: B must be >= 0");
+  DI_REQUIRE(min_occluders >= 0 && max_occluders >= min_occluders && max_occluders <= 7,
+             "sample_occluders: 0 <= min_occluders <= max_occluders <= 7");
+  DI_REQUIRE(lateral_lo >= 0.f && lateral_hi >= lateral_lo && toward_hi >= toward_lo,
+             "sample_occluders: the lateral range must be 0 <= lo <= hi and the toward range lo <= hi");
+  DI_REQUIRE(max_occluders == 0 || (n_occluder_classes >= 1 && n_classes >= 1), "sample_occluders: an empty class list or diameter table");
+  if (B == 0) return 0;
+  DI_REQUIRE(class_out && pose_out && label_value_out && target_class && target_pose, "sample_occluders: NULL argument");
+  DI_REQUIRE(max_occluders == 0 || (occluder_classes && diameters), "sample_occluders: occluder_classes and diameters are required");
+  const OccluderRule p = {min_occluders, max_occluders, n_occluder_classes, n_classes, lateral_lo, lateral_hi, toward_lo, toward_hi};
+  hipLaunchKernelGGL(sample_occluders_kernel, dim3(di_div_up(B, 256)), dim3(256), 0, ctx->stream, (int*)class_out, pose_out,
+                     (int*)label_value_out, (const int*)target_class, target_pose, (const int*)occluder_classes, diameters, p, seed,
+                     draw_base, draw_ids, B);
   DI_LAUNCH_CHECK();
   return 0;
 }

@@ -144,3 +144,29 @@ def sample_lights(ctx, B, seed, draw_base=0, draw_ids=None, brightness_ratios=BR
     lib.deepim_sample_lights(ctx.handle, offset, intensity, ratio, ratios, len(ratios), ctypes.c_ulonglong(int(seed) & U64),
                              ctypes.c_ulonglong(int(draw_base) & U64), device_draw_ids(ctx, draw_ids, B), B)
     return offset, intensity, ratio
+
+
+# ---- occluders of a synthetic scene: ours, the reference has no generator for occluded scenes -------------------------------
+MAX_SLOTS = 8        # deepim_render_scene_forward: the target and at most seven occluders share a z-buffer plane
+
+
+def sample_occluders(class_index, pose, occluder_classes, diameters, seed, draw_base=0, draw_ids=None, min_occluders=0,
+                     max_occluders=2, lateral=(0.2, 0.9), toward=(0.5, 1.5)):
+    """deepim_sample_occluders. class_index: device (B) int32 and pose: device (B,3,4) float32, the targets; occluder_classes:
+    device int32 list of class ids; diameters: device float32 (n_classes) in metres, indexed by class id.
+    -> device (class (B,S) int32, pose (B,S,3,4) float32, label_value (B,S) int32 = s + 1), S = max_occluders + 1. Slot 0 is the
+    target. Stream 7 of the pair's draw id gives the count n in [min_occluders, max_occluders] (attempt 0) and, for slot s = 1..n
+    (attempt s), the class out of the list and the translation t_target + d (rho cos phi, rho sin phi, -tau) with rho in
+    `lateral`, tau in `toward` (both in diameters d of the target's class) and phi in [0, 2 pi); stream 8, attempt s gives the
+    rotation (four normals as a unit quaternion). Slots beyond n, and an occluder behind the camera, are empty: class -1."""
+    for a, dt in ((class_index, np.int32), (pose, np.float32), (occluder_classes, np.int32), (diameters, np.float32)):
+        if not isinstance(a, DeviceArray) or a.dtype != dt:
+            raise TypeError("sample_occluders: class_index / occluder_classes are device int32, pose / diameters device float32 arrays")
+    ctx, B, S = class_index.context, class_index.size, int(max_occluders) + 1
+    cls, out, label = ctx.empty((B, S), np.int32), ctx.empty((B, S, 3, 4)), ctx.empty((B, S), np.int32)
+    cf = ctypes.c_float
+    lib.deepim_sample_occluders(ctx.handle, cls, out, label, class_index, pose, occluder_classes, occluder_classes.size, diameters,
+                                diameters.size, int(min_occluders), int(max_occluders), cf(lateral[0]), cf(lateral[1]), cf(toward[0]),
+                                cf(toward[1]), ctypes.c_ulonglong(int(seed) & U64), ctypes.c_ulonglong(int(draw_base) & U64),
+                                device_draw_ids(ctx, draw_ids, B), B)
+    return cls, out, label

@@ -13,7 +13,19 @@ deepim_render_observed_forward, lib/utils/synthetic_observed.py) at 480x640 with
     read-back, numpy quantisation to uint8 BGR / uint16 / label frames, upload of the frames. The parent route gets its poses
     and lights for free (it has no sampler for either). Alternating, host wall-clock around work that ends in a synchronise.
 (c) A whole TrainDataLoader step (make_batch + synchronise) without synthetic pairs and with half the batch synthetic,
-    alternating."""
+    alternating.
+
+    python tools/bench_synthetic.py --occluders N [--batch 32] ...
+
+measures the occluded scenes instead (deepim_sample_occluders, deepim_render_scene_forward with S = N + 1 slots per frame,
+deepim_occlusion_gate, SyntheticObserved(occluders=...)), every slot of every frame holding an object:
+(d) The occluder sampler, the gate and the scene draw's launch group (project and raster over B S samples, one resolve pass over
+    B frames), as in (a); the same launch group with every slot empty is the resolve pass over an untouched z-buffer, its
+    memory floor. Bytes: 8 B/px of key read, 6 B/px stored, per FRAME.
+(e) One batch of scenes by the scene entry against what there was before for the same frames: S deepim_render_observed_forward
+    draws of B samples, one float draw of the B S samples for their depths (the uint16 depths are truncated and cannot order
+    fragments), read-back, numpy composition (nearest float depth, lowest slot on ties) and upload. Alternating, as in (b).
+(f) A TrainDataLoader step with half the batch synthetic, without and with occluders, alternating, as in (c)."""
 import argparse
 import ctypes
 import json
@@ -31,7 +43,8 @@ from mx_deepim_amd.config import default_config  # noqa: E402
 from mx_deepim_amd.core.loader import TrainDataLoader  # noqa: E402
 from mx_deepim_amd.lib.pair_matching.pose_sampler import BRIGHTNESS_RATIOS, sample_lights, sample_observed_poses  # noqa: E402
 from mx_deepim_amd.lib.render_glumpy.render_py_light_modelnet_multi import Render_Py_Light_ModelNet_Multi  # noqa: E402
-from mx_deepim_amd.lib.utils.synthetic_observed import SyntheticObserved  # noqa: E402
+from mx_deepim_amd.lib.pair_matching.pose_sampler import sample_occluders  # noqa: E402
+from mx_deepim_amd.lib.utils.synthetic_observed import OccluderSpec, SyntheticObserved  # noqa: E402
 from mx_deepim_amd.runtime import Context, lib  # noqa: E402
 
 AXES = ([0.05, 0.04, 0.035], [0.03, 0.06, 0.04])
@@ -56,6 +69,148 @@ def pose_stats():
                     fallback=fallback) for c in (0, 1)}
 
 
+def occluded(ctx, a, rm, K, res):
+    """(d), (e), (f): the scenes with a.occluders occluder slots, all of them filled."""
+    B, H, W, S = a.batch, 480, 640, a.occluders + 1
+    n, h, u64 = B * H * W, ctx.handle, ctypes.c_ulonglong
+    spec = OccluderSpec([0, 1], {0: 0.10, 1: 0.12}, min_occluders=a.occluders, max_occluders=a.occluders)
+    syn = SyntheticObserved(rm, pose_stats(), K, seed=31, occluders=spec)
+    plain = SyntheticObserved(rm, pose_stats(), K, seed=31)
+    t = rm.mesh_table()
+    cls_host = (np.arange(B) % 2).astype(np.int32)
+    cls, ids = ctx.array(cls_host, dtype=np.int32), ctx.array(np.arange(B), dtype=np.uint64)
+    poses, _attempts = sample_observed_poses(cls, syn.pose_table, K, W, H, 31, draw_ids=ids)
+    off, inten, ratio = sample_lights(ctx, B, 31, draw_ids=ids)
+    res.update(occluders=a.occluders, slots=S)
+
+    # ---- (d) the kernels
+    o_out = ctx.empty((B, S), np.int32), ctx.empty((B, S, 3, 4)), ctx.empty((B, S), np.int32)
+    st = time_kernel(ctx, lambda i: lib.deepim_sample_occluders(h, o_out[0], o_out[1], o_out[2], cls, poses, syn.occluder_classes,
+                                                                syn.occluder_classes.size, syn.diameters, syn.diameters.size,
+                                                                spec.min_occluders, spec.max_occluders, cf(0.2), cf(0.9), cf(0.5), cf(1.5),
+                                                                u64(31), u64(0), ids, B), a.reps, a.rounds)
+    res["kernels"]["sample_occluders"] = st
+    print("sample_occluders      %8.2f us/call (min %.2f max %.2f)" % (st["median"], st["min"], st["max"]))
+    ocls, oposes, olabel = sample_occluders(cls, poses, syn.occluder_classes, syn.diameters, 31, draw_ids=ids,
+                                            min_occluders=spec.min_occluders, max_occluders=spec.max_occluders)
+    res["live_slots"] = int((ocls.asnumpy() >= 0).sum())
+    empty = ctx.array(np.full((B, S), -1, np.int32), dtype=np.int32)
+    visible = ctx.empty((B, S), np.int32)
+    nbytes = n * (8 + 6)
+    k = -(-2 * (256 << 20) // (n * 6)) + 1
+    sets = [(ctx.empty((B, H, W, 3), np.uint8), ctx.empty((B, H, W), np.uint16), ctx.empty((B, H, W), np.uint8)) for _ in range(k)]
+    for name, c, nsets in (("scene, %d slots live (rotating)" % S, ocls, k), ("scene, %d slots live (one set)" % S, ocls, 1),
+                           ("scene, every slot empty: the resolve pass alone (rotating)", empty, k)):
+        st = time_kernel(ctx, lambda i: syn.scene_into(sets[i][0], sets[i][1], sets[i][2], c, oposes, off, inten, ratio, S,
+                                                       label_value=olabel, visible=visible), a.reps, a.rounds, nsets)
+        st.update(bytes=nbytes, sets=nsets, share_of_copy_rate=nbytes / (st["median"] * 1e-6) / COPY_RATE)
+        res["kernels"][name] = st
+        print("%-62s %8.1f us/call (min %.1f max %.1f)  %.2f of the copy rate" % (name, st["median"], st["min"], st["max"],
+                                                                                 st["share_of_copy_rate"]))
+    st = time_kernel(ctx, lambda i: syn.draw_into(sets[i][0], sets[i][1], sets[i][2], cls, poses, off, inten, ratio), a.reps, a.rounds, k)
+    st.update(bytes=nbytes, sets=k, share_of_copy_rate=nbytes / (st["median"] * 1e-6) / COPY_RATE)
+    res["kernels"]["render_observed_forward, one object (rotating)"] = st
+    print("%-62s %8.1f us/call (min %.1f max %.1f)  %.2f of the copy rate" % ("render_observed_forward, one object (rotating)", st["median"],
+                                                                             st["min"], st["max"], st["share_of_copy_rate"]))
+    full, kept, totals = ctx.empty((B,), np.int32), ctx.empty((B,), np.int32), ctx.zeros((3,), np.uint64)
+    alone = sets[0] if k == 1 else sets[1]
+    syn.scene_into(alone[0], alone[1], alone[2], cls, poses, off, inten, ratio, 1, visible=full)
+    syn.scene_into(sets[0][0], sets[0][1], sets[0][2], ocls, oposes, off, inten, ratio, S, label_value=olabel, visible=visible)
+    for name, frac in (("occlusion_gate, min_visible 0 (every pair kept: the depth copy)", 0.0),
+                       ("occlusion_gate, min_visible 1 (pairs fall back: four copies)", 1.0)):
+        st = time_kernel(ctx, lambda i: lib.deepim_occlusion_gate(h, sets[0][0], sets[0][1], sets[0][2], None, kept, totals, None, B, alone[0],
+                                                                  alone[1], alone[2], visible, full, ocls, cf(frac), B, S, H, W),
+                         a.reps, a.rounds)
+        res["kernels"][name] = st
+        print("%-62s %8.1f us/call (min %.1f max %.1f)" % (name, st["median"], st["min"], st["max"]))
+    res["kept_at_min_visible_1"] = int(kept.asnumpy().sum())
+    del sets
+
+    # ---- (e) one batch of scenes by the two routes
+    flat_cls, flat_poses = ocls.reshape((B * S,)), oposes.reshape((B * S, 3, 4))
+    per_slot = []           # slot s of every frame as a batch of B samples for the observed entry, staged before the clock starts
+    oc_h, op_h, ol_h = ocls.asnumpy(), oposes.asnumpy(), olabel.asnumpy()
+    for s_ in range(S):
+        per_slot.append((ctx.array(oc_h[:, s_], dtype=np.int32), ctx.array(op_h[:, s_]), ctx.array(ol_h[:, s_], dtype=np.int32)))
+
+    def route_parent():
+        t0 = time.perf_counter()
+        image, depth = ctx.empty((B * S, 3, H, W)), ctx.empty((B * S, 1, H, W))
+        lib.deepim_render_classes_forward(h, image, depth, None, None, cf(0.0), flat_cls, t.mesh_desc, t.n_classes, t.max_V, t.max_F,
+                                          t.vertices, t.vertex_attr, None, t.faces, t.textures, flat_poses, K, None, None, None, cf(0.0),
+                                          B * S, H, W, cf(0.25), cf(6.0))
+        z = depth.asnumpy().reshape(B, S, H, W)
+        z[z == 0] = np.inf
+        win = np.argmin(z, 1)
+        frames = []
+        for c, p, lab in per_slot:
+            f = ctx.empty((B, H, W, 3), np.uint8), ctx.empty((B, H, W), np.uint16), ctx.empty((B, H, W), np.uint8)
+            syn.draw_into(f[0], f[1], f[2], c, p, off, inten, ratio, label_value=lab)
+            frames.append([x.asnumpy() for x in f])
+        out = []
+        for j, dt in enumerate((np.uint8, np.uint16, np.uint8)):
+            stack = np.stack([fr[j] for fr in frames], 1)
+            w = win.reshape((B, 1, H, W) + (1,) * (stack.ndim - 4))
+            out.append(ctx.array(np.take_along_axis(stack, w, 1)[:, 0], dtype=dt))
+        ctx.sync()
+        return (time.perf_counter() - t0) * 1e3, out
+
+    def route_new():
+        t0 = time.perf_counter()
+        f = ctx.empty((B, H, W, 3), np.uint8), ctx.empty((B, H, W), np.uint16), ctx.empty((B, H, W), np.uint8)
+        syn.scene_into(f[0], f[1], f[2], ocls, oposes, off, inten, ratio, S, label_value=olabel, visible=visible)
+        ctx.sync()
+        return (time.perf_counter() - t0) * 1e3, f
+
+    (_t, old_out), (_t, new_out) = route_parent(), route_new()
+    same = all(np.array_equal(x.asnumpy(), y.asnumpy()) for x, y in zip(old_out, new_out))
+    res["routes_give_the_same_frames"] = bool(same)
+    print("the two routes give the same frames:", same)
+    del old_out, new_out
+    old, new = [], []
+    for r in range(a.feed_rounds + 1):
+        to, tn = route_parent()[0], route_new()[0]
+        if r:
+            old.append(to)
+            new.append(tn)
+    res["routes"] = {"parent_S_draws_float_depths_readback_compose_upload_ms": stats(old), "scene_entry_ms": stats(new),
+                     "pcie_bytes_parent": n * S * (4 + 6) + n * 6, "pcie_bytes_new": 0}
+    for name in ("parent_S_draws_float_depths_readback_compose_upload_ms", "scene_entry_ms"):
+        v = res["routes"][name]
+        print("route %-56s %.3f ms (min %.3f max %.3f)" % (name, v["median"], v["min"], v["max"]))
+
+    # ---- (f) a loader step with half the batch synthetic, without and with occluders
+    cfg = default_config()
+    unlit, observed, points = loader_world(ctx, cfg, B, H, W, np.random.default_rng(31))
+    points[1] = points[0]
+    loaders = {name: TrainDataLoader(observed, cfg, unlit, batch_size=B, seed=31, points=points, synthetic=g, num_synthetic=B,
+                                     synthetic_classes=[0]) for name, g in (("half synthetic", plain), ("half synthetic, occluders", syn))}
+    half_pairs = np.concatenate([np.arange(B // 2), B + np.arange(B - B // 2)])
+    times = {name: [] for name in loaders}
+    for r in range(a.feed_rounds + 2):
+        for name, loader in loaders.items():
+            t0 = time.perf_counter()
+            batch = loader.make_batch(half_pairs, (half_pairs + r * 2 * B).astype(np.uint64))
+            ctx.sync()
+            if r >= 2:
+                times[name].append((time.perf_counter() - t0) * 1e3)
+            del batch
+    res["loader"] = {"step_ms " + name: stats(v) for name, v in times.items()}
+    res["loader"]["stats"] = loaders["half synthetic, occluders"].stats()
+    for name, v in res["loader"].items():
+        if name != "stats":
+            print("loader %-36s %.2f ms (min %.2f max %.2f)" % (name, v["median"], v["min"], v["max"]))
+    print("loader stats", res["loader"]["stats"])
+
+
+def finish(a, res):
+    print(json.dumps(res))
+    if a.json:
+        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+        with open(a.json, "w") as fh:
+            json.dump(res, fh, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=32)
@@ -63,6 +218,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--feed-rounds", type=int, default=9)
     ap.add_argument("--json", default=None)
+    ap.add_argument("--occluders", type=int, default=0, help="measure the occluded scenes with this many occluder slots (1..7) instead")
     a = ap.parse_args()
     B, H, W = a.batch, 480, 640
     n = B * H * W
@@ -70,6 +226,10 @@ def main():
     h = ctx.handle
     K = synthetic.K_LINEMOD.astype(np.float32)
     rm = Render_Py_Light_ModelNet_Multi(["a", "b"], None, K, W, H, 0.25, 6.0, brightness_ratios=[0.7], meshes=lit_meshes(), ctx=ctx)
+    if a.occluders:
+        res = {"batch": B, "height": H, "width": W, "reps": a.reps, "rounds": a.rounds, "kernels": {}, "routes": {}, "loader": {}}
+        occluded(ctx, a, rm, K, res)
+        return finish(a, res)
     syn = SyntheticObserved(rm, pose_stats(), K, seed=26)
     t = rm.mesh_table()
     cls_host = (np.arange(B) % 2).astype(np.int32)
@@ -191,11 +351,7 @@ def main():
     for k, v in res["loader"].items():
         if k != "stats":
             print("loader %-24s %.2f ms (min %.2f max %.2f)" % (k, v["median"], v["min"], v["max"]))
-    print(json.dumps(res))
-    if a.json:
-        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
-        with open(a.json, "w") as fh:
-            json.dump(res, fh, indent=1)
+    finish(a, res)
 
 
 if __name__ == "__main__":
