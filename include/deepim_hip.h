@@ -112,7 +112,7 @@ int deepim_graph_launch(deepim_ctx* ctx, int graph_id);
  * kernels read the rows when they run, so a captured graph of an iteration replays for any later batch's cameras, as it does for
  * any batch's class ids.
  * THE K_host RULE. In every entry whose K_host is marked "or NULL: camera table" — the zoom front ends, the five draws,
- * deepim_pose_error, deepim_calc_KT, deepim_flow_epe, deepim_pair_flow_labels — K_host == NULL means "sample b of this call reads
+ * deepim_pose_error, deepim_calc_KT, deepim_flow_epe, deepim_pair_flow_labels, the two depth-ICP passes — K_host == NULL means "sample b of this call reads
  * row b of the bound table". With K_host != NULL the entry does what it always did, whatever is bound. NULL with nothing bound, or
  * with n < B, fails on the host before any launch with a message naming the entry. A call on the slice [b0, b1) of a batch binds
  * K_table + 9*b0 with n = b1 - b0 first. A sample computed from row b has the bits of the same call with K_host = that row (the
@@ -672,6 +672,30 @@ int deepim_calc_se3(deepim_ctx* ctx, float* rotm, float* t, const float* pose_sr
  * points_shared != 0, one (3,N) set for all pairs. float64 accumulation, float32 results (B,5). */
 int deepim_pose_error(deepim_ctx* ctx, float* out /*B,5*/, const float* pose_est, const float* pose_gt,
                       const float* points, int points_shared, const float* K_host /*or NULL: camera table*/, int B, int N);
+/* Depth ICP (csrc/icp.hip): a projective point-to-plane refiner between a rendered ("source") and an observed ("target") depth
+ * map, the device counterpart of the `*-pose_icp.txt` poses the reference reads from files (deepim/core/tester.py:193-279).
+ * Every entry is asynchronous on the context stream, legal inside a graph capture once its scratch has grown (a first eager
+ * call), free of atomics (fixed-order reductions: the same inputs give the same bytes) and computes in double from the float32
+ * inputs, K⁻¹ included (inv3d, as the flow entries). Depths are (B,1,H,W) float32 metres, 0 = no measurement.
+ * deepim_depth_normals: vertex v(x,y) = depth · K⁻¹ · (x,y,1); n = normalize((v(x+1,y) − v(x−1,y)) × (v(x,y+1) − v(x,y−1))),
+ * negated where n·v > 0 (it faces the camera), rounded to float32. n = 0 on the one-pixel border, where one of the five depths
+ * is <= 0, where a neighbour's depth differs from the centre's by more than max_step, and where the cross product is zero. */
+int deepim_depth_normals(deepim_ctx* ctx, float* normals /*B,3,H,W*/, const float* depth /*B,1,H,W*/,
+                         const float* K_host /*or NULL: camera table*/, float max_step, int B, int H, int W);
+/* One Gauss-Newton step of every pair. A source pixel with depth_src > 0 is back-projected to p, moved to p' = R_T·p + t_T,
+ * dropped where p'_z <= 0, projected with K and rounded to the nearest pixel (ties to even), dropped outside the frame; with
+ * the target vertex q and normal n of that pixel it is dropped where the target depth is <= 0, n = 0 or |p' − q|² > dist_max²;
+ * else r = n·(p' − q), J = [p' × n ; n] — the twist (ω, v) of the left update T ← exp(ξ̂)·T. sys[b] (30 doubles, may be NULL):
+ * the 21 upper entries of ΣJJᵀ row by row, the 6 of −ΣJr, the pair count, Σr², one spare. Then, in the same call, Cholesky in
+ * double: status[b] = 1 when the count is below min_pairs, 2 when a pivot is <= rcond · max diag; either, or skip[b] != 0
+ * (skip may be NULL), leaves T[b] untouched; else status[b] = 0 and T[b] ← exp(ξ̂)·T[b] (Rodrigues with its V matrix), float32.
+ * The pixels of a pair are cut into blocks of 1024 whatever B is, so a pair's result does not depend on the batch around it. */
+int deepim_icp_step(deepim_ctx* ctx, float* T /*B,3,4 in and out*/, double* sys /*B,30 or NULL*/, int32_t* status /*B*/,
+                    const float* depth_src, const float* depth_tgt, const float* normals_tgt /*B,3,H,W*/,
+                    const float* K_host /*or NULL: camera table*/, const int32_t* skip /*B or NULL*/, float dist_max,
+                    int min_pairs, double rcond, int B, int H, int W);
+/* pose_out (B,3,4) = [R_T·R | R_T·t + t_T]: the increment applied to the object pose in camera coordinates (may alias pose_in) */
+int deepim_icp_apply(deepim_ctx* ctx, float* pose_out, const float* T, const float* pose_in, int B);
 /* Transform3D forward/backward (deepim/operator_py/transform3d.py:34-151) */
 int deepim_transform3d_forward(deepim_ctx* ctx, float* out /*B,3,N*/, const float* points /*B,3,N*/,
                                const float* rotation /*B,4*/, const float* translation /*B,3*/,

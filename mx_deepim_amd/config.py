@@ -92,7 +92,11 @@ def default_config():
     cfg.TEST = AttrDict(test_iter=4, FAST_TEST=True, UPDATE_MASK="box_rendered", INIT_MASK="box_rendered",
                         MASK_DILATE=False,   # yaml :104; image.py:380-381
                         # the other keys the test loop reads (core/tester.py; config.py:93-99): the three below are refused when set
-                        VISUALIZE=False, PRECOMPUTED_ICP=False, BEFORE_ICP=False)
+                        VISUALIZE=False, PRECOMPUTED_ICP=False, BEFORE_ICP=False,
+                        # not a reference key: refine each batch's final poses against frames["depth_observed"] with the device
+                        # depth ICP (lib/pair_matching/depth_icp.py) and report them as "icp" — the device counterpart of the
+                        # PRECOMPUTED_ICP row, whose poses the reference reads from files
+                        DEPTH_ICP=False)
     cfg.SCALES = [(480, 640)]
     return cfg
 

@@ -387,6 +387,8 @@ def observed_keys_of_test(config, have=()):
     if n.PRED_FLOW and not config.TEST.FAST_TEST:
         keys.append("depth_gt_observed" if ("depth_gt_observed" in have or "depth_observed" not in have) else "depth_observed")
         keys.append("mask_gt_observed")
+    if config.TEST.get("DEPTH_ICP", False):        # the depth ICP's target is the raw sensor depth (core/tester.py)
+        keys.append("depth_observed")
     return list(dict.fromkeys(keys))
 
 

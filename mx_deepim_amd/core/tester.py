@@ -30,6 +30,16 @@ Differences from the reference:
   * `test_data` may be a core/loader.TestDataLoader, which makes the batches from observed frames and initial poses alone and
     fills up its last batch by repeating the last pair. Such a record carries "pad": True (the reference's DataBatch.pad): it
     rides through the network like its original and enters no container, no num_inst, no sum, no EPE total and no pair count.
+  * TEST.DEPTH_ICP (not a reference key, default off): the device counterpart of the PRECOMPUTED_ICP row. The final poses of each
+    batch go through lib/pair_matching/depth_icp.DepthICP.refine against frames["depth_observed"] — the raw sensor depth in
+    metres, unmasked: the ICP's distance gate drops the background — with the no_point and pad rows skipped. Their errors
+    (deepim_pose_error) and the solver's status ride in the batch's one read-back: the staging buffer grows by one slot. The
+    result gains "icp": all_rot_err / all_trans_err / all_poses_est / all_poses_gt (num_cls x 1) and "status" (num_cls lists; 0
+    solved, 1 too few pairs, 2 rank-deficient, -1 for a no_point pair, which stores its rendered pose and errors of 1000 as in
+    the network rows), and tables["icp"] the three evaluations with their plots under add_plots_depth_ICP and
+    arp_2d_plots_depth_ICP. The containers are cached in the sidecar `<name>_pose_iter<N>_icp.pkl`, written only with the key on
+    and removed when a run with the key off rewrites the cache; with the key on a cache without that sidecar is not a hit.
+    With the key off the loop issues the launches, allocations and read-backs it always did.
 """
 from __future__ import print_function, division, absolute_import
 
@@ -42,6 +52,7 @@ import numpy as np
 
 from ..cameras import camera_table, has_cameras
 from ..lib.pair_matching.batch_updater_py_multi import update_test_batch
+from ..lib.pair_matching.depth_icp import DepthICP
 from ..lib.utils import image as _image
 from ..runtime import DeviceArray, lib
 from .loader import TestDataLoader
@@ -125,13 +136,13 @@ def _as_array(lists):
         return np.array(lists, dtype=object)
 
 
-def _evaluate(config, imdb_test, all_poses_est, all_poses_gt, all_K=None):
+def _evaluate(config, imdb_test, all_poses_est, all_poses_gt, all_K=None, plots_suffix=""):
     cams = {} if all_K is None else {"all_K": all_K}      # per-pair cameras (module docstring); without them the reference's calls
     res = {"pose": imdb_test.evaluate_pose(config, all_poses_est, all_poses_gt, **cams)}
-    pose_add_plots_dir = os.path.join(imdb_test.result_path, "add_plots")
+    pose_add_plots_dir = os.path.join(imdb_test.result_path, "add_plots" + plots_suffix)
     _mkdir_p(pose_add_plots_dir)
     res["add"] = imdb_test.evaluate_pose_add(config, all_poses_est, all_poses_gt, output_dir=pose_add_plots_dir, **cams)
-    pose_arp2d_plots_dir = os.path.join(imdb_test.result_path, "arp_2d_plots")
+    pose_arp2d_plots_dir = os.path.join(imdb_test.result_path, "arp_2d_plots" + plots_suffix)
     _mkdir_p(pose_arp2d_plots_dir)
     res["arp_2d"] = imdb_test.evaluate_pose_arp_2d(config, all_poses_est, all_poses_gt, output_dir=pose_arp2d_plots_dir, **cams)
     return res
@@ -142,17 +153,23 @@ def camera_cache_file(pose_err_file):
     return pose_err_file[:-len(".pkl")] + "_K.pkl"
 
 
-def save_result_cache(pose_err_file, containers, all_K=None):
+def icp_cache_file(pose_err_file):
+    """The sidecar of the result cache that keeps the depth ICP's containers: `<name>_pose_iter<N>_icp.pkl`."""
+    return pose_err_file[:-len(".pkl")] + "_icp.pkl"
+
+
+def save_result_cache(pose_err_file, containers, all_K=None, icp=None):
     """The reference's four containers to `pose_err_file`; all_K to the sidecar when per-pair cameras were used — and no
-    sidecar otherwise: one left by an earlier run is removed, it would give the cached poses another run's cameras."""
+    sidecar otherwise: one left by an earlier run is removed, it would give the cached poses another run's cameras. The same
+    rule for `icp`, the "icp" dict of a TEST.DEPTH_ICP run, and its sidecar."""
     with open(pose_err_file, "wb") as f:
         pickle.dump(list(containers), f, protocol=2)
-    side = camera_cache_file(pose_err_file)
-    if all_K is not None:
-        with open(side, "wb") as f:
-            pickle.dump(all_K, f, protocol=2)
-    elif os.path.exists(side):
-        os.remove(side)
+    for side, payload in ((camera_cache_file(pose_err_file), all_K), (icp_cache_file(pose_err_file), icp)):
+        if payload is not None:
+            with open(side, "wb") as f:
+                pickle.dump(payload, f, protocol=2)
+        elif os.path.exists(side):
+            os.remove(side)
 
 
 def load_result_cache(pose_err_file):
@@ -167,6 +184,22 @@ def load_result_cache(pose_err_file):
     return containers, all_K
 
 
+def load_icp_cache(pose_err_file):
+    """-> the "icp" dict a TEST.DEPTH_ICP run cached next to `pose_err_file`, or None without that sidecar"""
+    side = icp_cache_file(pose_err_file)
+    if not os.path.exists(side):
+        return None
+    with open(side, "rb") as fid:
+        return pickle.load(fid, encoding="latin1")
+
+
+def _evaluate_icp(config, imdb_test, icp, all_K, logger):
+    logger.info("evaluate pose after depth ICP:")
+    one = type(config)(config)                      # the evaluations take their column count from TEST.test_iter: one here
+    one.TEST = type(config.TEST)(config.TEST, test_iter=1)
+    return _evaluate(one, imdb_test, icp["all_poses_est"], icp["all_poses_gt"], all_K, plots_suffix="_depth_ICP")
+
+
 def pred_eval(config, predictor, test_data, imdb_test, vis=False, ignore_cache=None, logger=None, pairdb=None,
               render_machine=None):
     """tester.py:50-527 (see the module docstring for the shape of `test_data`).
@@ -175,23 +208,31 @@ def pred_eval(config, predictor, test_data, imdb_test, vis=False, ignore_cache=N
     :param ignore_cache: ignore the saved cache file
     :param render_machine: lib/render_glumpy Render_Py (or the lit ModelNet machine); needed from test_iter = 2 on
     Returns a dict: the four cached containers, "all_K" (None unless a pair record carried a "K"), sum_PoseErr, num_inst, "epe"
-    (the six totals and the three means) and "tables"."""
+    (the six totals and the three means) and "tables"; with TEST.DEPTH_ICP also "icp" and tables["icp"] (module docstring)."""
     for key, lines in (("VISUALIZE", ":112, :411-421"), ("PRECOMPUTED_ICP", ":193-242"), ("BEFORE_ICP", ":244-279")):
         if config.TEST.get(key, False):
             raise NotImplementedError("TEST.%s (deepim/core/tester.py%s) reads files and draws figures; it is not part of "
                                       "the device test loop" % (key, lines))
     test_iter = config.TEST.test_iter
+    do_icp = bool(config.TEST.get("DEPTH_ICP", False))
     logger.info(imdb_test.result_path)
     logger.info("test iter size: {}".format(test_iter))
     pose_err_file = os.path.join(imdb_test.result_path, imdb_test.name + "_pose_iter{}.pkl".format(test_iter))
-    if os.path.exists(pose_err_file) and not ignore_cache and not vis:
+    if (os.path.exists(pose_err_file) and not ignore_cache and not vis
+            and (not do_icp or os.path.exists(icp_cache_file(pose_err_file)))):
         [all_rot_err, all_trans_err, all_poses_est, all_poses_gt], all_K = load_result_cache(pose_err_file)
         tables = _evaluate(config, imdb_test, all_poses_est, all_poses_gt, all_K)
-        return {"all_rot_err": all_rot_err, "all_trans_err": all_trans_err, "all_poses_est": all_poses_est,
-                "all_poses_gt": all_poses_gt, "all_K": all_K, "tables": tables, "from_cache": True}
+        res = {"all_rot_err": all_rot_err, "all_trans_err": all_trans_err, "all_poses_est": all_poses_est,
+               "all_poses_gt": all_poses_gt, "all_K": all_K, "tables": tables, "from_cache": True}
+        if do_icp:
+            res["icp"] = load_icp_cache(pose_err_file)
+            tables["icp"] = _evaluate_icp(config, imdb_test, res["icp"], all_K, logger)
+        return res
 
     if test_iter > 1 and render_machine is None:
         raise ValueError("pred_eval: TEST.test_iter = %d re-renders between the iterations: pass render_machine" % test_iter)
+    if do_icp and render_machine is None:
+        raise ValueError("pred_eval: TEST.DEPTH_ICP draws the depth of the poses it refines: pass render_machine")
     net = predictor.net
     ctx = net.ctx
     num_cls = len(imdb_test.classes)
@@ -215,11 +256,19 @@ def pred_eval(config, predictor, test_data, imdb_test, vis=False, ignore_cache=N
     one_point = ctx.zeros((3, 1))       # deepim_pose_error's re / te need no model points; its add / adi / arp_2d go unused
     stage = rbuf = None
     pairs_done = 0
+    n_slots = test_iter + (1 if do_icp else 0)          # the depth ICP's poses and errors ride in one more slot of the staging buffer
+    icp = icp_res = None
+    if do_icp:
+        icp = DepthICP(render_machine, config)
+        icp_res = {k: [[[]] for _ in range(num_cls)] for k in ("all_rot_err", "all_trans_err", "all_poses_est", "all_poses_gt")}
+        icp_res["status"] = [[] for _ in range(num_cls)]
 
     t_start = time.time()
     t = time.time()
     for idx, (data, frames, pair_records) in enumerate(test_data):
         B = len(pair_records)
+        if do_icp and frames.get("depth_observed") is None:
+            raise ValueError("pred_eval: TEST.DEPTH_ICP refines against the sensor depth: the frames carry no 'depth_observed'")
         pose_rendered = np.stack([np.asarray(r["pose_rendered"], np.float32).reshape(3, 4) for r in pair_records])
         pose_observed = np.stack([np.asarray(r["pose_observed"], np.float32).reshape(3, 4) for r in pair_records])
         no_point = np.array([np.sum(r["pose_rendered"]) == -12 for r in pair_records])      # NO POINT VALID IN INIT POSE
@@ -236,7 +285,7 @@ def pred_eval(config, predictor, test_data, imdb_test, vis=False, ignore_cache=N
             print(pairs_done + b)
             print("in test: NO POINT_VALID IN rendered")
         if no_point.all():
-            poses_host = errs_host = None
+            poses_host = errs_host = status_host = None
         else:
             data = dict(data)
             cams_d = None
@@ -251,12 +300,12 @@ def pred_eval(config, predictor, test_data, imdb_test, vis=False, ignore_cache=N
             pose_rendered_d = ctx.array(pose_rendered)
             pose_observed_d = ctx.array(pose_observed)
             render_ids = ctx.array(np.array([class_name.index(r["gt_class"]) for r in pair_records], np.int32), dtype=np.int32)
-            if stage is None or stage.size != test_iter * B * 17:
-                stage = ctx.empty((test_iter * B * 17,))
+            if stage is None or stage.size != n_slots * B * 17 + (B if do_icp else 0):      # + the ICP's B status words
+                stage = ctx.empty((n_slots * B * 17 + (B if do_icp else 0),))
                 rbuf = {n: ctx.empty((B, 3 if n == "image_rendered" else 1, net.H, net.W))
                         for n in ("image_rendered", "depth_rendered", "mask_rendered", "mask_observed")}
-            poses_d = DeviceArray(ctx, (test_iter, B, 3, 4), ptr=stage.ptr, base=stage)
-            errs_d = DeviceArray(ctx, (test_iter, B, 5), ptr=stage.ptr + test_iter * B * 48, base=stage)
+            poses_d = DeviceArray(ctx, (n_slots, B, 3, 4), ptr=stage.ptr, base=stage)
+            errs_d = DeviceArray(ctx, (n_slots, B, 5), ptr=stage.ptr + n_slots * B * 48, base=stage)
             data_time += time.time() - t
 
             t = time.time()
@@ -290,9 +339,21 @@ def pred_eval(config, predictor, test_data, imdb_test, vis=False, ignore_cache=N
                     output_all = predictor.predict(data)
                     net_time += time.time() - t
             t = time.time()
+            if do_icp:      # "DeepIM + ICP": the final poses against the raw sensor depth; no_point and pad rows keep theirs
+                depth_sensor = _image._depth(ctx, frames, "depth_observed", config)
+                cur = poses_d[test_iter]
+                _, icp_status = icp.refine(poses_d[test_iter - 1], render_ids, depth_sensor, K=cams_d if cams_d is not None else K,
+                                           skip=skip, out=cur)
+                if cams_d is not None:
+                    ctx.bind_cameras(cams_d)
+                lib.deepim_pose_error(ctx.handle, errs_d[test_iter], cur, pose_observed_d, one_point, 1,
+                                      None if cams_d is not None else K, B, 1)
+                DeviceArray(ctx, (B,), np.int32, ptr=stage.ptr + n_slots * B * 68, base=stage).copyfrom(icp_status)
             host = stage.asnumpy()                      # the batch's one read-back
-            poses_host = host[:test_iter * B * 12].reshape(test_iter, B, 3, 4)
-            errs_host = host[test_iter * B * 12:].reshape(test_iter, B, 5)
+            poses_host = host[:n_slots * B * 12].reshape(n_slots, B, 3, 4)
+            errs_host = host[n_slots * B * 12:n_slots * B * 17].reshape(n_slots, B, 5)
+            if do_icp:
+                status_host = host[n_slots * B * 17:].view(np.int32)
             post_time += time.time() - t
 
         for b, rec in enumerate(pair_records):          # the containers, pair by pair in the reference's order
@@ -315,6 +376,17 @@ def pred_eval(config, predictor, test_data, imdb_test, vis=False, ignore_cache=N
                 all_trans_err[class_id][pose_iter_idx].append(t_dist)
                 sum_PoseErr[pose_iter_idx][class_id, :] += np.array([r_dist, t_dist])
                 sum_PoseErr[pose_iter_idx][-1, :] += np.array([r_dist, t_dist])
+            if do_icp:
+                if no_point[b]:
+                    pose_est, r_dist, t_dist, st = rec["pose_rendered"], 1000, 1000, -1
+                else:
+                    pose_est = poses_host[test_iter, b].copy()
+                    r_dist, t_dist, st = float(errs_host[test_iter, b, 0]), float(errs_host[test_iter, b, 1]), int(status_host[b])
+                icp_res["all_poses_est"][class_id][0].append(pose_est)
+                icp_res["all_poses_gt"][class_id][0].append(rec["pose_observed"])
+                icp_res["all_rot_err"][class_id][0].append(r_dist)
+                icp_res["all_trans_err"][class_id][0].append(t_dist)
+                icp_res["status"][class_id].append(st)
         first_pair = pairs_done + 1
         pairs_done += B - int(pad.sum())
 
@@ -331,7 +403,9 @@ def pred_eval(config, predictor, test_data, imdb_test, vis=False, ignore_cache=N
     if not cameras_used:
         all_K = None
     logger.info("saving result cache to {}".format(pose_err_file))
-    save_result_cache(pose_err_file, [all_rot_err, all_trans_err, all_poses_est, all_poses_gt], all_K)
+    if do_icp:
+        icp_res["all_rot_err"], icp_res["all_trans_err"] = _as_array(icp_res["all_rot_err"]), _as_array(icp_res["all_trans_err"])
+    save_result_cache(pose_err_file, [all_rot_err, all_trans_err, all_poses_est, all_poses_gt], all_K, icp_res)
     logger.info("done")
 
     epe = None
@@ -347,7 +421,12 @@ def pred_eval(config, predictor, test_data, imdb_test, vis=False, ignore_cache=N
 
     logger.info("evaluate pose:")
     tables = _evaluate(config, imdb_test, all_poses_est, all_poses_gt, all_K)
+    if do_icp:
+        tables["icp"] = _evaluate_icp(config, imdb_test, icp_res, all_K, logger)
     logger.info("using {} seconds in total".format(time.time() - t_start))
-    return {"all_rot_err": all_rot_err, "all_trans_err": all_trans_err, "all_poses_est": all_poses_est,
-            "all_poses_gt": all_poses_gt, "all_K": all_K, "sum_PoseErr": sum_PoseErr, "num_inst": num_inst, "epe": epe, "tables": tables,
-            "from_cache": False}
+    res = {"all_rot_err": all_rot_err, "all_trans_err": all_trans_err, "all_poses_est": all_poses_est,
+           "all_poses_gt": all_poses_gt, "all_K": all_K, "sum_PoseErr": sum_PoseErr, "num_inst": num_inst, "epe": epe, "tables": tables,
+           "from_cache": False}
+    if do_icp:
+        res["icp"] = icp_res
+    return res
