@@ -8,7 +8,10 @@ bound that by 1e-11 · Σ|term|), and sin / cos of the Rodrigues exponential (ea
 
 Besides the results the step reports what the tests need to know about the scene: cond(ΣJJᵀ), Σ|term| of every sum, and the
 smallest distance of any decision to its threshold (`margin`): the rounding tie of the projected pixel (pixels), the frame edge
-(pixels), dist_max (metres) and, from the normal pass, max_step (metres).
+(pixels), dist_max (metres) and, from the normal pass, max_step (metres). It also reports what it decided, so that a test can
+assert that its scene takes the paths it is about: how many source pixels of every pair met each outcome (`counts`), how many
+1024-pixel blocks of a pair hold a source pixel and how many hold none (`blocks`), θ² of the solved twist (`theta2`: the
+Rodrigues branch) and how far the Cholesky pivots stayed from rcond · max diag (`pivot`, `rho`).
 """
 import numpy as np
 
@@ -72,14 +75,23 @@ def depth_normals(depth, K, max_step):
     return out, margin
 
 
-def cholesky_solve(A, g, rcond):
-    """The finish's solve: A (6,6) symmetric (upper entries used), g (6). → (xi or None when a pivot ≤ rcond · max diag)"""
+BLOCK_PIX = 1024                                            # the pixel kernel's block: 256 lanes x 4 consecutive source pixels
+FOILS = (None, "no_behind", "no_skew")
+OUTCOMES = ("src", "behind", "outside", "hole", "no_normal", "far", "used")
+
+
+def cholesky_solve(A, g, rcond, pivots=None):
+    """The finish's solve: A (6,6) symmetric (upper entries used), g (6). → (xi or None when a pivot ≤ rcond · max diag).
+    `pivots`, a list, receives (v_j, max diag) of every pivot that was compared with rcond · max diag, the refused one included."""
     L = np.zeros((6, 6))
-    lim = rcond * max(A[i, i] for i in range(6))
+    maxdiag = max(A[i, i] for i in range(6))
+    lim = rcond * maxdiag
     for j in range(6):
         s = A[j, j]
         for k in range(j):
             s = s - L[j, k] * L[j, k]
+        if pivots is not None:
+            pivots.append((s, maxdiag))
         if not s > lim:
             return None
         L[j, j] = np.sqrt(s)
@@ -101,6 +113,12 @@ def cholesky_solve(A, g, rcond):
             s = s - L[k, i] * xi[k]
         xi[i] = s / L[i, i]
     return xi
+
+
+def theta2(xi):
+    """θ² of the twist as the finish computes it"""
+    w = xi[:3]
+    return (w[0] * w[0] + w[1] * w[1]) + w[2] * w[2]
 
 
 def se3_exp(xi):
@@ -131,10 +149,19 @@ def _compose(Ra, ta, Rb, tb):
     return R, t
 
 
-def icp_step(T, depth_src, depth_tgt, normals_tgt, K, skip=None, dist_max=0.02, min_pairs=12, rcond=1e-9):
+def icp_step(T, depth_src, depth_tgt, normals_tgt, K, skip=None, dist_max=0.02, min_pairs=12, rcond=1e-9, foil=None):
     """One deepim_icp_step. T (B,3,4) float32, depths (B,H,W) float32, normals (B,3,H,W) float32, K (B,3,3) float32.
     → (T_new (B,3,4) float32, sys (B,30) float64, status (B) int32, info) with info = {"cond": (B), "abs": (B,30) Σ|term| of
-    every sys entry, "margin": {"tie", "edge", "dist"}}."""
+    every sys entry, "margin": {"tie", "edge", "dist"}, "counts": {outcome: (B) int64} for the OUTCOMES (src = behind + outside +
+    hole + no_normal + far + used; a pixel counts for the first gate that rejects it, in the kernel's order), "nblk": blocks per
+    pair, "blocks": {"with", "without": (B)} blocks with and without a source pixel, "theta2": (B) θ² of the solved twist (nan
+    where none was solved), "rho": (B) smallest compared pivot / max diag, "pivot": (B) smallest |v_j − rcond · max diag| /
+    max diag over the compared pivots (inf where the count stopped the pair before the solve), "rim": {"left", "right", "top",
+    "bottom": (B)} the used pixels whose target pixel lies in the frame's first or last column or row, "tail": (B) the used
+    source pixels of a ragged last quad (H·W no multiple of 4)}.
+    `foil` names one way of being wrong, for a test to assert that its scene would notice it: "no_behind" is the step without
+    its z′ > 0 test, "no_skew" projects without K[0][1]. The default, None, is the device's arithmetic."""
+    assert foil in FOILS
     T = np.asarray(T, np.float32)
     depth_src, depth_tgt = np.asarray(depth_src, np.float32), np.asarray(depth_tgt, np.float32)
     normals_tgt = np.asarray(normals_tgt, np.float32)
@@ -146,6 +173,12 @@ def icp_step(T, depth_src, depth_tgt, normals_tgt, K, skip=None, dist_max=0.02, 
     status = np.zeros(B, np.int32)
     cond = np.full(B, np.inf)
     margin = {"tie": np.inf, "edge": np.inf, "dist": np.inf}
+    counts = {k: np.zeros(B, np.int64) for k in OUTCOMES}
+    nblk = -(-(H * W) // BLOCK_PIX)
+    blocks = {"with": np.zeros(B, np.int64), "without": np.zeros(B, np.int64)}
+    th2, rho, pivot = np.full(B, np.nan), np.full(B, np.inf), np.full(B, np.inf)
+    rim = {k: np.zeros(B, np.int64) for k in ("left", "right", "top", "bottom")}
+    tail = np.zeros(B, np.int64)
     xg, yg = np.meshgrid(np.arange(W, dtype=np.float64), np.arange(H, dtype=np.float64))
     for b in range(B):
         Kd = np.asarray(K[b], np.float32).astype(np.float64).reshape(9)
@@ -153,11 +186,18 @@ def icp_step(T, depth_src, depth_tgt, normals_tgt, K, skip=None, dist_max=0.02, 
         Td = T[b].astype(np.float64)
         ds = depth_src[b].astype(np.float64)
         sel = ds > 0
+        blocks["with"][b] = len(np.unique(np.flatnonzero(sel.reshape(-1)) // BLOCK_PIX))
+        blocks["without"][b] = nblk - blocks["with"][b]
+        counts["src"][b] = int(sel.sum())
         x, y, d = xg[sel], yg[sel], ds[sel]
+        in_tail = (y * W + x) >= (H * W) // 4 * 4
         p = _vertex(kinv, x, y, d)
         pp = [((Td[i, 0] * p[0] + Td[i, 1] * p[1]) + Td[i, 2] * p[2]) + Td[i, 3] for i in range(3)]
-        keep = pp[2] > 0
-        pp = [v[keep] for v in pp]
+        keep = pp[2] > 0 if foil != "no_behind" else np.ones(len(d), bool)
+        counts["behind"][b] = int((~keep).sum())
+        pp, in_tail = [v[keep] for v in pp], in_tail[keep]
+        if foil == "no_skew":
+            Kd[1] = 0.0
         uz = (Kd[6] * pp[0] + Kd[7] * pp[1]) + Kd[8] * pp[2]
         with np.errstate(divide="ignore", invalid="ignore"):
             u = ((Kd[0] * pp[0] + Kd[1] * pp[1]) + Kd[2] * pp[2]) / uz
@@ -172,17 +212,25 @@ def icp_step(T, depth_src, depth_tgt, normals_tgt, K, skip=None, dist_max=0.02, 
                 if len(c):
                     margin["edge"] = min(margin["edge"], float(np.min(np.minimum(np.abs(c + 0.5), np.abs(c - (n - 0.5))))))
         inside = (px >= 0) & (px <= W - 1) & (py >= 0) & (py <= H - 1)
-        pp = [v[inside] for v in pp]
+        counts["outside"][b] = int((~inside).sum())
+        pp, in_tail = [v[inside] for v in pp], in_tail[inside]
         ix, iy = px[inside].astype(np.int64), py[inside].astype(np.int64)
         dt = depth_tgt[b][iy, ix].astype(np.float64)
         n = [normals_tgt[b, i][iy, ix].astype(np.float64) for i in range(3)]
         ok = (dt > 0) & ~((n[0] == 0) & (n[1] == 0) & (n[2] == 0))
+        counts["hole"][b] = int((~(dt > 0)).sum())
+        counts["no_normal"][b] = int(((dt > 0) & ~ok).sum())
         q = _vertex(kinv, px[inside], py[inside], dt)
         e = [pp[i] - q[i] for i in range(3)]
         d2 = (e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]
         if ok.any():
             margin["dist"] = min(margin["dist"], float(np.min(np.abs(np.sqrt(d2[ok]) - dm))))
+        counts["far"][b] = int((ok & (d2 > dm2)).sum())
         ok &= ~(d2 > dm2)
+        counts["used"][b] = int(ok.sum())
+        for k, hit in (("left", ix == 0), ("right", ix == W - 1), ("top", iy == 0), ("bottom", iy == H - 1)):
+            rim[k][b] = int((ok & hit).sum())
+        tail[b] = int((ok & in_tail).sum())
         pp, n, e = [v[ok] for v in pp], [v[ok] for v in n], [v[ok] for v in e]
         r = _dot(n, e)
         J = _cross(pp, n) + n
@@ -197,16 +245,22 @@ def icp_step(T, depth_src, depth_tgt, normals_tgt, K, skip=None, dist_max=0.02, 
             status[b] = 1
             continue
         cond[b] = np.linalg.cond(A)
-        xi = cholesky_solve(A, sys_[b, 21:27], rcond)
+        pv = []
+        xi = cholesky_solve(A, sys_[b, 21:27], rcond, pv)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            rho[b] = min(v / m for v, m in pv)
+            pivot[b] = min(abs(v - rcond * m) / m for v, m in pv)
         if xi is None:
             status[b] = 2
             continue
         if skip is not None and skip[b]:
             continue
+        th2[b] = theta2(xi)
         Re, te = se3_exp(xi)
         Rn, tn = _compose(Re, te, Td[:, :3], Td[:, 3])
         T_new[b] = np.concatenate([Rn, tn[:, None]], 1).astype(np.float32)
-    return T_new, sys_, status, {"cond": cond, "abs": abs_, "margin": margin}
+    return T_new, sys_, status, {"cond": cond, "abs": abs_, "margin": margin, "counts": counts, "nblk": nblk, "blocks": blocks,
+                                 "theta2": th2, "rho": rho, "pivot": pivot, "rim": rim, "tail": tail}
 
 
 def icp_apply(T, pose):

@@ -76,3 +76,55 @@ def test_empty_source_has_too_few_pairs():
     T, sys_, status, _ = emu.icp_step(T0, np.zeros_like(d), d, normals, K[None])
     assert status[0] == 1 and (sys_[0] == 0).all()
     np.testing.assert_array_equal(T, T0)
+
+
+# ----------------------------------------------------- the scenes of tests/test_gpu_depth_icp_paths.py, judged without a GPU --
+import depth_icp_scenes as scenes  # noqa: E402
+
+
+@pytest.fixture(scope="module")
+def gates():
+    return scenes.gates_case()
+
+
+def test_gates_scene_rejects_pixels_at_every_gate(gates):
+    scenes.check_gates(gates)
+
+
+def test_without_max_step_only_the_holes_take_normals_away(gates):
+    scenes.check_wide_normals(gates)
+
+
+def test_half_turn_puts_every_source_point_behind_the_camera(gates):
+    scenes.check_behind(gates)
+
+
+def test_converged_input_stays_put_and_a_tiny_pose_takes_the_series(gates):
+    scenes.check_converged(gates)
+
+
+def test_rim_scene_uses_the_frames_rim_the_ragged_quad_and_the_skew(gates):
+    scenes.check_rim(gates)
+
+
+def test_rcond_and_min_pairs_are_decided_on_both_sides(gates):
+    scenes.check_thresholds(gates)
+
+
+@pytest.mark.parametrize("seed", scenes.CHAIN_SEEDS)
+def test_chains_scene_fills_163_blocks(seed):
+    scenes.check_chains(scenes.chains_case(seed))
+
+
+def test_the_outcome_counts_leave_the_arithmetic_alone(gates):
+    """the step's reports are by-products: with and without its z′ > 0 test it gives the same bytes on a scene all in front"""
+    c = gates
+    a, b = scenes.step(c), scenes.step(c, foil="no_behind")
+    assert all(x.tobytes() == y.tobytes() for x, y in zip(a[:3], b[:3]))
+    assert (a[3]["counts"]["behind"] == 0).all()
+
+
+def test_frames_without_an_interior_have_no_normals():
+    for H, W in ((2, 9), (1, 1)):
+        n, m = emu.depth_normals(np.full((2, H, W), 0.8, np.float32), np.stack([K, K]), 0.01)
+        assert n.shape == (2, 3, H, W) and (n == 0).all() and m == np.inf
