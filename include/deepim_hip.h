@@ -362,6 +362,28 @@ int deepim_zoom_inverse_factor(deepim_ctx* ctx, const float* zoom_factor, float*
  *            background is black */
 int deepim_zoom_status(deepim_ctx* ctx, int* status);
 
+/* The closed loop's shortcut from the render pass to the zoom front end. Between two refinement iterations the render pass
+ * already knows the boxes the front end's bbox pass would search both full-frame masks for: the box of mask_rendered is the one
+ * it reduces for the box_rendered rectangle, and the box of that rectangle (mask_box, the next mask_observed) follows from it.
+ * Both calls are ONE-SHOT requests kept on the context; neither launches anything, synchronises or allocates, and both are
+ * legal inside a graph capture (the kernels they steer are captured with the array's address).
+ *   boxes   caller-owned device int32 (B,2,4), {minx, maxx, miny, maxy}: row 0 the box of the rectangle (values > 0.3 of
+ *           mask_box), row 1 the box of mask_rendered (values > 0.2); an empty map has {INT_MAX, -1, INT_MAX, -1}. The
+ *           rectangle is half-open, so row 0 is {xs, xe-1, ys, ye-1} of row 1's {xs, xe, ys, ye}, and empty where the rendered
+ *           box is one pixel wide or high, or empty itself.
+ * deepim_render_export_boxes: the NEXT render entry on the context — which must draw mask_box (deepim_render_update_forward,
+ *   deepim_render_lit_forward, deepim_render_classes_forward; any other entry refuses) — writes `boxes` from its box-fill pass.
+ * deepim_zoom_seed_boxes: the NEXT deepim_zoom_concat_* call on the context, in any of its forms and given both masks, reads the
+ *   two boxes from `boxes` and launches no bbox pass; zoom_factor, the network input and the status bits are those of the
+ *   bbox pass on the masks the boxes were exported for. The array is read, not re-armed; the context's own accumulators stay
+ *   as the next unseeded call expects them. deepim_zoom_mask_forward / deepim_zoom_image_forward and the training front end's
+ *   mask_gt_observed refuse a seed.
+ * Either request is cleared by the call that takes it, also when that call fails; boxes == NULL withdraws it.
+ * deepim_bbox_launches: the number of bbox passes the context has queued since it was created (a seeded call adds none). */
+int deepim_render_export_boxes(deepim_ctx* ctx, int32_t* boxes /*device (B,2,4)*/);
+int deepim_zoom_seed_boxes(deepim_ctx* ctx, const int32_t* boxes /*device (B,2,4)*/);
+int deepim_bbox_launches(deepim_ctx* ctx, unsigned long long* count);
+
 /* ------------------------------------------ N-group: matching network ops -- */
 /* MXNet Convolution (+bias) [+LeakyReLU slope] (deepIM_flownet.py:63-107,123,145,176,317).
  * `packed_w` comes from deepim_conv_pack_weights (one-time re-layout of the

@@ -79,6 +79,12 @@ struct deepim_ctx {
   std::vector<const void*> attr_done;  // hipFuncSetAttribute groups already applied on THIS context's device (di_attr_needed)
   const float* cam_table;   // deepim_bind_cameras: device (cam_n,3,3) intrinsics read by the entries called with K_host == NULL
   int cam_n;                // (the caller's memory: only the pointer is kept, so a captured graph sees the table's later contents)
+  // The closed loop's two zoom boxes, handed from the render pass to the front end through a caller-owned (B,2,4) int32 array.
+  // Both are one-shot requests: taken and cleared by the next render entry / the next zoom-factor computation, also when it fails.
+  int* export_boxes;        // deepim_render_export_boxes: the next draw with mask_box also writes the boxes of its two masks here
+  const int* seed_boxes;    // deepim_zoom_seed_boxes: the next zoom-factor computation reads its boxes here and runs no bbox pass
+  unsigned long long bbox_launches;   // bbox_kernel launches this context has queued (deepim_bbox_launches)
+  int render_quad;          // 1 (default): resolve and box fill own four pixels per lane where the plane allows; 0: one pixel per lane
 };
 
 // true the first time `tag` is seen on this context: guards one-off hipFuncSetAttribute calls (per device, hence per context)
@@ -129,8 +135,9 @@ void deepim_set_error_msg(const char* msg);
     }                                                    \
   } while (0)
 
-// fill pass of the box_rendered rectangle from accumulated bbox words (csrc/flow.hip)
-int deepim_mask_box_fill(deepim_ctx* ctx, float* box, const int* words, int B, int H, int W);
+// fill pass of the box_rendered rectangle from accumulated bbox words (csrc/flow.hip); export_boxes: NULL, or (B,2,4) int32 that
+// receives, per sample, the zoom front end's observed box (that of the rectangle drawn) and rendered box (the words)
+int deepim_mask_box_fill(deepim_ctx* ctx, float* box, const int* words, int* export_boxes, int B, int H, int W);
 
 void deepim_ctx_default_options(deepim_ctx* c);
 // Grow-only scratch; never reallocated while a graph capture is open.

@@ -437,15 +437,35 @@ __global__ __launch_bounds__(256) void mask_bbox_kernel(int* __restrict__ words,
     atomicMin(&words[b * 4 + 2], ymin); atomicMax(&words[b * 4 + 3], ymax);
   }
 }
+// PX = 4 (W % 4 == 0 and a 16-byte aligned `box`): a lane owns four pixels of one row and stores them as one 16-byte word;
+// PX = 1: any size. boxes != NULL: the sample's first lane also writes the two boxes the zoom front end would find on this
+// rectangle and on the mask the words come from, {minx, maxx, miny, maxy} each: the rectangle is half-open, so its box ends one
+// short of the words', and it is empty — {INT_MAX, -1, INT_MAX, -1}, as is the box of an empty mask — where the words span a
+// single column or row.
+template <int PX>
 __global__ __launch_bounds__(256) void mask_box_fill_kernel(float* __restrict__ box, const int* __restrict__ words,
-                                                            int* __restrict__ status, int H, int W) {
+                                                            int* __restrict__ status, int* __restrict__ boxes, int H, int W) {
   const int b = blockIdx.y;
   const int xs = words[b * 4 + 0], xe = words[b * 4 + 1], ys = words[b * 4 + 2], ye = words[b * 4 + 3];
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i == 0 && xe < 0) atomicOr(status, DI_STATUS_MASK_BOX_EMPTY);   // the reference's np.min of an empty array raises
+  const long i = ((long)blockIdx.x * 256 + threadIdx.x) * PX;
+  if (i == 0) {
+    if (xe < 0) atomicOr(status, DI_STATUS_MASK_BOX_EMPTY);   // the reference's np.min of an empty array raises
+    if (boxes != nullptr) {
+      const bool rect = xe > xs && ye > ys;    // false for the armed words {INT_MAX, -1, ...} too
+      int* o = boxes + (long)b * 8;
+      o[0] = rect ? xs : INT_MAX; o[1] = rect ? xe - 1 : -1; o[2] = rect ? ys : INT_MAX; o[3] = rect ? ye - 1 : -1;
+      o[4] = xs; o[5] = xe; o[6] = ys; o[7] = ye;
+    }
+  }
   if (i >= (long)H * W) return;
   const int y = (int)(i / W), x = (int)(i - (long)y * W);
-  box[(long)b * H * W + i] = (xe >= 0 && y >= ys && y < ye && x >= xs && x < xe) ? 1.f : 0.f;
+  const bool row = xe >= 0 && y >= ys && y < ye;
+  float v[PX];
+#pragma unroll
+  for (int k = 0; k < PX; ++k) v[k] = (row && x + k >= xs && x + k < xe) ? 1.f : 0.f;
+  float* o = box + (long)b * H * W + i;
+  if constexpr (PX == 4) *reinterpret_cast<float4*>(o) = make_float4(v[0], v[1], v[2], v[3]);
+  else o[0] = v[0];
 }
 
 Mat3 load_mat3(const float* h) {
@@ -664,9 +684,13 @@ extern "C" int deepim_flow_updater_forward(deepim_ctx* ctx, float* flow, float* 
 }
 
 // second half of the rectangle op, shared with the fused re-render (csrc/render.hip accumulates the bbox itself)
-int deepim_mask_box_fill(deepim_ctx* ctx, float* box, const int* words, int B, int H, int W) {
-  hipLaunchKernelGGL(mask_box_fill_kernel, dim3(di_div_up((long)H * W, 256), B), dim3(256), 0, ctx->stream, box, words,
-                     ctx->status, H, W);
+int deepim_mask_box_fill(deepim_ctx* ctx, float* box, const int* words, int* export_boxes, int B, int H, int W) {
+  if (ctx->render_quad && (W & 3) == 0 && ((uintptr_t)box & 15) == 0)
+    hipLaunchKernelGGL(mask_box_fill_kernel<4>, dim3(di_div_up((long)H * W / 4, 256), B), dim3(256), 0, ctx->stream, box, words,
+                       ctx->status, export_boxes, H, W);
+  else
+    hipLaunchKernelGGL(mask_box_fill_kernel<1>, dim3(di_div_up((long)H * W, 256), B), dim3(256), 0, ctx->stream, box, words,
+                       ctx->status, export_boxes, H, W);
   DI_LAUNCH_CHECK();
   return 0;
 }
@@ -678,7 +702,7 @@ extern "C" int deepim_mask_box_forward(deepim_ctx* ctx, float* box, const float*
   int* words = ctx->box_words;
   hipLaunchKernelGGL(mask_box_arm_kernel, dim3(di_div_up(B * 4, 256)), dim3(256), 0, ctx->stream, words, B * 4);
   hipLaunchKernelGGL(mask_bbox_kernel, dim3(di_div_up(H, 8), B), dim3(256), 0, ctx->stream, words, mask, H, W);
-  return deepim_mask_box_fill(ctx, box, words, B, H, W);
+  return deepim_mask_box_fill(ctx, box, words, nullptr, B, H, W);
 }
 
 extern "C" int deepim_depth_to_mask(deepim_ctx* ctx, float* mask, const float* depth, float thresh, size_t n) {

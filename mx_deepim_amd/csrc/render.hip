@@ -305,32 +305,78 @@ __device__ __forceinline__ Frag resolve_pixel(bool hit, unsigned long long key, 
   return o;
 }
 
-template <class Src>
+// The lane's PX consecutive z-buffer keys (PX = 4 or 1), put back to all-ones where an object was: the z-buffer leaves the call
+// as it entered it. With PX = 4 the keys are 32 contiguous, 32-byte aligned bytes: two 16-byte loads.
+template <int PX>
+__device__ __forceinline__ void take_keys(unsigned long long* zb, unsigned long long (&keys)[PX]) {
+  if constexpr (PX == 4) {
+    const ulonglong2 k01 = reinterpret_cast<const ulonglong2*>(zb)[0], k23 = reinterpret_cast<const ulonglong2*>(zb)[1];
+    keys[0] = k01.x; keys[1] = k01.y; keys[2] = k23.x; keys[3] = k23.y;
+    if ((k01.x & k01.y & k23.x & k23.y) != ~0ull) {
+      const ulonglong2 ones = {~0ull, ~0ull};
+      reinterpret_cast<ulonglong2*>(zb)[0] = ones;
+      reinterpret_cast<ulonglong2*>(zb)[1] = ones;
+    }
+  } else {
+    keys[0] = zb[0];
+    if (keys[0] != ~0ull) zb[0] = ~0ull;
+  }
+}
+
+// One value per owned pixel of one output plane: PX = 4 as one 16-byte store.
+template <int PX>
+__device__ __forceinline__ void store_plane_pixels(float* dst, const float (&v)[PX]) {
+  if constexpr (PX == 4) *reinterpret_cast<float4*>(dst) = make_float4(v[0], v[1], v[2], v[3]);
+  else dst[0] = v[0];
+}
+
+// Resolve pass of the tensor entries: lane g of a sample owns the PX consecutive pixels PX g .. PX g + PX - 1. PX = 4 (the plane
+// is a multiple of 4 pixels and every output is 16-byte aligned): the keys come as two 16-byte loads and each output plane takes
+// one 16-byte store per lane; PX = 1: any size. Both give every pixel the same fragment and the box words the same reduction.
+// No lane leaves early: the box reduction shuffles across the whole wave.
+template <class Src, int PX>
 __global__ __launch_bounds__(256) void resolve_kernel(float* __restrict__ image, float* __restrict__ depth,
                                                       unsigned long long* __restrict__ zbuf,
                                                       const PV* __restrict__ pv_all, Src src, Vec3 means, int H, int W,
                                                       float znear, float* __restrict__ mask, float mask_thresh,
                                                       int* __restrict__ box_words, LitParams lit) {
   const int b = blockIdx.y;
-  const long p = (long)blockIdx.x * 256 + threadIdx.x;
+  const long p = ((long)blockIdx.x * 256 + threadIdx.x) * PX;
   const long plane = (long)H * W;
-  const bool inside = p < plane;
-  const unsigned long long key = inside ? zbuf[(long)b * plane + p] : ~0ull;
-  const bool hit = key != ~0ull;
-  if (inside && hit) zbuf[(long)b * plane + p] = ~0ull;      // the z-buffer leaves the call as it entered it: all-ones
-  const Frag fr = resolve_pixel(hit, key, b, p, pv_all, src, W, znear, lit);
-  const float* rgb = fr.rgb; const float z = fr.z;
+  const bool inside = p < plane;                 // PX = 4: plane % 4 == 0, so a lane owns four pixels or none
+  unsigned long long keys[PX];
+#pragma unroll
+  for (int i = 0; i < PX; ++i) keys[i] = ~0ull;
+  if (inside) take_keys<PX>(zbuf + (long)b * plane + p, keys);
+  float ch[3][PX], z[PX];
+#pragma unroll
+  for (int i = 0; i < PX; ++i) {
+    const Frag fr = resolve_pixel(keys[i] != ~0ull, keys[i], b, p + i, pv_all, src, W, znear, lit);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) ch[c][i] = fr.rgb[c] - means.v[c];
+    z[i] = fr.z;
+  }
   if (inside) {
 #pragma unroll
-    for (int c = 0; c < 3; ++c) image[((long)b * 3 + c) * plane + p] = rgb[c] - means.v[c];
-    depth[(long)b * plane + p] = z;
+    for (int c = 0; c < 3; ++c) store_plane_pixels<PX>(image + ((long)b * 3 + c) * plane + p, ch[c]);
+    store_plane_pixels<PX>(depth + (long)b * plane + p, z);
   }
   if (mask != nullptr) {
     // fused tester.py:440-442 (mask_rendered = depth > thresh) and the bbox pass of the box_rendered rectangle
-    const bool on = inside && z > mask_thresh;
-    if (inside) mask[(long)b * plane + p] = on ? 1.f : 0.f;
-    const int y = (int)(p / W), x = (int)(p - (long)y * W);
-    int xmin = on ? x : INT_MAX, xmax = on ? x : -1, ymin = on ? y : INT_MAX, ymax = on ? y : -1;
+    float mk[PX];
+    bool on = false;
+    int xmin = INT_MAX, xmax = -1, ymin = INT_MAX, ymax = -1;
+#pragma unroll
+    for (int i = 0; i < PX; ++i) {
+      const bool on_i = inside && z[i] > mask_thresh;
+      mk[i] = on_i ? 1.f : 0.f;
+      if (on_i) {
+        const int y = (int)((p + i) / W), x = (int)(p + i - (long)y * W);
+        xmin = min(xmin, x); xmax = max(xmax, x); ymin = min(ymin, y); ymax = max(ymax, y);
+      }
+      on = on || on_i;
+    }
+    if (inside) store_plane_pixels<PX>(mask + (long)b * plane + p, mk);
     if (box_words != nullptr && __ballot(on) != 0ull) {
 #pragma unroll
       for (int off = 32; off > 0; off >>= 1) {
@@ -358,24 +404,7 @@ struct FrameOut {
   int N;
 };
 
-// The two ends of a frame resolve pass, for the PX consecutive pixels a lane owns (PX = 4 or 1).
-// take_keys: the lane's z-buffer keys, put back to all-ones where an object was: the z-buffer leaves the call as it entered it.
-// With PX = 4 the keys are 32 contiguous, 32-byte aligned bytes: two 16-byte loads.
-template <int PX>
-__device__ __forceinline__ void take_keys(unsigned long long* zb, unsigned long long (&keys)[PX]) {
-  if constexpr (PX == 4) {
-    const ulonglong2 k01 = reinterpret_cast<const ulonglong2*>(zb)[0], k23 = reinterpret_cast<const ulonglong2*>(zb)[1];
-    keys[0] = k01.x; keys[1] = k01.y; keys[2] = k23.x; keys[3] = k23.y;
-    if ((k01.x & k01.y & k23.x & k23.y) != ~0ull) {
-      const ulonglong2 ones = {~0ull, ~0ull};
-      reinterpret_cast<ulonglong2*>(zb)[0] = ones;
-      reinterpret_cast<ulonglong2*>(zb)[1] = ones;
-    }
-  } else {
-    keys[0] = zb[0];
-    if (keys[0] != ~0ull) zb[0] = ~0ull;
-  }
-}
+// The far end of a frame resolve pass, for the PX consecutive pixels a lane owns (PX = 4 or 1); the near end is take_keys above.
 // store_frame_pixels: BGR levels, uint16 depths and labels (label == nullptr: not stored) at pixel q of the (N,H,W[,3]) outputs.
 template <int PX>
 __device__ __forceinline__ void store_frame_pixels(unsigned char* image, unsigned short* depth, unsigned char* label, long q,
@@ -569,12 +598,23 @@ static int render_front(deepim_ctx* ctx, const Src& src, const Plane& plane, int
 }
 
 // The launch group of the tensor entries: the front, resolve, box fill.
+// One-shot request of deepim_render_export_boxes: every render entry takes it first, before anything can fail, so that it
+// never outlives the call it was made for.
+static int* take_export(deepim_ctx* ctx) {
+  int* boxes = ctx->export_boxes;
+  ctx->export_boxes = nullptr;
+  return boxes;
+}
+#define DI_NO_EXPORT(ctx) \
+  DI_REQUIRE(take_export(ctx) == nullptr, "render: a boxes export is armed (deepim_render_export_boxes), but this entry draws no mask_box")
+
 template <class Src>
-static int render_launch(deepim_ctx* ctx, float* image, float* depth, float* mask, float* mask_box, float mask_thresh,
-                         const Src& src, int max_V, int max_F, const float* poses, const float* K_host,
+static int render_launch(deepim_ctx* ctx, float* image, float* depth, float* mask, float* mask_box, int* export_boxes,
+                         float mask_thresh, const Src& src, int max_V, int max_F, const float* poses, const float* K_host,
                          const float* pixel_means_host, int B, int H, int W, float znear, float zfar,
                          const float* light_offset_host, const float* light_intensity, float ratio) {
   DI_REQUIRE(mask_box == nullptr || (mask != nullptr && B <= DI_MAX_BOX_SAMPLES), "render: mask_box needs mask, B <= 4096");
+  DI_REQUIRE(export_boxes == nullptr || mask_box != nullptr, "render: the boxes export needs mask_box");
   Vec3 means = {{0, 0, 0}};
   if (pixel_means_host) for (int i = 0; i < 3; ++i) means.v[i] = pixel_means_host[i];
   int* words = mask_box ? ctx->box_words : nullptr;
@@ -584,23 +624,29 @@ static int render_launch(deepim_ctx* ctx, float* image, float* depth, float* mas
   int rc = render_front(ctx, src, OwnPlane{}, B, max_V, max_F, poses, K_host, B, H, W, znear, zfar, words, &pv);
   if (rc) return rc;
   unsigned long long* zbuf = ctx->zbuf;
-  hipLaunchKernelGGL(resolve_kernel<Src>, dim3(di_div_up((long)H * W, 256), B), dim3(256), 0, ctx->stream, image, depth, zbuf,
-                     pv, src, means, H, W, znear, mask, mask_thresh, words, lit);
+  const long plane = (long)H * W;
+  const bool quad = ctx->render_quad && plane % 4 == 0 && (((uintptr_t)image | (uintptr_t)depth | (uintptr_t)mask) & 15) == 0;
+  if (quad)
+    hipLaunchKernelGGL((resolve_kernel<Src, 4>), dim3(di_div_up(plane / 4, 256), B), dim3(256), 0, ctx->stream, image, depth, zbuf,
+                       pv, src, means, H, W, znear, mask, mask_thresh, words, lit);
+  else
+    hipLaunchKernelGGL((resolve_kernel<Src, 1>), dim3(di_div_up(plane, 256), B), dim3(256), 0, ctx->stream, image, depth, zbuf,
+                       pv, src, means, H, W, znear, mask, mask_thresh, words, lit);
   DI_LAUNCH_CHECK();
   ctx->zbuf_dirty = 0;        // the resolve pass is queued behind the raster pass: the buffer will be all-ones again
-  if (mask_box) return deepim_mask_box_fill(ctx, mask_box, words, B, H, W);
+  if (mask_box) return deepim_mask_box_fill(ctx, mask_box, words, export_boxes, B, H, W);
   return 0;
 }
 
-static int render_impl(deepim_ctx* ctx, float* image, float* depth, float* mask, float* mask_box, float mask_thresh,
-                       const float* vertices, const float* vertex_attr, const int32_t* faces, const float* texture,
+static int render_impl(deepim_ctx* ctx, float* image, float* depth, float* mask, float* mask_box, int* export_boxes,
+                       float mask_thresh, const float* vertices, const float* vertex_attr, const int32_t* faces, const float* texture,
                        int tex_h, int tex_w, const float* poses, const float* K_host, const float* pixel_means_host,
                        int V, int F, int B, int H, int W, float znear, float zfar, const float* normals = nullptr,
                        const float* light_offset_host = nullptr, const float* light_intensity = nullptr, float ratio = 0.f) {
   if (B == 0) return 0;
   DI_REQUIRE(V > 0 && F > 0 && H > 0 && W > 0, "render: empty mesh or image");
   const OneMesh src = {{vertices, vertex_attr, normals, (const int*)faces, texture, tex_h, tex_w, V, F}};
-  return render_launch(ctx, image, depth, mask, mask_box, mask_thresh, src, V, F, poses, K_host, pixel_means_host, B, H, W, znear,
+  return render_launch(ctx, image, depth, mask, mask_box, export_boxes, mask_thresh, src, V, F, poses, K_host, pixel_means_host, B, H, W, znear,
                        zfar, normals != nullptr ? light_offset_host : nullptr, light_intensity, ratio);
 }
 
@@ -609,9 +655,10 @@ extern "C" int deepim_render_forward(deepim_ctx* ctx, float* image, float* depth
                                      int tex_h, int tex_w, const float* poses, const float* K_host,
                                      const float* pixel_means_host, int V, int F, int B, int H, int W, float znear,
                                      float zfar) {
+  DI_NO_EXPORT(ctx);
   DI_DEVICE(ctx);
   DI_CAMERA(ctx, K_host, B, "deepim_render_forward");
-  return render_impl(ctx, image, depth, nullptr, nullptr, 0.f, vertices, vertex_attr, faces, texture, tex_h, tex_w, poses,
+  return render_impl(ctx, image, depth, nullptr, nullptr, nullptr, 0.f, vertices, vertex_attr, faces, texture, tex_h, tex_w, poses,
                      K_host, pixel_means_host, V, F, B, H, W, znear, zfar);
 }
 
@@ -621,10 +668,11 @@ extern "C" int deepim_render_update_forward(deepim_ctx* ctx, float* image, float
                                             int tex_h, int tex_w, const float* poses, const float* K_host,
                                             const float* pixel_means_host, int V, int F, int B, int H, int W,
                                             float znear, float zfar) {
+  int* export_boxes = take_export(ctx);
   DI_DEVICE(ctx);
   DI_CAMERA(ctx, K_host, B, "deepim_render_update_forward");
   DI_REQUIRE(mask_rendered != nullptr, "render_update: mask_rendered is NULL");
-  return render_impl(ctx, image, depth, mask_rendered, mask_box, mask_thresh, vertices, vertex_attr, faces, texture, tex_h,
+  return render_impl(ctx, image, depth, mask_rendered, mask_box, export_boxes, mask_thresh, vertices, vertex_attr, faces, texture, tex_h,
                      tex_w, poses, K_host, pixel_means_host, V, F, B, H, W, znear, zfar);
 }
 
@@ -636,13 +684,14 @@ extern "C" int deepim_render_lit_forward(deepim_ctx* ctx, float* image, float* d
                                          int tex_w, const float* poses, const float* K_host, const float* pixel_means_host,
                                          const float* light_offset_host, const float* light_intensity,
                                          float brightness_ratio, int V, int F, int B, int H, int W, float znear, float zfar) {
+  int* export_boxes = take_export(ctx);
   DI_DEVICE(ctx);
   DI_CAMERA(ctx, K_host, B, "deepim_render_lit_forward");
   DI_REQUIRE(normals != nullptr && light_offset_host != nullptr, "render_lit: normals and light offset are required");
   DI_REQUIRE(brightness_ratio >= 0.f && brightness_ratio <= 1.f, "render_lit: brightness_ratio in [0, 1]");
   DI_REQUIRE(mask_box == nullptr || mask_rendered != nullptr, "render_lit: mask_box needs mask_rendered");
-  return render_impl(ctx, image, depth, mask_rendered, mask_box, mask_thresh, vertices, vertex_attr, faces, texture, tex_h, tex_w,
-                     poses, K_host, pixel_means_host, V, F, B, H, W, znear, zfar, normals, light_offset_host, light_intensity,
+  return render_impl(ctx, image, depth, mask_rendered, mask_box, export_boxes, mask_thresh, vertices, vertex_attr, faces, texture,
+                     tex_h, tex_w, poses, K_host, pixel_means_host, V, F, B, H, W, znear, zfar, normals, light_offset_host, light_intensity,
                      brightness_ratio);
 }
 
@@ -656,6 +705,7 @@ extern "C" int deepim_render_classes_forward(deepim_ctx* ctx, float* image, floa
                                              const float* pixel_means_host, const float* light_offset_host,
                                              const float* light_intensity, float brightness_ratio, int B, int H, int W,
                                              float znear, float zfar) {
+  int* export_boxes = take_export(ctx);
   DI_DEVICE(ctx);
   if (B == 0) return 0;
   DI_CAMERA(ctx, K_host, B, "deepim_render_classes_forward");
@@ -670,7 +720,7 @@ extern "C" int deepim_render_classes_forward(deepim_ctx* ctx, float* image, floa
   }
   const MeshTable src = {(const int*)class_index, (const int*)mesh_desc, vertices, vertex_attr, normals, (const int*)faces,
                          textures, n_classes, max_V, max_F};
-  return render_launch(ctx, image, depth, mask_rendered, mask_box, mask_thresh, src, max_V, max_F, poses, K_host,
+  return render_launch(ctx, image, depth, mask_rendered, mask_box, export_boxes, mask_thresh, src, max_V, max_F, poses, K_host,
                        pixel_means_host, B, H, W, znear, zfar, light_offset_host, light_intensity, brightness_ratio);
 }
 
@@ -702,6 +752,7 @@ extern "C" int deepim_render_observed_forward(deepim_ctx* ctx, uint8_t* image, u
                                               const float* textures, const float* poses, const float* K_host,
                                               const float* light_offset, const float* light_intensity,
                                               const float* brightness_ratio, int B, int H, int W, float znear, float zfar) {
+  DI_NO_EXPORT(ctx);
   DI_DEVICE(ctx);
   DI_REQUIRE(B >= 0 && N >= B, "render_observed: the outputs need N >= B >= 0 rows");
   if (B == 0) return 0;
@@ -726,6 +777,7 @@ extern "C" int deepim_render_frames_forward(deepim_ctx* ctx, uint8_t* image, uin
                                             const float* vertices, const float* vertex_attr, const int32_t* faces,
                                             const float* textures, const float* poses, const float* K_host, int B, int H, int W,
                                             float znear, float zfar) {
+  DI_NO_EXPORT(ctx);
   DI_DEVICE(ctx);
   DI_REQUIRE(B >= 0 && N >= B, "render_frames: the outputs need N >= B >= 0 rows");
   if (B == 0) return 0;
@@ -752,6 +804,7 @@ extern "C" int deepim_render_scene_forward(deepim_ctx* ctx, uint8_t* image, uint
                                            const float* textures, const float* poses, const float* K_host, const float* light_offset,
                                            const float* light_intensity, const float* brightness_ratio, int B, int S, int H, int W,
                                            float znear, float zfar) {
+  DI_NO_EXPORT(ctx);
   DI_DEVICE(ctx);
   DI_REQUIRE(S >= 1 && S <= 8, "render_scene: S (slots per frame) must lie in 1..8");
   DI_REQUIRE(B >= 0 && N >= B, "render_scene: the outputs need N >= B >= 0 rows");
@@ -785,5 +838,15 @@ extern "C" int deepim_render_scene_forward(deepim_ctx* ctx, uint8_t* image, uint
                        W, znear, lit);
   DI_LAUNCH_CHECK();
   ctx->zbuf_dirty = 0;
+  return 0;
+}
+
+// One-shot: the NEXT render entry on this context, which must draw mask_box (deepim_render_update_forward, _lit_, _classes_),
+// also writes boxes (B,2,4) int32 {minx, maxx, miny, maxy}: row 0 the box of the rectangle it draws into mask_box, row 1 the box
+// of its mask_rendered: what the zoom front end's bbox pass would find on the two masks. No extra launch. The request is cleared
+// by that entry whether it succeeds or not; boxes == NULL withdraws it.
+extern "C" int deepim_render_export_boxes(deepim_ctx* ctx, int32_t* boxes) {
+  DI_REQUIRE(ctx != nullptr, "deepim_render_export_boxes: ctx is NULL");
+  ctx->export_boxes = (int*)boxes;
   return 0;
 }

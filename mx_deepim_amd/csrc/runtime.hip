@@ -36,6 +36,7 @@ void deepim_ctx_default_options(deepim_ctx* c) {
   c->conv_tail_slots = 1024;
   c->conv_force_plan = 0;
   c->conv_tail_split = 0;
+  c->render_quad = 1;
 }
 
 extern "C" int deepim_create(int device_id, deepim_ctx** out) {
@@ -55,6 +56,9 @@ extern "C" int deepim_create(int device_id, deepim_ctx** out) {
   c->comm_world = 1;
   c->cam_table = nullptr;
   c->cam_n = 0;
+  c->export_boxes = nullptr;
+  c->seed_boxes = nullptr;
+  c->bbox_launches = 0;
   deepim_ctx_default_options(c);
   hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
   if (e != hipSuccess) {
@@ -237,6 +241,7 @@ extern "C" int deepim_set_option(deepim_ctx* ctx, const char* name, int value) {
   if (strcmp(name, "wino_shared") == 0) { ctx->wino.shared = value ? 1 : 0; return 0; }
   if (strcmp(name, "wino_s2d_skip") == 0) { ctx->wino.s2d_skip = value ? 1 : 0; return 0; }
   if (strcmp(name, "f16_dev_flags") == 0) { DI_REQUIRE(value == 0 || value == DI_F16_NO_PP, "f16_dev_flags: 0 or 16"); ctx->f16_dev_flags = value; return 0; }
+  if (strcmp(name, "render_quad") == 0) { ctx->render_quad = value ? 1 : 0; return 0; }
   if (strcmp(name, "conv_xcd_swizzle") == 0) {
     ctx->conv_xcd_swizzle = value ? 1 : 0;
     return 0;
@@ -252,7 +257,7 @@ extern "C" int deepim_get_option(deepim_ctx* ctx, const char* name, int* value) 
       {"conv_max_split", ctx->conv_max_split}, {"conv_direct", ctx->conv_direct},
       {"conv_tail_split", ctx->conv_tail_split}, {"conv_force_plan", ctx->conv_force_plan}, {"conv_tail_slots", ctx->conv_tail_slots},
       {"conv_autotune", ctx->conv_autotune}, {"dgrad_group", ctx->dgrad_group},
-      {"wgrad_lds", ctx->wgrad_lds}, {"wino_two_wave", ctx->wino.two_wave}, {"wino_shared", ctx->wino.shared}, {"wino_wide", ctx->wino.wide}, {"wino_split", ctx->wino.split}, {"wino_persistent", ctx->wino.persistent}, {"wino_streamk", ctx->wino.streamk}, {"wino_fin", ctx->wino.fin}, {"conv_fewout_quad", ctx->conv_fewout_quad}, {"conv_fewout_blocks", ctx->conv_fewout_blocks}, {"conv_fewout_minc", ctx->conv_fewout_minc}, {"wino_s2d_skip", ctx->wino.s2d_skip}, {"f16_dev_flags", ctx->f16_dev_flags}, {"conv_xcd_swizzle", ctx->conv_xcd_swizzle}};
+      {"wgrad_lds", ctx->wgrad_lds}, {"wino_two_wave", ctx->wino.two_wave}, {"wino_shared", ctx->wino.shared}, {"wino_wide", ctx->wino.wide}, {"wino_split", ctx->wino.split}, {"wino_persistent", ctx->wino.persistent}, {"wino_streamk", ctx->wino.streamk}, {"wino_fin", ctx->wino.fin}, {"conv_fewout_quad", ctx->conv_fewout_quad}, {"conv_fewout_blocks", ctx->conv_fewout_blocks}, {"conv_fewout_minc", ctx->conv_fewout_minc}, {"wino_s2d_skip", ctx->wino.s2d_skip}, {"f16_dev_flags", ctx->f16_dev_flags}, {"conv_xcd_swizzle", ctx->conv_xcd_swizzle}, {"render_quad", ctx->render_quad}};
   for (const auto& o : opts)
     if (strcmp(name, o.n) == 0) { *value = o.v; return 0; }
   deepim_set_error_msg("deepim_get_option: unknown option");

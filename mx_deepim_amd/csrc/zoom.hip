@@ -38,7 +38,11 @@ __global__ void bbox_init_kernel(int* __restrict__ box, int n) {
 }
 
 // grid (rows/ROWS_PER_BLOCK, B, 2 maps); block 256 threads sweep ROWS_PER_BLOCK rows
+// QUAD (two mask maps, W % 4 == 0, 16-byte aligned): the block's rows are one contiguous run of pixel quads, swept with 16-byte
+// loads — whole rows whatever W is, where the row-by-row sweep leaves 128 of 256 lanes idle on the last pass of a 640-pixel
+// row. The same boxes: min and max do not care about the order.
 constexpr int BB_ROWS = 8;
+template <bool QUAD>
 __global__ __launch_bounds__(256) void bbox_kernel(int* __restrict__ box, const float* __restrict__ map0,
                                                    const float* __restrict__ map1, int mode0, int mode1, Vec3 means,
                                                    int H, int W) {
@@ -50,7 +54,22 @@ __global__ __launch_bounds__(256) void bbox_kernel(int* __restrict__ box, const 
   src += (size_t)b * nch * plane;
   const int r0 = blockIdx.x * BB_ROWS;
   int minx = INT_MAX, maxx = -1, miny = INT_MAX, maxy = -1;
-  for (int r = r0; r < min(r0 + BB_ROWS, H); ++r) {
+  if constexpr (QUAD) {
+    const float thresh = mode == BB_MASK_GT ? 0.3f : 0.2f;
+    const int qpr = W >> 2, nq = (min(r0 + BB_ROWS, H) - r0) * qpr;
+    const float4* quads = reinterpret_cast<const float4*>(src + (size_t)r0 * W);
+    for (int q = threadIdx.x; q < nq; q += 256) {
+      const float4 v = quads[q];
+      const bool v0 = v.x > thresh, v1 = v.y > thresh, v2 = v.z > thresh, v3 = v.w > thresh;
+      if (v0 || v1 || v2 || v3) {
+        const int dr = q / qpr, r = r0 + dr, x = (q - dr * qpr) << 2;
+        minx = min(minx, x + (v0 ? 0 : v1 ? 1 : v2 ? 2 : 3));
+        maxx = max(maxx, x + (v3 ? 3 : v2 ? 2 : v1 ? 1 : 0));
+        miny = min(miny, r); maxy = max(maxy, r);
+      }
+    }
+  }
+  for (int r = r0; !QUAD && r < min(r0 + BB_ROWS, H); ++r) {
     for (int x = threadIdx.x; x < W; x += 256) {
       const size_t p = (size_t)r * W + x;
       bool valid;
@@ -654,8 +673,31 @@ Chan make_chan(const float* src, float* dst, long sb, long db, float mean, int f
 
 // boxes + factor; scratch layout: [B*2*4 int boxes]; status word lives in ctx->status
 // K_host == NULL: the bound camera table (the entry has checked it with DI_CAMERA)
+// One-shot request of deepim_zoom_seed_boxes: every entry that computes a zoom factor takes it first, before anything can fail,
+// so that it never outlives the call it was made for.
+const int* take_seed(deepim_ctx* ctx) {
+  const int* boxes = ctx->seed_boxes;
+  ctx->seed_boxes = nullptr;
+  return boxes;
+}
+#define DI_NO_SEED(ctx) \
+  DI_REQUIRE(take_seed(ctx) == nullptr, "zoom: boxes are seeded (deepim_zoom_seed_boxes), but only the deepim_zoom_concat_* front ends take them")
+
+// seed != NULL (deepim_zoom_seed_boxes): the caller's (B,2,4) boxes of the two maps stand in for the bbox pass. They are read,
+// never re-armed, and the context's accumulators and their guard stay as the next unseeded call expects them.
 int compute_zoom_factor(deepim_ctx* ctx, float* zoom_factor, const float* map0, const float* map1, int mode0, int mode1,
-                        const float* means3, const float* src_pose, const float* K_host, int B, int H, int W) {
+                        const float* means3, const float* src_pose, const float* K_host, int B, int H, int W,
+                        const int* seed = nullptr) {
+  if (seed != nullptr) {
+    if (K_host)
+      hipLaunchKernelGGL(zoom_factor_kernel<CamOne>, dim3(di_div_up(B, 64)), dim3(64), 0, ctx->stream, zoom_factor, ctx->status,
+                         const_cast<int*>(seed), src_pose, cam_one(K_host), B, H, W, 0);
+    else
+      hipLaunchKernelGGL(zoom_factor_kernel<CamTable>, dim3(di_div_up(B, 64)), dim3(64), 0, ctx->stream, zoom_factor, ctx->status,
+                         const_cast<int*>(seed), src_pose, CamTable{ctx->cam_table}, B, H, W, 0);
+    DI_LAUNCH_CHECK();
+    return 0;
+  }
   // up to DI_MAX_BOX_SAMPLES pairs the accumulators are the context's persistent, self-re-arming ones (no init launch: one of the
   // ~4 µs launches per refinement iteration that carry no work); larger batches arm a scratch copy as before
   const bool persistent = B <= DI_MAX_BOX_SAMPLES;
@@ -677,7 +719,11 @@ int compute_zoom_factor(deepim_ctx* ctx, float* zoom_factor, const float* map0, 
   if (means3) for (int i = 0; i < 3; ++i) means.v[i] = means3[i];
   dim3 grid(di_div_up(H, BB_ROWS), B, 2);
   if (persistent) ctx->zoom_box_dirty = 1;
-  hipLaunchKernelGGL(bbox_kernel, grid, dim3(256), 0, ctx->stream, box, map0, map1, mode0, mode1, means, H, W);
+  ++ctx->bbox_launches;
+  if (mode0 != BB_IMAGE && mode1 != BB_IMAGE && (W & 3) == 0 && (((uintptr_t)map0 | (uintptr_t)map1) & 15) == 0)
+    hipLaunchKernelGGL(bbox_kernel<true>, grid, dim3(256), 0, ctx->stream, box, map0, map1, mode0, mode1, means, H, W);
+  else
+    hipLaunchKernelGGL(bbox_kernel<false>, grid, dim3(256), 0, ctx->stream, box, map0, map1, mode0, mode1, means, H, W);
   DI_LAUNCH_CHECK();
   if (K_host)
     hipLaunchKernelGGL(zoom_factor_kernel<CamOne>, dim3(di_div_up(B, 64)), dim3(64), 0, ctx->stream, zoom_factor, status, box,
@@ -696,6 +742,7 @@ extern "C" int deepim_zoom_mask_forward(deepim_ctx* ctx, const float* mask_obser
                                         const float* mask_rendered, const float* src_pose, const float* K_host,
                                         float* zoom_mask_observed, float* zoom_mask_gt_observed,
                                         float* zoom_mask_rendered, float* zoom_factor, int B, int H, int W) {
+  DI_NO_SEED(ctx);
   DI_DEVICE(ctx);
   if (B == 0) return 0;
   DI_CAMERA(ctx, K_host, B, "deepim_zoom_mask_forward");
@@ -723,6 +770,7 @@ extern "C" int deepim_zoom_image_forward(deepim_ctx* ctx, const float* image_obs
                                          const float* src_pose, const float* K_host, const float* pixel_means_host,
                                          float* zoom_image_observed, float* zoom_image_rendered, float* zoom_factor,
                                          int B, int H, int W) {
+  DI_NO_SEED(ctx);
   DI_DEVICE(ctx);
   if (B == 0) return 0;
   DI_CAMERA(ctx, K_host, B, "deepim_zoom_image_forward");
@@ -861,6 +909,7 @@ static const void* const FRONT_KERNEL[3][2][2][2] = {
 
 static int launch_front_end(deepim_ctx* ctx, FrontEnd e, const float* src_pose, const float* K_host,
                             const float* pixel_means_host, float* zoom_factor, int B, int H, int W) {
+  const int* seed = take_seed(ctx);
   DI_DEVICE(ctx);
   if (B == 0) return 0;
   DI_CAMERA(ctx, K_host, B, e.entry);
@@ -885,10 +934,13 @@ static int launch_front_end(deepim_ctx* ctx, FrontEnd e, const float* src_pose, 
   const bool aligned = (W & 3) == 0 && ((size_t)out & 15) == 0 && ((size_t)e.extra2 & 15) == 0;
   if (!plain) DI_REQUIRE(aligned && (e.form != FORM_H16 || e.main8), e.need_aligned);
 
+  // seeded boxes are those of mask_observed and mask_rendered: not of the images, nor of the training graph's mask_gt_observed
+  DI_REQUIRE(seed == nullptr || (with_mask && e.box_observed == nullptr),
+             "zoom front end: seeded boxes stand for the boxes of mask_observed and mask_rendered, which this call does not search");
   int rc;
   if (with_mask)  // ZoomMask; test graph: mask_gt_observed ≡ mask_observed (deepIM_flownet.py:564)
     rc = compute_zoom_factor(ctx, zoom_factor, e.box_observed ? e.box_observed : g.mask_observed, g.mask_rendered, BB_MASK_GT,
-                             BB_MASK_RENDERED, nullptr, src_pose, K_host, B, H, W);
+                             BB_MASK_RENDERED, nullptr, src_pose, K_host, B, H, W, seed);
   else            // ZoomImage: boxes of the non-black pixels (deepIM_flownet.py:594-605, zoom_image.py:31-37)
     rc = compute_zoom_factor(ctx, zoom_factor, g.image_observed, g.image_rendered, BB_IMAGE, BB_IMAGE, pixel_means_host,
                              src_pose, K_host, B, H, W);
@@ -1069,6 +1121,23 @@ extern "C" int deepim_zoom_inverse_factor(deepim_ctx* ctx, const float* zoom_fac
   if (B == 0) return 0;
   hipLaunchKernelGGL(inverse_factor_kernel, dim3(di_div_up(B, 64)), dim3(64), 0, ctx->stream, inv_factor, zoom_factor, B, H, W);
   DI_LAUNCH_CHECK();
+  return 0;
+}
+
+// One-shot: the NEXT deepim_zoom_concat_* call on this context, which must be given both masks, takes the boxes of
+// mask_observed (row 0) and mask_rendered (row 1) from boxes (B,2,4) int32 {minx, maxx, miny, maxy} — what
+// deepim_render_export_boxes wrote for the masks handed to it — and launches no bbox pass. The array is only read. The request is
+// cleared by the next zoom-factor computation whether it succeeds or not; boxes == NULL withdraws it.
+extern "C" int deepim_zoom_seed_boxes(deepim_ctx* ctx, const int32_t* boxes) {
+  DI_REQUIRE(ctx != nullptr, "deepim_zoom_seed_boxes: ctx is NULL");
+  ctx->seed_boxes = (const int*)boxes;
+  return 0;
+}
+
+// how many bbox passes (bbox_kernel launches) this context has queued since it was created
+extern "C" int deepim_bbox_launches(deepim_ctx* ctx, unsigned long long* count) {
+  DI_REQUIRE(ctx != nullptr && count != nullptr, "deepim_bbox_launches: NULL argument");
+  *count = ctx->bbox_launches;
   return 0;
 }
 

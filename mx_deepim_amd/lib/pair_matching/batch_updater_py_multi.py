@@ -125,15 +125,23 @@ def update_test_batch(cfg, data, render_machine, refined_pose, class_index=None,
     `class_index`: None, a scalar or a host sequence of B ids (one launch group per run of equal ids), or a device int32 array
     of B ids (one launch group for the whole batch, no read-back).
     data["intrinsics"] (DeviceArray (B,3,3), per-pair cameras) goes to the render machine as `K=` — its [b0:b1] slice to each run
-    on the host-id path — and stays in the returned batch; without it the machine draws with its own K."""
+    on the host-id path — and stays in the returned batch; without it the machine draws with its own K.
+    With the rectangle the batch also gets "zoom_boxes": a device int32 (B,2,4) array holding the boxes of the new mask_observed
+    and mask_rendered ({minx, maxx, miny, maxy}; written by the box-fill pass, no extra launch), kept in `out` when `out` is
+    given. The next deepIM_flownet.zoom() takes its boxes from it instead of searching the two masks again — as long as the batch
+    still carries the very mask objects this call wrote. That is the contract: the masks returned here are OUTPUTS, not scratch;
+    a caller that wants other masks puts other objects into the batch (and zoom() then searches them), it does not overwrite
+    these in place."""
     ctx = refined_pose.context
     cams = data.get("intrinsics")
     B, H, W = refined_pose.shape[0], render_machine.height, render_machine.width
-    out = out or {}
+    given = out is not None
+    out = out if given else {}
     image = out.get("image_rendered") or ctx.empty((B, 3, H, W))
     depth = out.get("depth_rendered") or ctx.empty((B, 1, H, W))
     new = dict(data)
-    mask = box = None
+    new.pop("zoom_boxes", None)              # those of the masks this call replaces
+    mask = box = boxes = None
     if cfg.network.INPUT_MASK:
         mask = out.get("mask_rendered") or ctx.empty((B, 1, H, W))
         if cfg.network.PRED_MASK:
@@ -141,14 +149,19 @@ def update_test_batch(cfg, data, render_machine, refined_pose, class_index=None,
                 # tester.py:445-449 hands the old mask_rendered over, but update_data_batch (data_pair.py:94-105) ignores
                 # it for this mode and draws the rectangle of the NEW rendered mask
                 box = out.get("mask_observed") or ctx.empty((B, 1, H, W))
+                boxes = out.get("zoom_boxes")
+                if boxes is None or boxes.shape != (B, 2, 4):
+                    boxes = ctx.empty((B, 2, 4), dtype=np.int32)
+                    if given:
+                        out["zoom_boxes"] = boxes
             elif cfg.TEST.UPDATE_MASK != "init":
                 raise Exception("Unknown UPDATE_MASK type: {}".format(cfg.TEST.UPDATE_MASK))
     if is_device_ids(class_index) and class_index.size == B:
         # class ids resident on the device: ONE fused pass (draw, mask_rendered = depth > 0.2, rectangle) over the whole mixed
         # batch; the host never reads the ids, so a captured graph of the iteration replays for any batch's objects
         render_machine.render_classes_into(image, depth, class_index, refined_pose, K=cams, mask_rendered=mask, mask_box=box,
-                                           mask_thresh=0.2, light_intensity=light_intensity)
-        return _updated(cfg, new, image, depth, mask, box, refined_pose)
+                                           mask_thresh=0.2, light_intensity=light_intensity, boxes=boxes)
+        return _updated(cfg, new, image, depth, mask, box, refined_pose, boxes)
     # host ids: one fused pass per run of equal class ids
     ids = np.zeros(B, np.int64) if class_index is None else np.broadcast_to(
         np.asarray(class_index).astype(np.int64).reshape(-1), (B,)) if np.size(class_index) == 1 else \
@@ -162,12 +175,13 @@ def update_test_batch(cfg, data, render_machine, refined_pose, class_index=None,
                                    K=None if cams is None else cams[b0:b1],
                                    mask_rendered=None if mask is None else mask[b0:b1],
                                    mask_box=None if box is None else box[b0:b1], mask_thresh=0.2,
-                                   light_intensity=None if light_intensity is None else light_intensity[b0:b1])
+                                   light_intensity=None if light_intensity is None else light_intensity[b0:b1],
+                                   boxes=None if boxes is None else boxes[b0:b1])
         b0 = b1
-    return _updated(cfg, new, image, depth, mask, box, refined_pose)
+    return _updated(cfg, new, image, depth, mask, box, refined_pose, boxes)
 
 
-def _updated(cfg, new, image, depth, mask, box, refined_pose):
+def _updated(cfg, new, image, depth, mask, box, refined_pose, boxes=None):
     new["image_rendered"], new["src_pose"] = image, refined_pose
     if cfg.network.INPUT_DEPTH:
         new["depth_rendered"] = depth
@@ -175,4 +189,7 @@ def _updated(cfg, new, image, depth, mask, box, refined_pose):
         new["mask_rendered"] = mask
     if box is not None:
         new["mask_observed"] = box
+    if boxes is not None:
+        boxes.masks = (box, mask)      # the objects the boxes belong to: zoom() uses them for these and no others
+        new["zoom_boxes"] = boxes
     return new

@@ -89,25 +89,26 @@ class Render_Py_Light_ModelNet_Multi(Render_Py):
 
     # -- device API ----------------------------------------------------------------------------------------------
     def render_into(self, image, depth, cls_idx, poses, K=None, pixel_means="default", mask_rendered=None, mask_box=None,
-                    mask_thresh=0.2, light_offset=None, light_intensity=None, brightness_k=0):
+                    mask_thresh=0.2, light_offset=None, light_intensity=None, brightness_k=0, boxes=None):
         """As Render_Py.render_into, lit: light at `light_offset` (default 0.5·[0,1,1]) + (t_x, −t_y, −t_z) of every sample's
-        pose, `light_intensity` = device (n,3) or None (white, 1.0). `K`: as in Render_Py.render_into."""
+        pose, `light_intensity` = device (n,3) or None (white, 1.0). `K` and `boxes`: as in Render_Py.render_into."""
         m, nrm = self.mesh_list[int(cls_idx)], self.normal_list[int(cls_idx)]
         K = self._camera(K, poses.shape[0])
         means = self.pixel_means if isinstance(pixel_means, str) else pixel_means
         off = np.ascontiguousarray(LIGHT_OFFSET if light_offset is None else light_offset, np.float32).reshape(3)
+        self._export_boxes(boxes, mask_box, poses.shape[0])
         lib.deepim_render_lit_forward(self.ctx.handle, image, depth, mask_rendered, mask_box, ctypes.c_float(mask_thresh), m.vertices,
                                       m.attr, nrm, m.faces, m.texture, m.tex_h, m.tex_w, poses, K, means, off, light_intensity,
                                       ctypes.c_float(self.brightness_ratios[brightness_k]), m.V, m.F, poses.shape[0], self.height,
                                       self.width, ctypes.c_float(self.zNear), ctypes.c_float(self.zFar))
 
     def render_classes_into(self, image, depth, class_index, poses, K=None, pixel_means="default", mask_rendered=None,
-                            mask_box=None, mask_thresh=0.2, light_offset=None, light_intensity=None, brightness_k=0):
+                            mask_box=None, mask_thresh=0.2, light_offset=None, light_intensity=None, brightness_k=0, boxes=None):
         """As `render_into`, lit, for a batch of mixed models: `class_index` (n) is a DEVICE int32 array, sample b draws model
         class_index[b]; one launch group, the ids never read on the host (Render_Py.render_classes_into)."""
         off = np.ascontiguousarray(LIGHT_OFFSET if light_offset is None else light_offset, np.float32).reshape(3)
         self._draw_classes(image, depth, class_index, poses, K, pixel_means, mask_rendered, mask_box, mask_thresh,
-                           light_offset=off, light_intensity=light_intensity, ratio=self.brightness_ratios[brightness_k])
+                           light_offset=off, light_intensity=light_intensity, ratio=self.brightness_ratios[brightness_k], boxes=boxes)
 
     # -- reference API -------------------------------------------------------------------------------------------
     def render(self, model_idx, r, t, light_position, light_intensity, brightness_k=0, r_type="quat"):

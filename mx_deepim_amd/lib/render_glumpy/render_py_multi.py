@@ -205,11 +205,12 @@ class Render_Py(object):
         return np.ascontiguousarray(K, dtype=np.float32).reshape(3, 3)
 
     def render_into(self, image, depth, cls_idx, poses, K=None, pixel_means="default", mask_rendered=None, mask_box=None,
-                    mask_thresh=0.2, light_intensity=None):
+                    mask_thresh=0.2, light_intensity=None, boxes=None):
         """image (n,3,H,W), depth (n,1,H,W), poses (n,3,4): all device arrays; one mesh. With `mask_rendered` (n,1,H,W)
         the same pass also writes depth > mask_thresh, and with `mask_box` its box_rendered rectangle. (`light_intensity` belongs
         to the lit ModelNet machine, render_py_light_modelnet_multi.py; this unlit draw ignores it.) `K`: None (the machine's), a
-        host (3,3), or a DeviceArray (n,3,3) of per-sample cameras (`_camera`)."""
+        host (3,3), or a DeviceArray (n,3,3) of per-sample cameras (`_camera`). `boxes`: None, or a device int32 (n,2,4) array
+        that receives the zoom front end's boxes of `mask_box` and `mask_rendered` (`deepim_render_export_boxes`; needs both)."""
         m = self.mesh_list[int(cls_idx)]
         n = poses.shape[0]
         K = self._camera(K, n)
@@ -219,10 +220,23 @@ class Render_Py(object):
         if mask_rendered is None:
             if mask_box is not None:
                 raise ValueError("mask_box needs mask_rendered")
+            if boxes is not None:
+                raise ValueError("boxes needs mask_box")
             lib.deepim_render_forward(self.ctx.handle, image, depth, *tail)
         else:
+            self._export_boxes(boxes, mask_box, n)
             lib.deepim_render_update_forward(self.ctx.handle, image, depth, mask_rendered, mask_box,
                                              ctypes.c_float(mask_thresh), *tail)
+
+    def _export_boxes(self, boxes, mask_box, n):
+        """Arm the one-shot boxes export for the draw that follows at once (the C entry clears it, also when it fails)."""
+        if boxes is None:
+            return
+        if mask_box is None:
+            raise ValueError("boxes needs mask_box")
+        if not isinstance(boxes, DeviceArray) or boxes.dtype != np.int32 or boxes.shape != (n, 2, 4):
+            raise ValueError("boxes must be a device int32 array (%d,2,4)" % n)
+        lib.deepim_render_export_boxes(self.ctx.handle, boxes)
 
     _lit = False         # the lit machine's mesh table carries the normals
 
@@ -233,7 +247,7 @@ class Render_Py(object):
         return self._table
 
     def _draw_classes(self, image, depth, class_index, poses, K, pixel_means, mask_rendered, mask_box, mask_thresh,
-                      light_offset=None, light_intensity=None, ratio=0.0):
+                      light_offset=None, light_intensity=None, ratio=0.0, boxes=None):
         if not is_device_ids(class_index):
             raise TypeError("render_classes_into needs class_index as a device int32 array")
         if mask_rendered is None and mask_box is not None:
@@ -241,6 +255,7 @@ class Render_Py(object):
         t = self.mesh_table()
         K = self._camera(K, poses.shape[0])
         means = self.pixel_means if isinstance(pixel_means, str) else pixel_means
+        self._export_boxes(boxes, mask_box, poses.shape[0])
         lib.deepim_render_classes_forward(self.ctx.handle, image, depth, mask_rendered, mask_box, ctypes.c_float(mask_thresh),
                                           class_index, t.mesh_desc, t.n_classes, t.max_V, t.max_F, t.vertices, t.vertex_attr,
                                           t.normals, t.faces, t.textures, poses, K, means, light_offset, light_intensity,
@@ -248,11 +263,11 @@ class Render_Py(object):
                                           ctypes.c_float(self.zNear), ctypes.c_float(self.zFar))
 
     def render_classes_into(self, image, depth, class_index, poses, K=None, pixel_means="default", mask_rendered=None,
-                            mask_box=None, mask_thresh=0.2, light_intensity=None):
+                            mask_box=None, mask_thresh=0.2, light_intensity=None, boxes=None):
         """As `render_into` for a batch of mixed classes: `class_index` (n) is a DEVICE int32 array and sample b draws mesh
         class_index[b], all in one launch group. The ids are never read on the host; a sample whose id is outside
         [0, len(classes)) comes out as an empty frame (see include/deepim_hip.h). (`light_intensity`: ignored, as in `render_into`.)"""
-        self._draw_classes(image, depth, class_index, poses, K, pixel_means, mask_rendered, mask_box, mask_thresh)
+        self._draw_classes(image, depth, class_index, poses, K, pixel_means, mask_rendered, mask_box, mask_thresh, boxes=boxes)
 
     def render_frames_into(self, image_u8, depth_u16, class_index_dev, poses, K=None, rows=None, label=None, label_value=None,
                            covered=None, depth_factor=1000.0):

@@ -234,6 +234,13 @@ class Context:
 
     cameras = None      # what bind_cameras bound last (kept alive here: the library holds a bare pointer)
 
+    def bbox_launches(self):
+        """How many bbox passes (full-frame searches for the zoom boxes) this context has queued so far; a front end that took
+        its boxes from the render pass (deepim_zoom_seed_boxes) adds none."""
+        n = ctypes.c_ulonglong()
+        lib.deepim_bbox_launches(self.handle, ctypes.byref(n))
+        return n.value
+
     # -- HIP-event stopwatch on the context stream
     def timer(self):
         t = ctypes.c_int()

@@ -204,6 +204,7 @@ class deepIM_flownet(TrainGraph):
         n = cfg.network
         self.input_mask = bool(n.INPUT_MASK)
         self.input_depth = bool(n.INPUT_DEPTH)
+        self.update_mask = cfg.TEST.UPDATE_MASK
         # deepIM_flownet.py:624 / :676 — which heads stay in the test graph
         self.with_mask_head = bool(n.PRED_MASK) and (cfg.TEST.UPDATE_MASK not in ["init", "box_rendered"]
                                                      or not cfg.TEST.FAST_TEST)
@@ -579,8 +580,23 @@ class deepIM_flownet(TrainGraph):
         return (self.conv1_nc8 and self.nc8 and self.cin == 8 and self.input_mask and not self.input_depth
                 and not self.fp16_conv and not self.x3_conv and not self.is_train and self.W % 4 == 0)
 
+    def _render_boxes(self, data):
+        """The boxes of this batch's two masks as update_test_batch left them (data["zoom_boxes"]), or None: search the masks.
+        They are used only for the very mask objects that render call wrote (identity, not address: a caller that swaps a mask
+        gets it searched), with TEST.UPDATE_MASK == "box_rendered" and network.INPUT_MASK. The first iteration, pre-staged
+        frames and UPDATE_MASK == "init" carry no boxes."""
+        boxes = data.get("zoom_boxes")
+        wrote = getattr(boxes, "masks", None)
+        if (boxes is None or wrote is None or not self.input_mask or getattr(self, "update_mask", None) != "box_rendered"
+                or boxes.shape != (self.B, 2, 4) or boxes.dtype != np.int32):
+            return None
+        if data.get("mask_observed") is not wrote[0] or data.get("mask_rendered") is not wrote[1]:
+            return None
+        return boxes
+
     def zoom(self, data):
         """The fused zoom front end: this iteration's network input and zoom factor. Two independent choices.
+        (With the masks of update_test_batch still in place, the two mask boxes come from that render pass: _render_boxes.)
         Observed source: the per-pair fp32 tensors, or a shared-frame batch (data["observed_frames"], lib/utils/image.ObservedFrames)
         whose observed image [and depth] are gathered from the N uint8 / uint16 frames through the device frame_index; the library
         refuses the mask-less ZoomImage configuration there.
@@ -623,6 +639,9 @@ class deepIM_flownet(TrainGraph):
                      "nchw": lib.deepim_zoom_concat_forward}[form]
             depths = () if form == "nc8" else (data.get("depth_observed") if self.input_depth else None, depth_rendered)
             src = (data["image_observed"], data["image_rendered"]) + masks + depths
+        boxes = self._render_boxes(data)
+        if boxes is not None:      # one-shot: taken by the entry below, which then runs no bbox pass (cleared even if it fails)
+            lib.deepim_zoom_seed_boxes(h, boxes)
         entry(h, *(src + (data["src_pose"], K, self.pixel_means) + out + (A["zoom_factor"], self.B, self.H, self.W)))
 
     def encoder_fp16(self):
