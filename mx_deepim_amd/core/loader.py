@@ -1,63 +1,54 @@
-"""The data iterators of deepim/core/loader.py. TestDataLoader (:17-108), which draws every pair's initial pose as decoded
-frames on the device, is at the end of this file with its own description; first
-
-The training iterator: TrainDataLoader (deepim/core/loader.py:111-262) over the device's own random draws.
-
-The reference's loader reads, for every observed frame, ten rendered images and poses that toolkit/LM6d_1_gen_rendered_pose.py
-and LM6d_2_gen_rendered.py wrote to disk once. This one needs no such dataset: it takes the observed frames and their
-ground-truth poses, DRAWS the rendered pose of every pair on the device (lib/pair_matching/pose_sampler.py, csrc/sample.hip),
-renders it with the device render machine and makes the labels with lib/pair_matching/data_pair.get_data_pair_train_batch.
-Every epoch sees fresh initial poses, no host random number goes into a pose, and nothing is read back inside an epoch.
+"""The data iterators of deepim/core/loader.py over an observed set: TrainDataLoader (:111-262) and, at the end of this file with
+its own description, TestDataLoader (:17-108). Neither needs a dataset of rendered images: the training loader DRAWS the rendered
+pose of every pair on the device and renders it, the test loader draws every pair's initial pose as decoded frames.
 
     loader = TrainDataLoader(observed, config, render_machine, batch_size=4, shuffle=True, seed=3, points=points)
     MutableModule(config, net).fit(loader, ..., updater=batchUpdaterPyMulti(config, H, W, render_machine=render_machine))
 
-`observed`: host numpy arrays for the whole set of M frames, as the decoder left them (lib/utils/image.py):
+The set. `observed` is the M observed frames and their ground truth, as the decoder left them (lib/utils/image.py): a dict of
+host numpy arrays, or a core/resident.ResidentObserved that holds the same arrays on the device.
     image_observed (M,H,W,3) uint8 BGR     depth_gt_observed (M,H,W) uint16     mask_gt_observed (M,H,W) uint8 label maps
     mask_idx (M)     pose_observed (M,3,4) float32     class_index (M)     depth_observed (M,H,W) uint16 with network.INPUT_DEPTH
+A dict is checked by resident.check_observed and wrapped in a resident.HostObserved; from there on the loader talks to the set's
+interface alone and every batch, draw id and byte is the same over both kinds (core/resident.py says what each uploads).
 `points`: {class id: ((3,N) model points, (3,N) weights)} for train_iter.SE3_PM_LOSS, the N points already sampled.
+`synthetic`: a lib/utils/synthetic_observed.SyntheticObserved built for the frames' (H, W), or None: S = `num_synthetic` fresh
+synthetic pairs per epoch (LM6D_REFINE_SYN.py: data_syn = True, mask_idx = 1), synthetic pair s being of class
+synthetic_classes[s mod len(synthetic_classes)] (default: the classes of the observed set, in order).
+`backgrounds`: a lib/utils/background.BackgroundPool built for the frames' (H, W), or None. `data_syn`: (M) bool, optional.
 
-An epoch is the M·R pairs p = m·R + r (R = num_rendered_per_observed), in order or, with `shuffle`, in a permutation drawn from
-the loader's own RandomState(seed) at every reset(); a trailing partial batch is dropped, as the reference's iter_next does.
-Pair p of epoch e has draw id e·M·R + p wherever the shuffle puts it, so its pose (and its mask-dilate draw) depends on
-(seed, e, p) alone. The rendered side is the unquantised float render the batch updater produces between iterations, not the
-8-bit / 16-bit files of the reference.
+An epoch is the n = M·R + S pairs p = m·R + r (R = num_rendered_per_observed), p >= M·R being synthetic pair p − M·R, in order or,
+with `shuffle`, in a permutation drawn from the loader's own RandomState(seed) at every reset(); a trailing partial batch is
+dropped, as the reference's iter_next does. Pair p of epoch e has draw id e·n + p wherever the shuffle puts it, so everything
+drawn for it depends on (seed, e, p) alone: every epoch sees fresh initial poses, no host random number goes into a pose, and
+nothing is read back inside an epoch.
 
-`backgrounds`: a lib/utils/background.BackgroundPool built for the frames' (H, W), or None. With it the observed image gets the
-background replacement of image.py:96-155 on the device: the frames flagged in `data_syn` ((M) bool, optional) always, the
-others with probability TRAIN.REPLACE_OBSERVED_BG_RATIO, on a pool image chosen by the pair's own draw (stream 3 of its draw
-id), cropped, resized and composited by one kernel (deepim_ingest_bgr8_pool). Like the pose, the background of pair p in epoch
-e depends on (seed, e, p) alone. Without it every batch is what it was before backgrounds existed.
+A batch holds, for each of its pairs:
+  * the observed side: its frame's image minus the pixel means, depth maps in metres and 0 / 1 label mask, made by the ingest
+    kernels from the uint8 / uint16 frames, with pose_observed, class_index and the class's point cloud. With `backgrounds` the
+    image gets the background replacement of image.py:96-155 on the device: a data_syn frame always, the others with probability
+    TRAIN.REPLACE_OBSERVED_BG_RATIO, on a pool image chosen by the pair's own draw (stream 3 of its draw id), cropped, resized and
+    composited by one kernel. With network.INPUT_DEPTH depth_observed, zeroed outside the pair's label with MASK_INPUTS;
+  * a synthetic pair's observed side: pose and light drawn (streams 4-6 of its draw id under the generator's own seed) and the
+    frame rendered on the device straight into the uint8 / uint16 arrays the real rows lie in. It counts as data_syn, its
+    mask_idx is 1 and its depth_observed its own depth. A generator built with occluders (OccluderSpec) puts up to max_occluders
+    other objects into the frame (streams 7 and 8): the label map shows the visible part of the target only, depth_gt_observed
+    stays the target drawn alone, depth_observed is the scene's depth, and a pair whose target keeps less than min_visible of its
+    pixels falls back to the unoccluded frame;
+  * the rendered side: a pose drawn around pose_observed (lib/pair_matching/pose_sampler.py, streams 0/1 of the draw id) and its
+    unquantised float render by the device render machine, not the 8-bit / 16-bit files of the reference;
+  * the labels of lib/pair_matching/data_pair.get_data_pair_train_batch, with TRAIN.MASK_DILATE on the pair's own draw.
+stats() counts the pairs drawn, their attempts and the exhausted ones, for the synthetic observed poses too, and with occluders
+the pairs gated, kept and the occluder slots drawn. The synthetic classes are checked against the generator's tables on the
+host, so no pair can come out with attempts = −1.
 
-`synthetic`: a lib/utils/synthetic_observed.SyntheticObserved built for the frames' (H, W), or None. With it an epoch is the M·R
-real pairs plus `num_synthetic` fresh synthetic ones (LM6D_REFINE_SYN.py: data_syn = True, mask_idx = 1): n = M·R + S pairs,
-pair p >= M·R being synthetic pair s = p − M·R of class synthetic_classes[s mod len(synthetic_classes)] (default: the classes of
-the observed set, in order). Every pair, real or synthetic, has draw id e·n + p. A synthetic pair's observed pose and light are
-drawn (streams 4-6 of that draw id under the generator's own seed) and its frame is rendered on the device straight into the batch's uint8 / uint16 arrays (deepim_render_observed_forward
-through `rows`), next to the uploaded real rows; its rendered pose is then drawn around that observed pose like any other pair's
-(streams 0/1 of the same draw id). It counts as data_syn: with a pool it always gets a pool background. Its depth_observed is
-its own depth and its mask_idx 1. The synthetic classes are checked against the generator's tables here, on the host, so no
-pair can come out with attempts = −1 and the observed attempts feed deepim_sample_stats_accumulate as they are. Without
-`synthetic` every batch, draw id and byte is what it is without the argument.
-
-A `synthetic` built with occluders (SyntheticObserved(..., occluders=OccluderSpec(...))) puts up to max_occluders other objects
-into a synthetic pair's frame (streams 7 and 8 of its draw id). The plan, the draw ids and the real rows do not change. The
-pair's label map shows the visible part of the target only (mask_idx stays 1), its depth_gt_observed stays the target drawn
-alone, and with network.INPUT_DEPTH its depth_observed is the scene's depth, occluders included. A pair whose target keeps less
-than min_visible of its pixels falls back to today's unoccluded frame. stats() then also counts the pairs gated, kept and the
-occluder slots drawn.
-
-`observed` = core/resident.ResidentObserved(observed, ctx, spare_rows=batch_size, points=points): the set uploaded once. The
-plan, the draw ids, the seeds and every refusal are the same and so is every byte of every batch, but a batch is made from
-indices alone: frame_index (B int32), the draw ids (B uint64) and, with synthetic pairs, their positions and class ids go up;
-image_observed is read in place by deepim_ingest_bgr8_frames (_pool_frames with `backgrounds`), the depth and label maps by the
-deepim_ingest_*_frames entries, and pose_observed, mask_idx, class_index, the data_syn flags and the point clouds are rows
-of resident tables gathered by deepim_gather_rows. The synthetic pair at batch position b is drawn into spare row M + b of the
-set (resident.batch_rows), which the loader claims when it is built: safe on one stream, since batch k's ingest is queued
-before batch k+1's draw and a batch keeps fp32 copies only. A dict holding a DeviceArray is still refused.
-
-Not part of this loader and refused: ready-made backgrounds (bg_image: the pool is the loader's way), TRAIN.MASK_SYN, resizing (a frame that is not config.SCALES[0]),
-shared-frame batches (frame_index), more than one target per synthetic frame, and a synthetic set kept across epochs (SyntheticObserved.to_host makes a fixed one for the `observed` argument).
+Refused at construction: a dict holding a DeviceArray, a missing array, a dtype or shape that is not the decoder's
+(resident.check_observed); ready-made backgrounds (bg_image: the pool is the loader's way), TRAIN.MASK_SYN, resizing (a frame
+that is not config.SCALES[0]), shared-frame batches (frame_index), a render machine, pool or generator of another frame size,
+classes without model points, fewer pairs than one batch, and a resident set on another context or with fewer spare rows than a
+batch.
+Not built: more than one target per synthetic frame, and a synthetic set kept across epochs (SyntheticObserved.to_host makes a
+fixed one for the `observed` argument).
 """
 import numpy as np
 
@@ -67,11 +58,8 @@ from ..lib.pair_matching.pose_sampler import pose_noise, sample_rendered_poses
 from ..lib.utils import image as _image
 from ..lib.utils.background import background_draws_device
 from ..lib.utils.mask_dilate import mask_dilate_draws_device
-from ..lib.utils.synthetic_observed import runs
-from ..runtime import DeviceArray, lib
-from .resident import ResidentObserved, batch_rows          # noqa: F401 (re-exported: the set both loaders take)
-
-_DTYPES = {"image_observed": np.uint8, "depth_gt_observed": np.uint16, "mask_gt_observed": np.uint8, "depth_observed": np.uint16}
+from ..runtime import lib
+from .resident import HostObserved, ResidentObserved, batch_frames, batch_rows          # noqa: F401 (re-exported with the loaders)
 
 
 def epoch_plan(M, R, batch_size, shuffle, rng, epoch, num_synthetic=0):
@@ -98,65 +86,39 @@ class TrainDataLoader(object):
         self.batch_size, self.shuffle, self.seed = int(batch_size), bool(shuffle), int(seed)
         self.R = int(num_rendered_per_observed)
         self.noise = pose_noise(noise)
-        self.resident = res = observed if isinstance(observed, ResidentObserved) else None
-        if res is not None:        # the host side of the set: its small tables; the frames stay on the device
-            if res.ctx is not self.ctx:
-                raise ValueError("TrainDataLoader: the resident set lives on another context")
-            for k in ("pose_observed", "mask_idx", "class_index"):
-                if k not in res.host_tables:
-                    raise KeyError("TrainDataLoader: the resident set was built without '%s'" % k)
-            observed = dict(res.host_tables)
-            if data_syn is None:
-                data_syn = observed.get("data_syn")
-        for k, v in observed.items():
-            if isinstance(v, DeviceArray):
-                raise TypeError("TrainDataLoader: observed['%s'] is a device array; the dataset is host numpy arrays (a batch is "
-                                "gathered on the host and uploaded) or a ResidentObserved" % k)
-        if observed.get("bg_image") is not None:
-            raise NotImplementedError("TrainDataLoader: ready-made backgrounds (bg_image) are not part of this loader; pass "
-                                      "backgrounds=BackgroundPool(...) and they are drawn, cropped and resized on the device")
-        if observed.get("frame_index") is not None:
-            raise NotImplementedError("TrainDataLoader: shared frames (frame_index) are a test-phase input; the training loader is "
-                                      "per pair")
-        if config.TRAIN.get("MASK_SYN", False):
-            raise NotImplementedError("TrainDataLoader: TRAIN.MASK_SYN (image.py:205-206) is not part of the device path")
         n = config.network
         self.keys = ["image_observed", "depth_gt_observed", "mask_gt_observed"] + (["depth_observed"] if n.INPUT_DEPTH else [])
-        self.observed = {}
-        for k in self.keys:
-            if res is not None:             # dtypes, shapes and equal M were checked when the set was built
-                if k not in res.arrays:
-                    raise KeyError("TrainDataLoader: the resident set holds no '%s'" % k)
-                continue
-            if observed.get(k) is None:
-                raise KeyError("TrainDataLoader: observed carries no '%s'" % k)
-            v = np.asarray(observed[k])
-            if v.dtype != np.dtype(_DTYPES[k]):
-                raise TypeError("observed['%s'] is %s; the decoded %s frame is expected" % (k, v.dtype, np.dtype(_DTYPES[k])))
-            self.observed[k] = v
-        if res is not None:
-            self.M, H, W = res.M, res.height, res.width
-        else:
-            img = self.observed["image_observed"]
-            if img.ndim != 4 or img.shape[3] != 3:
-                raise ValueError("observed['image_observed'] has shape %s; (M,H,W,3) expected" % (img.shape,))
-            self.M, H, W = img.shape[0], img.shape[1], img.shape[2]
+        tables = ("pose_observed", "mask_idx", "class_index")
+        self.resident = observed if isinstance(observed, ResidentObserved) else None
+        if self.resident is None:       # a host dict: what only a dict can ask for is refused, then it is checked and wrapped
+            if observed.get("bg_image") is not None:
+                raise NotImplementedError("TrainDataLoader: ready-made backgrounds (bg_image) are not part of this loader; pass "
+                                          "backgrounds=BackgroundPool(...) and they are drawn, cropped and resized on the device")
+            if observed.get("frame_index") is not None:
+                raise NotImplementedError("TrainDataLoader: shared frames (frame_index) are a test-phase input; the training loader "
+                                          "is per pair")
+        if config.TRAIN.get("MASK_SYN", False):
+            raise NotImplementedError("TrainDataLoader: TRAIN.MASK_SYN (image.py:205-206) is not part of the device path")
+        self.set = obs = self.resident or HostObserved(observed, self.ctx, self.keys, tables)
+        if obs.ctx is not self.ctx:
+            raise ValueError("TrainDataLoader: the resident set lives on another context")
+        missing = [k for k in self.keys if k not in obs.arrays] + [k for k in tables if k not in obs.host_tables]
+        if missing:
+            raise KeyError("TrainDataLoader: the observed set carries no '%s'" % "', '".join(missing))
+        self.M, H, W = obs.M, obs.height, obs.width
         _image._check_size(config, H, W)             # the resize of image.py:552-580 is the caller's
         if (render_machine.height, render_machine.width) != (H, W):
             raise ValueError("the render machine draws %dx%d, the frames are %dx%d" % (render_machine.height, render_machine.width, H, W))
-        for k in self.keys[1:]:
-            if res is None and self.observed[k].shape != (self.M, H, W):
-                raise ValueError("observed['%s'] has shape %s; %s expected" % (k, self.observed[k].shape, (self.M, H, W)))
         self.height, self.width = H, W
         if backgrounds is not None and (backgrounds.height, backgrounds.width) != (H, W):
             raise ValueError("the background pool was built for %dx%d frames, the frames are %dx%d"
                              % (backgrounds.height, backgrounds.width, H, W))
         self.backgrounds = backgrounds
         self.bg_ratio = float(config.TRAIN.get("REPLACE_OBSERVED_BG_RATIO", 0.0))
+        if data_syn is None:
+            data_syn = obs.host_tables.get("data_syn")
         self.data_syn = None if data_syn is None else np.asarray(data_syn).astype(bool).reshape(self.M)
-        self.pose_observed = np.ascontiguousarray(observed["pose_observed"], dtype=np.float32).reshape(self.M, 3, 4)
-        self.mask_idx = np.asarray(observed["mask_idx"]).astype(np.int32).reshape(self.M)
-        self.class_index = np.asarray(observed["class_index"]).astype(np.int32).reshape(self.M)
+        self.class_index = obs.host_tables["class_index"]
         self.synthetic, self.S = synthetic, int(num_synthetic) if synthetic is not None else 0
         if synthetic is None and (num_synthetic or synthetic_classes is not None):
             raise ValueError("TrainDataLoader: num_synthetic / synthetic_classes need synthetic=SyntheticObserved(...)")
@@ -175,24 +137,22 @@ class TrainDataLoader(object):
             synthetic.check_classes(self.synthetic_classes)         # on the host: no pair can draw attempts = -1
         self.points = None
         if config.train_iter.SE3_PM_LOSS:
-            if points is None and (res is None or res.point_tables is None):
+            if points is None and obs.point_classes is None:
                 raise ValueError("TrainDataLoader: train_iter.SE3_PM_LOSS needs `points` = {class id: (model points, weights)}")
-            if res is not None and res.point_tables is None:
-                res.set_points(points)           # once: the per-class tables are gathered on the device from then on
-            self.points = res.point_classes if res is not None else {
-                int(c): (np.ascontiguousarray(p, np.float32), np.ascontiguousarray(w, np.float32)) for c, (p, w) in points.items()}
+            if obs.point_classes is None:
+                obs.set_points(points)           # once: a resident set gathers its per-class tables on the device from then on
+            self.points = obs.point_classes
             missing = sorted((set(self.class_index.tolist()) | (set(self.synthetic_classes.tolist()) if self.S else set())) - set(self.points))
             if missing:
                 raise KeyError("TrainDataLoader: no model points for class ids {}".format(missing))
         if self.M * self.R + self.S < self.batch_size:
             raise ValueError("TrainDataLoader: %d pairs do not fill one batch of %d" % (self.M * self.R + self.S, self.batch_size))
-        if res is not None:
-            if self.S:               # synthetic pair at batch position b is drawn into spare row M + b
-                res.claim_spare_rows(self, self.batch_size)
-            if self.backgrounds is not None and (self.data_syn is not None or self.S):
-                want = np.zeros(self.M, bool) if self.data_syn is None else self.data_syn
-                if "data_syn" not in res.tables or not np.array_equal(res.host_tables["data_syn"], want):
-                    res.set_data_syn(want)
+        if self.S:               # a resident set draws the synthetic pair at batch position b into its spare row M + b
+            obs.claim_spare_rows(self, self.batch_size)
+        if self.backgrounds is not None and (self.data_syn is not None or self.S):
+            want = np.zeros(self.M, bool) if self.data_syn is None else self.data_syn
+            if not np.array_equal(obs.host_tables.get("data_syn"), want):
+                obs.set_data_syn(self.data_syn)
         self.K = np.ascontiguousarray(config.dataset.INTRINSIC_MATRIX, np.float32).reshape(3, 3)
         self._rng = np.random.RandomState(self.seed)
         # pairs drawn, sum of attempts, exhausted pairs: device-resident; with `synthetic` the same three of the observed-pose draws
@@ -227,76 +187,35 @@ class TrainDataLoader(object):
             out.update(occluded_pairs=int(t[6]), occluded_kept=int(t[7]), occluder_slots=int(t[8]))
         return out
 
-    def _image_observed(self, frames, always, ids):
-        """image_observed of the batch; with a background pool, on the backgrounds image.py:96-155 gives it: a data_syn frame
-        (`always`: the batch's flags, None = none) always, a real one with probability TRAIN.REPLACE_OBSERVED_BG_RATIO, both
-        from the pair's own draw (stream 3)."""
-        ctx, means = self.ctx, _image._means_rgb(self.config)
-        if self.backgrounds is None:
-            return _image.transform_batch(ctx, frames["image_observed"], means)
-        use_bg, bg_index = background_draws_device(ctx, ids.size, self.seed, ids, self.bg_ratio, len(self.backgrounds), always=always)
-        return _image.transform_batch_pool(ctx, frames["image_observed"], means, frames["mask_gt_observed"], use_bg, bg_index,
-                                           self.backgrounds)
-
-    def _upload(self, key, m, real):
-        """The batch's (B,H,W[,3]) device array of observed[key]: row b is frame m[b] where real[b]; the synthetic rows are left
-        for the generator. A batch of real rows is one upload, as without synthetic pairs; else one upload per run of real rows."""
-        src = self.observed[key]
-        if real.all():
-            return self.ctx.array(src[m], dtype=_DTYPES[key])      # 1 or 2 bytes per value cross PCIe
-        out = self.ctx.empty((len(m),) + src.shape[1:], _DTYPES[key])
-        for j0, j1, r0 in runs(np.nonzero(real)[0]):
-            out[r0:r0 + (j1 - j0)].copyfrom(src[m[r0:r0 + (j1 - j0)]])
-        return out
+    def _draw_synthetic(self, **target):
+        """Poses, lights and frames of a batch's synthetic pairs, made on the device where the set wants them (`target`)."""
+        totals = {"totals": self._totals[6:9]} if self.occluded else {}      # the occlusion gate's three running totals
+        drawn = self.synthetic.frames(**target, **totals)
+        lib.deepim_sample_stats_accumulate(self.ctx.handle, self._totals[3:6], drawn["attempts"], len(target["rows"]))
 
     def make_batch(self, pairs, draw_ids):
         """(data, label) of the given pairs (p = m·R + r, or M·R + s for synthetic pair s) with the given draw ids."""
         ctx, cfg = self.ctx, self.config
         pairs = np.asarray(pairs, np.int64)
-        if self.resident is not None:
-            return self._make_batch_resident(pairs, draw_ids)
-        real = pairs < self.M * self.R
-        m = np.where(real, pairs // self.R, 0)
-        B = len(m)
-        syn = np.nonzero(~real)[0]
-        mask_idx, cls, pose = self.mask_idx[m], self.class_index[m], self.pose_observed[m]
-        always = None if self.data_syn is None else self.data_syn[m]
-        if syn.size:
-            cls_syn = self.synthetic_classes[(pairs[syn] - self.M * self.R) % len(self.synthetic_classes)]
-            mask_idx[syn], cls[syn], pose[syn] = 1, cls_syn, 0.0
-            always = np.zeros(B, bool) if always is None else always.copy()
-            always[syn] = True
-        frames = {k: self._upload(k, m, real) for k in self.keys}
-        frames["mask_idx"] = ctx.array(mask_idx, dtype=np.int32)
-        ids = ctx.array(np.asarray(draw_ids).reshape(B), dtype=np.uint64)
-        pose_observed = ctx.array(pose)
-        if syn.size:      # the synthetic rows: poses, lights and frames made on the device, straight into the batch's arrays
-            drawn = self.synthetic.frames(cls_syn, np.asarray(draw_ids).reshape(B)[syn], rows=syn,
-                                          out=dict(frames, pose_observed=pose_observed), **self._gate_totals())
-            lib.deepim_sample_stats_accumulate(ctx.handle, self._totals[3:6], drawn["attempts"], int(syn.size))
-            if cfg.network.INPUT_DEPTH and not self.occluded:       # their depth_observed is their own depth (occluded: the scene's)
-                for j0, j1, r0 in runs(syn):
-                    frames["depth_observed"][r0:r0 + (j1 - j0)].copyfrom(frames["depth_gt_observed"][r0:r0 + (j1 - j0)])
-        batch = {"image_observed": self._image_observed(frames, always, ids),
+        B, n = len(pairs), self.M * self.R
+        cls_syn = self.synthetic_classes[(pairs[pairs >= n] - n) % len(self.synthetic_classes)] if (pairs >= n).any() else None
+        # a synthetic pair's depth_observed is its own depth (occluded: the scene's, which the generator wrote)
+        frames, ids, table, points = self.set.train_batch(pairs, np.asarray(draw_ids).reshape(B), self.R, self.keys, cls_syn,
+                                                          self._draw_synthetic, cfg.network.INPUT_DEPTH and not self.occluded)
+        use_bg = bg_index = None
+        if self.backgrounds is not None:       # image.py:96-155: a data_syn frame always, a real one with probability bg_ratio
+            use_bg, bg_index = background_draws_device(ctx, B, self.seed, ids, self.bg_ratio, len(self.backgrounds),
+                                                       always=table("data_syn"))
+        batch = {"image_observed": _image.image_observed(ctx, frames, cfg, use_bg, bg_index, self.backgrounds),
                  "depth_gt_observed": _image._depth(ctx, frames, "depth_gt_observed", cfg),
                  "mask_gt_observed": _image.label_mask(ctx, frames, "mask_gt_observed"),
-                 "pose_observed": pose_observed,
-                 "class_index": ctx.array(cls, dtype=np.int32)}
+                 "pose_observed": table("pose_observed"),
+                 "class_index": table("class_index")}
         if cfg.network.INPUT_DEPTH:       # get_pair_depth, train phase: zeroed outside the pair's label with MASK_INPUTS
             batch["depth_observed"] = _image._depth(ctx, frames, "depth_observed", cfg,
                                                     "mask_gt_observed" if cfg.network.get("MASK_INPUTS", False) else None)
         if self.points is not None:
-            batch["point_cloud_model"] = ctx.array(np.stack([self.points[int(c)][0] for c in cls]))
-            batch["point_cloud_weights"] = ctx.array(np.stack([self.points[int(c)][1] for c in cls]))
-        return self._finish(batch, ids, B)
-
-    def _gate_totals(self):
-        """The keyword that hands the generator the occlusion gate's three running totals; nothing without occluders."""
-        return {"totals": self._totals[6:9]} if self.occluded else {}
-
-    def _finish(self, batch, ids, B):
-        """The rendered side and the labels of a batch whose observed side is made: the same for both kinds of set."""
-        ctx, cfg = self.ctx, self.config
+            batch["point_cloud_model"], batch["point_cloud_weights"] = points(batch["class_index"])
         batch["pose_rendered"], attempts = sample_rendered_poses(batch["pose_observed"], self.K, self.width, self.height, self.seed,
                                                                  draw_ids=ids, noise=self.noise)
         lib.deepim_sample_stats_accumulate(ctx.handle, self._totals, attempts, B)
@@ -306,62 +225,12 @@ class TrainDataLoader(object):
         out = data_pair.get_data_pair_train_batch(batch, cfg)
         return out["data"], out["label"]
 
-    def _make_batch_resident(self, pairs, draw_ids):
-        """make_batch over a ResidentObserved: frame_index, the draw ids and, with synthetic pairs, their positions and class
-        ids go up; every row of the batch is read in place or gathered on the device."""
-        ctx, cfg, res = self.ctx, self.config, self.resident
-        rows, syn = batch_rows(pairs, self.M, self.R)
-        B = len(rows)
-        fi = ctx.array(rows, dtype=np.int32)
-        ids = ctx.array(np.asarray(draw_ids).reshape(B), dtype=np.uint64)
-        if syn.size:       # drawn into spare row M + b; class, pose (and mask_idx = data_syn = 1, set once) land in the tables' row
-            cls_syn = ctx.array(self.synthetic_classes[(pairs[syn] - self.M * self.R) % len(self.synthetic_classes)], dtype=np.int32)
-            if syn.size == B:
-                ids_syn, rows_syn = ids, fi
-            else:
-                at = ctx.array(syn, dtype=np.int32)
-                ids_syn = res.gather(ids.reshape((B, 1)), at, syn.size).reshape((syn.size,))
-                rows_syn = res.gather(fi, at, syn.size)
-            out = {k: res.arrays[k] for k in self.keys}       # depth_observed only with INPUT_DEPTH, as over a host set
-            drawn = self.synthetic.frames(cls_syn, ids_syn, rows=rows[syn], rows_device=rows_syn,
-                                          out=dict(out, pose_observed=res.tables["pose_observed"]), **self._gate_totals())
-            lib.deepim_sample_stats_accumulate(ctx.handle, self._totals[3:6], drawn["attempts"], int(syn.size))
-            for j0, j1, r0 in runs(rows[syn]):
-                res.tables["class_index"][r0:r0 + (j1 - j0)].copyfrom(cls_syn[j0:j1])
-                if cfg.network.INPUT_DEPTH and not self.occluded:       # their depth_observed is their own depth (occluded: the scene's)
-                    res.arrays["depth_observed"][r0:r0 + (j1 - j0)].copyfrom(res.arrays["depth_gt_observed"][r0:r0 + (j1 - j0)])
-        frames = {k: res.arrays[k] for k in self.keys}
-        frames["frame_index"] = fi
-        frames["mask_idx"] = res.gather(res.tables["mask_idx"], fi, B)
-        means = _image._means_rgb(cfg)
-        if self.backgrounds is None:
-            image = _image.transform_batch_frames(ctx, frames["image_observed"], fi, means)
-        else:
-            always = res.gather(res.tables["data_syn"], fi, B) if (self.data_syn is not None or self.S) else None
-            use_bg, bg_index = background_draws_device(ctx, B, self.seed, ids, self.bg_ratio, len(self.backgrounds), always=always)
-            image = _image.transform_batch_frames(ctx, frames["image_observed"], fi, means, frames["mask_gt_observed"], use_bg,
-                                                  bg_index, self.backgrounds)
-        batch = {"image_observed": image,
-                 "depth_gt_observed": _image._depth(ctx, frames, "depth_gt_observed", cfg),
-                 "mask_gt_observed": _image.label_mask(ctx, frames, "mask_gt_observed"),
-                 "pose_observed": res.gather(res.tables["pose_observed"], fi, B),
-                 "class_index": res.gather(res.tables["class_index"], fi, B)}
-        if cfg.network.INPUT_DEPTH:
-            batch["depth_observed"] = _image._depth(ctx, frames, "depth_observed", cfg,
-                                                    "mask_gt_observed" if cfg.network.get("MASK_INPUTS", False) else None)
-        if self.points is not None:
-            batch["point_cloud_model"] = res.gather(res.point_tables[0], batch["class_index"], B)
-            batch["point_cloud_weights"] = res.gather(res.point_tables[1], batch["class_index"], B)
-        return self._finish(batch, ids, B)
-
     def __iter__(self):
         for pairs, ids in zip(self.pairs, self.draw_ids):
             yield self.make_batch(pairs, ids)
 
 
 # ---------------------------------------------------------------------------------------------------------- the test phase --
-_TEST_DTYPES = {"image_observed": np.uint8, "depth_observed": np.uint16, "depth_gt_observed": np.uint16,
-                "mask_gt_observed": np.uint8, "mask_observed": np.uint8, "mask_observed_est": np.uint8}
 # TEST.INIT_MASK → the label map lib/utils/image.get_pair_mask reads for it (box_rendered reads the rendered depth alone)
 _INIT_MASK_SOURCE = {"mask_gt_observed": "mask_gt_observed", "box_gt_observed": "mask_gt_observed", "mask_observed": "mask_observed",
                      "box_": "mask_observed", "box_rendered": None}
@@ -406,13 +275,6 @@ def plan_test_batches(P, batch_size, shuffle, rng):
     return order.reshape(n_batches, batch_size), pad
 
 
-def batch_frames(frame_ids):
-    """The frames a shared-frame batch uploads, no device needed → (frames (N,) ascending distinct ids, frame_index (B,) int32):
-    pair b looks at row frame_index[b] of the N <= B uploaded frames."""
-    uniq, inv = np.unique(np.asarray(frame_ids, np.int64).reshape(-1), return_inverse=True)
-    return uniq, inv.reshape(-1).astype(np.int32)
-
-
 class TestDataLoader(object):
     """The test iterator: TestDataLoader (deepim/core/loader.py:17-108) from observed frames and initial poses alone.
 
@@ -423,32 +285,30 @@ class TestDataLoader(object):
     wrote to disk once. This one DRAWS it: every batch's initial poses are rendered on the device straight into uint8 / uint16
     frames with the bytes those files hold (Render_Py.render_frames_into), next to each pair's count of covered pixels.
 
-    `observed`: host numpy arrays for the F camera frames as the decoder left them (observed_keys_of_test says which the
-    configuration reads): image_observed (F,H,W,3) uint8 BGR; depth_observed / depth_gt_observed (F,H,W) uint16;
-    mask_gt_observed / mask_observed / mask_observed_est (F,H,W) uint8 label maps. H x W is config.SCALES[0].
+    `observed`: the F camera frames as the decoder left them, a dict of host numpy arrays or a core/resident.ResidentObserved
+    (observed_keys_of_test says which the configuration reads): image_observed (F,H,W,3) uint8 BGR; depth_observed /
+    depth_gt_observed (F,H,W) uint16; mask_gt_observed / mask_observed / mask_observed_est (F,H,W) uint8 label maps. H x W is
+    config.SCALES[0].
     `pairdb`: a list of P dicts with frame (index into the F frames), gt_class, mask_idx, pose_observed (3,4), pose_rendered
     (3,4) — the initial estimate, all −1 where the detector found nothing (tester.py:285-310) — and optionally K (3,3).
 
-    Every batch is (data, frames, pair_records) as core/tester.pred_eval takes it. With `shared_frames` the distinct frames of
-    the batch are uploaded once (N <= B rows) and the pairs name them through a frame_index; without, one row per pair. mask_idx,
+    Every batch is (data, frames, pair_records) as core/tester.pred_eval takes it. With `shared_frames` the batch holds N frames
+    once and the pairs name them through a frame_index; without, one row per pair (the set's test_frames, core/resident.py). mask_idx,
     the render machine's class ids and the poses are uploaded; when a record has a K, the batch's (B,3,3) camera table too
     (frames["intrinsics"]), and the draw uses it. frames["rendered_covered"] lets get_pair_mask zero mask_observed of a pair whose
     draw is empty (image.py:301-303) on the device. With TEST.MASK_DILATE the thicknesses come from the device generator with
     the pair's index in `pairdb` as its draw id: a pair's draw depends on (seed, pair) alone. Nothing is read back.
 
-    Differences from the reference: one upload per frame, not per pair; batch_size > 1; the last batch is filled up by repeating
+    Differences from the reference: a frame goes up once, not per pair; batch_size > 1; the last batch is filled up by repeating
     its last pair, and the repeats' records are copies carrying "pad": True, which pred_eval leaves out of everything it counts
     (the reference hands the pad count to DataBatch); the mask-dilate draws are the device generator's; the empty-draw rule is
     applied on the device and not printed. Order: arange(P), or with `shuffle` a permutation from RandomState(seed), drawn anew
     at each reset().
 
-    `observed` = core/resident.ResidentObserved(observed, ctx): the F frames uploaded once. With `shared_frames` a batch's
-    frames dict holds the set's own arrays (N = F) and frame_index = frame[pairs]; without, the per-pair rows are gathered on
-    the device by deepim_gather_rows (a frame that is not a multiple of 4 bytes is refused). Only ids, poses and cameras go up.
-
-    Refused: a dict holding a device array, a frame that is not config.SCALES[0] or not the render machine's size, a pair whose frame
-    is outside [0, F) or whose gt_class the render machine does not know, and shared_frames with network.INPUT_MASK off (the
-    library's shared-frame zoom front end has no mask-less variant: pass shared_frames=False)."""
+    Refused: what resident.check_observed refuses in a dict, a frame that is not config.SCALES[0] or not the render machine's
+    size, a pair whose frame is outside [0, F) or whose gt_class the render machine does not know, per-pair rows of a resident set
+    whose frames are no multiple of 4 bytes, and shared_frames with network.INPUT_MASK off (the library's shared-frame zoom front
+    end has no mask-less variant: pass shared_frames=False)."""
     __test__ = False          # a data iterator named after the reference's, not a pytest class
 
     def __init__(self, observed, pairdb, config, render_machine, batch_size=1, shuffle=False, seed=0, shared_frames=True):
@@ -456,46 +316,25 @@ class TestDataLoader(object):
         self.batch_size, self.shuffle, self.seed, self.shared_frames = int(batch_size), bool(shuffle), int(seed), bool(shared_frames)
         if self.batch_size < 1:
             raise ValueError("TestDataLoader: batch_size must be >= 1")
-        self.resident = res = observed if isinstance(observed, ResidentObserved) else None
-        if res is not None:
-            if res.ctx is not render_machine.ctx:
-                raise ValueError("TestDataLoader: the resident set lives on another context")
-            observed = res.arrays           # checked when the set was built; read below for its keys alone
-        else:
-            for k, v in observed.items():
-                if isinstance(v, DeviceArray):
-                    raise TypeError("TestDataLoader: observed['%s'] is a device array; the dataset is host numpy arrays (a batch's "
-                                    "frames are gathered on the host and uploaded) or a ResidentObserved" % k)
         if self.shared_frames and not config.network.INPUT_MASK:
             raise NotImplementedError("TestDataLoader: shared_frames needs network.INPUT_MASK — the shared-frame zoom front end "
                                       "has no mask-less variant; pass shared_frames=False")
-        self.keys = observed_keys_of_test(config, [k for k, v in observed.items() if v is not None])
-        self.observed = {}
+        self.resident = observed if isinstance(observed, ResidentObserved) else None
+        have = observed if self.resident is None else observed.arrays
+        self.keys = observed_keys_of_test(config, [k for k, v in have.items() if v is not None])
+        self.set = obs = self.resident or HostObserved(observed, render_machine.ctx, self.keys)      # a dict: checked and wrapped
+        if obs.ctx is not render_machine.ctx:
+            raise ValueError("TestDataLoader: the resident set lives on another context")
         for k in self.keys:
-            if observed.get(k) is None:
-                raise KeyError("TestDataLoader: observed carries no '%s'" % k)
-            if res is not None:
-                if not self.shared_frames and (res.arrays[k].nbytes // res.rows) % 4:
-                    raise ValueError("TestDataLoader: a '%s' frame of %d bytes is not a multiple of 4 bytes; the per-pair rows of "
-                                     "a resident set are gathered in 4-byte words" % (k, res.arrays[k].nbytes // res.rows))
-                continue
-            v = np.asarray(observed[k])
-            if v.dtype != np.dtype(_TEST_DTYPES[k]):
-                raise TypeError("observed['%s'] is %s; the decoded %s frame is expected" % (k, v.dtype, np.dtype(_TEST_DTYPES[k])))
-            self.observed[k] = v
-        if res is not None:
-            self.F, H, W = res.M, res.height, res.width
-        else:
-            img = self.observed["image_observed"]
-            if img.ndim != 4 or img.shape[3] != 3 or img.shape[0] < 1:
-                raise ValueError("observed['image_observed'] has shape %s; (F,H,W,3) expected" % (img.shape,))
-            self.F, H, W = img.shape[0], img.shape[1], img.shape[2]
+            if k not in obs.arrays:
+                raise KeyError("TestDataLoader: the observed set carries no '%s'" % k)
+        if not self.shared_frames:
+            obs.check_per_pair(self.keys)
+        self.observed = obs.arrays           # numpy arrays over a host dict
+        self.F, H, W = obs.M, obs.height, obs.width
         _image._check_size(config, H, W)
         if (render_machine.height, render_machine.width) != (H, W):
             raise ValueError("the render machine draws %dx%d, the frames are %dx%d" % (render_machine.height, render_machine.width, H, W))
-        for k in self.keys[1:]:
-            if res is None and self.observed[k].shape != (self.F, H, W):
-                raise ValueError("observed['%s'] has shape %s; %s expected" % (k, self.observed[k].shape, (self.F, H, W)))
         self.height, self.width = H, W
         self.pairdb = list(pairdb)
         self.size = len(self.pairdb)
@@ -546,21 +385,7 @@ class TestDataLoader(object):
         pairs = np.asarray(pairs, np.int64).reshape(-1)
         B, H, W = len(pairs), self.height, self.width
         records = [self.pairdb[p] if b < B - pad else dict(self.pairdb[p], pad=True) for b, p in enumerate(pairs)]
-        frames = {}
-        if self.resident is not None:       # the ids go up; the frames are the set's own (shared) or gathered on the device
-            index = ctx.array(self.frame[pairs], dtype=np.int32)
-            if self.shared_frames:
-                frames["frame_index"] = index
-            for k in self.keys:
-                frames[k] = self.resident.arrays[k] if self.shared_frames else self.resident.gather(self.resident.arrays[k], index, B)
-        else:
-            if self.shared_frames:
-                rows, index = batch_frames(self.frame[pairs])
-                frames["frame_index"] = ctx.array(index, dtype=np.int32)
-            else:
-                rows = self.frame[pairs]
-            for k in self.keys:
-                frames[k] = ctx.array(self.observed[k][rows], dtype=_TEST_DTYPES[k])       # 1 or 2 bytes per value cross PCIe
+        frames = self.set.test_frames(self.frame[pairs], self.keys, self.shared_frames)
         frames["mask_idx"] = ctx.array(self.mask_idx[pairs], dtype=np.int32)
         frames["class_index"] = ctx.array(self.class_index[pairs], dtype=np.int32)
         frames["pose_rendered"] = ctx.array(self.pose_rendered[pairs])

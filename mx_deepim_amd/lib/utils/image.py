@@ -191,49 +191,53 @@ def _depth_factor(config):
     return ctypes.c_float(float(config.dataset.get("DEPTH_FACTOR", 1000)))
 
 
+def _ingest_bgr8(ctx, frames_bgr, means_rgb, frame_index=None, bg=None, fg=None, use_bg=None, bg_index=None, pool=None):
+    """The four BGR entries behind one body → (B,3,H,W) fp32. frame_index (device int32 (B), never read by the host): pair b
+    reads frame frame_index[b] of frames_bgr (N,H,W,3) and fg (N,H,W), which stay where they are; None: B = N and its own.
+    pool: a BackgroundPool, composited by the pair's bg_index; else bg, the ready-made (B,H,W,3) backgrounds, or none."""
+    N, H, W, _ = frames_bgr.shape
+    B = N if frame_index is None else frame_index.size
+    if frame_index is not None and frame_index.dtype != np.int32:
+        raise TypeError("frame_index on the device must be int32")
+    means = None if means_rgb is None else np.ascontiguousarray(means_rgb, dtype=np.float32).reshape(3)
+    if pool is not None:
+        if (pool.height, pool.width) != (H, W):
+            raise ValueError("the background pool was built for %dx%d frames, these are %dx%d" % (pool.height, pool.width, H, W))
+        if frame_index is not None and (fg is None or fg.shape != (N, H, W)):
+            raise ValueError("the pool composite of shared frames needs fg labels of shape %s" % ((N, H, W),))
+        tail = (use_bg, bg_index, pool.pixels, pool.desc, pool.xtab, pool.ytab, len(pool), means, B, H, W)
+    out = ctx.empty((B, 3, H, W))
+    if pool is None and frame_index is None:
+        lib.deepim_ingest_bgr8(ctx.handle, out, frames_bgr, bg, fg, use_bg, means, B, H, W)
+    elif pool is None:
+        lib.deepim_ingest_bgr8_frames(ctx.handle, out, frames_bgr, frame_index, N, means, B, H, W)
+    elif frame_index is None:
+        lib.deepim_ingest_bgr8_pool(ctx.handle, out, frames_bgr, fg, *tail)
+    else:
+        lib.deepim_ingest_bgr8_pool_frames(ctx.handle, out, frames_bgr, fg, frame_index, N, *tail)
+    return out
+
+
 def transform_batch(ctx, frames_bgr, means_rgb=None, bg=None, fg=None, use_bg=None):
     """(B,H,W,3) uint8 BGR device frames → (B,3,H,W) fp32, channel i = image channel 2-i minus means_rgb[i]."""
-    B, H, W, _ = frames_bgr.shape
-    out = ctx.empty((B, 3, H, W))
-    means = None if means_rgb is None else np.ascontiguousarray(means_rgb, dtype=np.float32).reshape(3)
-    lib.deepim_ingest_bgr8(ctx.handle, out, frames_bgr, bg, fg, use_bg, means, B, H, W)
-    return out
+    return _ingest_bgr8(ctx, frames_bgr, means_rgb, bg=bg, fg=fg, use_bg=use_bg)
 
 
 def transform_batch_pool(ctx, frames_bgr, means_rgb, fg, use_bg, bg_index, pool):
     """transform_batch with the background of image.py:108-155 from a BackgroundPool: where fg (B,H,W) uint8 is 0, in the pairs
     with use_bg != 0 (device int32 (B), None: every pair), the pixel is image bg_index[b] (device int32 (B)) of the pool,
     cropped, resized and padded to the frame inside the kernel."""
-    B, H, W, _ = frames_bgr.shape
-    if (pool.height, pool.width) != (H, W):
-        raise ValueError("the background pool was built for %dx%d frames, these are %dx%d" % (pool.height, pool.width, H, W))
-    out = ctx.empty((B, 3, H, W))
-    means = None if means_rgb is None else np.ascontiguousarray(means_rgb, dtype=np.float32).reshape(3)
-    lib.deepim_ingest_bgr8_pool(ctx.handle, out, frames_bgr, fg, use_bg, bg_index, pool.pixels, pool.desc, pool.xtab, pool.ytab,
-                                len(pool), means, B, H, W)
-    return out
+    return _ingest_bgr8(ctx, frames_bgr, means_rgb, fg=fg, use_bg=use_bg, bg_index=bg_index, pool=pool)
 
 
-def transform_batch_frames(ctx, frames_bgr, frame_index, means_rgb=None, fg=None, use_bg=None, bg_index=None, pool=None):
-    """transform_batch / transform_batch_pool (with `pool`) of frames_bgr[frame_index] without the gather: frames_bgr (N,H,W,3)
-    uint8 and fg (N,H,W) uint8 stay where they are — a whole device-resident set, say — and pair b reads frame frame_index[b]
-    (device int32 (B), never read by the host) → (B,3,H,W) fp32. use_bg and bg_index stay per pair."""
-    N, H, W, _ = frames_bgr.shape
-    if frame_index.dtype != np.int32:
-        raise TypeError("transform_batch_frames: frame_index on the device must be int32")
-    B = frame_index.size
-    out = ctx.empty((B, 3, H, W))
-    means = None if means_rgb is None else np.ascontiguousarray(means_rgb, dtype=np.float32).reshape(3)
-    if pool is None:
-        lib.deepim_ingest_bgr8_frames(ctx.handle, out, frames_bgr, frame_index, N, means, B, H, W)
-        return out
-    if (pool.height, pool.width) != (H, W):
-        raise ValueError("the background pool was built for %dx%d frames, these are %dx%d" % (pool.height, pool.width, H, W))
-    if fg is None or fg.shape != (N, H, W):
-        raise ValueError("transform_batch_frames: the pool composite needs fg labels of shape %s" % ((N, H, W),))
-    lib.deepim_ingest_bgr8_pool_frames(ctx.handle, out, frames_bgr, fg, frame_index, N, use_bg, bg_index, pool.pixels, pool.desc,
-                                       pool.xtab, pool.ytab, len(pool), means, B, H, W)
-    return out
+def image_observed(ctx, frames, config, use_bg=None, bg_index=None, pool=None):
+    """frames["image_observed"] → device (B,3,H,W), RGB minus the pixel means; with `pool` on the pool's backgrounds outside
+    mask_gt_observed, as transform_batch_pool. In a shared-frame batch the frames are (N,H,W,3) and pair b reads frame
+    frame_index[b] without a gather (deepim_ingest_bgr8_frames / _pool_frames); use_bg and bg_index stay per pair."""
+    obs = _frame(ctx, frames, "image_observed", np.uint8, (3,))
+    fi = _frame_index(ctx, frames)[0] if is_shared(frames) else None
+    fg = None if pool is None else _frame(ctx, frames, "mask_gt_observed", np.uint8)
+    return _ingest_bgr8(ctx, obs, _means_rgb(config), fi, fg=fg, use_bg=use_bg, bg_index=bg_index, pool=pool)
 
 
 def transform(im, pixel_means):

@@ -1,12 +1,12 @@
 """core/resident.ResidentObserved without a GPU: the budget, every refusal of the constructor (raised with ctx = None, before a
-device is touched), the rows a batch with synthetic positions reads, and that a plain dict holding a device array is still
-refused by both loaders."""
+device is touched), the rows a batch with synthetic positions reads, that the set and both loaders refuse a bad dict through
+one validator, and that a plain dict holding a device array is still refused by both loaders."""
 import numpy as np
 import pytest
 
 from mx_deepim_amd.config import default_config
 from mx_deepim_amd.core import loader as L
-from mx_deepim_amd.core.resident import ResidentObserved, batch_rows
+from mx_deepim_amd.core.resident import ResidentObserved, batch_rows, check_observed
 from mx_deepim_amd.runtime import DeviceArray
 
 H, W, M = 6, 10, 4
@@ -75,6 +75,43 @@ def test_rows_of_a_batch_with_synthetic_positions():
     rows, syn = batch_rows([15, 12], M, R)
     assert rows.tolist() == [M, M + 1] and syn.tolist() == [0, 1]
     assert L.batch_rows is batch_rows and L.ResidentObserved is ResidentObserved
+
+
+def test_one_validator_speaks_through_all_three_constructors():
+    """resident.check_observed is the only check of an observed dict: the set and both loaders refuse the same dict with the
+    same exception type and the same words, naming the key and what was expected, before a device is touched."""
+    obs = _observed()
+    keys = ["image_observed", "depth_gt_observed", "mask_gt_observed"]
+    cfg = default_config()
+    cfg.SCALES = [(H, W)]
+    cfg.TEST.FAST_TEST = False                        # the flow EPE: the test loader reads the three arrays too
+    assert L.observed_keys_of_test(cfg, list(obs)) == keys and not cfg.network.INPUT_DEPTH
+    pose = np.concatenate([np.eye(3), [[0.0], [0.0], [0.6]]], 1).astype(np.float32)
+    pairdb = [{"frame": 0, "gt_class": "ape", "mask_idx": 1, "pose_observed": pose, "pose_rendered": pose}]
+    constructors = (lambda o: ResidentObserved(o, None, keys=keys), lambda o: L.TrainDataLoader(o, cfg, Machine()),
+                    lambda o: L.TestDataLoader(o, pairdb, cfg, Machine()))
+    dev = DeviceArray(None, (M, H, W), np.uint8, ptr=4096)          # a view: nothing is allocated
+    cases = (
+        (dict(obs, depth_gt_observed=obs["depth_gt_observed"].astype(np.float32)), TypeError,
+         r"observed\['depth_gt_observed'\] is float32; the decoded uint16 frame is expected"),
+        (dict(obs, mask_gt_observed=obs["mask_gt_observed"][:M - 1]), ValueError,                     # unequal M
+         r"observed\['mask_gt_observed'\] has shape \(3, 6, 10\); \(4, 6, 10\) expected"),
+        (dict(obs, depth_gt_observed=obs["depth_gt_observed"][:, :, :W - 1]), ValueError,
+         r"observed\['depth_gt_observed'\] has shape \(4, 6, 9\); \(4, 6, 10\) expected"),
+        (dict(obs, image_observed=obs["image_observed"][..., :2]), ValueError,
+         r"observed\['image_observed'\] has shape \(4, 6, 10, 2\); \(M,H,W,3\) expected"),
+        (dict(obs, mask_gt_observed=dev), TypeError, r"observed\['mask_gt_observed'\] is a device array"),
+        ({k: v for k, v in obs.items() if k != "mask_gt_observed"}, KeyError, r"observed carries no 'mask_gt_observed'"),
+    )
+    for bad, exc, match in cases:
+        for construct in constructors:
+            with pytest.raises(exc, match=match):
+                construct(bad)
+    # an array no configuration asked for is not looked at, whatever it holds
+    stray = dict(obs, depth_observed=np.zeros((2, 2), np.float32))
+    assert list(check_observed(stray, keys)[0]) == keys and L.TestDataLoader(stray, pairdb, cfg, Machine()).keys == keys
+    with pytest.raises(ValueError, match="context"):
+        ResidentObserved(stray, None, keys=keys)
 
 
 def test_a_dict_with_a_device_array_is_still_a_type_error_in_both_loaders():
