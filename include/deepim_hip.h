@@ -525,6 +525,14 @@ int deepim_conv_f16_pack_weights(deepim_ctx* ctx, void* packed, const float* w /
 int deepim_conv2d_f16_forward(deepim_ctx* ctx, void* out_nhwc_f16, const void* in_nhwc_f16, const void* packed_w,
                               const float* bias, int B, int Cin_pad, int H, int W, int Cout, int kh, int kw,
                               int stride, int pad, float slope);
+/* The launch plan deepim_conv2d_f16_forward (x3 = 0) or deepim_conv2d_x3_forward (x3 = 1, Cin_pad = Cin there) gives a geometry under
+ * the context's options (ctx == NULL: the defaults). Host arithmetic, no device work; the launchers read the same plan. plan[0..7] =
+ * kernel (0 register-staged, 1 four-wave LDS-DMA, 2 eight-wave ping-pong), BM (output channels per tile), BN (pixels per tile), tiles,
+ * K chunks of 64, ksplit (uniform split-K slices, 1 = none), tail_s (K slices of each tile of the last, partly filled round, 0 = no
+ * tail split), R (tiles of that round, 0 without a tail split). Geometries a launch refuses return non-zero here too, and leave
+ * plan at -1 (an X3 batch of 2 GiB or more runs as consecutive sub-batches, each a launch of its own: ask for a sub-batch). */
+int deepim_conv_f16_plan(deepim_ctx* ctx, int x3, int B, int Cin_pad, int H, int W, int Cout, int kh, int kw, int stride, int pad,
+                         int* plan /*8, host*/);
 /* fp16 Winograd F(2x2,3x3) for the fp16 path's 3x3 stride-1 pad-1 layers (csrc/wino_f16.hip; network.FP16_WINOGRAD, default off):
  * the tensors of deepim_conv2d_f16_forward (NHWC fp16 in and out, fp32 bias, LeakyReLU), 2.25x fewer MFMAs. Its own arithmetic
  * contract, stated operation by operation at the top of csrc/wino_f16.hip and restated in numpy by tests/fp16_wino_emulation.py:

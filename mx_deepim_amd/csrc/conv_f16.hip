@@ -1655,10 +1655,11 @@ namespace {
 //   tail split ts:       floor(blocks / slots) · nchunk + ceil(R·ts / slots) · ceil(nchunk / ts) + reduce(R·ts),  R = blocks mod slots
 // reduce(n) = c0 + c1·n·(BM·BN/16384): fp32 partial tiles written and read once; deterministic, no timing involved. Returns
 // the uniform split factor; tail splits are considered only for a kernel that has them (ts != nullptr: *ts = slices, 0 = none).
-int f16_plan_split(const deepim_ctx* ctx, int blocks, int nchunk, int BM, int BN, int slots, float c0, float c1, int* ts = nullptr) {
+// max_split: the context's "conv_max_split" (0 auto, 1 off, n cap).
+int f16_plan_split(int max_split, int blocks, int nchunk, int BM, int BN, int slots, float c0, float c1, int* ts = nullptr) {
   int ks = 1;
   if (ts) *ts = 0;
-  if (ctx->conv_max_split != 1) {
+  if (max_split != 1) {
     float best = 1e30f;
     const float tile_w = (float)(BM * BN) / 16384.f;
     for (int s_ : {1, 2, 3, 4, 6, 8, 12, 16}) {
@@ -1668,7 +1669,7 @@ int f16_plan_split(const deepim_ctx* ctx, int blocks, int nchunk, int BM, int BN
       if (cost < best * 0.985f) { best = cost; ks = s_; }
     }
     const int R = blocks % slots;
-    if (ts && blocks > slots && R > 0 && ctx->conv_max_split == 0) {
+    if (ts && blocks > slots && R > 0 && max_split == 0) {
       for (int t_ : {2, 3, 4, 5, 6, 8}) {
         if (t_ > max(1, nchunk / 4)) continue;
         const float cost = (float)(blocks / slots) * (float)nchunk + (float)di_div_up(R * t_, slots) * (float)di_div_up(nchunk, t_) +
@@ -1677,33 +1678,86 @@ int f16_plan_split(const deepim_ctx* ctx, int blocks, int nchunk, int BM, int BN
       }
     }
   }
-  if (ctx->conv_max_split > 1) ks = min(ks, ctx->conv_max_split);
+  if (max_split > 1) ks = min(ks, max_split);
   return ks;
 }
 
-// Plan + launch of the LDS-DMA kernels (fp16 or X3): the 4-wave kernel on 128x64 wave tiles, two blocks per CU, or (pp, fp16
-// only) the ping-pong kernel, one 8-wave block per CU.
+// The launch plan of an fp16 (deepim_conv2d_f16_forward) or X3 (deepim_conv2d_x3_forward) convolution: kernel, tile and K slicing,
+// from the geometry and two context options alone (the same plan on every rank). The launchers and deepim_conv_f16_plan read it here.
+enum F16Kernel { F16_REG = 0, F16_DMA = 1, F16_PP = 2 };   // register-staged, four-wave LDS-DMA, eight-wave ping-pong
+struct F16Plan {
+  int kernel, BM, BN, gx, gy, blocks, nchunk;
+  long npix;
+  int ksplit, chunks_per_split;    // uniform split-K (ksplit == 1: none)
+  int n_full, tail_s, tail_cps;    // tail split (tail_s == 0: none): tiles [0, n_full) whole, blocks - n_full cut into tail_s slices
+};
+
+// Cv: fp16 channels per pixel (Cin_pad; X3: 2·Cin). max_split / dev_flags: the context's "conv_max_split" / "f16_dev_flags".
+F16Plan f16_plan(int max_split, int dev_flags, bool x3, int B, int Cv, int H, int W, int Cout, int kh, int kw, int stride, int pad) {
+  F16Plan q;
+  q.nchunk = f16_chunks(Cv, kh, kw);
+  q.npix = (long)B * ((H + 2 * pad - kh) / stride + 1) * ((W + 2 * pad - kw) / stride + 1);
+  q.BM = f16_bm(Cout);
+  float c0 = 1.5f, c1 = 0.009f;
+  if (x3) {
+    // 128x64 wave tiles; the plan model of the fp16 path with a chunk 1.5x as long (96 instead of 64 MFMAs per wave)
+    q.kernel = F16_DMA;
+    q.BN = q.BM == 256 ? 128 : 256;
+    c0 = 1.0f; c1 = 0.006f;
+  } else {
+    const bool ut = ((Cv >> 3) & 7) == 0;
+    q.BN = f16_bn(Cout, ut);
+    // register-staged kernel (Cout <= 64, or Cin_pad % 64 != 0): one 256-thread block per CU (the LDS double buffer and the 256
+    // accumulator registers leave room for one), uniform split-K only
+    q.kernel = ut && q.BM >= 128 ? F16_DMA : F16_REG;
+    // Ping-pong kernel (one 8-wave block per CU, 256x256 / 128x512 tiles) from DI_F16_PP_MIN_TILES tiles on: conv2 … conv5_1 at
+    // B = 32, conv2 … conv4_1 at B = 8 (150-tile layers run 1.2x faster on it than on the 4-wave kernel even half filled). Smaller
+    // grids keep the 4-wave kernel on 256x128 tiles (two blocks per CU: twice the blocks for the same split factor). Fixed by the
+    // geometry: the same plan on every rank.
+    if (q.kernel == F16_DMA && (Cout % 128) == 0 && !(dev_flags & DI_F16_NO_PP)) {
+      const int bn_pp = q.BM == 256 ? 256 : 512;
+      const long tiles_pp = (long)di_div_up(q.npix, bn_pp) * di_div_up(Cout, q.BM);
+      if (tiles_pp >= DI_F16_PP_MIN_TILES) { q.kernel = F16_PP; q.BN = bn_pp; }
+    }
+  }
+  q.gx = di_div_up(q.npix, q.BN); q.gy = di_div_up(Cout, q.BM);
+  q.blocks = q.gx * q.gy;
+  const int slots = q.kernel == F16_DMA ? 512 : 256;   // resident blocks on the chip
+  int ts = 0;
+  const int ks = f16_plan_split(max_split, q.blocks, q.nchunk, q.BM, q.BN, slots, c0, c1, q.kernel == F16_REG ? nullptr : &ts);
+  q.chunks_per_split = di_div_up(q.nchunk, ks);
+  q.ksplit = di_div_up(q.nchunk, q.chunks_per_split);
+  q.n_full = 0; q.tail_s = 0; q.tail_cps = 0;
+  if (q.ksplit == 1 && ts > 1) {
+    q.n_full = q.blocks - q.blocks % slots;
+    q.tail_cps = di_div_up(q.nchunk, ts);
+    q.tail_s = di_div_up(q.nchunk, q.tail_cps);
+  }
+  return q;
+}
+
+inline F16Plan f16_plan(const deepim_ctx* ctx, bool x3, int B, int Cv, int H, int W, int Cout, int kh, int kw, int stride, int pad) {
+  return f16_plan(ctx ? ctx->conv_max_split : 0, ctx ? ctx->f16_dev_flags : 0, x3, B, Cv, H, W, Cout, kh, kw, stride, pad);
+}
+
+// Launch of a plan on the LDS-DMA kernels (fp16 or X3): the 4-wave kernel on 128x64 wave tiles, two blocks per CU, or (fp16 only)
+// the ping-pong kernel, one 8-wave block per CU.
 template <bool X3>
-int launch_f16_dma(deepim_ctx* ctx, ConvF16Params p, int BM, int BN, float c0, float c1, bool pp = false) {
-  const int blocks = p.gx * p.gy;
-  const int slots = pp ? 256 : 512;   // resident blocks on the chip
-  int ts;
-  const int ks = f16_plan_split(ctx, blocks, p.nchunk, BM, BN, slots, c0, c1, &ts);
-  p.chunks_per_split = di_div_up(p.nchunk, ks);
-  p.ksplit = di_div_up(p.nchunk, p.chunks_per_split);
+int launch_f16_dma(deepim_ctx* ctx, ConvF16Params p, const F16Plan& q) {
+  const int blocks = q.blocks, BM = q.BM, BN = q.BN;
+  const bool pp = q.kernel == F16_PP;
+  p.chunks_per_split = q.chunks_per_split;
+  p.ksplit = q.ksplit;
   p.partial = nullptr;
-  p.n_full = 0; p.tail_s = 0; p.tail_cps = 0; p.tail_partial = nullptr;
+  p.n_full = q.n_full; p.tail_s = q.tail_s; p.tail_cps = q.tail_cps; p.tail_partial = nullptr;
   int grid = blocks * p.ksplit;
   if (p.ksplit > 1) {
     void* scratch;
     int rc = deepim_scratch(ctx, (size_t)p.ksplit * p.npix * p.Cout * sizeof(float), &scratch);
     if (rc) return rc;
     p.partial = (float*)scratch;
-  } else if (ts > 1) {
-    const int R = blocks % slots;
-    p.n_full = blocks - R;
-    p.tail_cps = di_div_up(p.nchunk, ts);
-    p.tail_s = di_div_up(p.nchunk, p.tail_cps);
+  } else if (p.tail_s > 1) {
+    const int R = blocks - p.n_full;
     void* scratch;
     int rc = deepim_scratch(ctx, (size_t)p.tail_s * R * BM * BN * sizeof(float), &scratch);
     if (rc) return rc;
@@ -1788,31 +1842,15 @@ extern "C" int deepim_conv2d_f16_forward(deepim_ctx* ctx, void* out_nhwc_f16, co
     ctx->conv_tabs.push_back({2, Cin_pad, kh, kw, H, W, (void*)tab});
   }
   p.tab = tab;
-  const bool ut = ((Cin_pad >> 3) & 7) == 0;
-  const int BM = f16_bm(Cout);
-  int BN = f16_bn(Cout, ut);
   p.n_full = 0; p.tail_s = 0; p.tail_cps = 0; p.tail_partial = nullptr; p.acc_scale = p.out_scale = 1.f; p.status = ctx->status;
-  // Ping-pong kernel (one 8-wave block per CU, 256x256 / 128x512 tiles) from DI_F16_PP_MIN_TILES tiles on: conv2 … conv5_1 at
-  // B = 32, conv2 … conv4_1 at B = 8 (150-tile layers run 1.2x faster on it than on the 4-wave kernel even half filled). Smaller
-  // grids keep the 4-wave kernel on 256x128 tiles (two blocks per CU: twice the blocks for the same split factor). Fixed by the
-  // geometry: the same plan on every rank.
-  if (ut && BM >= 128 && (Cout % 128) == 0 && !(ctx->f16_dev_flags & DI_F16_NO_PP)) {
-    const int bn_pp = BM == 256 ? 256 : 512;
-    const long tiles_pp = (long)di_div_up(p.npix, bn_pp) * di_div_up(Cout, BM);
-    if (tiles_pp >= DI_F16_PP_MIN_TILES) {
-      BN = bn_pp;
-      p.gx = di_div_up(p.npix, BN); p.gy = di_div_up(Cout, BM);
-      return launch_f16_dma<false>(ctx, p, BM, BN, 1.5f, 0.009f, true);
-    }
-  }
-  p.gx = di_div_up(p.npix, BN); p.gy = di_div_up(Cout, BM);
-  if (ut && BM >= 128) return launch_f16_dma<false>(ctx, p, BM, BN, 1.5f, 0.009f);
-  // register-staged kernel (Cout <= 64, or Cin_pad % 64 != 0): one 256-thread block per CU (the LDS double buffer and the 256
-  // accumulator registers leave room for one), uniform split-K only
-  const int blocks = p.gx * p.gy;
-  const int ks = f16_plan_split(ctx, blocks, p.nchunk, BM, BN, 256, 1.5f, 0.009f);
-  p.chunks_per_split = di_div_up(p.nchunk, ks);
-  p.ksplit = di_div_up(p.nchunk, p.chunks_per_split);
+  const F16Plan q = f16_plan(ctx, false, B, Cin_pad, H, W, Cout, kh, kw, stride, pad);
+  const int BM = q.BM, BN = q.BN, blocks = q.blocks;
+  p.gx = q.gx; p.gy = q.gy;
+  if (q.kernel != F16_REG) return launch_f16_dma<false>(ctx, p, q);
+  // register-staged kernel
+  const bool ut = ((Cin_pad >> 3) & 7) == 0;
+  p.chunks_per_split = q.chunks_per_split;
+  p.ksplit = q.ksplit;
   p.partial = nullptr;
   if (p.ksplit > 1) {
     void* scratch;
@@ -1939,10 +1977,28 @@ extern "C" int deepim_conv2d_x3_forward(deepim_ctx* ctx, void* out_split16, cons
   const size_t in_bytes = (size_t)B * H * W * Cv * 2;
   DI_REQUIRE(in_bytes + p.pad_bytes < 0x7fffffffUL, "conv2d_x3: input tensor must be < 2 GiB per launch");
   p.in_bytes = (unsigned)in_bytes;
-  const int BM = f16_bm(Cout), BN = BM == 256 ? 128 : 256;   // 128x64 wave tiles
-  p.gx = di_div_up(p.npix, BN); p.gy = di_div_up(Cout, BM);
-  // the plan model of the fp16 path with a chunk 1.5x as long (96 instead of 64 MFMAs per wave)
-  return launch_f16_dma<true>(ctx, p, BM, BN, 1.0f, 0.006f);
+  const F16Plan q = f16_plan(ctx, true, B, Cv, H, W, Cout, kh, kw, stride, pad);
+  p.gx = q.gx; p.gy = q.gy;
+  return launch_f16_dma<true>(ctx, p, q);
+}
+
+extern "C" int deepim_conv_f16_plan(deepim_ctx* ctx, int x3, int B, int Cin_pad, int H, int W, int Cout, int kh, int kw, int stride,
+                                    int pad, int* plan) {
+  DI_REQUIRE(plan != nullptr, "conv_f16_plan: null plan");
+  for (int i = 0; i < 8; ++i) plan[i] = -1;
+  DI_REQUIRE(B >= 1 && H >= 1 && W >= 1 && Cout >= 1 && kh >= 1 && kw >= 1 && stride >= 1 && pad >= 0 && H + 2 * pad >= kh &&
+                 W + 2 * pad >= kw,
+             "conv_f16_plan: empty geometry");
+  DI_REQUIRE(kh <= 7 && kw <= 7, "conv_f16_plan: kernel larger than 7 not supported");
+  if (x3) DI_REQUIRE((Cin_pad & 31) == 0 && (Cout & 127) == 0, "conv_f16_plan: x3 needs Cin % 32 == 0 and Cout % 128 == 0");
+  else DI_REQUIRE((Cin_pad & 7) == 0 && (Cout & 3) == 0, "conv_f16_plan: Cin_pad % 8 and Cout % 4 must be 0");
+  const int Cv = x3 ? 2 * Cin_pad : Cin_pad;
+  DI_REQUIRE((size_t)B * H * W * Cv * 2 + (size_t)(pad * W + pad) * Cv * 2 < 0x7fffffffUL,
+             "conv_f16_plan: input tensor must be < 2 GiB per launch");
+  const F16Plan q = f16_plan(ctx, x3 != 0, B, Cv, H, W, Cout, kh, kw, stride, pad);
+  const int out[8] = {q.kernel, q.BM, q.BN, q.blocks, q.nchunk, q.ksplit, q.tail_s, q.tail_s > 1 ? q.blocks - q.n_full : 0};
+  for (int i = 0; i < 8; ++i) plan[i] = out[i];
+  return 0;
 }
 
 extern "C" size_t deepim_conv1_x3_packed_size(void) { return (size_t)2 * C1_WH * 16; }

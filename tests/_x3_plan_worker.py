@@ -1,6 +1,8 @@
 """Worker of tests/test_gpu_x3.py::test_x3_and_fp16_plans_do_not_depend_on_the_process_environment: runs the x3 and fp16 conv
-kernels on fixed seeded inputs (layers that take the tail split, the split-K and the whole-tile plans) and prints one sha256
-over all output bytes. Launched twice with different environments (the tiling switches of round 2 were environment variables)."""
+kernels on fixed seeded inputs and prints one sha256 over all output bytes. Plans (deepim_conv_f16_plan): x3 takes a tail split on the
+first and the last layer and uniform split-K on the others; plain fp16 takes the register-staged kernel whole on the first (Cin 32),
+the four-wave kernel with split-K on the next three and the ping-pong kernel with a tail split on the last. Launched twice with different environments (the tiling switches of round 2 were environment
+variables)."""
 import ctypes
 import hashlib
 import os
@@ -17,7 +19,7 @@ h = ctx.handle
 sha = hashlib.sha256()
 rng = np.random.default_rng(31)
 for (B, cin, H, W, cout, k, s, p) in [(4, 32, 120, 160, 256, 3, 1, 1), (2, 256, 15, 20, 512, 3, 2, 1), (3, 1024, 8, 10, 1024, 3, 1, 1),
-                                      (2, 64, 60, 80, 128, 5, 2, 2)]:
+                                      (2, 64, 60, 80, 128, 5, 2, 2), (1, 64, 132, 256, 512, 3, 1, 1)]:
     x = rng.standard_normal((B, cin, H, W)).astype(np.float32)
     w = (rng.standard_normal((cout, cin, k, k)) / np.sqrt(cin * k * k)).astype(np.float32)
     b = rng.standard_normal(cout).astype(np.float32)

@@ -37,7 +37,8 @@ def _conv_f16(ctx, x, w, b, s, p, slope):
 
 @pytest.mark.parametrize("case", [(2, 8, 96, 128, 64, 7, 2, 3), (1, 64, 60, 80, 128, 5, 2, 2), (2, 24, 15, 20, 256, 3, 1, 1),
                                   (2, 5, 9, 11, 68, 3, 1, 1), (1, 128, 30, 40, 512, 3, 2, 1), (3, 1024, 8, 10, 1024, 3, 1, 1),
-                                  (4, 64, 120, 160, 256, 3, 1, 1)])   # last: 300 tiles → tail split of the DMA kernel
+                                  (4, 64, 120, 160, 256, 3, 1, 1)])   # last: 300 tiles of 256x256 on the ping-pong kernel, no K slicing
+                                                                       # (9 K chunks: the plan model rejects the tail split; tail splits: test_gpu_fp16_plans.py)
 def test_conv_f16_matches_emulation(ctx, case):
     B, cin, H, W, cout, k, s, p = case
     rng = np.random.default_rng(sum(case))
@@ -55,7 +56,7 @@ def test_conv_f16_matches_emulation(ctx, case):
                                   (6, 64, 240, 320, 128, 5, 2, 2),      # conv2's geometry: 225 tiles of 128x512 (Cout = 128)
                                   (1, 128, 231, 233, 512, 3, 1, 1),     # two M tiles, ragged last pixel tile, odd frame
                                   (13, 128, 120, 160, 256, 5, 2, 2),    # conv3's geometry: stride 2, 5x5, 100 stages
-                                  (4, 64, 120, 160, 256, 3, 1, 1)])     # 300 tiles: 256 whole + a tail split of 44
+                                  (4, 64, 120, 160, 256, 3, 1, 1)])     # 300 tiles in two rounds, the second of 44: no tail split (rejected at 9 K chunks)
 def test_conv_f16_pingpong_kernel(ctx, case):
     """conv_f16_pp_kernel (round 4: one 8-wave block per CU, the two waves of a SIMD alternating between fragment reads + LDS-DMA
     issue and the MFMAs, 4- / 5-stage ring with counted vmcnt) on grids of >= 200 tiles: against the fp16 emulation (<= 1 fp16 ulp),
