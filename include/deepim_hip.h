@@ -965,6 +965,12 @@ int deepim_lrelu_bias_backward_x3(deepim_ctx* ctx, void* dz_split16, float* db, 
  * (Cout,k*k,Cin), as deepim_conv2d_wgrad_f16. Cin % 16 == 0, Cout % 16 == 0 (whole records). */
 int deepim_conv2d_wgrad_x3(deepim_ctx* ctx, float* dw, const void* x_split16, const void* dz_split16, unsigned* state, int B, int Cin,
                            int H, int W, int Cout, int k, int stride, int pad, int layout, float x_scale);
+/* The launch plan deepim_conv2d_wgrad_f16 (x3 = 0) or deepim_conv2d_wgrad_x3 (x3 = 1, Cin_pad = Cin there) gives a geometry. Host
+ * arithmetic from the geometry alone, no context and no device work; the launcher reads the same plan. plan[0..5] = m-tiles (128
+ * output channels each), n-tiles (128 GEMM columns of k*k*Cin_pad each), k-steps (32 pixels each), S (split-K slices, 1 = direct
+ * store), steps_per_split (the last slice may be shorter), 1 if B*Ho*Wo % 32 != 0 (a ragged last k-step) else 0. Geometries the
+ * entry point of the mode refuses return non-zero here too, and leave plan at -1. */
+int deepim_conv_wgrad_half_plan(int x3, int B, int Cin_pad, int H, int W, int Cout, int k, int stride, int pad, int* plan /*6, host*/);
 /* Split-fp16 weights of the convolution that is the data gradient of layer (Co_l, Ci_l, k, k), in deepim_conv2d_x3_forward's packed
  * order (Cout = Ci_l, Cin = Co_l, kernel nky x nkx; deepim_conv_x3_packed_size(Ci_l, Co_l, nky, nkx) bytes): tap (a, b) =
  * split(layer tap (ky0 + st (nky-1-a), kx0 + st (nkx-1-b)), w_scale). With st = 1 and the full kernel it equals

@@ -347,29 +347,57 @@ template <bool X3> __global__ __launch_bounds__(256) void wgrad_reduce_kernel(Wg
   wgrad_store<X3>(p, (int)(i / p.N), (int)(i % p.N), s);
 }
 
+// The launch plan of a weight gradient, from the geometry alone (the same in both modes: N counts real channels, x3's Cin_pad = Cin).
+// launch_wgrad and deepim_conv_wgrad_half_plan read it here.
+struct WgPlan { int Ho, Wo, N, tiles_m, tiles_n, ksteps, S, steps_per_split; long npix; };
+WgPlan wgrad_plan(int B, int Cin_pad, int H, int W, int Cout, int k, int stride, int pad) {
+  WgPlan q;
+  q.Ho = (H + 2 * pad - k) / stride + 1; q.Wo = (W + 2 * pad - k) / stride + 1;
+  q.N = k * k * Cin_pad;
+  q.npix = (long)B * q.Ho * q.Wo;
+  q.ksteps = (int)di_div_up(q.npix, (long)WG_BK);
+  q.tiles_m = di_div_up(Cout, WG_BM);
+  q.tiles_n = di_div_up(q.N, WG_BN);
+  // fixed slices from the geometry alone: about 512 blocks, never an empty slice
+  const int S = std::max(1, std::min(q.ksteps, di_div_up(512, q.tiles_m * q.tiles_n)));
+  q.steps_per_split = di_div_up(std::max(q.ksteps, 1), S);
+  q.S = di_div_up(std::max(q.ksteps, 1), q.steps_per_split);
+  return q;
+}
+
+// what both modes ask of a weight gradient's geometry beyond their channel rules: WG_OK, or the reason it is refused
+enum { WG_OK = 0, WG_EMPTY, WG_TOO_LARGE };
+int wgrad_refusal(bool x3, int B, int Cin_pad, int H, int W, int Cout, int k, int stride, int pad) {
+  if (!(B >= 0 && H >= 1 && W >= 1 && stride >= 1 && pad >= 0 && H + 2 * pad >= k && W + 2 * pad >= k)) return WG_EMPTY;
+  const size_t ebytes = x3 ? 4 : 2;
+  const size_t Ho = (H + 2 * pad - k) / stride + 1, Wo = (W + 2 * pad - k) / stride + 1;
+  const size_t xb = (size_t)B * H * W * Cin_pad * ebytes, zb = (size_t)B * Ho * Wo * Cout * ebytes;
+  return xb < 0x7fffffffUL && zb < 0x7fffffffUL ? WG_OK : WG_TOO_LARGE;
+}
+
 // the caller has checked the channel counts of its mode; x_scale: the scale x was stored at (fp16: 1)
 template <bool X3>
 int launch_wgrad(deepim_ctx* ctx, float* dw, const void* x, const void* dz, unsigned* state, int B, int Cin, int Cin_pad, int H, int W,
                  int Cout, int k, int stride, int pad, int layout, float x_scale) {
+  const int why = wgrad_refusal(X3, B, Cin_pad, H, W, Cout, k, stride, pad);
+  DI_REQUIRE(why != WG_EMPTY, HALF_MSG("conv2d_wgrad", "no output pixel: H + 2 pad < k, or stride < 1"));
+  DI_REQUIRE(why != WG_TOO_LARGE, HALF_MSG("conv2d_wgrad", "operands must be < 2 GiB"));
+  const WgPlan q = wgrad_plan(B, Cin_pad, H, W, Cout, k, stride, pad);
   WgradParams p;
   p.x = (const _Float16*)x; p.dz = (const _Float16*)dz; p.dw = dw; p.state = state;
   p.Cin = Cin; p.Cin_pad = Cin_pad; p.H = H; p.W = W; p.Cout = Cout; p.k = k; p.stride = stride; p.pad = pad;
-  p.Ho = (H + 2 * pad - k) / stride + 1; p.Wo = (W + 2 * pad - k) / stride + 1;
+  p.Ho = q.Ho; p.Wo = q.Wo;
   p.layout = layout ? 1 : 0;
-  p.N = k * k * Cin_pad;
-  p.npix = (long)B * p.Ho * p.Wo;
+  p.N = q.N;
+  p.npix = q.npix;
   p.unscale = 1.f / x_scale;
   constexpr size_t ebytes = 2 * WgImage<X3>::HALVES;
-  const size_t xb = (size_t)B * H * W * Cin_pad * ebytes, zb = (size_t)p.npix * Cout * ebytes;
-  DI_REQUIRE(xb < 0x7fffffffUL && zb < 0x7fffffffUL, HALF_MSG("conv2d_wgrad", "operands must be < 2 GiB"));
-  p.x_bytes = (unsigned)xb; p.dz_bytes = (unsigned)zb;
-  p.ksteps = (int)di_div_up(p.npix, (long)WG_BK);
-  p.tiles_n = di_div_up(p.N, WG_BN);
-  const int tiles = di_div_up(Cout, WG_BM) * p.tiles_n;
-  // fixed slices from the geometry alone: about 512 blocks, never an empty slice
-  int S = std::max(1, std::min(p.ksteps, di_div_up(512, tiles)));
-  p.steps_per_split = di_div_up(std::max(p.ksteps, 1), S);
-  p.S = di_div_up(std::max(p.ksteps, 1), p.steps_per_split);
+  p.x_bytes = (unsigned)((size_t)B * H * W * Cin_pad * ebytes); p.dz_bytes = (unsigned)((size_t)p.npix * Cout * ebytes);
+  p.ksteps = q.ksteps;
+  p.tiles_n = q.tiles_n;
+  const int tiles = q.tiles_m * q.tiles_n;
+  p.steps_per_split = q.steps_per_split;
+  p.S = q.S;
   p.partial = nullptr;
   if (p.S > 1) {
     void* scratch;
@@ -572,6 +600,24 @@ extern "C" int deepim_conv2d_wgrad_x3(deepim_ctx* ctx, float* dw, const void* x_
              "conv2d_wgrad_x3: Cin % 16 and Cout % 16 must be 0 (whole split16 records), k <= 7");
   DI_REQUIRE(x_scale > 0.f, "conv2d_wgrad_x3: x_scale must be positive");
   return launch_wgrad<true>(ctx, dw, x_split16, dz_split16, state, B, Cin, Cin, H, W, Cout, k, stride, pad, layout, x_scale);
+}
+
+extern "C" int deepim_conv_wgrad_half_plan(int x3, int B, int Cin_pad, int H, int W, int Cout, int k, int stride, int pad, int* plan) {
+  DI_REQUIRE(plan != nullptr, "conv_wgrad_half_plan: null plan");
+  for (int i = 0; i < 6; ++i) plan[i] = -1;
+  if (x3)
+    DI_REQUIRE(Cin_pad > 0 && Cin_pad % 16 == 0 && Cout > 0 && Cout % 16 == 0 && k >= 1 && k <= 7,
+               "conv_wgrad_half_plan: x3 needs Cin % 16 and Cout % 16 == 0 (whole split16 records), k <= 7");
+  else
+    DI_REQUIRE(Cin_pad > 0 && Cin_pad % 8 == 0 && Cout > 0 && Cout % 8 == 0 && k >= 1 && k <= 7,
+               "conv_wgrad_half_plan: Cin_pad % 8, Cout % 8 must be 0, k <= 7");
+  const int why = wgrad_refusal(x3 != 0, B, Cin_pad, H, W, Cout, k, stride, pad);
+  DI_REQUIRE(why != WG_EMPTY, "conv_wgrad_half_plan: no output pixel: H + 2 pad < k, or stride < 1");
+  DI_REQUIRE(why != WG_TOO_LARGE, "conv_wgrad_half_plan: operands must be < 2 GiB");
+  const WgPlan q = wgrad_plan(B, Cin_pad, H, W, Cout, k, stride, pad);
+  const int out[6] = {q.tiles_m, q.tiles_n, q.ksteps, q.S, q.steps_per_split, q.npix % WG_BK != 0 ? 1 : 0};
+  for (int i = 0; i < 6; ++i) plan[i] = out[i];
+  return 0;
 }
 
 extern "C" size_t deepim_conv_dgrad_f16_workspace_size(int B, int Ci_l, int Hd, int Wd, int Co_l, int k, int stride, int pad) {

@@ -7,7 +7,10 @@ reach every branch of the kernels and their launchers, and every gradient of one
 tests/test_gpu_train_half_digests.py recomputes every digest with the tree's own library. The entry points are deterministic (fixed
 slices, sums in a fixed order), so a digest moves only when a result bit moves: the file is regenerated only for a change that means
 to alter the arithmetic, and its diff then names the cases that moved. The committed file was recorded with the library of the commit
-before the two modes' sources were merged, so it also pins the merged kernels to the separate ones bit for bit."""
+before the two modes' sources were merged, so it also pins the merged kernels to the separate ones bit for bit.
+
+A digest pins bits; it does not say they are right. tests/train_half_cases.py takes WGRAD, LRELU, DGRAD and DGRAD_CH from here and
+tests/test_gpu_train_half_edges.py checks every one of these shapes against a float64 reference."""
 import collections
 import ctypes
 import hashlib
