@@ -614,16 +614,25 @@ int deepim_deconv_f16_pack_weights(deepim_ctx* ctx, void* packed, const float* w
 int deepim_deconv4x4s2_crop_f16_forward(deepim_ctx* ctx, void* out_nhwc_f16, const void* in_nhwc_f16, const void* packed_w,
                                         const float* bias, int B, int Cin_pad, int in_ctotal, int H, int W, int Cout, int Ho,
                                         int Wo, float slope, int out_ctotal, int out_coff);
+/* The launch plan deepim_deconv4x4s2_crop_f16_forward gives a geometry: host arithmetic, no context, no device; the launcher reads the
+ * same plan. plan[0..7] = block tiles of all four parity classes, pixels (all images) of class 0..3 (class = 2·(oy % 2) + ox % 2),
+ * k-steps of 16 (= Cin_pad / 4), ksplit (K slices, 1 = none), k-steps per slice (the last slice may hold fewer). Geometries the
+ * launcher refuses for B, Cin_pad, H, W, Cout, Ho or Wo (an empty batch included) return non-zero and leave plan at -1. */
+int deepim_deconv_f16_plan(int B, int Cin_pad, int H, int W, int Cout, int Ho, int Wo, int* plan /*8, host*/);
 /* Few-filter 3x3 stride-1 pad-1 Convolution + bias (Convolution1 / 2 / 3, mask_conv3) from an NHWC fp16 input into fp32 NCHW: up to
  * 3 filters in one pass over the input, n0 of them into out0 (B,n0,H,W), n1 into out1 (B,n1,H,W) (n1 = 0, out1 = NULL: one tensor).
  * fp16 weights x fp16 activations (products exact), fp32 sums, fp32 bias. w0 (n0,Cin,3,3), w1 (n1,Cin,3,3) fp32 → packed
- * (deepim_fewout_f16_packed_size bytes); Cin_pad % 8 == 0, at most 2048. */
+ * (deepim_fewout_f16_packed_size bytes); Cin_pad % 8 == 0, above 0 and at most 2048; H, W > 0 (B = 0: nothing to do). */
 size_t deepim_fewout_f16_packed_size(int Cin_pad);
 int deepim_fewout_f16_pack_weights(deepim_ctx* ctx, void* packed, const float* w0, int n0, const float* w1, int n1, int Cin,
                                    int Cin_pad);
 int deepim_conv3x3_fewout_f16_forward(deepim_ctx* ctx, float* out0, int n0, float* out1, int n1, const void* in_nhwc_f16,
                                       const void* packed_w, const float* bias0, const float* bias1, int B, int H, int W,
                                       int in_ctotal, int Cin_pad);
+/* The launch plan deepim_conv3x3_fewout_f16_forward gives a geometry (host arithmetic; the launcher reads the same plan): plan[0..3] =
+ * threads per block (one per input octet, in whole waves), columns per row segment, segments per row, waves per block. B, H, W or
+ * Cin_pad of 0, Cin_pad % 8 != 0 and Cin_pad > 2048 return non-zero, as in the launcher, and leave plan at -1. */
+int deepim_fewout_f16_plan(int B, int H, int W, int Cin_pad, int* plan /*4, host*/);
 /* upsample_flow6to5 / 5to4: Deconvolution k4 s2 (2 → 2 channels) + bias + Crop(1,1) of an fp32 NCHW flow (B,2,H,W) in fp32,
  * rounded once into channels [out_coff, out_coff + 2) of an NHWC fp16 output (Ho,Wo); w (2,2,4,4) fp32 as stored */
 int deepim_upsample_flow_f16_forward(deepim_ctx* ctx, void* out_nhwc_f16, const float* in, const float* w, const float* bias,

@@ -358,6 +358,49 @@ int deconv_f16_split(int tiles, int nsteps) {
   return std::max(1, s);
 }
 
+// The launch plan of the deconvolution, from the geometry alone: the launcher and deepim_deconv_f16_plan both read it here.
+struct DeconvF16Plan {
+  int rows[2], cols[2], npix[4], tile_base[5];
+  int nsteps, ksplit, steps_per_split;
+};
+
+int deconv_f16_plan(int B, int Cin_pad, int H, int W, int Cout, int Ho, int Wo, DeconvF16Plan& q) {
+  DI_REQUIRE(B > 0, "deconv_f16: empty batch");
+  DI_REQUIRE((Cout & 63) == 0 && Cout > 0 && (Cin_pad & 7) == 0 && Cin_pad > 0,
+             "deconv_f16: needs Cout % 64 == 0 and Cin_pad % 8 == 0");
+  DI_REQUIRE(Ho <= 2 * H && Wo <= 2 * W && Ho > 0 && Wo > 0, "deconv_f16: Ho <= 2H, Wo <= 2W (crop 1,1 of the 2H+2 x 2W+2 output)");
+  q.nsteps = Cin_pad / 4;
+  for (int k = 0; k < 2; ++k) { q.rows[k] = (Ho - k + 1) / 2; q.cols[k] = (Wo - k + 1) / 2; }
+  const int MT = di_div_up(Cout, DC_BM);
+  q.tile_base[0] = 0;
+  for (int c = 0; c < 4; ++c) {
+    q.npix[c] = B * q.rows[c >> 1] * q.cols[c & 1];
+    q.tile_base[c + 1] = q.tile_base[c] + MT * di_div_up(q.npix[c], DC_BN);
+  }
+  q.ksplit = deconv_f16_split(q.tile_base[4], q.nsteps);
+  q.steps_per_split = di_div_up(q.nsteps, q.ksplit);
+  q.ksplit = di_div_up(q.nsteps, q.steps_per_split);
+  return 0;
+}
+
+// The launch plan of the few-filter kernel: one thread per input octet in whole waves; row segments of up to 64 columns, rows split
+// further (up to 4 segments) until ~1024 blocks run. The launcher and deepim_fewout_f16_plan both read it here.
+struct FewoutF16Plan { int threads, seg, nseg, waves; };
+
+int fewout_f16_plan(int B, int H, int W, int Cin_pad, FewoutF16Plan& q) {
+  DI_REQUIRE(B > 0 && H > 0 && W > 0, "conv3x3_fewout_f16: empty input (B, H, W > 0)");
+  DI_REQUIRE((Cin_pad & 7) == 0 && Cin_pad > 0 && Cin_pad <= 8 * 64 * FO_MAXWAVES,
+             "conv3x3_fewout_f16: Cin_pad % 8 == 0, 0 < Cin_pad <= 2048");
+  const int rows = B * H;
+  int nseg = std::max(di_div_up(W, FO_MAXSEG), std::min(4, di_div_up(1024, rows)));
+  nseg = std::min(nseg, W);
+  q.seg = di_div_up(W, nseg);
+  q.nseg = di_div_up(W, q.seg);
+  q.waves = di_div_up(Cin_pad / 8, 64);
+  q.threads = 64 * q.waves;
+  return 0;
+}
+
 }  // namespace
 
 extern "C" size_t deepim_deconv_f16_packed_size(int Cin_pad, int Cout) {
@@ -382,29 +425,22 @@ extern "C" int deepim_deconv4x4s2_crop_f16_forward(deepim_ctx* ctx, void* out_nh
                                                    int out_coff) {
   DI_DEVICE(ctx);
   if (B == 0) return 0;
-  DI_REQUIRE((Cout & 63) == 0 && (Cin_pad & 7) == 0 && Cin_pad > 0, "deconv_f16: needs Cout % 64 == 0 and Cin_pad % 8 == 0");
+  DeconvF16Plan q;
+  if (int rc = deconv_f16_plan(B, Cin_pad, H, W, Cout, Ho, Wo, q)) return rc;
   DI_REQUIRE((in_ctotal & 7) == 0 && Cin_pad <= in_ctotal, "deconv_f16: in_ctotal % 8 == 0 and Cin_pad <= in_ctotal");
-  DI_REQUIRE((out_ctotal & 3) == 0 && (out_coff & 3) == 0 && out_coff + Cout <= out_ctotal,
+  DI_REQUIRE((out_ctotal & 3) == 0 && (out_coff & 3) == 0 && out_coff >= 0 && out_coff + Cout <= out_ctotal,
              "deconv_f16: out_ctotal, out_coff % 4 == 0 and the slice inside the output record");
-  DI_REQUIRE(Ho <= 2 * H && Wo <= 2 * W && Ho > 0 && Wo > 0, "deconv_f16: Ho <= 2H, Wo <= 2W (crop 1,1 of the 2H+2 x 2W+2 output)");
   DI_REQUIRE((long)B * H * W * in_ctotal < (1L << 31), "deconv_f16: input must hold < 2^31 halves");
   DeconvF16Params p;
   p.in = (const _Float16*)in_nhwc_f16; p.wp = (const h8*)packed_w; p.bias = bias; p.out = (_Float16*)out_nhwc_f16;
   p.partial = nullptr;
   p.B = B; p.H = H; p.W = W; p.Cin_pad = Cin_pad; p.in_ctotal = in_ctotal; p.Cout = Cout; p.Ho = Ho; p.Wo = Wo;
   p.out_ctotal = out_ctotal; p.out_coff = out_coff; p.slope = slope;
-  p.nsteps = Cin_pad / 4;
-  for (int q = 0; q < 2; ++q) { p.rows[q] = (Ho - q + 1) / 2; p.cols[q] = (Wo - q + 1) / 2; }
-  const int MT = di_div_up(Cout, DC_BM);
-  p.tile_base[0] = 0;
-  for (int c = 0; c < 4; ++c) {
-    p.npix[c] = B * p.rows[c >> 1] * p.cols[c & 1];
-    p.tile_base[c + 1] = p.tile_base[c] + MT * di_div_up(p.npix[c], DC_BN);
-  }
+  p.nsteps = q.nsteps; p.ksplit = q.ksplit; p.steps_per_split = q.steps_per_split;
+  for (int k = 0; k < 2; ++k) { p.rows[k] = q.rows[k]; p.cols[k] = q.cols[k]; }
+  for (int c = 0; c < 4; ++c) p.npix[c] = q.npix[c];
+  for (int c = 0; c < 5; ++c) p.tile_base[c] = q.tile_base[c];
   const int tiles = p.tile_base[4];
-  p.ksplit = deconv_f16_split(tiles, p.nsteps);
-  p.steps_per_split = di_div_up(p.nsteps, p.ksplit);
-  p.ksplit = di_div_up(p.nsteps, p.steps_per_split);
   const long npix_out = (long)B * Ho * Wo;
   if (p.ksplit > 1) {
     void* scratch;
@@ -423,6 +459,16 @@ extern "C" int deepim_deconv4x4s2_crop_f16_forward(deepim_ctx* ctx, void* out_nh
   return 0;
 }
 
+extern "C" int deepim_deconv_f16_plan(int B, int Cin_pad, int H, int W, int Cout, int Ho, int Wo, int* plan) {
+  DI_REQUIRE(plan != nullptr, "deconv_f16_plan: null plan");
+  for (int i = 0; i < 8; ++i) plan[i] = -1;
+  DeconvF16Plan q;
+  if (int rc = deconv_f16_plan(B, Cin_pad, H, W, Cout, Ho, Wo, q)) return rc;
+  const int out[8] = {q.tile_base[4], q.npix[0], q.npix[1], q.npix[2], q.npix[3], q.nsteps, q.ksplit, q.steps_per_split};
+  for (int i = 0; i < 8; ++i) plan[i] = out[i];
+  return 0;
+}
+
 extern "C" size_t deepim_fewout_f16_packed_size(int Cin_pad) { return (size_t)(Cin_pad / 8) * 9 * FO_MAXOUT * 16; }
 
 extern "C" int deepim_fewout_f16_pack_weights(deepim_ctx* ctx, void* packed, const float* w0, int n0, const float* w1, int n1,
@@ -430,8 +476,8 @@ extern "C" int deepim_fewout_f16_pack_weights(deepim_ctx* ctx, void* packed, con
   DI_DEVICE(ctx);
   DI_REQUIRE(n0 >= 1 && n1 >= 0 && n0 + n1 <= FO_MAXOUT && (n1 == 0 || w1 != nullptr),
              "fewout_f16_pack: 1 to 3 filters in all, n0 >= 1");
-  DI_REQUIRE((Cin_pad & 7) == 0 && Cin_pad >= Cin && Cin_pad <= 8 * 64 * FO_MAXWAVES,
-             "fewout_f16_pack: Cin_pad % 8 == 0, Cin <= Cin_pad <= 2048");
+  DI_REQUIRE((Cin_pad & 7) == 0 && Cin_pad > 0 && Cin_pad >= Cin && Cin_pad <= 8 * 64 * FO_MAXWAVES,
+             "fewout_f16_pack: Cin_pad % 8 == 0, Cin <= Cin_pad <= 2048, Cin_pad > 0");
   const int noct = Cin_pad / 8, total = noct * 9 * FO_MAXOUT;
   hipLaunchKernelGGL(pack_fewout_f16_kernel, dim3(di_div_up(total, 256)), dim3(256), 0, ctx->stream, (h8*)packed, w0, n0, w1, n1,
                      Cin, noct);
@@ -446,25 +492,30 @@ extern "C" int deepim_conv3x3_fewout_f16_forward(deepim_ctx* ctx, float* out0, i
   if (B == 0) return 0;
   DI_REQUIRE(n0 >= 1 && n1 >= 0 && n0 + n1 <= FO_MAXOUT && out0 && bias0 && (n1 == 0 || (out1 && bias1)),
              "conv3x3_fewout_f16: 1 to 3 filters in all, n0 >= 1, an output and a bias per tensor");
-  DI_REQUIRE((Cin_pad & 7) == 0 && Cin_pad <= in_ctotal && (in_ctotal & 7) == 0 && Cin_pad <= 8 * 64 * FO_MAXWAVES,
-             "conv3x3_fewout_f16: Cin_pad % 8 == 0, in_ctotal % 8 == 0, Cin_pad <= in_ctotal, Cin_pad <= 2048");
+  FewoutF16Plan q;
+  if (int rc = fewout_f16_plan(B, H, W, Cin_pad, q)) return rc;
+  DI_REQUIRE(Cin_pad <= in_ctotal && (in_ctotal & 7) == 0, "conv3x3_fewout_f16: in_ctotal % 8 == 0, Cin_pad <= in_ctotal");
   FewoutParams p;
   p.in = (const _Float16*)in_nhwc_f16; p.wp = (const h8*)packed_w; p.bias0 = bias0; p.bias1 = bias1; p.out0 = out0; p.out1 = out1;
   p.n0 = n0; p.n1 = n1; p.B = B; p.H = H; p.W = W; p.in_ctotal = in_ctotal; p.noct = Cin_pad / 8;
-  // row segments: up to 64 columns; rows split further (up to 4 segments) until ~1024 blocks run
-  const int rows = B * H;
-  int nseg = std::max(di_div_up(W, FO_MAXSEG), std::min(4, di_div_up(1024, rows)));
-  nseg = std::min(nseg, W);
-  p.seg = di_div_up(W, nseg);
-  p.nseg = di_div_up(W, p.seg);
-  const int threads = 64 * di_div_up(p.noct, 64);
-  const dim3 grid(rows * p.nseg);
+  p.seg = q.seg; p.nseg = q.nseg;
+  const int threads = q.threads;
+  const dim3 grid(B * H * p.nseg);
   switch (n0 + n1) {
     case 1: hipLaunchKernelGGL(fewout_f16_kernel<1>, grid, dim3(threads), 0, ctx->stream, p); break;
     case 2: hipLaunchKernelGGL(fewout_f16_kernel<2>, grid, dim3(threads), 0, ctx->stream, p); break;
     default: hipLaunchKernelGGL(fewout_f16_kernel<3>, grid, dim3(threads), 0, ctx->stream, p); break;
   }
   DI_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int deepim_fewout_f16_plan(int B, int H, int W, int Cin_pad, int* plan) {
+  DI_REQUIRE(plan != nullptr, "fewout_f16_plan: null plan");
+  for (int i = 0; i < 4; ++i) plan[i] = -1;
+  FewoutF16Plan q;
+  if (int rc = fewout_f16_plan(B, H, W, Cin_pad, q)) return rc;
+  plan[0] = q.threads; plan[1] = q.seg; plan[2] = q.nseg; plan[3] = q.waves;
   return 0;
 }
 
