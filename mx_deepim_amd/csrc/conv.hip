@@ -6,7 +6,7 @@
 // Implicit GEMM  D[co][pixel] = Σ_k Wp[co][k] · X[k][pixel]  on v_mfma_f32_32x32x2_f32 — exact fp32, each output a
 // single fmaf chain in the kernel's K order (bit-identical to the oracle run in that order), at the fp32 peak (157 TF).
 // Pixels are flattened over (n,ho,wo); 4 waves per block, each a 64x64 accumulator tile; zero padding by out-of-range
-// buffer offsets; XCD-aware 1-D tile order; deterministic split-K, autotuned per geometry; fused bias + LeakyReLU.
+// buffer offsets; XCD-aware 1-D tile order; deterministic split-K, its factor from a cost model of the geometry; fused bias + LeakyReLU.
 // Three kernels:
 //   conv_nc8_kernel     LDS-free, channel-blocked (NC8) activations, K = (c/8,ky,kx,s,h): encoder conv2 … conv6_1
 //   conv_direct_kernel  LDS-free, NCHW input, K = (ci/2,ky,kx,ci%2): conv1 (writes NC8); the encoder with nc8 off
@@ -1496,70 +1496,98 @@ __global__ __launch_bounds__(256) void upsample16x4_kernel(float* __restrict__ o
   *reinterpret_cast<float4*>(out + (bc * Ho + yo) * Wo + 4 * xq) = make_float4(acc.x * scale, acc.y * scale, acc.z * scale, acc.w * scale);
 }
 
-struct TileChoice { int bm, bn, ksplit, tail_s; };
-// Tile/split plan, deterministic (the same geometry gets the same summation order in every run, process and rank):
-// 128x128 tiles (best MFMA density per gathered activation); 64x256 / 64x128 when Cout <= 64; when the grid leaves the
-// chip under-filled, split K across grid.z (fixed-order two-pass reduction). The split factor minimises a cost model
+// ---- which kernel runs a layer: the one statement of it; whoever packs, plans or launches asks here ----------------------------------
+//   FEWOUT    VALU stream over the input, Cout <= 4 (the heads)             packed operand order 1, no tile
+//   LDS       conv_mfma_kernel: canonical K order, any Cin, also transposed  packed operand order 1
+//   REG_NCHW  conv_direct_kernel: LDS-free, NCHW input with an even Cin      packed operand order 2
+//   REG_NC8   conv_nc8_kernel: LDS-free, channel-blocked input               packed operand order 4
+enum ConvFamily { FAM_FEWOUT, FAM_LDS, FAM_REG_NCHW, FAM_REG_NC8 };
+struct ConvKernel { ConvFamily fam; int bm, bn; };   // family and block tile: bm rows of Cout x bn pixels
+
+// May an NCHW layer leave the LDS kernel? conv_max_split = 1 asks for the canonical single (ci,ky,kx)-ordered chain per output, which
+// only the LDS kernel provides; conv_direct = 2 forces the register-fed kernels regardless (their chain runs over (ci/2,ky,kx,ci%2)).
+inline bool reg_fed_allowed(const deepim_ctx* ctx) { return ctx->conv_direct == 2 || (ctx->conv_direct == 1 && ctx->conv_max_split != 1); }
+
+// Tiles: 128x128 (best MFMA density per gathered activation); 64 rows when Cout <= 64, by 256 pixels from 256 K pixels on and for every
+// NC8 / split16 output, else by 128. The register-fed NCHW kernel has the 128x128 and the 64x256 shape only and is the only writer of
+// NC8 / split16 output from NCHW input; the transposed gather (MODE_DECONV) exists in the LDS kernel only.
+ConvKernel conv_kernel_for(const deepim_ctx* ctx, int mode, int Cin, int Cout, long npix, int in_nc8, int out_nc8) {
+  const bool wide = out_nc8 || npix >= 256L * 1024;
+  const int bm = Cout <= 64 ? 64 : 128, bn = Cout <= 64 && wide ? 256 : 128;
+  if (mode == MODE_DECONV) return {FAM_LDS, bm, bn};
+  if (in_nc8) return {FAM_REG_NC8, bm, bn};
+  if (Cout <= 4 && ctx->conv_max_split != 1 && !out_nc8) return {FAM_FEWOUT, 0, 0};   // a stream over the input, not an MFMA problem
+  if ((out_nc8 || reg_fed_allowed(ctx)) && (Cin & 1) == 0 && (Cout > 64 || wide)) return {FAM_REG_NCHW, bm, bn};
+  return {FAM_LDS, bm, bn};
+}
+
+// Split-K plan, deterministic (the same geometry gets the same summation order in every run, process and rank): when the grid leaves
+// the chip under-filled, split K across grid.z (fixed-order two-pass reduction). The split factor minimises a cost model
 // fitted to what the timing autotuner picked on MI355X at B = 1 … 32 (profiles/r02_conv_plans.md):
 //   cost(s) = ceil(tiles·s / 256) · ceil(nchunk / s)        MFMA time: blocks sharing a CU share its matrix pipes, so what
 //                                                            counts is the most loaded CU, in units of one K chunk (≈1 µs)
 //           + [s > 1] · (3 + 0.016 · tiles · s)             split-K reduce: launch + 64 KB of partial sums per block
-// over s ∈ {1,…,10,12,14,16,20,24}, s ≤ nchunk/4, tiles·s ≤ 4096; ties go to the smaller s.
+// over the candidates below; ties go to the smaller s.
+constexpr int KSPLIT_CANDS[] = {1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 12, 14, 16, 20, 24};
+inline bool ksplit_allowed(int s, long tiles, int nchunk) { return s == 1 || (tiles * s <= 4096 && s <= max(1, nchunk / 4)); }
 int plan_ksplit(long tiles, int nchunk) {
-  const int cands[] = {1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 12, 14, 16, 20, 24};
   float best = 1e30f;
   int best_s = 1;
-  for (int s : cands) {
-    if (s > 1 && (tiles * s > 4096 || s > max(1, nchunk / 4))) continue;
+  for (int s : KSPLIT_CANDS) {
+    if (!ksplit_allowed(s, tiles, nchunk)) continue;
     const float cost = (float)di_div_up(tiles * s, 256) * (float)di_div_up(nchunk, s) +
                        (s > 1 ? 3.f + 0.016f * (float)(tiles * s) : 0.f);
     if (cost < best * 0.985f) { best = cost; best_s = s; }
   }
   return best_s;
 }
-TileChoice choose_tile(int Cout, long npix, int nchunk, int classes, bool wide64 = false) {
-  int bm = 128, bn = 128;
-  if (Cout <= 64) { bm = 64; bn = (wide64 || npix >= 256L * 1024) ? 256 : 128; }   // wide64: the only 64-row LDS-free shape
-  const long tiles = (long)di_div_up(Cout, bm) * di_div_up(npix, bn) * classes;
-  return {bm, bn, plan_ksplit(tiles, nchunk), 0};
+
+struct ConvSplit { int ksplit, tail_s; };   // uniform split-K factor; K slices of the tail split (0 = none)
+// a plan as one int (the autotuner's cache, "conv_force_plan"): > 0 uniform split-K factor, < 0 tail split with -value slices
+inline ConvSplit split_of(int plan) { return {plan > 0 ? plan : 1, plan < 0 ? -plan : 0}; }
+// the tail split cuts 128x128 tiles of the register-fed NCHW kernel only
+inline bool tail_split_ok(const ConvKernel& k) { return k.fam == FAM_REG_NCHW && k.bm == 128; }
+
+// n floats of the context's scratch; n = 0 asks for nothing and gives nullptr
+int scratch_floats(deepim_ctx* ctx, size_t n, float** out) {
+  void* s = nullptr;
+  const int rc = n ? deepim_scratch(ctx, n * sizeof(float), &s) : 0;
+  *out = (float*)s;
+  return rc;
 }
 
-template <int MODE>
-int launch_one(deepim_ctx* ctx, ConvParams p, int classes, TileChoice t) {
-  if (p.out_nc8 == 2) t.ksplit = 1, t.tail_s = 0;   // the split16 epilogue has no split-K second pass
-  if (p.ep_y) {   // only the register-fed kernels' epilogue and the plain split-K second pass apply it
-    t.tail_s = 0;
-    DI_REQUIRE(MODE == MODE_CONV && p.tab2 != nullptr && !p.in_nc8 && !p.out_nc8 && ((t.bm == 128 && t.bn == 128) || (t.bm == 64 && t.bn == 256)),
-               "conv: activation-gradient epilogue asked of a kernel family that has none");
-  }
-  p.ksplit = t.ksplit;
-  p.chunks_per_split = di_div_up(p.nchunk, t.ksplit);
-  if (p.in_nc8) p.chunks_per_split = (p.chunks_per_split + 1) & ~1;   // the NC8 kernel consumes whole pairs of chunks
+// The split-K and grid fields of a launch, set here and nowhere else: ksplit slices asked for → K chunks per slice (whole pairs of
+// chunks for the NC8 kernel) → the number of slices that leaves none empty. The partial sums are the caller's to place.
+void set_split(ConvParams& p, const ConvKernel& k, int classes, int ksplit) {
+  p.chunks_per_split = di_div_up(p.nchunk, ksplit);
+  if (p.in_nc8) p.chunks_per_split = (p.chunks_per_split + 1) & ~1;
   p.ksplit = di_div_up(p.nchunk, p.chunks_per_split);
   p.partial = nullptr;
   p.partial_stride = (long)p.B * p.Cout * p.Ho * p.Wo;
-  if (p.ksplit > 1) {
-    void* scratch;
-    int rc = deepim_scratch(ctx, (size_t)p.ksplit * p.partial_stride * sizeof(float), &scratch);
-    if (rc) return rc;
-    p.partial = (float*)scratch;
+  p.gx = di_div_up(p.npix, k.bn); p.gy = di_div_up(p.Cout, k.bm); p.gz = classes * p.ksplit;
+}
+
+template <int MODE>
+int launch_one(deepim_ctx* ctx, ConvParams p, int classes, const ConvKernel& k, ConvSplit s) {
+  if (p.out_nc8 == 2) s = {1, 0};   // the split16 epilogue has no split-K second pass
+  if (p.ep_y) {   // only the register-fed NCHW kernels' epilogue and the plain split-K second pass apply it
+    s.tail_s = 0;
+    DI_REQUIRE(k.fam == FAM_REG_NCHW && !p.out_nc8, "conv: activation-gradient epilogue asked of a kernel family that has none");
   }
-  p.swizzle = ctx->conv_xcd_swizzle;
-  p.gx = di_div_up(p.npix, t.bn); p.gy = di_div_up(p.Cout, t.bm); p.gz = classes * p.ksplit;
-  p.n_full = 0; p.tail_s = 0; p.tail_cps = 0; p.n_tail_pad = 0; p.tail_partial = nullptr;
-  const bool direct_ok = MODE == MODE_CONV && t.bm == 128 && t.bn == 128 && p.tab2 != nullptr;
-  if (direct_ok && t.tail_s > 1 && t.ksplit == 1) {
+  set_split(p, k, classes, s.ksplit);
+  int rc = scratch_floats(ctx, p.ksplit > 1 ? (size_t)p.ksplit * p.partial_stride : 0, &p.partial);
+  if (rc) return rc;
+  // tail split: tiles [0, n_full) run their whole K range, the R tiles of the under-filled last round are cut into K slices
+  if (tail_split_ok(k) && s.tail_s > 1 && s.ksplit == 1) {
     const int tiles = p.gx * p.gy, slots = ctx->conv_tail_slots;
     const int n_full = tiles / slots * slots, R = tiles - n_full;
     if (n_full > 0 && R > 0) {
       p.n_full = n_full;
-      p.tail_cps = di_div_up(p.nchunk, t.tail_s);
+      p.tail_cps = di_div_up(p.nchunk, s.tail_s);
       p.tail_s = di_div_up(p.nchunk, p.tail_cps);
       p.n_tail_pad = di_div_up(R * p.tail_s, 8) * 8;
-      void* scratch;
-      int rc = deepim_scratch(ctx, (size_t)R * p.tail_s * 16384 * sizeof(float), &scratch);
+      rc = scratch_floats(ctx, (size_t)R * p.tail_s * 16384, &p.tail_partial);
       if (rc) return rc;
-      p.tail_partial = (float*)scratch;
       hipLaunchKernelGGL(conv_direct_kernel<2>, dim3(p.n_full + p.n_tail_pad), dim3(256), 0, ctx->stream, p);
       hipLaunchKernelGGL(tail_reduce_kernel, dim3(R), dim3(256), 0, ctx->stream, p.out, p.tail_partial, p.bias, n_full, R,
                          p.tail_s, p.gx, p.Cout, p.npix, p.Ho * p.Wo, p.out_ctotal, p.out_coff, p.slope, remap_of(p));
@@ -1568,23 +1596,15 @@ int launch_one(deepim_ctx* ctx, ConvParams p, int classes, TileChoice t) {
     }
   }
   DI_REQUIRE((long)p.gx * p.gy * p.gz < (1L << 31) && p.gx > 0, "conv: grid too large");
-  dim3 grid(p.gx * p.gy * p.gz);
-  if (MODE == MODE_CONV && p.in_nc8) {
-    if (t.bm == 64) {
-      DI_REQUIRE(t.bn == 256 && p.out_nc8 == 1, "conv: the 64-row NC8 kernel writes NC8 output on 64x256 tiles");
-      hipLaunchKernelGGL((conv_nc8_kernel<1, 1>), grid, dim3(256), 0, ctx->stream, p);
-    } else if (p.out_nc8) hipLaunchKernelGGL(conv_nc8_kernel<1>, grid, dim3(256), 0, ctx->stream, p);
-    else hipLaunchKernelGGL(conv_nc8_kernel<0>, grid, dim3(256), 0, ctx->stream, p);
-  } else if (direct_ok)
-    hipLaunchKernelGGL(conv_direct_kernel<2>, grid, dim3(256), 0, ctx->stream, p);
-  else if (MODE == MODE_CONV && t.bm == 64 && t.bn == 256 && p.tab2 != nullptr)
-    hipLaunchKernelGGL(conv_direct_kernel<1>, grid, dim3(256), 0, ctx->stream, p);
-  else if (t.bm == 128)
-    hipLaunchKernelGGL((conv_mfma_kernel<128, 128, MODE>), grid, dim3(256), 0, ctx->stream, p);
-  else if (t.bn == 256)
-    hipLaunchKernelGGL((conv_mfma_kernel<64, 256, MODE>), grid, dim3(256), 0, ctx->stream, p);
-  else
-    hipLaunchKernelGGL((conv_mfma_kernel<64, 128, MODE>), grid, dim3(256), 0, ctx->stream, p);
+  void (*kernel)(ConvParams) = nullptr;
+  if (k.fam == FAM_REG_NC8)   // 64 rows: Cout = 64 with NC8 output, on 64x256 tiles
+    kernel = k.bm == 64 ? conv_nc8_kernel<1, 1> : p.out_nc8 ? conv_nc8_kernel<1> : conv_nc8_kernel<0>;
+  else if (k.fam == FAM_REG_NCHW)
+    kernel = k.bm == 64 ? conv_direct_kernel<1> : conv_direct_kernel<2>;
+  else if (k.fam == FAM_LDS)
+    kernel = k.bm == 128 ? conv_mfma_kernel<128, 128, MODE> : k.bn == 256 ? conv_mfma_kernel<64, 256, MODE> : conv_mfma_kernel<64, 128, MODE>;
+  DI_REQUIRE(kernel != nullptr, "conv: no MFMA kernel of this family");
+  hipLaunchKernelGGL(kernel, dim3(p.gx * p.gy * p.gz), dim3(256), 0, ctx->stream, p);
   if (p.ksplit > 1) {
     const long total = p.partial_stride;
     if (p.out_nc8)
@@ -1600,36 +1620,31 @@ int launch_one(deepim_ctx* ctx, ConvParams p, int classes, TileChoice t) {
   return 0;
 }
 
-// Opt-in ("conv_autotune" = 1; default 0 so that plans never depend on wall-clock noise): on the first call of a
-// geometry (outside graph capture) time a few split-K factors with HIP events and remember the fastest. The kernel is
-// idempotent, so the trial launches only rewrite `out`.
+// The plan of a launch: the cost model's split factor, unless the opt-in autotuner ("conv_autotune" = 1; default 0 so that plans
+// never depend on wall-clock noise) holds one: on the first call of a geometry (outside graph capture) it times a few split-K
+// factors with HIP events and remembers the fastest. The kernel is idempotent, so the trial launches only rewrite `out`.
 template <int MODE>
-int launch_conv(deepim_ctx* ctx, const ConvParams& p, int classes) {
-  TileChoice t = choose_tile(p.Cout, p.npix, p.nchunk, classes, p.out_nc8 != 0);
-  const ConvPlanKey key = {MODE, p.B, p.Cin, p.H, p.W, p.Cout, p.Ho, p.Wo, p.stride, p.pad, p.nchunk,
-                           ctx->conv_tail_split * 8 + (p.tab2 != nullptr ? ctx->conv_direct : 0) + 1024 * (p.in_nc8 * 2 + p.out_nc8),
-                           0};
+int launch_conv(deepim_ctx* ctx, const ConvParams& p, int classes, const ConvKernel& k) {
+  const long tiles = (long)di_div_up(p.Cout, k.bm) * di_div_up(p.npix, k.bn) * classes;
+  ConvSplit s = {plan_ksplit(tiles, p.nchunk), 0};
   if (ctx->conv_autotune && ctx->conv_max_split != 1) {
-    bool found = false;
-    for (auto& e : ctx->conv_plans)
-      if (memcmp(&e.key, &key, sizeof(key)) == 0) {   // plan value: > 0 uniform split-K factor, < 0 tail split with -value slices
-        t.ksplit = e.ksplit > 0 ? e.ksplit : 1;
-        t.tail_s = e.ksplit < 0 ? -e.ksplit : 0;
-        found = true;
-        break;
-      }
-    if (!found && !ctx->capturing) {
-      const int tiles = di_div_up(p.Cout, t.bm) * di_div_up(p.npix, t.bn) * classes;
+    const ConvPlanKey key = {MODE, p.B, p.Cin, p.H, p.W, p.Cout, p.Ho, p.Wo, p.stride, p.pad, p.nchunk,
+                             ctx->conv_tail_split * 8 + (k.fam == FAM_REG_NCHW ? ctx->conv_direct : 0) + 1024 * (p.in_nc8 * 2 + p.out_nc8),
+                             0};
+    const ConvPlan* hit = nullptr;
+    for (const ConvPlan& e : ctx->conv_plans)
+      if (memcmp(&e.key, &key, sizeof(key)) == 0) { hit = &e; break; }
+    if (hit) s = split_of(hit->ksplit);
+    else if (!ctx->capturing) {
       int cands[24], nc = 0;
-      const int base[] = {1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 12, 14, 16, 20, 24};
-      for (int c : base)
-        if ((c == 1 || (long)tiles * c <= 4096) && c <= max(1, p.nchunk / 4)) cands[nc++] = c;
-      // tail split (LDS-free kernel only, opt-in): cut just the tiles of the under-filled last round, so that their
-      // slices about fill one round of the chip; candidates are encoded as negative values. Off by default: measured
-      // +2.8 % on conv2, ±1 % elsewhere, and a pair's summation order then depends on its position in the batch
-      // (results stop being bit-identical under a permutation of the pairs).
-      if (ctx->conv_tail_split && MODE == MODE_CONV && t.bm == 128 && t.bn == 128 && p.tab2 != nullptr && classes == 1) {
-        const int slots = ctx->conv_tail_slots, R = tiles % slots;
+      for (int c : KSPLIT_CANDS)
+        if (ksplit_allowed(c, tiles, p.nchunk)) cands[nc++] = c;
+      // tail split (opt-in): cut just the tiles of the under-filled last round, so that their slices about fill one round of
+      // the chip; candidates are encoded as negative values. Off by default: measured +2.8 % on conv2, ±1 % elsewhere, and a
+      // pair's summation order then depends on its position in the batch (results stop being bit-identical under a
+      // permutation of the pairs).
+      if (ctx->conv_tail_split && tail_split_ok(k)) {
+        const int slots = ctx->conv_tail_slots, R = (int)(tiles % slots);
         if (tiles >= slots && R > 0) {
           const int s0 = min(slots / R, max(1, p.nchunk / 4));
           for (int sN : {s0, s0 - 1, s0 * 2})
@@ -1642,38 +1657,31 @@ int launch_conv(deepim_ctx* ctx, const ConvParams& p, int classes) {
       } ev;
       DI_CHECK(hipEventCreate(&ev.a));
       DI_CHECK(hipEventCreate(&ev.b));
-      const hipEvent_t e0 = ev.a, e1 = ev.b;
       float best = 1e30f;
-      int best_ks = t.ksplit;
+      int best_plan = s.ksplit;
       for (int ci = 0; ci < nc; ++ci) {
-        TileChoice tc = t;
-        tc.ksplit = cands[ci] > 0 ? cands[ci] : 1;
-        tc.tail_s = cands[ci] < 0 ? -cands[ci] : 0;
-        int rc = launch_one<MODE>(ctx, p, classes, tc);  // warm (also grows the scratch once)
+        const ConvSplit sc = split_of(cands[ci]);
+        int rc = launch_one<MODE>(ctx, p, classes, k, sc);  // warm (also grows the scratch once)
         if (rc) return rc;
-        DI_CHECK(hipEventRecord(e0, ctx->stream));
-        for (int r = 0; r < 3; ++r) launch_one<MODE>(ctx, p, classes, tc);
-        DI_CHECK(hipEventRecord(e1, ctx->stream));
-        DI_CHECK(hipEventSynchronize(e1));
+        DI_CHECK(hipEventRecord(ev.a, ctx->stream));
+        for (int r = 0; r < 3; ++r) launch_one<MODE>(ctx, p, classes, k, sc);
+        DI_CHECK(hipEventRecord(ev.b, ctx->stream));
+        DI_CHECK(hipEventSynchronize(ev.b));
         float ms = 0.f;
-        DI_CHECK(hipEventElapsedTime(&ms, e0, e1));
-        if (ms < best * 0.985f) { best = ms; best_ks = cands[ci]; }  // prefer fewer splits on near-ties
+        DI_CHECK(hipEventElapsedTime(&ms, ev.a, ev.b));
+        if (ms < best * 0.985f) { best = ms; best_plan = cands[ci]; }  // prefer fewer splits on near-ties
       }
       if (getenv("DEEPIM_CONV_VERBOSE"))
-        fprintf(stderr, "[deepim] conv plan B=%d Cin=%d %dx%d Cout=%d s%d: %d tiles, %s %d (%.3f ms)\n", p.B, p.Cin, p.H, p.W,
-                p.Cout, p.stride, tiles, best_ks < 0 ? "tail split" : "split-K", best_ks < 0 ? -best_ks : best_ks, best / 3);
-      ctx->conv_plans.push_back({key, best_ks});
-      t.ksplit = best_ks > 0 ? best_ks : 1;
-      t.tail_s = best_ks < 0 ? -best_ks : 0;
+        fprintf(stderr, "[deepim] conv plan B=%d Cin=%d %dx%d Cout=%d s%d: %ld tiles, %s %d (%.3f ms)\n", p.B, p.Cin, p.H, p.W,
+                p.Cout, p.stride, tiles, best_plan < 0 ? "tail split" : "split-K", best_plan < 0 ? -best_plan : best_plan, best / 3);
+      ctx->conv_plans.push_back({key, best_plan});
+      s = split_of(best_plan);
     }
   }
-  if (ctx->conv_force_plan != 0) {   // dev knob: bypass heuristic and autotuner (> 0 uniform split-K, < 0 tail split)
-    t.ksplit = ctx->conv_force_plan > 0 ? ctx->conv_force_plan : 1;
-    t.tail_s = ctx->conv_force_plan < 0 ? -ctx->conv_force_plan : 0;
-  }
-  if (ctx->conv_max_split > 0 && t.ksplit > ctx->conv_max_split) t.ksplit = ctx->conv_max_split;
-  if (ctx->conv_max_split > 0 && t.tail_s > ctx->conv_max_split) t.tail_s = ctx->conv_max_split > 1 ? ctx->conv_max_split : 0;
-  return launch_one<MODE>(ctx, p, classes, t);
+  if (ctx->conv_force_plan != 0) s = split_of(ctx->conv_force_plan);   // dev knob: bypass heuristic and autotuner
+  if (ctx->conv_max_split > 0 && s.ksplit > ctx->conv_max_split) s.ksplit = ctx->conv_max_split;
+  if (ctx->conv_max_split > 0 && s.tail_s > ctx->conv_max_split) s.tail_s = ctx->conv_max_split > 1 ? ctx->conv_max_split : 0;
+  return launch_one<MODE>(ctx, p, classes, k, s);
 }
 
 inline int gran_count(int Cout) { return di_div_up(Cout, 128) * 2; }  // whole 128-row tiles → BM=128 never overruns
@@ -1710,12 +1718,49 @@ int get_tab(deepim_ctx* ctx, int mode, int Cin, int kh, int kw, int H, int W, in
   return 0;
 }
 
-}  // namespace
-
 // the packed buffer holds three layouts back to back, each gran·nchunk·1024 floats: [granule][chunk][16][64] for the
 // LDS kernel, [32-row tile][k-pair/4][lane][4] for the LDS-free kernel on NCHW input, and the same shape in the
 // channel order of the NC8 kernel
 inline size_t packed_half(int Cout, int K) { return (size_t)gran_count(Cout) * chunk_count(K) * KT * GRAN; }
+
+// What every launch shares: in (B,Cin,H,W) → a (Ho,Wo) result of Cout channels over K = Cin·taps, written to channels [out_coff,
+// out_coff + Cout) of an out_ctotal-channel tensor (0: Cout). Everything else is zero: no crop, no remap, NCHW in and out, no
+// epilogue, no tables, no split. A site states what differs from this; set_operands adds tables and operand slot, set_split the split.
+ConvParams conv_params(const deepim_ctx* ctx, float* out, const float* in, const float* bias, int B, int Cin, int H, int W, int Cout,
+                       int Ho, int Wo, int stride, int pad, int K, float slope, int out_ctotal, int out_coff) {
+  ConvParams p = {};
+  p.in = in; p.bias = bias; p.out = out;
+  p.B = B; p.Cin = Cin; p.H = H; p.W = W; p.Cout = Cout; p.Ho = Ho; p.Wo = Wo;
+  p.stride = stride; p.pad = pad;
+  p.nchunk = chunk_count(K);
+  p.ngran = gran_count(Cout);
+  p.out_ctotal = out_ctotal > 0 ? out_ctotal : Cout; p.out_coff = out_coff;
+  p.slope = slope; p.out_scale = 1.f; p.ep_slope = 1.f;
+  p.npix = (long)B * Ho * Wo;
+  p.pad_bytes = (pad * W + pad) * 4;
+  p.in_bytes = (unsigned)((size_t)B * Cin * H * W * 4);
+  p.status = ctx->status;
+  p.swizzle = ctx->conv_xcd_swizzle;
+  return p;
+}
+
+// Tap tables and operand slot of a convolution (not the transposed one) run by family `fam` on weights packed at packed_w
+int set_operands(deepim_ctx* ctx, ConvParams& p, ConvFamily fam, const float* packed_w, int kh, int kw) {
+  int2* tab;
+  int rc = get_tab(ctx, MODE_CONV, p.Cin, kh, kw, p.H, p.W, &tab);
+  if (rc) return rc;
+  p.wp = packed_w; p.tab = tab;
+  if (fam != FAM_REG_NCHW && fam != FAM_REG_NC8) return 0;
+  const size_t half = packed_half(p.Cout, p.Cin * kh * kw);
+  rc = get_tab(ctx, fam == FAM_REG_NC8 ? MODE_NC8_TAB : MODE_DIRECT_TAB, p.Cin, kh, kw, p.H, p.W, &tab);
+  if (rc) return rc;
+  if (fam == FAM_REG_NC8) { p.tab8 = tab; p.wd8 = packed_w + 2 * half; }
+  else { p.tab2 = tab; p.wd = packed_w + half; }
+  p.wd_bytes = (unsigned)(half * sizeof(float));
+  return 0;
+}
+
+}  // namespace
 
 extern "C" size_t deepim_conv_packed_size(int Cout, int Cin, int kh, int kw) {
   return 3 * packed_half(Cout, Cin * kh * kw) * sizeof(float);
@@ -1769,53 +1814,12 @@ extern "C" int deepim_conv_pack_dgrad(deepim_ctx* ctx, float* packed_w, const fl
 }
 
 // Which ONE of the packed operand orders deepim_conv2d_forward (NCHW in, NCHW out) reads for this geometry under the context's
-// current options — the selection of conv2d_forward_impl / choose_tile / launch_one restated, so that a caller that re-packs
-// weights it uses once (the data gradients of the training graph) packs only that order. Returns 1 (LDS kernel / few-output
-// kernel) or 2 (NCHW register-fed kernel).
+// current options, so that a caller that re-packs weights it uses once (the data gradients of the training graph) packs only that
+// order. Returns 1 (LDS kernel / few-output kernel) or 2 (NCHW register-fed kernel).
 extern "C" int deepim_conv_weight_order(deepim_ctx* ctx, int B, int Cin, int H, int W, int Cout, int kh, int kw, int stride,
                                         int pad) {
   const long npix = (long)B * ((H + 2 * pad - kh) / stride + 1) * ((W + 2 * pad - kw) / stride + 1);
-  if (Cout <= 4 && ctx->conv_max_split != 1) return 1;
-  const bool direct = ctx->conv_direct == 2 || (ctx->conv_direct == 1 && ctx->conv_max_split != 1);
-  if (!(direct && (Cin & 1) == 0 && (Cout > 64 || npix >= 256L * 1024))) return 1;
-  return 2;                                                   // 128x128 or 64x256 tiles of the register-fed kernel
-}
-
-extern "C" int deepim_conv2d_forward(deepim_ctx* ctx, float* out, const float* in, const float* packed_w,
-                                     const float* bias, int B, int Cin, int H, int W, int Cout, int kh, int kw,
-                                     int stride, int pad, float slope, int out_ctotal, int out_coff) {
-  DI_DEVICE(ctx);
-  return deepim_conv2d_forward_ex(ctx, out, in, packed_w, bias, B, Cin, H, W, Cout, kh, kw, stride, pad, slope, out_ctotal,
-                                  out_coff, 0, 0);
-}
-
-static int conv2d_forward_impl(deepim_ctx* ctx, float* out, const float* in, const float* packed_w, const float* bias, int B,
-                               int Cin, int H, int W, int Cout, int kh, int kw, int stride, int pad, float slope,
-                               int out_ctotal, int out_coff, int in_nc8, int out_nc8, float out_scale,
-                               const Remap* rm = nullptr, const ActGrad* ag = nullptr);
-
-extern "C" int deepim_conv2d_forward_ex(deepim_ctx* ctx, float* out, const float* in, const float* packed_w,
-                                        const float* bias, int B, int Cin, int H, int W, int Cout, int kh, int kw,
-                                        int stride, int pad, float slope, int out_ctotal, int out_coff, int in_nc8,
-                                        int out_nc8) {
-  return conv2d_forward_impl(ctx, out, in, packed_w, bias, B, Cin, H, W, Cout, kh, kw, stride, pad, slope, out_ctotal, out_coff,
-                             in_nc8, out_nc8 == 3 ? 3 : (out_nc8 ? 1 : 0), 1.f);   // 3: NC8 in space-to-depth order
-}
-
-// One output parity class of a stride-2 data gradient, straight into dx: a stride-1 convolution of the un-dilated gradient `in`
-// (B,Cin,H,W) with the class's flipped sub-kernel (kh x kw, symmetric pad), whose result window [cy, cy + hq) x [cx, cx + wq)
-// — hq = ⌈(Hd - py) / 2⌉, wq = ⌈(Wd - px) / 2⌉ — is written to out (B,Cout,Hd,Wd)[.., 2i + py, 2j + px]. No bias, no activation.
-extern "C" int deepim_conv2d_forward_remap(deepim_ctx* ctx, float* out, const float* in, const float* packed_w, int B, int Cin,
-                                           int H, int W, int Cout, int kh, int kw, int pad, int cy, int cx, int Hd, int Wd,
-                                           int py, int px) {
-  Remap rm;
-  rm.on = 1; rm.cy = cy; rm.cx = cx; rm.py = py; rm.px = px; rm.H = Hd; rm.W = Wd;
-  rm.hq = (Hd - py + 1) / 2; rm.wq = (Wd - px + 1) / 2;
-  rm.Wo = W + 2 * pad - kw + 1;
-  const int Ho = H + 2 * pad - kh + 1;
-  DI_REQUIRE(py >= 0 && py < 2 && px >= 0 && px < 2 && cy >= 0 && cx >= 0 && rm.hq + cy <= Ho && rm.wq + cx <= rm.Wo,
-             "conv2d_forward_remap: class window outside the convolution result");
-  return conv2d_forward_impl(ctx, out, in, packed_w, nullptr, B, Cin, H, W, Cout, kh, kw, 1, pad, 1.f, 0, 0, 0, 0, 1.f, &rm);
+  return conv_kernel_for(ctx, MODE_CONV, Cin, Cout, npix, 0, 0).fam == FAM_REG_NCHW ? 2 : 1;
 }
 
 // ---- the whole data gradient of a stride-2 convolution ----------------------------------------------------------------------
@@ -1868,43 +1872,6 @@ int actgrad_pass(deepim_ctx* ctx, float* dx, const ActGrad& ag, size_t n) {
 // input map (the Crop may keep fewer rows than the adjoint's full frame), bias + LeakyReLU + channel slice in the final stores,
 // weights packed once (s2_pack_direct_group; prepacked skips the pack launch)
 struct S2Forward { int Ho, Wo; const float* bias; float slope; int out_ctotal, out_coff; bool prepacked; };
-static int conv2d_dgrad_s2_impl(deepim_ctx* ctx, float* dx, const float* dz, const float* w_layer, float* packed_ws, int B,
-                                int Ci_l, int Hd, int Wd, int Co_l, int k, int pad, const ActGrad* ag, const S2Forward* fw = nullptr);
-
-extern "C" int deepim_conv2d_dgrad_s2(deepim_ctx* ctx, float* dx, const float* dz, const float* w_layer, float* packed_ws, int B,
-                                      int Ci_l, int Hd, int Wd, int Co_l, int k, int pad) {
-  return conv2d_dgrad_s2_impl(ctx, dx, dz, w_layer, packed_ws, B, Ci_l, Hd, Wd, Co_l, k, pad, nullptr);
-}
-
-extern "C" size_t deepim_conv_dgrad_packed_size(int Co_l, int Ci_l, int k, int stride, int pad) {
-  return stride == 2 ? deepim_conv_dgrad_s2_packed_size(Co_l, Ci_l, k, pad) : deepim_conv_packed_size(Ci_l, Co_l, k, k);
-}
-
-// Data gradient of a Convolution layer (Co_l,Ci_l,k,k; stride 1 or 2) from its raw weights, optionally already multiplied by the
-// activation gradient of the layer below: dx = lrelu'(act_y)·(dgrad [+ add]) — act_y = that layer's saved output, add = the
-// gradient reaching it over a skip connection (both laid out like dx; NULL act_y = plain dgrad). The epilogue rides in the final
-// stores of the register-fed kernels / their split-K second passes; other kernel families get it as one extra pass.
-extern "C" int deepim_conv2d_dgrad(deepim_ctx* ctx, float* dx, const float* dz, const float* w_layer, float* packed_ws, int B,
-                                   int Ci_l, int Hd, int Wd, int Co_l, int k, int stride, int pad, const float* act_y,
-                                   const float* add, float slope) {
-  DI_DEVICE(ctx);
-  if (B == 0) return 0;
-  DI_REQUIRE(stride == 1 || stride == 2, "conv2d_dgrad: stride 1 or 2");
-  DI_REQUIRE(act_y != nullptr || add == nullptr, "conv2d_dgrad: add without act_y");
-  const ActGrad ag = {act_y, add, slope};
-  if (stride == 2) return conv2d_dgrad_s2_impl(ctx, dx, dz, w_layer, packed_ws, B, Ci_l, Hd, Wd, Co_l, k, pad, act_y ? &ag : nullptr);
-  const int Ho = Hd + 2 * pad - k + 1, Wo = Wd + 2 * pad - k + 1, P = k - 1 - pad;
-  DI_REQUIRE(P >= 0, "conv2d_dgrad: pad > k - 1");
-  const int order = deepim_conv_weight_order(ctx, B, Co_l, Ho, Wo, Ci_l, k, k, 1, P);
-  int rc = deepim_conv_pack_dgrad(ctx, packed_ws, w_layer, Co_l, Ci_l, k, k, 0, 0, 1, k, k, order);
-  if (rc) return rc;
-  const bool fused = act_y && order == 2 && (size_t)B * Co_l * Ho * Wo * 4 + (size_t)(P * Wo + P) * 4 < 0x7fffffffUL;
-  rc = conv2d_forward_impl(ctx, dx, dz, packed_ws, nullptr, B, Co_l, Ho, Wo, Ci_l, k, k, 1, P, 1.f, 0, 0, 0, 0, 1.f, nullptr,
-                           fused ? &ag : nullptr);
-  if (rc) return rc;
-  if (act_y && !fused) return actgrad_pass(ctx, dx, ag, (size_t)B * Ci_l * Hd * Wd);
-  return 0;
-}
 
 // The four parity classes of a stride-2 layer's operand buffer, a function of (Ci_l, Co_l, k, pad) only: class z at slot[z] (three
 // halves each: LDS-kernel packing, then the register-fed kernel's operand order), members of a grouped launch in descending K
@@ -1959,7 +1926,7 @@ static int s2_pack_direct_group(deepim_ctx* ctx, const float* w_layer, float* pa
 }
 
 static int conv2d_dgrad_s2_impl(deepim_ctx* ctx, float* dx, const float* dz, const float* w_layer, float* packed_ws, int B,
-                                int Ci_l, int Hd, int Wd, int Co_l, int k, int pad, const ActGrad* ag, const S2Forward* fw) {
+                                int Ci_l, int Hd, int Wd, int Co_l, int k, int pad, const ActGrad* ag, const S2Forward* fw = nullptr) {
   DI_DEVICE(ctx);
   if (B == 0) return 0;
   DI_REQUIRE(k >= 2 && k <= 7 && pad >= 0 && pad < k, "conv2d_dgrad_s2: kernel 2 … 7, pad < k");
@@ -1968,12 +1935,11 @@ static int conv2d_dgrad_s2_impl(deepim_ctx* ctx, float* dx, const float* dz, con
   const S2Class* cls = L.cls;
   const size_t* slot = L.slot;
   const int* ord = L.ord;
-  const bool direct = ctx->conv_direct == 2 || (ctx->conv_direct == 1 && ctx->conv_max_split != 1);
   const size_t in_bytes = (size_t)B * Co_l * Ho * Wo * 4;
-  const bool grouped = fw != nullptr || (ctx->dgrad_group && direct && (Co_l & 1) == 0 &&
+  const bool grouped = fw != nullptr || (ctx->dgrad_group && reg_fed_allowed(ctx) && (Co_l & 1) == 0 &&
                                          in_bytes + (size_t)(4 * Wo + 4) * 4 < 0x7fffffffUL);
   // tile of the register-fed kernel: 128 x 128, or 64 rows x 256 pixels when dx has at most 64 channels (conv2's data gradient)
-  const int bm = Ci_l <= 64 ? 64 : 128, bn = Ci_l <= 64 ? 256 : 128;
+  const ConvKernel kern = {FAM_REG_NCHW, Ci_l <= 64 ? 64 : 128, Ci_l <= 64 ? 256 : 128};
   if (!grouped) {   // class by class: whatever kernel family deepim_conv2d_forward picks for the geometry
     for (int z = 0; z < 4; ++z) {
       const S2Class& c = cls[z];
@@ -1995,33 +1961,15 @@ static int conv2d_dgrad_s2_impl(deepim_ctx* ctx, float* dx, const float* dz, con
   for (int m = 0; m < 4; ++m) {
     const S2Class& c = cls[ord[m]];
     ConvParams& p = g.p[m];
-    const size_t half = packed_half(Ci_l, Co_l * c.nky * c.nkx);
-    p.in = dz; p.wp = packed_ws + slot[ord[m]]; p.bias = fw ? fw->bias : nullptr; p.out = dx;
-    p.B = B; p.Cin = Co_l; p.H = Ho; p.W = Wo; p.Cout = Ci_l;
-    p.Ho = Ho + 2 * c.P - c.nky + 1; p.Wo = Wo + 2 * c.P - c.nkx + 1;
-    p.stride = 1; p.pad = c.P;
-    p.nchunk = chunk_count(Co_l * c.nky * c.nkx);
-    p.ngran = gran_count(Ci_l);
-    p.out_ctotal = fw && fw->out_ctotal > 0 ? fw->out_ctotal : Ci_l; p.out_coff = fw ? fw->out_coff : 0;
-    p.slope = fw ? fw->slope : 1.f; p.crop_y = p.crop_x = 0;
+    p = conv_params(ctx, dx, dz, fw ? fw->bias : nullptr, B, Co_l, Ho, Wo, Ci_l, Ho + 2 * c.P - c.nky + 1, Wo + 2 * c.P - c.nkx + 1, 1,
+                    c.P, Co_l * c.nky * c.nkx, fw ? fw->slope : 1.f, fw ? fw->out_ctotal : 0, fw ? fw->out_coff : 0);
     p.rm_on = 1; p.rm_cy = c.cy; p.rm_cx = c.cx; p.rm_hq = (Hd - c.py + 1) / 2; p.rm_wq = (Wd - c.px + 1) / 2;
     p.rm_py = c.py; p.rm_px = c.px; p.rm_H = Hd; p.rm_W = Wd;
     DI_REQUIRE(p.rm_hq + c.cy <= p.Ho && p.rm_wq + c.cx <= p.Wo, "conv2d_dgrad_s2: class window outside the convolution result");
-    p.npix = (long)B * p.Ho * p.Wo;
-    p.pad_bytes = (c.P * Wo + c.P) * 4;
-    p.in_bytes = (unsigned)in_bytes;
-    int2 *tab, *tab2;
-    int rc = get_tab(ctx, MODE_CONV, Co_l, c.nky, c.nkx, Ho, Wo, &tab);
+    int rc = set_operands(ctx, p, kern.fam, packed_ws + slot[ord[m]], c.nky, c.nkx);
     if (rc) return rc;
-    rc = get_tab(ctx, MODE_DIRECT_TAB, Co_l, c.nky, c.nkx, Ho, Wo, &tab2);
-    if (rc) return rc;
-    p.tab = tab; p.tab2 = tab2;
-    p.wd = packed_ws + slot[ord[m]] + half; p.wd_bytes = (unsigned)(half * sizeof(float));
-    p.in_nc8 = 0; p.out_nc8 = 0; p.out_s2d = 0; p.out_scale = 1.f; p.status = ctx->status; p.wd8 = nullptr; p.tab8 = nullptr;
-    p.ep_y = ag ? ag->y : nullptr; p.ep_add = ag ? ag->add : nullptr; p.ep_slope = ag ? ag->slope : 1.f;
-    p.swizzle = ctx->conv_xcd_swizzle;
-    p.gx = di_div_up(p.npix, bn); p.gy = di_div_up(Ci_l, bm);
-    p.n_full = 0; p.tail_s = 0; p.tail_cps = 0; p.n_tail_pad = 0; p.tail_partial = nullptr;
+    if (ag) { p.ep_y = ag->y; p.ep_add = ag->add; p.ep_slope = ag->slope; }
+    set_split(p, kern, 1, 1);   // unsplit, for the tile count; the joint plan below sets the slices
     tiles[m] = (long)p.gx * p.gy;
   }
   // joint plan: T = K chunks per block; member m runs ceil(nchunk_m / T) slices. cost as plan_ksplit: rounds of 256 blocks x the
@@ -2046,20 +1994,12 @@ static int conv2d_dgrad_s2_impl(deepim_ctx* ctx, float* dx, const float* dz, con
   size_t partial_floats = 0;
   for (int m = 0; m < 4; ++m) {
     ConvParams& p = g.p[m];
-    p.ksplit = di_div_up(p.nchunk, best_T);
-    p.chunks_per_split = di_div_up(p.nchunk, p.ksplit);
-    p.ksplit = di_div_up(p.nchunk, p.chunks_per_split);
-    p.gz = p.ksplit;
-    p.partial_stride = (long)B * Ci_l * p.Ho * p.Wo;
+    set_split(p, kern, 1, di_div_up(p.nchunk, best_T));
     if (p.ksplit > 1) partial_floats += (size_t)p.ksplit * p.partial_stride;
   }
-  float* scratch = nullptr;
-  if (partial_floats) {
-    void* sp;
-    int rc = deepim_scratch(ctx, partial_floats * sizeof(float), &sp);
-    if (rc) return rc;
-    scratch = (float*)sp;
-  }
+  float* scratch;
+  const int rc = scratch_floats(ctx, partial_floats, &scratch);
+  if (rc) return rc;
   ReduceGroup rg;
   rg.out = dx; rg.Cout = Ci_l; rg.n = 0;
   rg.ep_y = ag ? ag->y : nullptr; rg.ep_add = ag ? ag->add : nullptr; rg.ep_slope = ag ? ag->slope : 1.f;
@@ -2069,7 +2009,6 @@ static int conv2d_dgrad_s2_impl(deepim_ctx* ctx, float* dx, const float* dz, con
   size_t poff = 0;
   for (int m = 0; m < 4; ++m) {
     ConvParams& p = g.p[m];
-    p.partial = nullptr;
     if (p.ksplit > 1) {
       p.partial = scratch + poff;
       poff += (size_t)p.ksplit * p.partial_stride;
@@ -2084,27 +2023,17 @@ static int conv2d_dgrad_s2_impl(deepim_ctx* ctx, float* dx, const float* dz, con
   g.start[4] = cstart;
   for (int j = rg.n; j <= CONV_GROUP_MAX; ++j) rg.start[j] = rstart;
   if (!(fw && fw->prepacked)) hipLaunchKernelGGL(pack_direct_group_kernel, dim3(pstart), dim3(256), 0, ctx->stream, w_layer, pg);
-  if (bm == 64) hipLaunchKernelGGL(conv_direct_group_kernel<1>, dim3(cstart), dim3(256), 0, ctx->stream, g);
+  if (kern.bm == 64) hipLaunchKernelGGL(conv_direct_group_kernel<1>, dim3(cstart), dim3(256), 0, ctx->stream, g);
   else hipLaunchKernelGGL(conv_direct_group_kernel<2>, dim3(cstart), dim3(256), 0, ctx->stream, g);
   if (rg.n) hipLaunchKernelGGL(splitk_reduce_group_kernel, dim3(rstart), dim3(256), 0, ctx->stream, rg);
   DI_LAUNCH_CHECK();
   return 0;
 }
 
-// NCHW fp32 in → split16 out (conv1 of the split-fp16 encoder): the fp32 MFMA convolution with the split folded into its
-// epilogue. Cout % 16 == 0; LDS-free kernels only (even Cin).
-extern "C" int deepim_conv2d_forward_split16(deepim_ctx* ctx, void* out_split16, const float* in, const float* packed_w,
-                                             const float* bias, int B, int Cin, int H, int W, int Cout, int kh, int kw,
-                                             int stride, int pad, float slope, float out_scale) {
-  DI_REQUIRE((Cout & 15) == 0 && (Cin & 1) == 0, "conv2d_split16: needs Cout % 16 == 0 and an even Cin");
-  return conv2d_forward_impl(ctx, (float*)out_split16, in, packed_w, bias, B, Cin, H, W, Cout, kh, kw, stride, pad, slope, 0, 0,
-                             0, 2, out_scale);
-}
-
 static int conv2d_forward_impl(deepim_ctx* ctx, float* out, const float* in, const float* packed_w, const float* bias, int B,
                                int Cin, int H, int W, int Cout, int kh, int kw, int stride, int pad, float slope,
-                               int out_ctotal, int out_coff, int in_nc8, int out_nc8, float out_scale, const Remap* rm,
-                               const ActGrad* ag) {
+                               int out_ctotal, int out_coff, int in_nc8, int out_nc8, float out_scale,
+                               const Remap* rm = nullptr, const ActGrad* ag = nullptr) {
   DI_DEVICE(ctx);
   if (B == 0) return 0;
   DI_REQUIRE((long)Cin * H * W < (1L << 31), "conv2d: per-sample input too large for 32-bit offsets");
@@ -2127,53 +2056,30 @@ static int conv2d_forward_impl(deepim_ctx* ctx, float* out, const float* in, con
       return 0;
     }
   }
-  ConvParams p;
-  p.in = in; p.wp = packed_w; p.bias = bias; p.out = out;
-  p.B = B; p.Cin = Cin; p.H = H; p.W = W; p.Cout = Cout;
-  p.Ho = (H + 2 * pad - kh) / stride + 1;
-  p.Wo = (W + 2 * pad - kw) / stride + 1;
-  p.stride = stride; p.pad = pad;
-  p.nchunk = chunk_count(Cin * kh * kw);
-  p.ngran = gran_count(Cout);
-  p.out_ctotal = out_ctotal > 0 ? out_ctotal : Cout;
-  p.out_coff = out_coff;
-  p.slope = slope; p.crop_y = p.crop_x = 0;
-  p.rm_on = 0; p.rm_cy = p.rm_cx = p.rm_hq = p.rm_wq = p.rm_py = p.rm_px = p.rm_H = p.rm_W = 0;
+  ConvParams p = conv_params(ctx, out, in, bias, B, Cin, H, W, Cout, (H + 2 * pad - kh) / stride + 1, (W + 2 * pad - kw) / stride + 1,
+                             stride, pad, Cin * kh * kw, slope, out_ctotal, out_coff);
   if (rm) {
     DI_REQUIRE(!in_nc8 && !out_nc8 && Cout > 4, "conv2d remap: NCHW in / out on the MFMA kernels only");
     p.rm_on = 1; p.rm_cy = rm->cy; p.rm_cx = rm->cx; p.rm_hq = rm->hq; p.rm_wq = rm->wq; p.rm_py = rm->py; p.rm_px = rm->px;
     p.rm_H = rm->H; p.rm_W = rm->W;
   }
-  p.npix = (long)B * p.Ho * p.Wo;
-  p.pad_bytes = (pad * W + pad) * 4;
   DI_REQUIRE((size_t)B * Cin * H * W * 4 + p.pad_bytes < 0x7fffffffUL, "conv2d: input tensor must be < 2 GiB per launch");
   DI_REQUIRE(kh <= 7 && kw <= 7, "conv2d: kernel larger than 7 not supported");
-  p.in_bytes = (unsigned)((size_t)B * Cin * H * W * 4);
-  int2* tab;
-  int rc = get_tab(ctx, MODE_CONV, Cin, kh, kw, H, W, &tab);
-  if (rc) return rc;
-  p.tab = tab;
-  p.wd = nullptr; p.tab2 = nullptr; p.wd_bytes = 0;
   p.out_s2d = out_nc8 == 3 ? 1 : 0;
   if (out_nc8 == 3) out_nc8 = 1;
-  p.in_nc8 = in_nc8 ? 1 : 0; p.out_nc8 = out_nc8; p.out_scale = out_scale; p.status = ctx->status; p.wd8 = nullptr; p.tab8 = nullptr;
-  p.ep_y = ag ? ag->y : nullptr; p.ep_add = ag ? ag->add : nullptr; p.ep_slope = ag ? ag->slope : 1.f;
+  p.in_nc8 = in_nc8 ? 1 : 0; p.out_nc8 = out_nc8; p.out_scale = out_scale;
+  if (ag) { p.ep_y = ag->y; p.ep_add = ag->add; p.ep_slope = ag->slope; }
   if (out_nc8 == 2) DI_REQUIRE(!in_nc8, "conv2d: split16 output is built for the NCHW-input LDS-free kernel (conv1)");
   if (out_nc8) DI_REQUIRE((Cout & 7) == 0 && p.out_ctotal == Cout && out_coff == 0, "conv2d: NC8 output needs Cout % 8 == 0 and no channel slice");
   if (p.out_s2d) DI_REQUIRE(((p.Ho | p.Wo) & 1) == 0, "conv2d: space-to-depth output needs even output height and width");
-  if (in_nc8) {
+  if (in_nc8)
     DI_REQUIRE((Cin & 7) == 0 && (Cout > 64 || (Cout == 64 && out_nc8 == 1)),
                "conv2d: NC8 input needs Cin % 8 == 0 and Cout > 64 (or Cout == 64 with NC8 output: the 64x256-tile kernel)");
-    const size_t half = packed_half(Cout, Cin * kh * kw);
-    int2* tab8;
-    rc = get_tab(ctx, MODE_NC8_TAB, Cin, kh, kw, H, W, &tab8);
-    if (rc) return rc;
-    p.tab8 = tab8;
-    p.wd8 = packed_w + 2 * half;
-    p.wd_bytes = (unsigned)(half * sizeof(float));
-    return launch_conv<MODE_CONV>(ctx, p, 1);
-  }
-  if (Cout <= 4 && ctx->conv_max_split != 1 && p.out_nc8 == 0) {   // heads: a stream over the input, not an MFMA problem
+  else if (out_nc8) DI_REQUIRE((Cin & 1) == 0, "conv2d: NC8 output needs an even Cin (LDS-free kernels only)");
+  const ConvKernel kern = conv_kernel_for(ctx, MODE_CONV, Cin, Cout, p.npix, in_nc8, out_nc8);
+  int rc = set_operands(ctx, p, kern.fam, packed_w, kh, kw);
+  if (rc) return rc;
+  if (kern.fam == FAM_FEWOUT) {
     // channel slices when the pixels alone leave the chip empty: ~512 blocks, slices of at least 32 channels (fixed by the geometry)
     // the 3x3 stride-1 pad-1 heads on rows of whole quads: four pixels per lane (conv_fewout_quad_kernel); dev option conv_fewout_quad = 0: the one-pixel form
     const bool quad = kh == 3 && kw == 3 && stride == 1 && pad == 1 && (W & 3) == 0 && ctx->conv_fewout_quad &&
@@ -2185,14 +2091,10 @@ static int conv2d_forward_impl(deepim_ctx* ctx, float* out, const float* in, con
     int S = max(1, min(min(target / nblk, Cin / ctx->conv_fewout_minc), 32));
     const int cslice = di_div_up(Cin, S);
     S = di_div_up(Cin, cslice);
-    float* partial = nullptr;
     const long total = (long)B * Cout * p.Ho * p.Wo;
-    if (S > 1) {
-      void* scratch;
-      rc = deepim_scratch(ctx, (size_t)S * total * sizeof(float), &scratch);
-      if (rc) return rc;
-      partial = (float*)scratch;
-    }
+    float* partial;
+    rc = scratch_floats(ctx, S > 1 ? (size_t)S * total : 0, &partial);
+    if (rc) return rc;
     const dim3 grid(nblk, S);
     if (quad) {
 #define DI_FEWOUT_Q(C)                                                                                                  \
@@ -2219,21 +2121,84 @@ static int conv2d_forward_impl(deepim_ctx* ctx, float* out, const float* in, con
     DI_LAUNCH_CHECK();
     return 0;
   }
-  // LDS-free kernel: 128x128-tiled layers with even Cin. conv_max_split = 1 asks for the canonical single
-  // (ci,ky,kx)-ordered chain per output, which only the LDS kernel provides; conv_direct = 2 forces the LDS-free kernel
-  // regardless (its chain runs over (ci/2,ky,kx,ci%2)).
-  const bool direct = out_nc8 || ctx->conv_direct == 2 || (ctx->conv_direct == 1 && ctx->conv_max_split != 1);
-  if (out_nc8) DI_REQUIRE((Cin & 1) == 0, "conv2d: NC8 output needs an even Cin (LDS-free kernels only)");
-  if (direct && (Cin & 1) == 0 && (Cout > 64 || out_nc8 || p.npix >= 256L * 1024)) {   // the tile shapes the LDS-free kernel has
-    const size_t half = packed_half(Cout, Cin * kh * kw);
-    int2* tab2;
-    rc = get_tab(ctx, MODE_DIRECT_TAB, Cin, kh, kw, H, W, &tab2);
-    if (rc) return rc;
-    p.tab2 = tab2;
-    p.wd = packed_w + half;
-    p.wd_bytes = (unsigned)(half * sizeof(float));
-  }
-  return launch_conv<MODE_CONV>(ctx, p, 1);
+  return launch_conv<MODE_CONV>(ctx, p, 1, kern);
+}
+
+extern "C" int deepim_conv2d_forward_ex(deepim_ctx* ctx, float* out, const float* in, const float* packed_w,
+                                        const float* bias, int B, int Cin, int H, int W, int Cout, int kh, int kw,
+                                        int stride, int pad, float slope, int out_ctotal, int out_coff, int in_nc8,
+                                        int out_nc8) {
+  return conv2d_forward_impl(ctx, out, in, packed_w, bias, B, Cin, H, W, Cout, kh, kw, stride, pad, slope, out_ctotal, out_coff,
+                             in_nc8, out_nc8 == 3 ? 3 : (out_nc8 ? 1 : 0), 1.f);   // 3: NC8 in space-to-depth order
+}
+
+extern "C" int deepim_conv2d_forward(deepim_ctx* ctx, float* out, const float* in, const float* packed_w,
+                                     const float* bias, int B, int Cin, int H, int W, int Cout, int kh, int kw,
+                                     int stride, int pad, float slope, int out_ctotal, int out_coff) {
+  DI_DEVICE(ctx);
+  return deepim_conv2d_forward_ex(ctx, out, in, packed_w, bias, B, Cin, H, W, Cout, kh, kw, stride, pad, slope, out_ctotal,
+                                  out_coff, 0, 0);
+}
+
+// NCHW fp32 in → split16 out (conv1 of the split-fp16 encoder): the fp32 MFMA convolution with the split folded into its
+// epilogue. Cout % 16 == 0; LDS-free kernels only (even Cin).
+extern "C" int deepim_conv2d_forward_split16(deepim_ctx* ctx, void* out_split16, const float* in, const float* packed_w,
+                                             const float* bias, int B, int Cin, int H, int W, int Cout, int kh, int kw,
+                                             int stride, int pad, float slope, float out_scale) {
+  DI_REQUIRE((Cout & 15) == 0 && (Cin & 1) == 0, "conv2d_split16: needs Cout % 16 == 0 and an even Cin");
+  return conv2d_forward_impl(ctx, (float*)out_split16, in, packed_w, bias, B, Cin, H, W, Cout, kh, kw, stride, pad, slope, 0, 0,
+                             0, 2, out_scale);
+}
+
+// One output parity class of a stride-2 data gradient, straight into dx: a stride-1 convolution of the un-dilated gradient `in`
+// (B,Cin,H,W) with the class's flipped sub-kernel (kh x kw, symmetric pad), whose result window [cy, cy + hq) x [cx, cx + wq)
+// — hq = ⌈(Hd - py) / 2⌉, wq = ⌈(Wd - px) / 2⌉ — is written to out (B,Cout,Hd,Wd)[.., 2i + py, 2j + px]. No bias, no activation.
+extern "C" int deepim_conv2d_forward_remap(deepim_ctx* ctx, float* out, const float* in, const float* packed_w, int B, int Cin,
+                                           int H, int W, int Cout, int kh, int kw, int pad, int cy, int cx, int Hd, int Wd,
+                                           int py, int px) {
+  Remap rm;
+  rm.on = 1; rm.cy = cy; rm.cx = cx; rm.py = py; rm.px = px; rm.H = Hd; rm.W = Wd;
+  rm.hq = (Hd - py + 1) / 2; rm.wq = (Wd - px + 1) / 2;
+  rm.Wo = W + 2 * pad - kw + 1;
+  const int Ho = H + 2 * pad - kh + 1;
+  DI_REQUIRE(py >= 0 && py < 2 && px >= 0 && px < 2 && cy >= 0 && cx >= 0 && rm.hq + cy <= Ho && rm.wq + cx <= rm.Wo,
+             "conv2d_forward_remap: class window outside the convolution result");
+  return conv2d_forward_impl(ctx, out, in, packed_w, nullptr, B, Cin, H, W, Cout, kh, kw, 1, pad, 1.f, 0, 0, 0, 0, 1.f, &rm);
+}
+
+extern "C" int deepim_conv2d_dgrad_s2(deepim_ctx* ctx, float* dx, const float* dz, const float* w_layer, float* packed_ws, int B,
+                                      int Ci_l, int Hd, int Wd, int Co_l, int k, int pad) {
+  return conv2d_dgrad_s2_impl(ctx, dx, dz, w_layer, packed_ws, B, Ci_l, Hd, Wd, Co_l, k, pad, nullptr);
+}
+
+extern "C" size_t deepim_conv_dgrad_packed_size(int Co_l, int Ci_l, int k, int stride, int pad) {
+  return stride == 2 ? deepim_conv_dgrad_s2_packed_size(Co_l, Ci_l, k, pad) : deepim_conv_packed_size(Ci_l, Co_l, k, k);
+}
+
+// Data gradient of a Convolution layer (Co_l,Ci_l,k,k; stride 1 or 2) from its raw weights, optionally already multiplied by the
+// activation gradient of the layer below: dx = lrelu'(act_y)·(dgrad [+ add]) — act_y = that layer's saved output, add = the
+// gradient reaching it over a skip connection (both laid out like dx; NULL act_y = plain dgrad). The epilogue rides in the final
+// stores of the register-fed kernels / their split-K second passes; other kernel families get it as one extra pass.
+extern "C" int deepim_conv2d_dgrad(deepim_ctx* ctx, float* dx, const float* dz, const float* w_layer, float* packed_ws, int B,
+                                   int Ci_l, int Hd, int Wd, int Co_l, int k, int stride, int pad, const float* act_y,
+                                   const float* add, float slope) {
+  DI_DEVICE(ctx);
+  if (B == 0) return 0;
+  DI_REQUIRE(stride == 1 || stride == 2, "conv2d_dgrad: stride 1 or 2");
+  DI_REQUIRE(act_y != nullptr || add == nullptr, "conv2d_dgrad: add without act_y");
+  const ActGrad ag = {act_y, add, slope};
+  if (stride == 2) return conv2d_dgrad_s2_impl(ctx, dx, dz, w_layer, packed_ws, B, Ci_l, Hd, Wd, Co_l, k, pad, act_y ? &ag : nullptr);
+  const int Ho = Hd + 2 * pad - k + 1, Wo = Wd + 2 * pad - k + 1, P = k - 1 - pad;
+  DI_REQUIRE(P >= 0, "conv2d_dgrad: pad > k - 1");
+  const int order = deepim_conv_weight_order(ctx, B, Co_l, Ho, Wo, Ci_l, k, k, 1, P);
+  int rc = deepim_conv_pack_dgrad(ctx, packed_ws, w_layer, Co_l, Ci_l, k, k, 0, 0, 1, k, k, order);
+  if (rc) return rc;
+  const bool fused = act_y && order == 2 && (size_t)B * Co_l * Ho * Wo * 4 + (size_t)(P * Wo + P) * 4 < 0x7fffffffUL;
+  rc = conv2d_forward_impl(ctx, dx, dz, packed_ws, nullptr, B, Co_l, Ho, Wo, Ci_l, k, k, 1, P, 1.f, 0, 0, 0, 0, 1.f, nullptr,
+                           fused ? &ag : nullptr);
+  if (rc) return rc;
+  if (act_y && !fused) return actgrad_pass(ctx, dx, ag, (size_t)B * Ci_l * Hd * Wd);
+  return 0;
 }
 
 // [LDS-kernel operand order of the four output-parity classes | the same four 2x2-tap sub-kernels in the register-fed kernel's
@@ -2270,37 +2235,25 @@ extern "C" int deepim_deconv4x4s2_crop_forward(deepim_ctx* ctx, float* out, cons
   // stride-2 data gradient (deepim_conv2d_dgrad_s2), here with weights packed once. Round 3 ran them on the LDS-staged kernel at
   // 64-77 TFLOP/s (profiles/r03_heads_b4_iteration_trace.txt). Not in the bit-exact configuration (conv_max_split = 1 keeps the
   // canonical (ci,ky,kx) order of the LDS kernel, as for the encoder).
-  const bool direct = ctx->conv_direct == 2 || (ctx->conv_direct == 1 && ctx->conv_max_split != 1);
-  if (direct && crop_y == 1 && crop_x == 1 && deconv_direct_ok(Cin, Cout) &&
+  if (reg_fed_allowed(ctx) && crop_y == 1 && crop_x == 1 && deconv_direct_ok(Cin, Cout) &&
       (size_t)B * Cin * H * W * 4 + (size_t)(4 * W + 4) * 4 < 0x7fffffffUL) {
     const S2Forward fw = {H, W, bias, slope, out_ctotal > 0 ? out_ctotal : Cout, out_coff, true};
     return conv2d_dgrad_s2_impl(ctx, out, in, nullptr, const_cast<float*>(packed_w) + deconv_lds_pack_floats(Cin, Cout), B, Cout, Ho, Wo,
                                 Cin, 4, 1, nullptr, &fw);
   }
-  ConvParams p;
-  p.in = in; p.wp = packed_w; p.bias = bias; p.out = out;
-  p.B = B; p.Cin = Cin; p.H = H; p.W = W; p.Cout = Cout;
-  p.Ho = Ho; p.Wo = Wo; p.stride = 2; p.pad = 0;
-  p.nchunk = chunk_count(Cin * 4);
-  p.ngran = gran_count(Cout);
-  p.out_ctotal = out_ctotal > 0 ? out_ctotal : Cout;
-  p.out_coff = out_coff;
-  p.slope = slope; p.crop_y = crop_y; p.crop_x = crop_x;
-  p.rm_on = 0; p.rm_cy = p.rm_cx = p.rm_hq = p.rm_wq = p.rm_py = p.rm_px = p.rm_H = p.rm_W = 0;
-  // every parity class has at most ceil(Ho/2)*ceil(Wo/2) pixels; size the grid for the largest, the
-  // kernel masks with its own per-class count
+  // the transposed gather of the LDS kernel, one grid z-slice per output parity class: K = Cin x 2x2 taps, tap origin one row and
+  // one pixel up-left. Every class has at most ceil(Ho/2)*ceil(Wo/2) pixels; the grid is sized for the largest, the kernel masks
+  // with its own per-class count
+  ConvParams p = conv_params(ctx, out, in, bias, B, Cin, H, W, Cout, Ho, Wo, 2, 0, Cin * 4, slope, out_ctotal, out_coff);
+  p.crop_y = crop_y; p.crop_x = crop_x;
   p.npix = (long)B * ((Ho + 1) / 2) * ((Wo + 1) / 2);
   p.pad_bytes = (W + 1) * 4;
   DI_REQUIRE((size_t)B * Cin * H * W * 4 + p.pad_bytes < 0x7fffffffUL, "deconv: input tensor must be < 2 GiB per launch");
-  p.in_bytes = (unsigned)((size_t)B * Cin * H * W * 4);
   int2* tab;
   int rc = get_tab(ctx, MODE_DECONV, Cin, 4, 4, H, W, &tab);
   if (rc) return rc;
-  p.tab = tab;
-  p.wd = nullptr; p.tab2 = nullptr; p.wd_bytes = 0;
-  p.in_nc8 = p.out_nc8 = p.out_s2d = 0; p.wd8 = nullptr; p.tab8 = nullptr;
-  p.ep_y = p.ep_add = nullptr; p.ep_slope = 1.f;
-  return launch_conv<MODE_DECONV>(ctx, p, 4);
+  p.wp = packed_w; p.tab = tab;
+  return launch_conv<MODE_DECONV>(ctx, p, 4, conv_kernel_for(ctx, MODE_DECONV, Cin, Cout, p.npix, 0, 0));
 }
 
 extern "C" int deepim_upsample16_crop_forward(deepim_ctx* ctx, float* out, const float* in, const float* w, int B,

@@ -495,3 +495,51 @@ def test_default_split_k_plan_is_deterministic(ctx):
     np.testing.assert_array_equal(a, b)
     ref = onet.conv2d(x, w, None, 1, 1, 0.1)
     assert np.abs(a - ref).max() <= 1e-5 * np.abs(ref).max()
+
+
+_THRESHOLD = (1, 2, 512, 512, 8, 1, 1, 0)   # npix = 262 144, the 256 K threshold: the register-fed kernel on 64x256 tiles
+_OVER_64 = (1, 2, 8, 8, 65, 3, 1, 1)        # Cout > 64: the register-fed kernel on 128x128 tiles
+_FEW = (1, 4, 8, 8, 4, 3, 1, 1)             # Cout <= 4: the few-output stream kernel (the LDS kernel under conv_max_split = 1)
+_CANONICAL = {"conv_max_split": 1}
+_FORCED = {"conv_max_split": 1, "conv_direct": 2}
+_NO_DIRECT = {"conv_direct": 0}
+
+
+@pytest.mark.parametrize("case,options,expected", [
+    (_THRESHOLD, {}, 2), ((1, 2, 511, 512, 8, 1, 1, 0), {}, 1),     # just below the threshold
+    (_OVER_64, {}, 2), ((1, 2, 8, 8, 64, 3, 1, 1), {}, 1),
+    ((1, 3, 8, 8, 128, 3, 1, 1), {}, 1),                              # odd Cin
+    (_FEW, {}, 1),
+    (_THRESHOLD, _CANONICAL, 1), (_OVER_64, _CANONICAL, 1),
+    (_THRESHOLD, _FORCED, 2), (_OVER_64, _FORCED, 2),
+    (_THRESHOLD, _NO_DIRECT, 1), (_OVER_64, _NO_DIRECT, 1),
+    (_FEW, _CANONICAL, 1),
+])
+def test_conv_weight_order_names_the_slot_the_forward_reads(ctx, case, options, expected):
+    """deepim_conv_weight_order on both sides of each of its rules (256 K pixels, Cout 64 / 65, odd Cin, Cout <= 4, the conv_direct and
+    conv_max_split options): with every other slot of the packed buffer left NaN the forward gives the bits it gives on a buffer
+    with all three orders packed — a NaN in the output means another slot was read."""
+    B, cin, H, W, cout, k, s, p = case
+    rng = np.random.default_rng(hash(case) % (2 ** 31))
+    x = ctx.array(rng.standard_normal((B, cin, H, W)).astype(np.float32))
+    w = (rng.standard_normal((cout, cin, k, k)) / np.sqrt(cin * k * k)).astype(np.float32)
+    b = ctx.array(rng.standard_normal(cout).astype(np.float32))
+    ho, wo = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
+    h = ctx.handle
+    outs = []
+    try:
+        for name, value in options.items():
+            lib.deepim_set_option(h, name.encode(), value)
+        order = lib.load().deepim_conv_weight_order(h, B, cin, H, W, cout, k, k, s, p)
+        only = ctx.array(np.full(lib.load().deepim_conv_packed_size(cout, cin, k, k) // 4, np.nan, np.float32))
+        lib.deepim_conv_pack_weights_ex(h, only, ctx.array(w), cout, cin, k, k, order)
+        for pk in (only, _pack_conv(ctx, w)):
+            out = ctx.empty((B, cout, ho, wo))
+            lib.deepim_conv2d_forward(h, out, x, pk, b, B, cin, H, W, cout, k, k, s, p, cf(0.1), 0, 0)
+            outs.append(out.asnumpy())
+    finally:
+        lib.deepim_set_option(h, b"conv_max_split", 0)
+        lib.deepim_set_option(h, b"conv_direct", 1)
+    assert order == expected
+    assert not np.isnan(outs[0]).any()
+    np.testing.assert_array_equal(outs[0].view(np.uint32), outs[1].view(np.uint32))
