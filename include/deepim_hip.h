@@ -854,6 +854,17 @@ int deepim_extract_channels(deepim_ctx* ctx, float* dst, const float* src, int s
  * with the pixels as the reduction dimension; Ho*Wo must be a multiple of 4 */
 int deepim_conv2d_wgrad(deepim_ctx* ctx, float* dw, const float* x, const float* dz, int B, int Cin, int H, int W, int Cout,
                         int kh, int kw, int stride, int pad);
+/* The launch plan the fp32 weight-gradient entries (deepim_conv2d_wgrad, _tm, _tm_nc8, _bias) give a geometry with option "wgrad_lds"
+ * at that value. Host arithmetic from the geometry alone, no context and no device work; the launcher reads the same plan. plan[0..9] =
+ * family (0 few-filter stream kernel, 1 LDS-staged MFMA, 2 register-fed MFMA), bm (rows of an output-channel tile), m-tiles, k-tiles
+ * (128 columns of Cin*kh*kw each), units (LDS-staged: chunks of 16 pixels of one sample, B*ceil(Ho*Wo/16); register-fed: groups of 8),
+ * S (slices of whole units), units per slice, units of the last slice, second pass (0 none: the kernel writes dw itself, 1 scalar
+ * walk over the slices, 2 four quarters of ceil(S/4) slices), 1 if the last unit of a sample is ragged (Ho*Wo % 16, % 8) else 0. The
+ * few-filter kernel has no units, slices or second pass: 0, 1, 0, 0, 0, 0. Operands of 2 GiB and more take the register-fed kernel
+ * whatever the option says: that stays the launcher's decision, the query answers for the option. Geometries the entries refuse
+ * (Ho*Wo % 4 != 0, no output pixel) and B < 1 return non-zero here too, and leave plan at -1. */
+int deepim_conv_wgrad_plan(int wgrad_lds, int B, int Cin, int H, int W, int Cout, int kh, int kw, int stride, int pad,
+                           int* plan /*10, host*/);
 /* the weight gradient in TAP-MAJOR layout dw_tm (Cout, kh*kw, Cin) — what the LDS-staged kernel produces fastest (one range
  * check and one address per eight channels of a tap). Same sums, same order as deepim_conv2d_wgrad; needs Cin % 8 == 0, Cout > 4,
  * option "wgrad_lds" on. deepim_sgd_mom_update_multi reads it in place; deepim_weight_grad_to_natural gives (Cout,Cin,kh,kw). */

@@ -1032,8 +1032,11 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(const unsigned long lon
   }
 }
 
-void launch_wgrad_reduce(deepim_ctx* ctx, float* dw, const float* partial, long n, int S) {
-  if (S >= 8 && n % 4 == 0)
+// the second pass over S slices of n floats: which kernel (wgrad_plan records it), and its launch
+enum { WG_REDUCE_NONE = 0, WG_REDUCE_SCALAR = 1, WG_REDUCE_QUARTERS = 2 };
+int wgrad_reduce_kind(long n, int S) { return S >= 8 && n % 4 == 0 ? WG_REDUCE_QUARTERS : WG_REDUCE_SCALAR; }
+void launch_wgrad_reduce(deepim_ctx* ctx, float* dw, const float* partial, long n, int kind, int S) {
+  if (kind == WG_REDUCE_QUARTERS)
     hipLaunchKernelGGL(wgrad_reduce4_kernel, dim3(di_div_up(n / 4, 64)), dim3(256), 0, ctx->stream, dw, partial, n / 4, S);
   else
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(di_div_up(n, 256)), dim3(256), 0, ctx->stream, dw, partial, n, S);
@@ -1291,6 +1294,92 @@ extern "C" int deepim_weight_grad_to_natural(deepim_ctx* ctx, float* dw, const f
   return 0;
 }
 
+namespace {
+// The launch plan of an fp32 weight gradient, from the geometry and the "wgrad_lds" option alone. conv2d_wgrad_impl and
+// deepim_conv_wgrad_plan read it here. unit = what a slice counts: 16-pixel chunks of one sample (LDS-staged kernel) or groups of 8
+// pixels (register-fed kernel); the few-filter stream kernel has neither slices nor a second pass.
+enum { WG_FEW = 0, WG_LDS = 1, WG_REG = 2 };
+struct WgPlan { int family, bm, mtiles, ktiles, Ho, Wo, K; long units; int S, per_slice, reduce; };
+
+// what every fp32 weight-gradient entry asks of a geometry: nullptr, or why it is refused
+const char* wgrad_refusal(int B, int Cin, int H, int W, int Cout, int kh, int kw, int stride, int pad) {
+  if (!(B >= 1 && Cin >= 1 && Cout >= 1 && kh >= 1 && kw >= 1 && stride >= 1 && pad >= 0 && H >= 1 && W >= 1 && H + 2 * pad >= kh &&
+        W + 2 * pad >= kw))
+    return "conv2d_wgrad: no output pixel: empty operand, H + 2 pad < kh, W + 2 pad < kw, or stride < 1";
+  const long Ho = (H + 2 * pad - kh) / stride + 1, Wo = (W + 2 * pad - kw) / stride + 1;
+  if (Ho * Wo >= (1L << 30)) return "conv2d_wgrad: plane too large";
+  if (((Ho * Wo) & 3) != 0) return "conv2d_wgrad: Ho*Wo must be a multiple of 4";
+  return nullptr;
+}
+
+// lds: the LDS-staged kernel takes the layer (the option is on and both operands lie inside the 2 GiB buffer range)
+WgPlan wgrad_plan(bool lds_option, bool lds, int B, int Cin, int H, int W, int Cout, int kh, int kw, int stride, int pad) {
+  WgPlan q;
+  q.Ho = (H + 2 * pad - kh) / stride + 1;
+  q.Wo = (W + 2 * pad - kw) / stride + 1;
+  q.K = Cin * kh * kw;
+  const int HW = q.Ho * q.Wo;
+  q.ktiles = di_div_up(q.K, 128);
+  q.bm = (lds_option && Cout <= 64) ? 64 : 128;
+  q.mtiles = di_div_up(Cout, q.bm);
+  const long n_dw = (long)Cout * q.K;
+  if (lds_option && Cout <= 4 && kh == kw && (kh == 3 || kh == 4)) {   // prediction heads, flow upsamplers
+    q.family = WG_FEW;
+    q.units = 0; q.S = 1; q.per_slice = 0; q.reduce = WG_REDUCE_NONE;
+    return q;
+  }
+  if (lds) {
+    // LDS-staged kernel: chunks of 16 pixels of one sample; slices of whole chunks, fixed by the geometry (deterministic)
+    q.family = WG_LDS;
+    const long chunks = (long)B * di_div_up(HW, WG_PIX);
+    q.units = chunks;
+    // slice count: the blocks of a launch run in rounds of `slots` (256 CUs x 3 resident blocks, 4 for the 64-row tile); a
+    // count just above a multiple of that leaves a nearly empty last round (1024 blocks on 768 slots: a third of the chip
+    // idle for half the kernel). Pick S minimising rounds x chunks-per-slice (+ the reduce pass), slices >= 16 chunks.
+    const long tiles = (long)q.ktiles * q.mtiles, slots = q.bm == 64 ? 1024 : 768;
+    long S = 1;
+    float best = 1e30f;
+    for (long cand = 1; cand <= max(1L, min(chunks / 16, 4 * slots / tiles)); ++cand) {
+      const long cps_ = di_div_up(chunks, cand), s_eff = di_div_up(chunks, cps_);
+      // + the second pass: every slice writes and re-reads Cout·K floats (≈4.5e-7 chunk times per float at ≈4 TB/s)
+      const float cost = (float)di_div_up(tiles * s_eff, slots) * (float)cps_ +
+                         (s_eff > 1 ? 2.f + (float)s_eff * (0.02f + 4.5e-7f * (float)n_dw) : 0.f);
+      if (cost < best * 0.99f) { best = cost; S = cand; }
+    }
+    q.per_slice = (int)di_div_up(chunks, S);
+    q.S = (int)di_div_up(chunks, q.per_slice);
+    q.reduce = q.S == 1 ? WG_REDUCE_NONE : wgrad_reduce_kind(n_dw, q.S);   // a single slice writes the gradient itself
+    return q;
+  }
+  q.family = WG_REG;
+  const long groups = (long)B * ((HW + 7) >> 3);
+  q.units = groups;
+  // enough pixel slices to fill the chip (~1024 blocks), each at least 64 groups (512 pixels) long; fixed by the geometry
+  long S = di_div_up(1024, q.ktiles * q.mtiles);
+  S = min(S, max(1L, groups / 64));
+  q.per_slice = (int)di_div_up(groups, S);
+  q.S = (int)di_div_up(groups, q.per_slice);
+  q.reduce = wgrad_reduce_kind(n_dw, q.S);   // this kernel always writes slices, even a single one
+  return q;
+}
+}  // namespace
+
+extern "C" int deepim_conv_wgrad_plan(int wgrad_lds, int B, int Cin, int H, int W, int Cout, int kh, int kw, int stride, int pad,
+                                      int* plan) {
+  DI_REQUIRE(plan != nullptr, "conv_wgrad_plan: null plan");
+  for (int i = 0; i < 10; ++i) plan[i] = -1;
+  const char* why = wgrad_refusal(B, Cin, H, W, Cout, kh, kw, stride, pad);
+  DI_REQUIRE(why == nullptr, why);
+  const WgPlan q = wgrad_plan(wgrad_lds != 0, wgrad_lds != 0, B, Cin, H, W, Cout, kh, kw, stride, pad);
+  DI_REQUIRE(q.units < (1L << 30), "conv2d_wgrad: too many pixel chunks");
+  const int HW = q.Ho * q.Wo, unit = q.family == WG_LDS ? WG_PIX : 8;
+  const int out[10] = {q.family, q.bm, q.mtiles, q.ktiles, (int)q.units, q.S, q.per_slice,
+                       q.family == WG_FEW ? 0 : (int)(q.units - (long)(q.S - 1) * q.per_slice), q.reduce,
+                       q.family != WG_FEW && HW % unit != 0 ? 1 : 0};
+  for (int i = 0; i < 10; ++i) plan[i] = out[i];
+  return 0;
+}
+
 static int conv2d_wgrad_impl(deepim_ctx* ctx, float* dw, float* db, const float* x, const float* dz, int B, int Cin, int H, int W,
                              int Cout, int kh, int kw, int stride, int pad, bool tap_major, int x_mode) {
   DI_DEVICE(ctx);
@@ -1299,19 +1388,19 @@ static int conv2d_wgrad_impl(deepim_ctx* ctx, float* dw, float* db, const float*
     if (db) DI_CHECK(hipMemsetAsync(db, 0, (size_t)Cout * sizeof(float), ctx->stream));
     return 0;
   }
+  const char* why = wgrad_refusal(B, Cin, H, W, Cout, kh, kw, stride, pad);
+  DI_REQUIRE(why == nullptr, why);
+  const bool lds = ctx->wgrad_lds && (size_t)B * Cin * H * W * 4 < 0x7fffffffUL &&
+                   (size_t)B * Cout * ((H + 2 * pad - kh) / stride + 1) * ((W + 2 * pad - kw) / stride + 1) * 4 < 0x7fffffffUL;
+  const WgPlan q = wgrad_plan(ctx->wgrad_lds != 0, lds, B, Cin, H, W, Cout, kh, kw, stride, pad);
   WgradParams p;
   p.x = x; p.dz = dz;
   p.B = B; p.Cin = Cin; p.H = H; p.W = W; p.Cout = Cout; p.kh = kh; p.kw = kw; p.stride = stride; p.pad = pad;
-  p.Ho = (H + 2 * pad - kh) / stride + 1;
-  p.Wo = (W + 2 * pad - kw) / stride + 1;
-  p.K = Cin * kh * kw;
-  const int HW = p.Ho * p.Wo;
-  DI_REQUIRE((HW & 3) == 0, "conv2d_wgrad: Ho*Wo must be a multiple of 4");
-  p.ktiles = di_div_up(p.K, 128);
-  const int bm = (ctx->wgrad_lds && Cout <= 64) ? 64 : 128;
-  p.mtiles = di_div_up(Cout, bm);
+  p.Ho = q.Ho; p.Wo = q.Wo; p.K = q.K;
+  p.ktiles = q.ktiles; p.mtiles = q.mtiles;
+  const int HW = p.Ho * p.Wo, bm = q.bm;
   const long n_dw = (long)Cout * p.K;
-  if (ctx->wgrad_lds && Cout <= 4 && kh == kw && (kh == 3 || kh == 4)) {   // prediction heads, flow upsamplers
+  if (q.family == WG_FEW) {
 #define DI_WG_FEW(CO, KS) hipLaunchKernelGGL((wgrad_fewout_kernel<CO, KS>), dim3(Cin), dim3(256), 0, ctx->stream, dw, x, dz, B, Cin, H, W, Cout, p.Ho, p.Wo, stride, pad, db)
     if (kh == 3) { if (Cout == 1) DI_WG_FEW(1, 3); else if (Cout == 2) DI_WG_FEW(2, 3); else DI_WG_FEW(4, 3); }
     else { if (Cout == 1) DI_WG_FEW(1, 4); else if (Cout == 2) DI_WG_FEW(2, 4); else DI_WG_FEW(4, 4); }
@@ -1323,62 +1412,32 @@ static int conv2d_wgrad_impl(deepim_ctx* ctx, float* dw, float* db, const float*
     const int rc = deepim_bias_grad(ctx, db, dz, B, Cout, (size_t)HW);
     if (rc) return rc;
   }
-  if (ctx->wgrad_lds && (size_t)B * Cin * H * W * 4 < 0x7fffffffUL && (size_t)B * Cout * HW * 4 < 0x7fffffffUL) {
-    // LDS-staged kernel: chunks of 16 pixels of one sample; slices of whole chunks, fixed by the geometry (deterministic)
-    const long chunks = (long)B * di_div_up(HW, WG_PIX);
-    DI_REQUIRE(chunks < (1L << 30), "conv2d_wgrad: too many pixel chunks");
-    // slice count: the blocks of a launch run in rounds of `slots` (256 CUs x 3 resident blocks, 4 for the 64-row tile); a
-    // count just above a multiple of that leaves a nearly empty last round (1024 blocks on 768 slots: a third of the chip
-    // idle for half the kernel). Pick S minimising rounds x chunks-per-slice (+ the reduce pass), slices >= 16 chunks.
-    const long tiles = (long)p.ktiles * p.mtiles, slots = bm == 64 ? 1024 : 768;
-    long S = 1;
-    float best = 1e30f;
-    for (long cand = 1; cand <= max(1L, min(chunks / 16, 4 * slots / tiles)); ++cand) {
-      const long cps_ = di_div_up(chunks, cand), s_eff = di_div_up(chunks, cps_);
-      // + the second pass: every slice writes and re-reads Cout·K floats (≈4.5e-7 chunk times per float at ≈4 TB/s)
-      const float cost = (float)di_div_up(tiles * s_eff, slots) * (float)cps_ +
-                         (s_eff > 1 ? 2.f + (float)s_eff * (0.02f + 4.5e-7f * (float)n_dw) : 0.f);
-      if (cost < best * 0.99f) { best = cost; S = cand; }
-    }
-    p.groups_per_slice = (int)di_div_up(chunks, S);
-    p.S = (int)di_div_up(chunks, p.groups_per_slice);
-    if (p.S == 1) {
-      p.partial = dw;                                  // a single slice writes the gradient itself
-    } else {
-      void* scratch;
-      int rc = deepim_scratch(ctx, (size_t)p.S * n_dw * sizeof(float), &scratch);
-      if (rc) return rc;
-      p.partial = (float*)scratch;
-    }
-    const dim3 grid(p.ktiles * p.mtiles * p.S);
-    if (tap_major && x_mode) {
-      if (bm == 64 && x_mode == 3) hipLaunchKernelGGL((wgrad_lds_kernel<64, true, 3>), grid, dim3(256), 0, ctx->stream, p);
-      else if (bm == 64) hipLaunchKernelGGL((wgrad_lds_kernel<64, true, 1>), grid, dim3(256), 0, ctx->stream, p);
-      else if (x_mode == 3) hipLaunchKernelGGL((wgrad_lds_kernel<128, true, 3>), grid, dim3(256), 0, ctx->stream, p);
-      else hipLaunchKernelGGL((wgrad_lds_kernel<128, true, 1>), grid, dim3(256), 0, ctx->stream, p);
-    } else if (tap_major) {
-      if (bm == 64) hipLaunchKernelGGL((wgrad_lds_kernel<64, true>), grid, dim3(256), 0, ctx->stream, p);
-      else hipLaunchKernelGGL((wgrad_lds_kernel<128, true>), grid, dim3(256), 0, ctx->stream, p);
-    } else if (bm == 64) hipLaunchKernelGGL(wgrad_lds_kernel<64>, grid, dim3(256), 0, ctx->stream, p);
-    else hipLaunchKernelGGL(wgrad_lds_kernel<128>, grid, dim3(256), 0, ctx->stream, p);
-    if (p.S > 1) launch_wgrad_reduce(ctx, dw, p.partial, n_dw, p.S);
-    DI_LAUNCH_CHECK();
-    return 0;
+  if (q.family == WG_LDS) DI_REQUIRE(q.units < (1L << 30), "conv2d_wgrad: too many pixel chunks");
+  else DI_REQUIRE(!tap_major, "conv2d_wgrad_tm: tensors of 2 GiB and more take the register-fed kernel, which has no tap-major order");
+  p.groups_per_slice = q.per_slice;
+  p.S = q.S;
+  if (q.family == WG_LDS && p.S == 1) {
+    p.partial = dw;                                  // a single slice writes the gradient itself
+  } else {
+    void* scratch;
+    int rc = deepim_scratch(ctx, (size_t)p.S * n_dw * sizeof(float), &scratch);
+    if (rc) return rc;
+    p.partial = (float*)scratch;
   }
-  DI_REQUIRE(!tap_major, "conv2d_wgrad_tm: tensors of 2 GiB and more take the register-fed kernel, which has no tap-major order");
-  const long groups = (long)B * ((HW + 7) >> 3);
-  // enough pixel slices to fill the chip (~1024 blocks), each at least 64 groups (512 pixels) long; fixed by the geometry
-  long S = di_div_up(1024, p.ktiles * p.mtiles);
-  S = min(S, max(1L, groups / 64));
-  p.groups_per_slice = (int)di_div_up(groups, S);
-  p.S = (int)di_div_up(groups, p.groups_per_slice);
-  const long n = (long)Cout * p.K;
-  void* scratch;
-  int rc = deepim_scratch(ctx, (size_t)p.S * n * sizeof(float), &scratch);
-  if (rc) return rc;
-  p.partial = (float*)scratch;
-  hipLaunchKernelGGL(wgrad_mfma_kernel, dim3(p.ktiles * p.mtiles * p.S), dim3(256), 0, ctx->stream, p);
-  launch_wgrad_reduce(ctx, dw, p.partial, n, p.S);
+  const dim3 grid(p.ktiles * p.mtiles * p.S);
+  if (q.family == WG_REG) {
+    hipLaunchKernelGGL(wgrad_mfma_kernel, grid, dim3(256), 0, ctx->stream, p);
+  } else if (tap_major && x_mode) {
+    if (bm == 64 && x_mode == 3) hipLaunchKernelGGL((wgrad_lds_kernel<64, true, 3>), grid, dim3(256), 0, ctx->stream, p);
+    else if (bm == 64) hipLaunchKernelGGL((wgrad_lds_kernel<64, true, 1>), grid, dim3(256), 0, ctx->stream, p);
+    else if (x_mode == 3) hipLaunchKernelGGL((wgrad_lds_kernel<128, true, 3>), grid, dim3(256), 0, ctx->stream, p);
+    else hipLaunchKernelGGL((wgrad_lds_kernel<128, true, 1>), grid, dim3(256), 0, ctx->stream, p);
+  } else if (tap_major) {
+    if (bm == 64) hipLaunchKernelGGL((wgrad_lds_kernel<64, true>), grid, dim3(256), 0, ctx->stream, p);
+    else hipLaunchKernelGGL((wgrad_lds_kernel<128, true>), grid, dim3(256), 0, ctx->stream, p);
+  } else if (bm == 64) hipLaunchKernelGGL(wgrad_lds_kernel<64>, grid, dim3(256), 0, ctx->stream, p);
+  else hipLaunchKernelGGL(wgrad_lds_kernel<128>, grid, dim3(256), 0, ctx->stream, p);
+  if (q.reduce != WG_REDUCE_NONE) launch_wgrad_reduce(ctx, dw, p.partial, n_dw, q.reduce, p.S);
   DI_LAUNCH_CHECK();
   return 0;
 }
